@@ -4,6 +4,15 @@
     python bench.py --gpus N --steps K --warmup W          (N>1: one rank per GPU over RCCL -- under torch.distributed.run, or
                                                             self-launched: with no launcher in the environment this command starts
                                                             its own N ranks as fresh child processes)
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints ONE JSON line: the headline (`value`, `ms_per_step` = wall ms of one
+timed step), the configuration and the roofline of the timed launches.  --full adds every leg that takes runs of its own (the
+other scaling mode and the serial all_gather for N > 1; cpu_baseline, parity, parity_mode, ert and training for N = 1).
+--dump-outputs DIR: after the timed steps, the frame(s) of the LAST timed step as a caller receives them, DIR/rgb.npy
+(views, H, W, 3) and DIR/depth.npy (views, H, W), float32; the inputs are fixed by the arguments (seeded weights, fixed poses, no
+jitter), so two builds can be compared output for output.  Above 64 MB the files hold a fixed seeded sample of the rays instead
+(rgb (n, 3), depth (n,)).
 
 Workload (BASELINE.json metric): synthetic 800x800 camera frames, 64 samples per ray, the 8x256
 NeRF MLP (nerf_model.NeRFMLP, 951 808 FLOP per ray-sample), deterministic random-init weights
@@ -15,13 +24,14 @@ dealt round-robin over the ranks, so per-GPU work is one frame's worth of rays w
 tiles of ALL views with ONE kernel launch straight into the gather buffer and the tiles are exchanged with ONE RCCL
 all_gather per step so that every rank holds all frames; the all_gather of step i runs on RCCL's stream while step i+1 renders
 (two gather buffers; --no-overlap serialises them).  --scaling strong: ONE view per step cut over the ranks
-(BASELINE.json config 5's shape with --samples 128).  Whichever is the headline, the other one is measured too (a few
-steps after the timed region) and reported as `strong_scaling` / `weak_scaling`; the all_gather is timed separately
+(BASELINE.json config 5's shape with --samples 128).  With --full, whichever is the headline, the other one is measured too (a
+few steps after the timed region) and reported as `strong_scaling` / `weak_scaling`, and the all_gather is timed separately
 (`gather_ms`).  Inputs are generated in-kernel (camera mode): nothing is read from the host in the timed region.
 
 The JSON line also carries
   roofline     -- algorithmic FLOPs of the render kernel / its mean launch duration (HIP events on the launch stream)
                   against the dense bf16 MFMA peak (2.5 PFLOP/s);
+and, with --full,
   cpu_baseline -- the CPU oracle (oracle/nerf_oracle.py, a port of the reference's PyTorch CPU path) timed on a band of
                   rows of the same frame on this host's cores;
   parity       -- max abs error / PSNR of every arithmetic mode vs that oracle band, and the PSNR delta against a common
@@ -30,7 +40,8 @@ The JSON line also carries
                   parity.headline_mode: whether the mode of `value` meets the 0.01 dB bar on both;
   parity_mode  -- the parity-grade fast mode (f16x3: split-f16, 3 MFMAs per product): ms per frame, TFLOP/s credited 1x,
                   fraction of the 2.5 PFLOP/s peak -- the mode that meets the 1e-4 / 0.01 dB bars -- beside f16 and f32;
-  ert          -- early ray termination on the "smooth" scene: ms, speed-up, max |d rgb| vs the full march (must be <= eps).
+  ert          -- early ray termination on the "smooth" scene: ms, speed-up, max |d rgb| vs the full march (must be <= eps);
+  training     -- one optimisation step at the reference's batch (training_line).
 """
 import argparse
 import json
@@ -141,6 +152,25 @@ def training_line(N, args, dev):
     return out
 
 
+DUMP_LIMIT = 64 * 10**6          # bytes that --dump-outputs may write in all
+
+
+def dump_outputs(frames, H, W, out_dir, limit=DUMP_LIMIT):
+    """--dump-outputs: frames (views, H*W, 4) = [r,g,b,depth] in ray-id order -> out_dir/rgb.npy (views, H, W, 3) and
+    out_dir/depth.npy (views, H, W), float32.  When that exceeds `limit` bytes: the same seeded sample of rays on every run,
+    in ray order over all views, rgb (n, 3) and depth (n,)."""
+    import numpy as np
+    a = frames.detach().float().cpu().numpy().reshape(-1, H, W, 4)
+    head = 1024                  # room for the two .npy headers
+    if a.nbytes + head > limit:
+        n = (limit - head) // (4 * a.itemsize)
+        idx = np.sort(np.random.default_rng(0).choice(a.shape[0] * H * W, size=n, replace=False))
+        a = a.reshape(-1, 4)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rgb.npy"), np.ascontiguousarray(a[..., :3]))
+    np.save(os.path.join(out_dir, "depth.npy"), np.ascontiguousarray(a[..., 3]))
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser()
@@ -156,13 +186,18 @@ def main(argv=None):
     ap.add_argument("--ert", type=float, default=0.0)
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: n_gpus views per step (one frame's worth of rays per GPU); strong: ONE view per step cut over the ranks")
-    ap.add_argument("--other-steps", type=int, default=10, help="steps of the other scaling mode measured after the timed region (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: other scaling mode, serial gather (N > 1); CPU baseline, parity, "
+                         "parity_mode, ert, training (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame(s) of the last timed step to DIR/rgb.npy and DIR/depth.npy (float32; a fixed sample above 64 MB)")
+    ap.add_argument("--other-steps", type=int, default=10, help="--full: steps of the other scaling mode measured after the timed region (0 = skip)")
     ap.add_argument("--tile-rows", type=int, default=0, help="rows per pixel tile; 0 = largest <= 16 that deals the tiles evenly")
-    ap.add_argument("--no-train", action="store_true", help="skip the optimisation-step timing appended as 'training' (N=1 only)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the parity_mode / ert legs (N=1 only)")
+    ap.add_argument("--no-train", action="store_true", help="--full: skip the optimisation-step timing appended as 'training' (N=1 only)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the parity_mode / ert legs (N=1 only)")
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: do not overlap the all_gather of a step with the next step's render")
-    ap.add_argument("--cpu-rows", type=int, default=16, help="rows of the frame the CPU baseline renders (0 = skip)")
-    ap.add_argument("--no-trained-scene", action="store_true", help="skip parity.trained_scene (train a field on a generated scene, PSNR delta of every mode; N=1 only)")
+    ap.add_argument("--cpu-rows", type=int, default=16, help="--full: rows of the frame the CPU baseline renders (0 = skip)")
+    ap.add_argument("--no-trained-scene", action="store_true", help="--full: skip parity.trained_scene (train a field on a generated scene, PSNR delta of every mode; N=1 only)")
     ap.add_argument("--rehearse", action="store_true",
                     help="N > 1 on a box with ONE GPU: every rank on cuda:0, tiles exchanged over gloo through host memory (RCCL refuses two ranks on "
                          "one card).  Exercises the launcher, the tile dealing and the gather; its numbers are not multi-GPU numbers")
@@ -253,7 +288,8 @@ def main(argv=None):
         torch.cuda.synchronize()
 
     def run(n_views, steps, warmup, overlap):
-        """`warmup` untimed + `steps` timed steps: (wall seconds [max over ranks], mean kernel ms, mean gather ms or None, rays/launch).
+        """`warmup` untimed + `steps` timed steps: (wall seconds [max over ranks], mean kernel ms, mean gather ms or None, rays/launch,
+        launches/step, the last step's frames (views, H*W, 4) = [r,g,b,depth] in ray-id order as this rank holds them).
         overlap (N > 1): two jobs with their own gather buffers take turns; the all_gather of step i is enqueued asynchronously (RCCL
         runs it on its own stream, after the render it depends on) while step i+1 renders -- every step still ends with every rank
         holding every frame, the exchange just no longer sits between two renders.  A buffer is rendered into again only after the
@@ -312,17 +348,28 @@ def main(argv=None):
             dt = float(t.item())
         kms = sum(a.elapsed_time(b) for a, b in kev) / max(len(kev), 1)
         gms = sum(a.elapsed_time(b) for a, b in gev) / max(len(gev), 1) if (world > 1 and len(jobs) == 1) else None
-        return dt, kms, gms, jobs[0].rays_per_step, jobs[0].launches_per_step
+        k = (warmup + steps - 1) % len(jobs)                       # the slot the last step wrote
+        if async_gather:
+            g = ex.gathered(k)
+            last = torch.stack([tiles.reassemble(g[:, v], H * W, world, tile_rays) for v in range(g.shape[1])])
+        elif world > 1:
+            last = frames[k]
+        else:
+            last = tiles.gather_frames(jobs[k].buf, H * W, tile_rays, world=1)
+        return dt, kms, gms, jobs[0].rays_per_step, jobs[0].launches_per_step, last
 
     views_main = world if args.scaling == "weak" else 1
     overlap = world > 1 and backend == "nccl" and not args.no_overlap
     # no automatic fall-back to the serial exchange: a rank that switched protocol on its own would leave the others inside
     # mismatched collectives (a hang instead of an error).  An RCCL failure surfaces; --no-overlap selects the serial form.
-    dt, kernel_ms, gather_ms, rays_per_step_rank, launches_per_step = run(views_main, args.steps, args.warmup, overlap)
+    dt, kernel_ms, gather_ms, rays_per_step_rank, launches_per_step, last = run(views_main, args.steps, args.warmup, overlap)
     print(f"[bench] rank {rank}: timed region done", file=sys.stderr, flush=True)
-    if world > 1 and gather_ms is None and args.other_steps > 0:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last, H, W, args.dump_outputs)
+    del last
+    if args.full and world > 1 and gather_ms is None and args.other_steps > 0:
         # the exchange on its own: a few steps with the all_gather NOT overlapped, timed with events around it
-        _, _, gather_ms, _, _ = run(views_main, min(args.other_steps, 5), 1, False)
+        _, _, gather_ms, _, _, _ = run(views_main, min(args.other_steps, 5), 1, False)
 
     samples_per_launch = rays_per_step_rank * S                   # what this rank's launch(es) of one step march: kernel_ms spans exactly them
     samples_per_step = views_main * H * W * S                     # all ranks together
@@ -363,19 +410,19 @@ def main(argv=None):
     }
 
     # the other scaling mode, a few steps (every rank takes part)
-    if args.other_steps > 0 and world > 1:
+    if args.full and args.other_steps > 0 and world > 1:
         other = "strong" if args.scaling == "weak" else "weak"
         views_o = 1 if other == "strong" else world
-        dto, kmo, gmo, rays_o, _ = run(views_o, args.other_steps, 2, overlap)
+        dto, kmo, gmo, rays_o, _, _ = run(views_o, args.other_steps, 2, overlap)
         if gmo is None:
-            _, _, gmo, _, _ = run(views_o, min(args.other_steps, 5), 1, False)
+            _, _, gmo, _, _, _ = run(views_o, min(args.other_steps, 5), 1, False)
         out[f"{other}_scaling"] = {
             "workload": f"{views_o} view(s) of {H}x{W}x{S} per step cut over {world} GPU(s)", "steps": args.other_steps,
             "value": round(views_o * H * W * S * args.other_steps / dto / 1e6, 2), "unit": "M ray-samples/s",
             "ms_per_step": round(dto / args.other_steps * 1e3, 4), "kernel_ms": round(kmo, 4), "gather_ms": None if gmo is None else round(gmo, 4),
             "rays_per_gpu_per_step": rays_o}
 
-    single = rank == 0 and world == 1
+    single = args.full and rank == 0 and world == 1          # the single-GPU legs of --full
     if single and args.cpu_rows > 0:
         # CPU oracle on a band of rows of the same frame (port of the reference's torch-CPU path)
         # the box's CPU share, not the host's core count (a cgroup-limited box reports far more cores than it may use)
