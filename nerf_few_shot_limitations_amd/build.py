@@ -27,7 +27,8 @@ HALF16 = ["-DNRF_TU_HALF=16", "-DNRF_ACT_AGPR=1", "-mllvm", "-amdgpu-mfma-vgpr-f
 HALF32 = ["-DNRF_TU_HALF=32"]
 FUSED = [(f"fused_{fam}.hip", f"fused_{fam}_{half}", flags) for fam in ("v1", "v2", "v3", "v3w") for half, flags in (("16", HALF16), ("32", HALF32))]
 SOURCES = FUSED + [(f, os.path.splitext(f)[0], []) for f in
-                   ("fused_kernels.hip", "train_v1.hip", "train_v2.hip", "train_v3.hip", "staged_kernels.hip", "api.cpp", "packing.cpp")]
+                   ("fused_kernels.hip", "train_shared.hip", "train_v1.hip", "train_v2.hip", "train_v3.hip", "staged_kernels.hip", "api.cpp",
+                    "packing.cpp")]
 # -Rpass-analysis=kernel-resource-usage: the backend reports every kernel's registers / spills / scratch; kept beside the object
 # (<name>.o.remarks, see kernel_resources()) so that a toolchain or flag change that breaks the AGPR parking or introduces
 # spills in a headline kernel is caught by tests/test_kernel_resources.py
@@ -68,31 +69,19 @@ def _obj_fresh(obj: str, cmd_key: str) -> bool:
     return all(os.path.exists(p) and os.path.getmtime(p) <= t for p in files)
 
 
-def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str = LIB, obj_dir: str = OBJ, fused_only: bool = False, only=None) -> str:
-    """Compile (what is stale) and return the path of libnerfhip.so.  `extra_flags`/`out`/`obj_dir` build a tuning variant
-    beside the product (loaded with NRF_LIB=<path> for same-box A/B runs); `fused_only` recompiles only the fused
-    renderer / forward objects with the extra flags and reuses the product build's other objects; `only` = the object names
-    (e.g. {"train_v1"}) to recompile instead."""
+def build(force: bool = False, verbose: bool = False) -> str:
+    """Compile (what is stale) and return the path of libnerfhip.so."""
     deps = _deps()
     # fast path (and the only one on the GPU box, where the object directory does not travel): the library is newer than every
     # source, header and this file
-    if not force and not extra_flags and os.path.exists(out) and os.path.getmtime(out) >= _newest(deps):
-        return out
-    os.makedirs(obj_dir, exist_ok=True)
+    if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(deps):
+        return LIB
+    os.makedirs(OBJ, exist_ok=True)
 
     def one(item):
         src, name, flags = item
-        obj = os.path.join(obj_dir, name + ".o")
-        if (fused_only and item not in FUSED) or (only is not None and name not in only):
-            # a variant that recompiles only the fused kernels links the PRODUCT build's other objects: they must exist and be
-            # newer than every source (else the A/B would silently compare against stale code)
-            prod = os.path.join(OBJ, name + ".o")
-            prod_cmd = " ".join([hipcc(), *FLAGS, *flags, "-MD", "-MF", prod + ".d", "-c", os.path.join(CSRC, src), "-o", prod])
-            if not _obj_fresh(prod, prod_cmd):
-                raise RuntimeError(f"variant build: product object {prod} is missing or older than a file it was built from; run the plain build first")
-            shutil.copyfile(prod, obj)
-            return obj, False
-        cmd = [hipcc(), *FLAGS, *flags, *extra_flags, "-MD", "-MF", obj + ".d", "-c", os.path.join(CSRC, src), "-o", obj]
+        obj = os.path.join(OBJ, name + ".o")
+        cmd = [hipcc(), *FLAGS, *flags, "-MD", "-MF", obj + ".d", "-c", os.path.join(CSRC, src), "-o", obj]
         cmd_key = " ".join(cmd)
         if not force and _obj_fresh(obj, cmd_key):
             return obj, False
@@ -110,17 +99,17 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str =
     with cf.ThreadPoolExecutor(max_workers=os.cpu_count() or 8) as ex:
         res = list(ex.map(one, SOURCES))
     objs = [o for o, _ in res]
-    if not any(built for _, built in res) and os.path.exists(out) and os.path.getmtime(out) >= _newest(objs):
-        os.utime(out)          # nothing to do (e.g. only a comment of this file changed): restore the fast path
-        return out
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out + ".tmp", *objs]
+    if not any(built for _, built in res) and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(objs):
+        os.utime(LIB)          # nothing to do (e.g. only a comment of this file changed): restore the fast path
+        return LIB
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB + ".tmp", *objs]
     if verbose:
         print(" ".join(cmd), flush=True)
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
-    os.replace(out + ".tmp", out)
-    return out
+    os.replace(LIB + ".tmp", LIB)
+    return LIB
 
 
 def kernel_resources(obj_dir: str = OBJ):
@@ -153,14 +142,4 @@ def kernel_resources(obj_dir: str = OBJ):
 
 
 if __name__ == "__main__":
-    # python -m nerf_few_shot_limitations_amd.build [--force] [--variant NAME [--fused-only | --only train_v1,...] -DNRF_PREFETCH=6 ...]
-    argv = sys.argv[1:]
-    if "--variant" in argv:
-        name = argv[argv.index("--variant") + 1]
-        flags = [a for a in argv if a.startswith("-D")]
-        only = set(argv[argv.index("--only") + 1].split(",")) if "--only" in argv else None
-        path = build(force=True, verbose=False, extra_flags=flags, out=os.path.join(PKG, f"libnerfhip_{name}.so"),
-                     obj_dir=os.path.join(PKG, "build", name), fused_only="--fused-only" in argv, only=only)
-    else:
-        path = build(force="--force" in argv, verbose=True)
-    print(path)
+    print(build(force="--force" in sys.argv[1:], verbose=True))

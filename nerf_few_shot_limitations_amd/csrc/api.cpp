@@ -464,39 +464,24 @@ int nrf_model_update_device(nrf_model* m, const float* flat_params, int mode_mas
     int rc = ensure_sources(m);
     if (rc != NRF_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((mode_mask & (mode_mask - 1)) == 0) {
-        // the per-step case: one mode -> forward stream, backward stream (once training is set up; the split mode has none)
-        // and bias table in one launch
-        int mode = 0;
-        while (!(mode_mask & (1 << mode))) ++mode;
-        const int kind = nrf::stream_kind(mode);
-        const bool bwd = m->train_ready && mode < 3;
-        const int32_t* src[3] = {m->d_src[0][kind], bwd ? m->d_src[1][kind] : nullptr, m->d_bias_src};
-        const int64_t n[3] = {m->n_src[0][kind], bwd ? m->n_src[1][kind] : 0, m->plan.n_bias};
-        const int modes[3] = {mode, mode, NRF_MMA_F32};
-        void* out[3] = {m->d_stream[mode], bwd ? m->d_bstream[mode] : nullptr, m->d_bias};
-        rc = nrf::launch_repack3(flat_params, src, n, modes, out, s);
-        if (rc != NRF_OK) return fail(rc, "repack launch failed");
-        m->lin_stale = true;
-        for (int k = 0; k < 3; ++k) m->bfresh[k] = (k == mode) && m->train_ready;
-        return NRF_OK;
-    }
+    // one launch per mode in the mask: its forward stream, its backward stream (once training is set up; the split mode has none)
+    // and, with the first mode, the bias table
+    bool bias = true;
     for (int mode = 0; mode < nrf::kModes; ++mode) {
         if (!(mode_mask & (1 << mode))) continue;
         const int kind = nrf::stream_kind(mode);
-        rc = nrf::launch_repack(flat_params, m->d_src[0][kind], m->n_src[0][kind], mode, m->d_stream[mode], s);
+        const bool bwd = m->train_ready && mode < 3;
+        const int32_t* src[3] = {m->d_src[0][kind], bwd ? m->d_src[1][kind] : nullptr, bias ? m->d_bias_src : nullptr};
+        const int64_t n[3] = {m->n_src[0][kind], bwd ? m->n_src[1][kind] : 0, bias ? m->plan.n_bias : 0};
+        const int modes[3] = {mode, mode, NRF_MMA_F32};
+        void* out[3] = {m->d_stream[mode], bwd ? m->d_bstream[mode] : nullptr, bias ? m->d_bias : nullptr};
+        rc = nrf::launch_repack3(flat_params, src, n, modes, out, s);
         if (rc != NRF_OK) return fail(rc, "repack launch failed");
-        if (m->train_ready && mode < 3) {
-            rc = nrf::launch_repack(flat_params, m->d_src[1][kind], m->n_src[1][kind], mode, m->d_bstream[mode], s);
-            if (rc != NRF_OK) return fail(rc, "repack launch failed");
-            m->bfresh[mode] = true;
-        }
+        bias = false;
     }
     m->lin_stale = true;
-    for (int mode = 0; mode < 3; ++mode)
-        if (!(mode_mask & (1 << mode))) m->bfresh[mode] = false;
-    rc = nrf::launch_repack(flat_params, m->d_bias_src, m->plan.n_bias, NRF_MMA_F32, m->d_bias, s);
-    return rc == NRF_OK ? NRF_OK : fail(rc, "repack launch failed");
+    for (int k = 0; k < 3; ++k) m->bfresh[k] = (mode_mask & (1 << k)) && m->train_ready;
+    return NRF_OK;
 }
 
 int64_t nrf_train_context_bytes(nrf_model* m, int mma_mode, int64_t n) {

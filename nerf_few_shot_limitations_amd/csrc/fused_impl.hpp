@@ -29,7 +29,6 @@ struct NetArgs {
     uint32_t n_chunks;
     int n_bias;
     int n_layers;
-    uint32_t ablate;
 };
 
 struct RenderKArgs {
@@ -129,18 +128,8 @@ __global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P)
     load_bias_table(bias, P.net.bias, P.net.n_bias);      // ends with __syncthreads()
 
     Pipe<WAVES, pinned_walk<Mode, NT>()> pipe;
-    pipe.init(P.net.stream, P.net.n_chunks, lds, P.net.ablate);
+    pipe.init(P.net.stream, P.net.n_chunks, lds);
     pipe.start();
-#ifdef NRF_ABLATE_BUILD
-    // timing experiment (pair with 2 = no barriers, which would re-align the waves): wave w starts w x 16 (512) or w x 64 (1024)
-    // cycles late, so that the four waves no longer reach each LDS-DMA instruction in the same cycle
-    if (P.net.ablate & (512 | 1024)) {
-        const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        for (int i = 0; i < w; ++i) {
-            if (P.net.ablate & 512) asm volatile("s_nop 15"); else __builtin_amdgcn_s_sleep(1);
-        }
-    }
-#endif
 
     auto z_base = [&](int s) -> float { return zl[s]; };
     // Samples per ray and MLP pass (host: pick_spw_log2).  The wave's COLS sample columns are RPW = COLS/SPW rays x SPW consecutive
@@ -224,28 +213,6 @@ __global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P)
             DinoHeld<Mode, Net::kDino ? Net::KT0 - KT0 : 1> held[NT];
             auto inputs = [&](const float (&w0)[NT], const float (&w1)[NT], Act (&x)[Net::KT0][NT], auto pass_) {
                 constexpr int PASS = decltype(pass_)::value;
-#ifdef NRF_ABLATE_BUILD
-                if (P.net.ablate & 16) {      // timing experiment: no encoder (and no compositor below)
-                    // hashed bit patterns in bf16 [0.008, 2): realistic toggling (all-zero operands let the clock rise) at ~1/6 of the encoder's VALU work
-#pragma unroll
-                    for (int n = 0; n < NT; ++n)
-#pragma unroll
-                        for (int t = 0; t < Net::KT0; ++t) {
-                            i32x4 w0v, w1v;
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-                                const unsigned hsh = (unsigned)(tid_now * 2654435761u) + (unsigned)(p * 40503 + (8 * t + q + 4 * n) * 7919);
-                                w0v[q] = (int)(((hsh * 2246822519u) & 0x3FFF3FFFu) | 0x3C003C00u) ^ ((hsh & 1u) << 31);
-                                w1v[q] = (int)(((hsh * 3266489917u) & 0x3FFF3FFFu) | 0x3C003C00u) ^ ((hsh & 2u) << 14);
-                            }
-                            Act e = {};
-                            __builtin_memcpy(&e, &w0v, 16);
-                            __builtin_memcpy((char*)&e + 16, &w1v, 16);
-                            x[t][n] = e;
-                        }
-                    return;
-                }
-#endif
 #pragma unroll
                 for (int n = 0; n < NT; ++n) {
                     // depth of this column's sample (columns past the last sample repeat it; their outputs are not used)
@@ -264,46 +231,17 @@ __global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P)
                     // V3, first pass: start the feature-map gather of this column BEFORE its positional encoding, blend behind it
                     DinoTaps tp;
                     DinoRaw<Net::kDino ? Net::KT0 - KT0 : 1> raw;
-                    bool split_gather = false;
                     if constexpr (Net::kDino && PASS == 0) {
-#ifdef NRF_ABLATE_BUILD
-                        if (!(P.net.ablate & (32 | 256)))
-#endif
-                        {
-                            tp = dino_taps(a.dino, pt);
-                            raw.issue(a.dino.features, tp, h);
-                            split_gather = true;
-                        }
+                        tp = dino_taps(a.dino, pt);
+                        raw.issue(a.dino.features, tp, h);
                     }
                     Act e1[KT0];
-#ifdef NRF_ABLATE_BUILD
-                    // timing experiments on V3 (results are wrong): 64 = the second fusion pass reuses un-gated first-layer tiles of the
-                    // sample position instead of re-encoding; 32 = no feature-map gather (a constant map, no global loads)
-                    if (PASS == 1 && (P.net.ablate & 64)) {
-                        Act c1[pe_tiles(1)];
-                        encode3<Mode, 1>(pt, h, c1, w0[n]);
-#pragma unroll
-                        for (int t = 0; t < KT0; ++t) e1[t] = c1[0];
-                    } else
-#endif
                     encode3<Mode, LP>(pt, h, e1, w0[n]);
 #pragma unroll
                     for (int t = 0; t < KT0; ++t) x[t][n] = e1[t];
                     if constexpr (Net::kDino) {
                         constexpr int DT = Net::KT0 - KT0;
-#ifdef NRF_ABLATE_BUILD
-                        if (PASS == 0 && (P.net.ablate & 32)) {
-                            DinoTaps tp;
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) { tp.off[k] = 0; tp.w[k] = 0.25f; }
-                            if (P.net.ablate & 128) held[n].gather(a.dino.features, tp, h);      // 128: keep the loads, one L2-hot address
-                            else { tp.off[0] = tp.off[1] = tp.off[2] = tp.off[3] = -1; held[n].gather(a.dino.features, tp, h); }
-                        } else
-#endif
-                        if constexpr (PASS == 0) {
-                            if (split_gather) held[n].finish(raw, tp);
-                            else held[n].gather(a.dino.features, dino_taps(a.dino, pt), h);      // (ablation 256: the round-2 order)
-                        }
+                        if constexpr (PASS == 0) held[n].finish(raw, tp);
                         Act dt[DT];
                         held[n].template tiles<PASS>(w1[n], dt);
 #pragma unroll
@@ -331,25 +269,20 @@ __global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P)
             const float norm = ST(F_NORM);
             if (SPW == 1) {
                 const int s = p;
-#ifdef NRF_ABLATE_BUILD
-                if (P.net.ablate & 16) { comp.r += out4[0][0] + out4[NT - 1][3]; } else
-#endif
-                {
-                    const bool last = (s + 1 == S);
-                    float v[4];
-                    // NT == 2: lane L owns column L = tile h, column c -- and holds that tile's head rows itself
+                const bool last = (s + 1 == S);
+                float v[4];
+                // NT == 2: lane L owns column L = tile h, column c -- and holds that tile's head rows itself
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = NT == 2 ? pick_reg(out4[0][k], out4[NT - 1][k], h != 0) : out4[0][k];
-                    const float zn = last ? 0.0f : z_ray(rid, s + 1);
-                    const float dist = last ? __fmul_rn(1e10f, norm) : __fmul_rn(__fsub_rn(zn, zo), norm);
-                    const float w = comp.template add<Mode::FAST_EXP>(v[3], sigmoid_sel<Mode::FAST_EXP>(v[0]), sigmoid_sel<Mode::FAST_EXP>(v[1]),
-                                                                      sigmoid_sel<Mode::FAST_EXP>(v[2]), zo, dist);
-                    if (own_valid) {
-                        if (a.weights) a.weights[rid * S + s] = w;
-                        if (a.z_vals) a.z_vals[rid * S + s] = zo;
-                    }
-                    zo = zn;
+                for (int k = 0; k < 4; ++k) v[k] = NT == 2 ? pick_reg(out4[0][k], out4[NT - 1][k], h != 0) : out4[0][k];
+                const float zn = last ? 0.0f : z_ray(rid, s + 1);
+                const float dist = last ? __fmul_rn(1e10f, norm) : __fmul_rn(__fsub_rn(zn, zo), norm);
+                const float w = comp.template add<Mode::FAST_EXP>(v[3], sigmoid_sel<Mode::FAST_EXP>(v[0]), sigmoid_sel<Mode::FAST_EXP>(v[1]),
+                                                                  sigmoid_sel<Mode::FAST_EXP>(v[2]), zo, dist);
+                if (own_valid) {
+                    if (a.weights) a.weights[rid * S + s] = w;
+                    if (a.z_vals) a.z_vals[rid * S + s] = zo;
                 }
+                zo = zn;
             } else {
                 // SPW > 1.  Column phase, every lane in parallel: lane q holds the head rows of column q (NT == 2: tile q div 32; NT == 1:
                 // both lane halves hold column c) and its state rows mirror that column's ray -- it turns its sample's network outputs
@@ -463,7 +396,7 @@ __global__ void __launch_bounds__(WAVES * 64) render_queue_kernel(const RenderKA
     load_bias_table(bias, P.net.bias, P.net.n_bias);      // ends with __syncthreads()
 
     Pipe<WAVES, pinned_walk<Mode, NT>()> pipe;     // a wave that has run dry keeps computing (on stale inputs, storing nothing): the workgroup moves in lockstep anyway, and the skip paths cost registers in every layer
-    pipe.init(P.net.stream, P.net.n_chunks, lds, P.net.ablate);
+    pipe.init(P.net.stream, P.net.n_chunks, lds);
     pipe.start();
 
     auto z_base = [&](int s) -> float { return zl[s]; };
@@ -670,7 +603,7 @@ __global__ void __launch_bounds__(WAVES * 64) forward_kernel(const ForwardKArgs 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     load_bias_table(bias, P.net.bias, P.net.n_bias);
     Pipe<WAVES, pinned_walk<Mode, NT>()> pipe;
-    pipe.init(P.net.stream, P.net.n_chunks, lds, P.net.ablate);
+    pipe.init(P.net.stream, P.net.n_chunks, lds);
     pipe.start();
     const int own = (NT == 2) ? h : 0;
     const bool owner = h < NT;
@@ -777,9 +710,24 @@ int prepare(K kernel, int device, unsigned char (&done)[64], std::string& err, i
 NetArgs net_args(const DeviceNet& net, int mode) {
     NetArgs n;
     n.stream = net.stream[mode]; n.bias = net.bias; n.n_chunks = net.n_chunks[mode]; n.n_bias = net.n_bias; n.n_layers = net.arch.n_layers;
-    static const uint32_t ablate = [] { const char* e = getenv("NRF_ABLATE"); return e ? (uint32_t)atoi(e) : 0u; }();
-    n.ablate = ablate;   // timing experiments only: results are wrong when set
     return n;
+}
+
+// The persistent-grid launch of the renderer, the staged forward and the training chain kernels: k (with the weight stream
+// `na`) walks n_tiles work items on min(n_tiles, CUs) workgroups of WAVES waves.  A template per kernel, so that each kernel
+// keeps its own once-per-device attribute cache (prepare).
+template <auto kernel, int WAVES, int LDS = kLdsBytes, class KArgs>
+int launch_persistent(const DeviceNet& net, const NetArgs& na, KArgs k, int64_t n_tiles, hipStream_t s, const char* what, std::string& err) {
+    static unsigned char done[64] = {};
+    const int prepared = prepare(kernel, net.device, done, err, LDS);
+    if (prepared != NRF_OK) return prepared;
+    k.net = na;
+    k.n_tiles = n_tiles;
+    const int64_t grid = n_tiles < net.cu_count ? n_tiles : net.cu_count;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(WAVES * 64), LDS, s, k);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { err = std::string(what) + " launch: " + hipGetErrorString(e); return NRF_EHIP; }
+    return NRF_OK;
 }
 
 // Samples per ray and pass (log2; render_kernel): the work items of a launch are tiles of WAVES * COLS/SPW rays marched in
@@ -809,21 +757,12 @@ inline int pick_spw_log2(int64_t n_rays, int S, int waves, int cols_per_wave, in
 
 template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
 int run_render_v(const DeviceNet& net, int mode, const RenderArgs& a, hipStream_t s, std::string& err) {
-    auto kernel = render_kernel<Net, Mode, NT, WAVES, LP, LD>;
-    static unsigned char done[64] = {};
-    const int prepared = prepare(kernel, net.device, done, err, kLdsBytesQueue);
-    if (prepared != NRF_OK) return prepared;
     RenderKArgs k;
-    k.net = net_args(net, mode);
     k.a = a;
     k.a.spw_log2 = pick_spw_log2(a.n_rays, a.n_samples, WAVES, 32 * NT, net.cu_count);
     const int64_t tile = (int64_t)WAVES * ((32 * NT) >> k.a.spw_log2);
-    k.n_tiles = (a.n_rays + tile - 1) / tile;
-    const int64_t grid = k.n_tiles < net.cu_count ? k.n_tiles : net.cu_count;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(WAVES * 64), kLdsBytesQueue, s, k);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { err = std::string("render launch: ") + hipGetErrorString(e); return NRF_EHIP; }
-    return NRF_OK;
+    return launch_persistent<render_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, (a.n_rays + tile - 1) / tile,
+                                                                                                 s, "render", err);
 }
 
 template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
@@ -860,19 +799,9 @@ int run_render(const DeviceNet& net, int mode, const RenderArgs& a, hipStream_t 
 }
 
 template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
-int run_forward(const DeviceNet& net, int mode, ForwardKArgs k, hipStream_t s, std::string& err) {
-    auto kernel = forward_kernel<Net, Mode, NT, WAVES, LP, LD>;
-    static unsigned char done[64] = {};
-    const int prepared = prepare(kernel, net.device, done, err);
-    if (prepared != NRF_OK) return prepared;
-    k.net = net_args(net, mode);
+int run_forward(const DeviceNet& net, int mode, const ForwardKArgs& k, hipStream_t s, std::string& err) {
     constexpr int TILE = WAVES * 32 * NT;
-    k.n_tiles = (k.n + TILE - 1) / TILE;
-    const int64_t grid = k.n_tiles < net.cu_count ? k.n_tiles : net.cu_count;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(WAVES * 64), kLdsBytes, s, k);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { err = std::string("forward launch: ") + hipGetErrorString(e); return NRF_EHIP; }
-    return NRF_OK;
+    return launch_persistent<forward_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES>(net, net_args(net, mode), k, (k.n + TILE - 1) / TILE, s, "forward", err);
 }
 
 bool check_net(const DeviceNet& net, int mode, std::string& err) {
@@ -893,37 +822,27 @@ bool check_net(const DeviceNet& net, int mode, std::string& err) {
 //     layers), +2.7 % (AGPR operands), +0.8 % (spread LDS-DMA issue); V3 +3 % (its per-pass feature-map gather -- global loads,
 //     twice per pass -- is latency one wave per SIMD cannot cover: profiles/r02_ab_v3_geometry.txt).
 //   * fp32 and split-f16: 4 waves x 32 columns (their activations take 16 registers per tile).
-// The images are bit-identical across geometries (tools/image_hash.py): a column's arithmetic does not depend on where it sits.
+// The images are bit-identical across geometries: a column's arithmetic does not depend on where it sits.
 // Each family's translation unit is compiled twice (build.py): NRF_TU_HALF == 16 holds the two 16-bit modes (VGPR-form MFMAs,
 // operand images parked in AGPRs), NRF_TU_HALF == 32 the fp32-class modes; fused_kernels.hip routes by mode.
 #if !defined(NRF_TU_HALF)
 // (fused_kernels.hip: routing only, no kernels)
 #elif NRF_TU_HALF == 16
 #define NRF_TU_NAME(f) f##_16
-#define NRF_DISPATCH_MODE(FN, NET, LP, ...)                                                                 \
-    switch (mode) {                                                                                         \
-        case NRF_MMA_BF16: return FN<NET<ModeBF16, 2, LP>, ModeBF16, 2, 4, LP, 4>(__VA_ARGS__);             \
-        default:           return FN<NET<ModeF16, 2, LP>, ModeF16, 2, 4, LP, 4>(__VA_ARGS__);               \
-    }
-// V2 / V3 (NT16, WAVES16: the 16-bit modes' geometry)
-#define NRF_DISPATCH_MODE1(FN, NETT, LP, NT16, WAVES16, ...)                                                \
-    switch (mode) {                                                                                         \
-        case NRF_MMA_BF16: return FN<NETT(ModeBF16, NT16), ModeBF16, NT16, WAVES16, LP, 4>(__VA_ARGS__);    \
-        default:           return FN<NETT(ModeF16, NT16), ModeF16, NT16, WAVES16, LP, 4>(__VA_ARGS__);      \
+#define NRF_DISPATCH_MODE(FN, NETT, LP, ...)                                                         \
+    switch (mode) {                                                                                   \
+        case NRF_MMA_BF16: return FN<NETT(ModeBF16, 2), ModeBF16, 2, 4, LP, 4>(__VA_ARGS__);          \
+        default:           return FN<NETT(ModeF16, 2), ModeF16, 2, 4, LP, 4>(__VA_ARGS__);            \
     }
 #else
 #define NRF_TU_NAME(f) f##_32
-#define NRF_DISPATCH_MODE(FN, NET, LP, ...)                                                                 \
-    switch (mode) {                                                                                         \
-        case NRF_MMA_F16X3: return FN<NET<ModeF16X3, 1, LP>, ModeF16X3, 1, 4, LP, 4>(__VA_ARGS__);         \
-        default:            return FN<NET<ModeF32, 1, LP>, ModeF32, 1, 4, LP, 4>(__VA_ARGS__);              \
-    }
-#define NRF_DISPATCH_MODE1(FN, NETT, LP, NT16, WAVES16, ...)                                                \
-    switch (mode) {                                                                                         \
-        case NRF_MMA_F16X3: return FN<NETT(ModeF16X3, 1), ModeF16X3, 1, 4, LP, 4>(__VA_ARGS__);           \
-        default:            return FN<NETT(ModeF32, 1), ModeF32, 1, 4, LP, 4>(__VA_ARGS__);                 \
+#define NRF_DISPATCH_MODE(FN, NETT, LP, ...)                                                         \
+    switch (mode) {                                                                                   \
+        case NRF_MMA_F16X3: return FN<NETT(ModeF16X3, 1), ModeF16X3, 1, 4, LP, 4>(__VA_ARGS__);       \
+        default:            return FN<NETT(ModeF32, 1), ModeF32, 1, 4, LP, 4>(__VA_ARGS__);           \
     }
 #endif
+#define NRF_NET_V1_10(M, NT) NetV1<M, NT, 10>
 #define NRF_NET_V2_10(M, NT) NetV2<M, NT, 10>
 #define NRF_NET_V3_12_64(M, NT) NetV3<M, NT, 12, 2>
 #define NRF_NET_V3_12_128(M, NT) NetV3<M, NT, 12, 4>

@@ -74,7 +74,7 @@ int launch_forward_v1(const DeviceNet& net, int mma_mode, const float* x_enc, in
 int launch_forward(const DeviceNet& net, int mma_mode, const float* pos, const float* dir, const float* dino, int64_t n,
                    float* rgb, float* density, hipStream_t s, std::string& err);
 
-// ---- training path (train_v1.hip) -------------------------------------------------
+// ---- training path (train_shared.hip, train_v1.hip ... train_v3.hip) ----------------
 constexpr int kMaxSlots = 40;
 constexpr int kMaxJobs = 24;
 constexpr int kMaxMaskSlots = 20;
@@ -108,7 +108,6 @@ int launch_train_forward_v3(const DeviceNet& net, const TrainDev& t, int mma_mod
                             float* rgb, float* density, void* ctx, hipStream_t s, std::string& err);
 int launch_train_backward_v3(const DeviceNet& net, const TrainDev& t, int mma_mode, const float* rgb, const float* density,
                              const float* g_rgb, const float* g_density, int64_t n, void* ctx, float* grad, hipStream_t s, std::string& err);
-int launch_repack(const float* flat, const int32_t* src, int64_t n_elems, int mma_mode, void* out, hipStream_t s);
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd, int step,
                 const float* ray_loss, int64_t n_rays, float loss_weight, float* loss, hipStream_t s);
 int launch_mse_grad(const float* pred, const float* target, int64_t n, float weight, float* g_pred, float* loss, hipStream_t s);

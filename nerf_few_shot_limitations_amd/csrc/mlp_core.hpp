@@ -57,9 +57,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #define NRF_GLB __attribute__((address_space(1)))
 
 constexpr int kFragBytes = 1024;                     // 64 lanes x 16 B
-constexpr int kChunkFrags = NRF_CHUNK_FRAGS;
-constexpr int kChunkBytes = kFragBytes * kChunkFrags;  // 16 KiB
-constexpr int kSlots = NRF_SLOTS;                      // ring depth (128 KiB)
+constexpr int kChunkBytes = kFragBytes * kChunkFrags;  // 16 KiB (kChunkFrags, kSlots: stream_config.hpp)
 
 // An epilogue slice of the pinned walk ends in an empty, opaque asm on the words it produced (see ModeF16X3::to_act_pair).
 #define NRF_PIN_ACT1(a) asm volatile("" : "+v"(a))
@@ -108,11 +106,9 @@ struct Pipe {
     uint32_t read_slot;
     uint32_t wave_off;         // wave * kFragsPerWave KiB (wave-uniform)
     uint32_t lane_off;         // lane * 16
-    uint32_t ablate;           // timing experiments only (builds with -DNRF_ABLATE_BUILD, env NRF_ABLATE): 1 = stop streaming after the first fill, 2 = no barriers
     uint32_t skip;             // wave-uniform flag of the ray-queue kernel: this wave has run dry (it keeps computing, stores nothing)
 
-    __device__ __forceinline__ void init(const void* stream, uint32_t chunks, NRF_LDS char* ring_base, uint32_t ablate_flags = 0) {
-        ablate = ablate_flags;
+    __device__ __forceinline__ void init(const void* stream, uint32_t chunks, NRF_LDS char* ring_base) {
         skip = 0;
         const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         lane_off = (threadIdx.x & 63) * 16;
@@ -161,15 +157,9 @@ struct Pipe {
     // make the next chunk of the stream readable through base[parity]
     __device__ __forceinline__ void acquire(int parity) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kFragsPerWave * (kAhead - 1)) : "memory");
-#ifdef NRF_ABLATE_BUILD
-        if (!(ablate & 2)) __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(ablate & 1)) issue_one();
-#else
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         issue_one();
-#endif
         base[parity] = ring + read_slot * kChunkBytes + lane_off;
         read_slot = (read_slot + 1 == (uint32_t)kSlots) ? 0u : read_slot + 1;
     }
@@ -184,9 +174,6 @@ struct Pipe {
     uint32_t dma_m0;
     __device__ __forceinline__ void acquire_begin(int parity) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kFragsPerWave * (kAhead - 1)) : "memory");
-#ifdef NRF_ABLATE_BUILD
-        if (!(ablate & 2))
-#endif
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         dma_g = src + (size_t)issue_chunk * kChunkBytes;
@@ -200,9 +187,6 @@ struct Pipe {
     template <int K>
     __device__ __forceinline__ void issue_part() {
         static_assert(ASM_DMA && K < kFragsPerWave, "issue_part: the pinned walk's pipe");
-#ifdef NRF_ABLATE_BUILD
-        if ((ablate & 1) || ((ablate & 4) && K >= 1) || ((ablate & 8) && K >= 2)) return;      // 4 / 8: a quarter / half of the DMA instructions (vmcnt no longer counts right: pair with 2)
-#endif
         asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off offset:%2"
                      : : "v"(dma_g), "s"(dma_m0), "n"(K * kFragBytes) : "memory", "m0");
     }
@@ -393,14 +377,8 @@ constexpr __host__ __device__ int chunks_for_frags(int frags) { return (frags + 
 template <class Mode, int NT>
 constexpr __host__ __device__ bool pinned_walk() { return Mode::kPinned || NT > 1; }
 
-#ifndef NRF_PREFETCH
-#define NRF_PREFETCH 3
-#endif
-#ifndef NRF_EPILOGUE_AT
-#define NRF_EPILOGUE_AT 3
-#endif
-constexpr int kPrefetch = NRF_PREFETCH;
-constexpr int kEpilogueAt = NRF_EPILOGUE_AT;   // the epilogue of tile m-1 runs after this many fragments of tile m have been issued
+constexpr int kPrefetch = 3;
+constexpr int kEpilogueAt = 3;   // the epilogue of tile m-1 runs after this many fragments of tile m have been issued
 
 template <class Mode, int KT, int MT, int NT, class P, class Fin>
 __device__ __forceinline__ void dense(P& pipe, const NRF_LDS float* bias, int h,

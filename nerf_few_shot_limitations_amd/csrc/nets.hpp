@@ -343,31 +343,9 @@ __device__ __forceinline__ DinoTaps dino_taps(const DinoT& d, const float p[3]) 
     return t;
 }
 
-// the fetched channels of lane half h, blended in fp32: e[16 t + 4 g + q] = channel 32t + 8g + 4h + q
-template <int DT>
-__device__ __forceinline__ void dino_blend(const float* __restrict__ feat, const DinoTaps& tp, int h, float (&e)[16 * DT]) {
-#pragma unroll
-    for (int t = 0; t < DT; ++t) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int ch = 32 * t + 8 * g + 4 * h;
-            f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (tp.off[k] >= 0) {
-                    const f32x4 v = *(const f32x4*)(feat + tp.off[k] + ch);
-                    acc += v * tp.w[k];
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) e[16 * t + 4 * g + q] = acc[q];
-        }
-    }
-}
-
-// The same gather in two steps, so that the caller can put work between them: issue() starts all 16 DT tap loads of a lane half
-// unconditionally (a tap outside the map reads the map's first texel with weight 0: 0 * v adds exactly nothing, as zeros padding does),
-// finish() blends them in the order of dino_blend (bit-identical result).  The loads are L2 hits whose latency a lone wave per SIMD
+// The feature-map gather in two steps, so that the caller can put work between them: issue() starts all 16 DT tap loads of a lane
+// half unconditionally (a tap outside the map reads the map's first texel with weight 0: 0 * v adds exactly nothing, as zeros
+// padding does), finish() blends them in fp32, in tap order: e[16 t + 4 g + q] = channel 32t + 8g + 4h + q.  The loads are L2 hits whose latency a lone wave per SIMD
 // cannot cover by itself: with the positional encoding of the same column (~600 VALU instructions) between the two calls it is
 // (ablation: the gather cost 3.7 % of a V3 frame, the same with every load on one hot address).
 template <int DT>
@@ -418,17 +396,9 @@ __device__ __forceinline__ void dino_scaled_tiles(const float (&e)[16 * DT], flo
 //     choosing (profiles/r03_ab_v3_hold.txt): at dino_dim 64 the two holds run at the same speed (57.0 ms either way) once the
 //     other spill sources are gone, f16 loses 0.2 dB of its 87 dB against the oracle -- and bf16 loses 24 dB (70.8 -> 46.7 dB, max
 //     rgb error 0.009 -> 0.85: a second 2^-8 rounding in front of the softmax gate), so bf16 never holds packed.
-#ifndef NRF_DINO_HOLD_F32
-#define NRF_DINO_HOLD_F32 0      // 1 (A/B builds): every mode holds fp32 channels
-#endif
-#ifndef NRF_DINO_HOLD_PACKED
-#define NRF_DINO_HOLD_PACKED 0   // 1 (A/B builds): both 16-bit modes hold packed tiles at every width (the first round-3 build)
-#endif
-template <class Mode, int DT, bool PACKED = (sizeof(typename Mode::Act) == 32 && !NRF_DINO_HOLD_F32 &&
-                                              (NRF_DINO_HOLD_PACKED || (std::is_same<Mode, ModeF16>::value && DT > 2)))>
+template <class Mode, int DT, bool PACKED = (sizeof(typename Mode::Act) == 32 && std::is_same<Mode, ModeF16>::value && DT > 2)>
 struct DinoHeld {
     float e[16 * DT];
-    __device__ __forceinline__ void gather(const float* __restrict__ feat, const DinoTaps& tp, int h) { dino_blend<DT>(feat, tp, h, e); }
     __device__ __forceinline__ void finish(const DinoRaw<DT>& raw, const DinoTaps& tp) { raw.finish(tp, e); }
     template <int PASS>
     __device__ __forceinline__ void tiles(float scale, typename Mode::Act (&out)[DT]) const { dino_scaled_tiles<Mode, DT>(e, scale, out); }
@@ -437,11 +407,6 @@ struct DinoHeld {
 template <class Mode, int DT>
 struct DinoHeld<Mode, DT, true> {
     typename Mode::Act t[DT];
-    __device__ __forceinline__ void gather(const float* __restrict__ feat, const DinoTaps& tp, int h) {
-        float e[16 * DT];
-        dino_blend<DT>(feat, tp, h, e);
-        dino_scaled_tiles<Mode, DT>(e, 1.0f, t);
-    }
     __device__ __forceinline__ void finish(const DinoRaw<DT>& raw, const DinoTaps& tp) {
         float e[16 * DT];
         raw.finish(tp, e);
@@ -467,13 +432,5 @@ struct DinoHeld<Mode, DT, true> {
         }
     }
 };
-
-template <class Mode, int DT>
-__device__ __forceinline__ void dino_tiles(const float* __restrict__ feat, const DinoTaps& tp, int h, float scale,
-                                           typename Mode::Act (&out)[DT]) {
-    float e[16 * DT];
-    dino_blend<DT>(feat, tp, h, e);
-    dino_scaled_tiles<Mode, DT>(e, scale, out);
-}
 
 }  // namespace nrf

@@ -10,7 +10,7 @@
 namespace nrf {
 
 namespace {
-constexpr int kFragBytes = 1024, kChunkFrags = NRF_CHUNK_FRAGS;
+constexpr int kFragBytes = 1024;
 
 uint32_t f32_bits(float x) { uint32_t u; std::memcpy(&u, &x, 4); return u; }
 }  // namespace

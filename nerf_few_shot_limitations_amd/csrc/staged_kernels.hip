@@ -264,7 +264,7 @@ __global__ void __launch_bounds__(kBlock) composite_backward_kernel(const float*
 // its gradient, compositor backward (train.py:236,36-44,285) -- as ONE: the loss gradient of a ray needs nothing but the ray's own
 // prediction and target, d loss / d pred = 2 w (pred - target) / (3 R).  Same per-ray arithmetic as the three kernels (the two bodies
 // above), so d_rgb / d_sigma are bit-equal to the staged sequence.  The loss VALUE needs all rays: every ray leaves its squared error
-// in `ray_loss` and a later launch adds them up in a fixed order (adam_kernel's side job, train_v1.hip) -- a device-wide
+// in `ray_loss` and a later launch adds them up in a fixed order (adam_kernel's side job, train_shared.hip) -- a device-wide
 // "last workgroup sums" inside this kernel costs a release fence (an L2 write-back on this chip) per workgroup: measured 53 us
 // against 16 us for the three separate launches.  Side job: `zero_buf` (the caller's flat gradient vector, which the
 // weight-gradient reduction adds into) is cleared by the same launch.

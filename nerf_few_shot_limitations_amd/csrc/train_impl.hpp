@@ -43,7 +43,7 @@ struct TrainKArgs {
     int64_t partial_off;               // weight-gradient partial sums: one kPartialFloats block per workgroup
 };
 
-// ---- host-side helpers shared by train_v1.hip / train_v2.hip -------------------------------------------------
+// ---- host-side helpers shared by the training translation units ---------------------------------------------
 constexpr int kWgSamples = 256;          // the context is laid out for whole 256-sample groups, whatever the geometry
 
 inline int64_t tiles32(int64_t n) { return (n + kWgSamples - 1) / kWgSamples * (kWgSamples / 32); }
@@ -100,12 +100,37 @@ inline bool fill_slots(const TrainDev& t, int mode, int64_t n, TrainKArgs& k, st
 // Geometry of the chain kernels: 8 waves x 32 samples per workgroup (two waves per SIMD) is the throughput shape; a batch
 // that does not even give every CU one such workgroup runs 4 waves x 32 instead (twice the workgroups, one wave per SIMD:
 // the pass of a lone wave is latency, not throughput, and the reference's last schedule stage is 512 rays x 64 samples).
-inline bool small_batch(const DeviceNet& net, int64_t n) {
-    static const int forced = [] { const char* e = getenv("NRF_TRAIN_WAVES"); return e ? atoi(e) : 0; }();      // A/B runs: 4 or 8
-    if (forced == 4) return true;
-    if (forced == 8) return false;
-    return tiles32(n) / 4 <= net.cu_count;
+inline bool small_batch(const DeviceNet& net, int64_t n) { return tiles32(n) / 4 <= net.cu_count; }
+
+namespace {
+
+// f(ChainGeo<Mode, WAVES>{}): the chain kernels' instantiation for `mode` and n samples -- the 16-bit modes at 4 or 8 waves
+// (small_batch), the fp32 mode at 4
+template <class M, int W>
+struct ChainGeo {
+    typedef M Mode;
+    static constexpr int kWaves = W;
+};
+
+template <class F>
+int dispatch_chain(const DeviceNet& net, int mode, int64_t n, F&& f) {
+    const bool small = small_batch(net, n);
+    switch (mode) {
+        case NRF_MMA_BF16: return small ? f(ChainGeo<ModeBF16, 4>{}) : f(ChainGeo<ModeBF16, 8>{});
+        case NRF_MMA_F16:  return small ? f(ChainGeo<ModeF16, 4>{}) : f(ChainGeo<ModeF16, 8>{});
+        default:           return f(ChainGeo<ModeF32, 4>{});
+    }
 }
+
+// the backward chains stream the transposed weights
+NetArgs backward_net_args(const DeviceNet& net, const TrainDev& t, int mode) {
+    NetArgs n = net_args(net, mode);
+    n.stream = t.bstream[mode];
+    n.n_chunks = t.n_bchunks[mode];
+    return n;
+}
+
+}  // namespace
 
 inline bool check_train_common(const DeviceNet& net, const TrainDev& t, int mode, std::string& err) {
     if (mode < 0 || mode > 2) { err = "unknown mma_mode"; return false; }
@@ -115,7 +140,7 @@ inline bool check_train_common(const DeviceNet& net, const TrainDev& t, int mode
     return true;
 }
 
-// dW/db of every Linear from the saved tensors (defined in train_v1.hip; network independent)
+// dW/db of every Linear from the saved tensors (defined in train_shared.hip; network independent)
 int launch_weight_grad(const DeviceNet& net, const TrainDev& t, int mode, const TrainKArgs& k, float* grad, hipStream_t s, std::string& err);
 
 __device__ __forceinline__ i32x4* mask_ptr(const TrainKArgs& P, int mslot, int64_t st, int lane) {
@@ -143,7 +168,7 @@ __global__ void __launch_bounds__(WAVES * 64) train_forward_kernel(const TrainKA
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     load_bias_table(bias, P.net.bias, P.net.n_bias);
     Pipe<WAVES> pipe;
-    pipe.init(P.net.stream, P.net.n_chunks, lds, 0);
+    pipe.init(P.net.stream, P.net.n_chunks, lds);
     pipe.start();
 
     for (int64_t tile = blockIdx.x; tile < P.n_tiles; tile += gridDim.x) {
@@ -231,7 +256,7 @@ __global__ void __launch_bounds__(WAVES * 64) train_backward_kernel(const TrainK
     for (int i = threadIdx.x; i < 32 * HT; i += blockDim.x) zero_bias[i] = 0.0f;     // the chain has no bias: accumulators start at 0
     __syncthreads();
     Pipe<WAVES> pipe;
-    pipe.init(P.net.stream, P.net.n_chunks, lds, 0);
+    pipe.init(P.net.stream, P.net.n_chunks, lds);
     pipe.start();
     const int n = P.net.n_layers;
 
@@ -312,17 +337,13 @@ struct GradKArgs {
 // 131 kFLOP.  Per stage of ST sample tiles, wave w transposes dZ tile w and X tile w of every sample tile on the
 // matrix core (train_core.hpp) -- each tile exactly once per workgroup -- and parks the transposed operand tiles in
 // LDS, where all waves read the 2 + 4 tiles their outputs need; the saved tiles of the next stage are already in
-// flight (registers) while the current one is multiplied.  Two LDS buffers, one barrier per stage.
-// PF = stages of saved tiles in flight per wave (registers): the kernel is a stream of 1-KiB tile loads whose only latency cover is
-// what is already in flight -- at PF = 1 (rounds 1-2) a workgroup keeps 2 ST KiB per wave on the wire, 8 MB chip-wide, about half of
-// what 8 TB/s x ~2 us of loaded HBM latency asks for, and the kernel sat at 3.8 TB/s.  PF = 2 doubles it in the 16-bit modes
-// (2 x ST x 16 more registers; the fp32 mode's tiles are twice as large and stay at PF = 1).
-template <class Mode, int ST, int PF = 1>
+// flight (registers) while the current one is multiplied.  Two LDS buffers, one barrier per stage.  (Two stages in flight per
+// wave measured the same: profiles/r03_ab_wgrad_prefetch.txt.)
+template <class Mode, int ST>
 __global__ void __launch_bounds__(512) weight_grad_kernel(const GradKArgs P) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef typename Mode::Act Act;
     typedef ActIO<Mode> IO;
-    static_assert(PF == 1 || PF == 2, "one or two stages of saved tiles in flight");
     constexpr int RT = 2, CT = 4;
     constexpr int TB = tile_bytes<Mode>();
     constexpr int kStageBytes = ST * 16 * TB;
@@ -349,33 +370,31 @@ __global__ void __launch_bounds__(512) weight_grad_kernel(const GradKArgs P) {
     const char* xb = P.ctx + J.x_off + lane * 16;
     const char* zb = P.ctx + J.dz_off + lane * 16;
     const Act zero = Mode::template to_act<false>(f32x16{});
-    Act rz[PF][ST], rx[PF][ST];
-    auto fetch = [&](auto b_, int64_t st0) {
-        constexpr int b = decltype(b_)::value;
+    Act rz[ST], rx[ST];
+    auto fetch = [&](int64_t st0) {
 #pragma unroll
         for (int q = 0; q < ST; ++q) {
             const bool in = st0 + q < t1;
-            rz[b][q] = (in && has_z) ? IO::template load_g<Act>(zb + ((st0 + q) * J.dz_stride + wave) * (int64_t)TB) : zero;
-            rx[b][q] = (in && has_x) ? IO::template load_g<Act>(xb + ((st0 + q) * J.x_stride + J.x_first + wave) * (int64_t)TB) : zero;
+            rz[q] = (in && has_z) ? IO::template load_g<Act>(zb + ((st0 + q) * J.dz_stride + wave) * (int64_t)TB) : zero;
+            rx[q] = (in && has_x) ? IO::template load_g<Act>(xb + ((st0 + q) * J.x_stride + J.x_first + wave) * (int64_t)TB) : zero;
         }
     };
-    // one stage: transpose + park the register set `b`, refill it with the stage PF ahead, multiply
-    auto stage_step = [&](auto b_, int64_t st0, int buf) {
-        constexpr int b = decltype(b_)::value;
+    // one stage: transpose + park the registers, refill them with the next stage, multiply
+    auto stage_step = [&](int64_t st0, int buf) {
         char* stage = smem + buf * kStageBytes + lane * 16;
 #pragma unroll
         for (int q = 0; q < ST; ++q) {
             if (has_z) {
-                const f32x16 t = tr.run(rz[b][q]);
+                const f32x16 t = tr.run(rz[q]);
                 float s = 0.0f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s += t[r];
                 bsum += s;
                 IO::store(stage + (q * 16 + wave) * TB, Mode::template to_act<false>(t));
             }
-            if (has_x) IO::store(stage + (q * 16 + 8 + wave) * TB, Mode::template to_act<false>(tr.run(rx[b][q])));
+            if (has_x) IO::store(stage + (q * 16 + 8 + wave) * TB, Mode::template to_act<false>(tr.run(rx[q])));
         }
-        if (st0 + PF * ST < t1) fetch(b_, st0 + PF * ST);         // the saved tiles PF stages ahead: in flight across the barrier and the MFMAs
+        if (st0 + ST < t1) fetch(st0 + ST);                       // the next stage's saved tiles: in flight across the barrier and the MFMAs
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < ST; ++q) {
@@ -393,19 +412,11 @@ __global__ void __launch_bounds__(512) weight_grad_kernel(const GradKArgs P) {
             }
         }
     };
-    if (t0 < t1) fetch(std::integral_constant<int, 0>{}, t0);
-    if constexpr (PF == 2)
-        if (t0 + ST < t1) fetch(std::integral_constant<int, 1>{}, t0 + ST);
+    if (t0 < t1) fetch(t0);
     int buf = 0;
-    for (int64_t st0 = t0; st0 < t1; st0 += PF * ST) {
-        stage_step(std::integral_constant<int, 0>{}, st0, buf);
+    for (int64_t st0 = t0; st0 < t1; st0 += ST) {
+        stage_step(st0, buf);
         buf ^= 1;
-        if constexpr (PF == 2) {
-            if (st0 + ST < t1) {
-                stage_step(std::integral_constant<int, 1>{}, st0 + ST, buf);
-                buf ^= 1;
-            }
-        }
     }
     // hand the partial sums over: [wave][tile i*CT+j][register group of 4][lane][4 floats], 16 B per lane and store
     float* part = P.partial + (int64_t)blockIdx.x * kPartialFloats;

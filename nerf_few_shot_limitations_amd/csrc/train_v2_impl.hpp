@@ -29,7 +29,7 @@ __global__ void __launch_bounds__(WAVES * 64) train_forward_v2_kernel(const Trai
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     load_bias_table(bias, P.net.bias, P.net.n_bias);
     Pipe<WAVES> pipe;
-    pipe.init(P.net.stream, P.net.n_chunks, lds, 0);
+    pipe.init(P.net.stream, P.net.n_chunks, lds);
     pipe.start();
     const int n = P.net.n_layers;
 
@@ -152,7 +152,7 @@ __global__ void __launch_bounds__(WAVES * 64) train_backward_v2_kernel(const Tra
     for (int i = threadIdx.x; i < 32 * HT; i += blockDim.x) zero_bias[i] = 0.0f;
     __syncthreads();
     Pipe<WAVES> pipe;
-    pipe.init(P.net.stream, P.net.n_chunks, lds, 0);
+    pipe.init(P.net.stream, P.net.n_chunks, lds);
     pipe.start();
     const int n = P.net.n_layers;
 

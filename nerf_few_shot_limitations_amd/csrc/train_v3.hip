@@ -1,43 +1,9 @@
-// train_v3.hip -- host launchers of the V3 (NeRFWithDINO) training kernels (pos_freq 12, dir_freq 4, dino_dim 64 / 128)
+// train_v3.hip -- host entry points of the V3 (NeRFWithDINO) training kernels (pos_freq 12, dir_freq 4, dino_dim 64 / 128)
 #include "train_v3_impl.hpp"
 
 namespace nrf {
 
 namespace {
-
-template <class Mode, int WAVES, int DT>
-int run_forward(const DeviceNet& net, int mode, TrainKArgs k, hipStream_t s, std::string& err) {
-    auto kernel = train_forward_v3_kernel<Mode, WAVES, 12, 4, DT>;
-    static unsigned char done[64] = {};
-    const int prepared = prepare(kernel, net.device, done, err);
-    if (prepared != NRF_OK) return prepared;
-    k.net = net_args(net, mode);
-    k.net.ablate = 0;
-    k.n_tiles = tiles32(k.n) / WAVES;
-    const int64_t grid = k.n_tiles < net.cu_count ? k.n_tiles : net.cu_count;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(WAVES * 64), kLdsBytes, s, k);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { err = std::string("train forward launch: ") + hipGetErrorString(e); return NRF_EHIP; }
-    return NRF_OK;
-}
-
-template <class Mode, int WAVES, int DT>
-int run_backward(const DeviceNet& net, const TrainDev& t, int mode, TrainKArgs k, hipStream_t s, std::string& err) {
-    auto kernel = train_backward_v3_kernel<Mode, WAVES, 12, DT>;
-    static unsigned char done[64] = {};
-    const int prepared = prepare(kernel, net.device, done, err);
-    if (prepared != NRF_OK) return prepared;
-    k.net = net_args(net, mode);
-    k.net.ablate = 0;
-    k.net.stream = t.bstream[mode];
-    k.net.n_chunks = t.n_bchunks[mode];
-    k.n_tiles = tiles32(k.n) / WAVES;
-    const int64_t grid = k.n_tiles < net.cu_count ? k.n_tiles : net.cu_count;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(WAVES * 64), kLdsBytes, s, k);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { err = std::string("train backward launch: ") + hipGetErrorString(e); return NRF_EHIP; }
-    return NRF_OK;
-}
 
 bool check(const DeviceNet& net, const TrainDev& t, int mode, std::string& err) {
     if (!check_train_common(net, t, mode, err)) return false;
@@ -49,23 +15,12 @@ bool check(const DeviceNet& net, const TrainDev& t, int mode, std::string& err) 
     return true;
 }
 
-#define NRF_V3_DISPATCH(FN, ...)                                                          \
-    const bool small = small_batch(net, k.n);                                             \
-    if (net.arch.dino_dim == 64) {                                                        \
-        switch (mode) {                                                                   \
-            case NRF_MMA_BF16: return small ? FN<ModeBF16, 4, 2>(__VA_ARGS__) : FN<ModeBF16, 8, 2>(__VA_ARGS__);   \
-            case NRF_MMA_F16:  return small ? FN<ModeF16, 4, 2>(__VA_ARGS__) : FN<ModeF16, 8, 2>(__VA_ARGS__);     \
-            default:           return FN<ModeF32, 4, 2>(__VA_ARGS__);                     \
-        }                                                                                 \
-    }                                                                                     \
-    switch (mode) {                                                                       \
-        case NRF_MMA_BF16: return small ? FN<ModeBF16, 4, 4>(__VA_ARGS__) : FN<ModeBF16, 8, 4>(__VA_ARGS__);       \
-        case NRF_MMA_F16:  return small ? FN<ModeF16, 4, 4>(__VA_ARGS__) : FN<ModeF16, 8, 4>(__VA_ARGS__);         \
-        default:           return FN<ModeF32, 4, 4>(__VA_ARGS__);                         \
-    }
-
-int forward_any(const DeviceNet& net, int mode, const TrainKArgs& k, hipStream_t s, std::string& err) { NRF_V3_DISPATCH(run_forward, net, mode, k, s, err) }
-int backward_any(const DeviceNet& net, const TrainDev& t, int mode, const TrainKArgs& k, hipStream_t s, std::string& err) { NRF_V3_DISPATCH(run_backward, net, t, mode, k, s, err) }
+// f(ChainGeo, DT): dispatch_chain with the feature width as DT = dino_dim / 32 operand tiles
+template <class F>
+int dispatch_v3(const DeviceNet& net, int mode, int64_t n, F&& f) {
+    if (net.arch.dino_dim == 64) return dispatch_chain(net, mode, n, [&](auto g) { return f(g, std::integral_constant<int, 2>{}); });
+    return dispatch_chain(net, mode, n, [&](auto g) { return f(g, std::integral_constant<int, 4>{}); });
+}
 
 }  // namespace
 
@@ -76,7 +31,11 @@ int launch_train_forward_v3(const DeviceNet& net, const TrainDev& t, int mode, c
     TrainKArgs k{};
     k.pos = pos; k.dir = dir; k.dino = dino; k.n = n; k.rgb = rgb; k.density = density; k.ctx = (char*)ctx;
     if (!fill_slots(t, mode, n, k, err)) return NRF_EINVAL;
-    return forward_any(net, mode, k, s, err);
+    return dispatch_v3(net, mode, n, [&](auto g, auto dt) {
+        typedef decltype(g) G;
+        return launch_persistent<train_forward_v3_kernel<typename G::Mode, G::kWaves, 12, 4, decltype(dt)::value>, G::kWaves>(
+            net, net_args(net, mode), k, tiles32(n) / G::kWaves, s, "train forward", err);
+    });
 }
 
 int launch_train_backward_v3(const DeviceNet& net, const TrainDev& t, int mode, const float* rgb, const float* density,
@@ -87,7 +46,11 @@ int launch_train_backward_v3(const DeviceNet& net, const TrainDev& t, int mode, 
     k.n = n; k.rgb = const_cast<float*>(rgb); k.density = const_cast<float*>(density); k.g_rgb = g_rgb; k.g_density = g_density;
     k.ctx = (char*)ctx;
     if (!fill_slots(t, mode, n, k, err)) return NRF_EINVAL;
-    const int r = backward_any(net, t, mode, k, s, err);
+    const int r = dispatch_v3(net, mode, n, [&](auto g, auto dt) {
+        typedef decltype(g) G;
+        return launch_persistent<train_backward_v3_kernel<typename G::Mode, G::kWaves, 12, decltype(dt)::value>, G::kWaves>(
+            net, backward_net_args(net, t, mode), k, tiles32(n) / G::kWaves, s, "train backward", err);
+    });
     if (r != NRF_OK) return r;
     return launch_weight_grad(net, t, mode, k, grad, s, err);
 }

@@ -331,7 +331,7 @@ def test_model_update_repacks(N, golden):
 
 
 def test_split_mode_device_repack_equals_host_pack(N, golden):
-    """nrf_model_update_device in the split mode (hi / lo parts converted on the device, train_v1.hip:convert_pair) produces
+    """nrf_model_update_device in the split mode (hi / lo parts converted on the device, train_shared.hip:convert_pair) produces
     the very stream the host packer builds (packing.cpp:pack_stream): same outputs to the last bit.  Also: a module in the
     split mode trains through the exact-fp32 training kernels (_lib.TRAIN_MODE)."""
     g = golden("mlp_v1_fog")

@@ -117,3 +117,22 @@ def test_entry_points_and_tools_compile():
     import importlib
     entry = importlib.import_module("__graft_entry__")
     assert callable(entry.build) and callable(entry.smoke)
+
+
+def test_no_tuning_switches_in_the_library():
+    """What the library computes depends on its arguments and build.py's flags alone: no environment variable or extra -D flag
+    changes a kernel, its geometry or which library is loaded.  The one variable the sources read is NRF_SPW, which pins the
+    renderer's samples-per-pass split (every split gives the same bits: test_gpu_parity.py)."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "nerf_few_shot_limitations_amd", "csrc")
+    env, macros = [], set()
+    for fn in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, fn)) as f:
+            text = f.read()
+        env += [(fn, m) for m in re.findall(r"getenv\(([^)]*)\)", text)]
+        macros |= set(re.findall(r"#\s*if(?:n?def\s+|.*defined\s*\(\s*)(\w+)", text))
+    assert env and all(arg == '"NRF_SPW"' for _, arg in env), env
+    assert macros <= {"NRF_TU_HALF", "NRF_ACT_AGPR"}, macros           # build.py's own per-object flags
+    with open(os.path.join(root, "nerf_few_shot_limitations_amd", "_lib.py")) as f:
+        assert "environ" not in f.read()                                 # the library next to the package, no other
