@@ -343,22 +343,31 @@ __device__ __forceinline__ DinoTaps dino_taps(const DinoT& d, const float p[3]) 
     return t;
 }
 
+// What a tap outside the map reads: zeros padding means such a tap contributes exactly 0 whatever the map holds, and a texel of
+// the map times weight 0 is NaN when the texel is NaN or Inf.  128 channels = the widest feature map (DT = 4).
+static __device__ __attribute__((aligned(16))) float dino_zero_texel[128];
+
 // The feature-map gather in two steps, so that the caller can put work between them: issue() starts all 16 DT tap loads of a lane
-// half unconditionally (a tap outside the map reads the map's first texel with weight 0: 0 * v adds exactly nothing, as zeros
-// padding does), finish() blends them in fp32, in tap order: e[16 t + 4 g + q] = channel 32t + 8g + 4h + q.  The loads are L2 hits whose latency a lone wave per SIMD
+// half unconditionally (a tap outside the map reads dino_zero_texel instead, with weight 0: the blend stays a plain FMA chain and
+// adds exactly nothing for it, as zeros padding does), finish() blends them in fp32, in tap order: e[16 t + 4 g + q] = channel
+// 32t + 8g + 4h + q.  The loads are L2 hits whose latency a lone wave per SIMD
 // cannot cover by itself: with the positional encoding of the same column (~600 VALU instructions) between the two calls it is
 // (ablation: the gather cost 3.7 % of a V3 frame, the same with every load on one hot address).
 template <int DT>
 struct DinoRaw {
+    static_assert(32 * DT <= 128, "dino_zero_texel holds 128 channels");
     f32x4 v[DT][4][4];       // [tile][register group][tap]
     __device__ __forceinline__ void issue(const float* __restrict__ feat, const DinoTaps& tp, int h) {
+        const float* base[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) base[k] = tp.off[k] >= 0 ? feat + tp.off[k] : dino_zero_texel;
 #pragma unroll
         for (int t = 0; t < DT; ++t)
 #pragma unroll
             for (int g = 0; g < 4; ++g)
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
-                    v[t][g][k] = *(const f32x4*)(feat + (tp.off[k] >= 0 ? tp.off[k] : 0) + 32 * t + 8 * g + 4 * h);
+                    v[t][g][k] = *(const f32x4*)(base[k] + 32 * t + 8 * g + 4 * h);
     }
     __device__ __forceinline__ void finish(const DinoTaps& tp, float (&e)[16 * DT]) const {
 #pragma unroll

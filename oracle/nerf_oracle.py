@@ -280,7 +280,9 @@ def project_points_to_image(points, pose, focal, H, W):
 def sample_features_at_points(features, points_2d):
     """src/models/dino_feature_model.py:114-148: bilinear grid_sample of a
     (1,Hp,Wp,C) map at (N,2) normalised points, zeros padding,
-    align_corners=False -> (N,C).  Written out tap by tap (no F.grid_sample)."""
+    align_corners=False -> (N,C).  Written out tap by tap (no F.grid_sample).
+    A tap outside the map contributes exactly 0 whatever the map holds (zeros padding: grid_sample never reads it), so a NaN / Inf
+    texel reaches only the points that have it among their on-map taps."""
     fm = torch.as_tensor(features, dtype=torch.float32)[0]          # (Hp,Wp,C)
     Hp, Wp, C = fm.shape
     gx = ((points_2d[:, 0] + 1) * Wp - 1) / 2                       # align_corners=False unnormalise
@@ -297,8 +299,8 @@ def sample_features_at_points(features, points_2d):
             ok = (xi >= 0) & (xi <= Wp - 1) & (yi >= 0) & (yi <= Hp - 1)
             xi_c = xi.clamp(0, Wp - 1).long()
             yi_c = yi.clamp(0, Hp - 1).long()
-            tap = fm[yi_c, xi_c]                                    # (N,C)
-            out = out + tap * (wx * wy * ok)[:, None]
+            tap = fm[yi_c, xi_c]                                    # (N,C); an off-map tap's clamped read is discarded below
+            out = out + torch.where(ok[:, None], tap * (wx * wy)[:, None], 0.0)
     return out
 
 

@@ -333,7 +333,83 @@ def training():
     save("train_grads", **out)
 
 
+def dino_views_geometry():
+    """The two source views of dino_views.npz, each with its own intrinsics (focal, H, W), all unlike the rendered camera's:
+    'orbit': the rendered camera turned 75 degrees about the world z axis (most samples on the map, some partly, some off it);
+    'near': a wide-angle camera moved into the sampled depth range, 2 units beside the ray bundle and yawed by -20 degrees, so that
+    ~45 % of the samples lie behind it (camera-space Z > 0, projected mirrored; some of those land on the map)."""
+    c2w = torch.from_numpy(O.LEGO_LIKE_C2W.copy())
+    a = np.radians(75.0)
+    rz = torch.eye(4)
+    rz[0, 0], rz[0, 1], rz[1, 0], rz[1, 1] = np.cos(a), -np.sin(a), np.sin(a), np.cos(a)
+    orbit = rz @ c2w
+    b = np.radians(-20.0)
+    ry = torch.eye(4)
+    ry[0, 0], ry[0, 2], ry[2, 0], ry[2, 2] = np.cos(b), np.sin(b), -np.sin(b), np.cos(b)
+    near = c2w @ ry
+    near[:3, 3] = c2w[:3, 3] - 3.0 * c2w[:3, 2] + 2.0 * c2w[:3, 0]
+    return {"orbit": (orbit, O.focal_for(400), 300, 400), "near": (near, 0.35 * O.focal_for(400), 300, 400)}
+
+
+def dino_views():
+    """V3 renders conditioned on ANOTHER view's feature map (train.py:188-242 with feat_idx != the rendered view, as evaluate() does
+    for every test view): non-square maps at dino_dim 64 and 128, two source poses with their own intrinsics, plain and jittered
+    sampling; plus the reference's fetch on a map holding NaN / Inf texels.  Written by `make_golden.py --dino-views-only`, which
+    touches no other fixture."""
+    H, W, S = 12, 16, 32
+    _, _, f, c2w = cam(H, W)
+    ro, rd = ref_get_rays_flat(H, W, f, c2w)
+    ro, rd = ro.reshape(-1, 3).contiguous(), rd.reshape(-1, 3).contiguous()
+    R = ro.shape[0]
+    tr = torch.from_numpy(O.uniform01(81, R * S).reshape(R, S))
+    vr = ref_mlp.VolumeRenderer().eval()
+    fetch = ref_dfm.SpatialDINOFeatures.sample_features_at_points
+    # maps on a 1/256 grid in [-1, 1): every texel distinct in all channels, and the fixture compresses
+    maps = {64: (np.floor(O.uniform01(82, 14 * 22 * 64) * 512) - 256).reshape(1, 14, 22, 64).astype(np.float32) / 256,
+            128: (np.floor(O.uniform01(83, 10 * 12 * 128) * 512) - 256).reshape(1, 10, 12, 128).astype(np.float32) / 256}
+    weights = {64: O.make_weights("v3", 2), 128: O.make_weights("v3", 3, dino_dim=128)}
+    geo = dino_views_geometry()
+    out = dict(H=H, W=W, S=S, focal=np.float32(f), c2w=npf(c2w), t_rand=npf(tr), map64=maps[64], map128=maps[128])
+    for name, (pose, fs, Hs, Ws) in geo.items():
+        out[f"{name}_pose"], out[f"{name}_focal"], out[f"{name}_H"], out[f"{name}_W"] = npf(pose), np.float32(fs), Hs, Ws
+    for jit in (False, True):
+        tag = "jit" if jit else "plain"
+        if jit:
+            with _patched_rand(tr):
+                pts, z = ref_sample_flat(ro, rd, 2.0, 6.0, S, perturb=True)
+        else:
+            pts, z = ref_sample_flat(ro, rd, 2.0, 6.0, S, perturb=False)
+        pf = pts.reshape(-1, 3)
+        df = rd.unsqueeze(1).expand(-1, S, -1).reshape(-1, 3)
+        for name, dd in (("orbit", 64), ("orbit", 128), ("near", 64), ("near", 128)):
+            pose, fs, Hs, Ws = geo[name]
+            xy, _, _ = ref_project(pf, pose, fs, Hs, Ws)
+            ft = fetch(types.SimpleNamespace(), torch.from_numpy(maps[dd]), xy)
+            col, dn = load_ref_v3(weights[dd], dd)(pf, df, ft)
+            c, dpt, w = vr(col.reshape(R, S, 3), dn.reshape(R, S, 1), z, rd)
+            key = f"{name}_d{dd}_{tag}"
+            out[key + "_rgb"], out[key + "_depth"], out[key + "_w"] = npf(c), npf(dpt), npf(w)
+    # non-finite texels: NaN at (0, 0), +Inf at (Hp-1, Wp-1), NaN at an interior texel; the fetch at points off the map, partly on it,
+    # inside it, on texel centres and next to the bad texels (pixel-space grid, then normalised as align_corners=False does)
+    bad = np.array([[0, 0], [13, 21], [6, 9]], np.int32)
+    poisoned = maps[64].copy()
+    poisoned[0, 0, 0] = np.nan
+    poisoned[0, 13, 21] = np.inf
+    poisoned[0, 6, 9] = np.nan
+    gx = np.concatenate([np.linspace(-1.6, 22.4, 11), [-1.0, -0.5, 0.0, 0.25, 8.5, 9.0, 20.75, 21.0, 21.5, 22.0]])
+    gy = np.concatenate([np.linspace(-1.6, 14.4, 7), [-1.0, -0.5, 0.0, 0.4, 5.5, 6.0, 12.5, 13.0, 13.6]])
+    GX, GY = np.meshgrid(gx, gy)
+    xy_bad = np.stack([(2 * GX.ravel() + 1) / 22 - 1, (2 * GY.ravel() + 1) / 14 - 1], -1).astype(np.float32)
+    out.update(bad_texels=bad, fetch_xy=xy_bad,
+               fetch_poisoned=npf(fetch(types.SimpleNamespace(), torch.from_numpy(poisoned), torch.from_numpy(xy_bad))))
+    save("dino_views", **out)
+
+
 if __name__ == "__main__":
+    if "--dino-views-only" in sys.argv:
+        dino_views()
+        sys.exit(0)
     if "--training-only" not in sys.argv:
         main()
     training()
+    dino_views()

@@ -22,6 +22,37 @@ def mk(variant, scene, mode):
         m = N.NeRFMLP(pos_freq=10, dir_freq=4, hidden_dim=256, num_density_layers=8, use_dino=False, mma_mode=mode); m.load_state_dict(p, strict=False)
     return m.cuda().eval(), p
 
+def dino_views_report():
+    """V3 conditioned on another view (dino_views.npz, both source views) in the 16-bit modes at both widths, and the 128-d forward
+    against mlp_v3_d128.npz: the numbers behind the bounds of tests/test_gpu_dino_views.py."""
+    v = g("dino_views")
+    ro, rd = N.get_rays(int(v["H"]), int(v["W"]), float(v["focal"]), T(v["c2w"]))
+    for dd in (64, 128):
+        p = O.make_weights("v3", 2) if dd == 64 else O.make_weights("v3", 3, dino_dim=128)
+        m = N.NeRFMLP(pos_freq=12, dir_freq=4, hidden_dim=256, num_density_layers=8, use_dino=True, dino_dim=dd, mma_mode="f16")
+        m.load_state_dict(p, strict=False); m = m.cuda().eval()
+        for name in ("orbit", "near"):
+            dino = dict(features=T(v[f"map{dd}"]), pose=T(v[f"{name}_pose"]), focal=float(v[f"{name}_focal"]), H=int(v[f"{name}_H"]), W=int(v[f"{name}_W"]))
+            key = f"{name}_d{dd}_plain"
+            for mode in ("f32", "f16x3", "f16", "bf16"):
+                out = N.render_rays(m, ro, rd, 2.0, 6.0, int(v["S"]), dino=dino, mma_mode=mode)
+                print(f"dino_views d{dd} {name} {mode}: rgb {md(out['rgb'], v[key + '_rgb']):.2e} depth {md(out['depth'], v[key + '_depth']):.2e} "
+                      f"w {md(out['weights'], v[key + '_w']):.2e} psnr {O.psnr(out['rgb'].cpu(), T(v[key + '_rgb'])):.1f} dB")
+    gm = g("mlp_v3_d128")
+    m = N.NeRFMLP(pos_freq=12, dir_freq=4, hidden_dim=256, num_density_layers=8, use_dino=True, dino_dim=128, mma_mode="f16")
+    m.load_state_dict(O.make_weights("v3", 3, dino_dim=128), strict=False); m = m.cuda().eval()
+    for mode in ("f32", "f16x3", "f16", "bf16"):
+        m.mma_mode = mode
+        with torch.no_grad():
+            rgb, dens = m(T(gm["pos"]), T(gm["dirs"]), T(gm["dino"]))
+        print(f"mlp_v3_d128 {mode}: rgb {md(rgb, gm['rgb']):.2e} density {md(dens, gm['density']):.2e} (max {gm['density'].max():.1f})")
+
+
+if "--dino-views" in sys.argv:
+    dino_views_report()
+    sys.exit(0)
+
+
 e = g("end_to_end")
 H, W, S = int(e["H"]), int(e["W"]), int(e["S"])
 ro, rd = N.get_rays(H, W, float(e["focal"]), T(e["c2w"]))
@@ -90,3 +121,4 @@ dino = dict(features=fm, pose=T(e["c2w"]), focal=float(e["focal"]), H=H, W=W)
 for mode in ("f16", "bf16"):
     out = N.render_rays(m3, ro, rd, 2.0, 6.0, S, dino=dino, mma_mode=mode)
     print(f"e2e v3 fog {mode}: rgb {md(out['rgb'], e['v3_fog_plain_rgb']):.2e} depth {md(out['depth'], e['v3_fog_plain_depth']):.2e} psnr {O.psnr(out['rgb'].cpu(), T(e['v3_fog_plain_rgb'])):.1f} dB")
+dino_views_report()

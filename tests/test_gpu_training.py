@@ -535,10 +535,16 @@ def test_v3_gradients_fp32_mode_match_autograd(N, n, n_layers, dino_dim):
     assert checked == 2 * (n_layers + 10)
 
 
-@pytest.mark.parametrize("mode,cos_min,n", [("bf16", 0.90, 3000), ("f16", 0.99, 3000), ("bf16", 0.90, 40000)])
-def test_v3_gradients_16bit_modes_vs_fp32_autograd(N, mode, cos_min, n):
-    model, p = make_v3(N, mode)
-    pos, dirs, dino, g_rgb, g_den = v3_inputs(n, 64, seed=35)
+@pytest.mark.parametrize("mode,cos_min,n,dino_dim", [pytest.param("bf16", 0.90, 3000, 64, id="bf16-0.9-3000"),
+                                                      pytest.param("f16", 0.99, 3000, 64, id="f16-0.99-3000"),
+                                                      pytest.param("bf16", 0.90, 40000, 64, id="bf16-0.9-40000"),
+                                                      # dino_dim 128 (multiscale.yaml); measured worst cosines (the fusion gate's
+                                                      # 64 -> 2 layer, attention.2): bf16 0.955, f16 0.989
+                                                      pytest.param("bf16", 0.90, 3000, 128, id="bf16-0.9-3000-d128"),
+                                                      pytest.param("f16", 0.98, 3000, 128, id="f16-0.98-3000-d128")])
+def test_v3_gradients_16bit_modes_vs_fp32_autograd(N, mode, cos_min, n, dino_dim):
+    model, p = make_v3(N, mode, dino_dim=dino_dim)
+    pos, dirs, dino, g_rgb, g_den = v3_inputs(n, dino_dim, seed=35)
     rgb, den = model(pos.cuda(), dirs.cuda(), dino.cuda())
     ((rgb * g_rgb.cuda()).sum() + (den * g_den.cuda()).sum()).backward()
     pp = {k: v.clone().requires_grad_(True) for k, v in p.items()}
@@ -709,7 +715,8 @@ def test_v3_backward_matches_reference_golden(N, golden):
 # ---------------------------------------------------------------------------------------------
 # FusedStep: the same step without autograd in between
 # ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("net,mode", [("v1", "f32"), ("v1", "bf16"), ("v2", "f32"), ("v2", "bf16"), ("v3", "f32"), ("v3", "bf16")])
+@pytest.mark.parametrize("net,mode", [("v1", "f32"), ("v1", "bf16"), ("v2", "f32"), ("v2", "bf16"), ("v3", "f32"), ("v3", "bf16"),
+                                      ("v3w", "f32"), ("v3w", "bf16")])        # v3w: V3 at dino_dim 128 (multiscale.yaml)
 def test_fused_step_equals_autograd_route(N, net, mode):
     from nerf_few_shot_limitations_amd.training import Adam, FusedStep
     R, S, steps = 160, 32, 4
@@ -727,10 +734,14 @@ def test_fused_step_equals_autograd_route(N, net, mode):
         b, _ = make_v2(N, mode, scene="solid")
         pts = pos.cuda()
     else:
-        a, _ = make_v3(N, mode, scene="solid")
-        b, _ = make_v3(N, mode, scene="solid")
+        dd = 128 if net == "v3w" else 64
+        # at dino_dim 128 seed 2's densities are all <= 0 on these inputs (no gradient) and seed 3's first Adam steps overshoot
+        # (fp32 autograd on the CPU: 0.199 -> 0.325 in 4 steps); seed 4: 0.190 -> 0.100
+        seed = 4 if net == "v3w" else 2
+        a, _ = make_v3(N, mode, scene="solid", dino_dim=dd, seed=seed)
+        b, _ = make_v3(N, mode, scene="solid", dino_dim=dd, seed=seed)
         pts = pos.cuda()
-    dino = torch.from_numpy(O.uniform01(105, R * S * 64).reshape(R * S, 64) * 2 - 1).float().cuda() if net == "v3" else None
+    dino = torch.from_numpy(O.uniform01(105, R * S * dd).reshape(R * S, dd) * 2 - 1).float().cuda() if net in ("v3", "v3w") else None
     opt = Adam(a, lr=5e-4, weight_decay=1e-6)
     vr = N.VolumeRenderer()
     ref_losses = []

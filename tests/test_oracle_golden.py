@@ -161,6 +161,86 @@ def test_dino_fetch_golden(golden):
     assert np.abs(g["sampled_in"]).max() > 0.1        # the in-range case really hits the map
 
 
+def dino_views_case(g, name, dino_dim):
+    """(weights, dino dict) of one source view of dino_views.npz, as the reference's evaluate() builds it (another view's map)."""
+    p = O.make_weights("v3", 2) if dino_dim == 64 else O.make_weights("v3", 3, dino_dim=128)
+    dino = dict(features=T(g[f"map{dino_dim}"]), pose=T(g[f"{name}_pose"]), focal=float(g[f"{name}_focal"]),
+                H=int(g[f"{name}_H"]), W=int(g[f"{name}_W"]))
+    return p, dino
+
+
+@pytest.mark.parametrize("dino_dim", [64, 128])
+@pytest.mark.parametrize("name", ["orbit", "near"])
+def test_dino_views_end_to_end_golden(golden, name, dino_dim):
+    """V3 conditioned on a source view that is not the rendered camera (non-square map, its own intrinsics; 'near' puts ~45 % of the
+    samples behind the source camera): the oracle against the reference's train.py:188-242 on the same inputs."""
+    g = golden("dino_views")
+    H, W, S = int(g["H"]), int(g["W"]), int(g["S"])
+    ro, rd = O.get_rays(H, W, float(g["focal"]), T(g["c2w"]))
+    p, dino = dino_views_case(g, name, dino_dim)
+    for tag, tr in (("plain", None), ("jit", T(g["t_rand"]))):
+        out = O.render_rays(p, "v3", ro, rd, 2.0, 6.0, S, t_rand=tr, dino=dino, chunk=64)
+        key = f"{name}_d{dino_dim}_{tag}"
+        close(out["rgb"], g[key + "_rgb"])
+        close(out["depth"], g[key + "_depth"], 2e-5)                  # depths up to 6: a few ulps (test_end_to_end_golden's bound)
+        close(out["weights"], g[key + "_w"])
+
+
+def grid_sample64(fm, xy):
+    """F.grid_sample (bilinear, zeros padding, align_corners=False) in float64 at (N,2) points of a (1,Hp,Wp,C) map -> (N,C)."""
+    grid = torch.as_tensor(xy, dtype=torch.float64)[None, :, None, :]
+    out = torch.nn.functional.grid_sample(torch.as_tensor(fm, dtype=torch.float64).permute(0, 3, 1, 2), grid, mode="bilinear",
+                                          padding_mode="zeros", align_corners=False)
+    return out[0, :, :, 0].T
+
+
+def assert_same_with_nans(got, want, tol):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    assert np.array_equal(np.isnan(got), np.isnan(want))
+    fin = np.isfinite(want)
+    assert np.array_equal(np.isfinite(got), fin) and np.array_equal(got[np.isinf(want)], want[np.isinf(want)])
+    assert np.max(np.abs(got[fin] - want[fin]), initial=0.0) <= tol
+
+
+def test_oracle_fetch_is_grid_sample_with_zeros_padding():
+    """The oracle's tap-by-tap fetch against F.grid_sample in float64 on non-square maps, at points off the map, partly on it, on its
+    border, on texel centres and inside; on a finite map and on one with NaN / Inf texels (corner, opposite corner, interior): an
+    off-map tap contributes exactly 0 whatever the map holds, an on-map tap on a bad texel poisons its point -- NaN positions equal."""
+    for Hp, Wp, C, seed in ((5, 7, 3, 91), (14, 22, 64, 92), (1, 6, 2, 93)):
+        fm = torch.from_numpy((O.uniform01(seed, Hp * Wp * C).reshape(1, Hp, Wp, C) * 2 - 1).astype(np.float32))
+        u = O.uniform01(seed + 100, 600 * 2).reshape(600, 2)
+        # random points over the map and a margin around it; both borders' texel rows (the map's edge: gx = -0.5 / gy = Hp - 0.5),
+        # walked at quarter offsets (a point within an ulp of a texel column would round differently in float32 and float64)
+        gx = np.concatenate([u[:, 0] * (Wp + 3) - 2, np.arange(-1.25, Wp + 1, 0.5), np.full(2 * Hp + 4, -0.5)])
+        gy = np.concatenate([u[:, 1] * (Hp + 3) - 2, np.full(2 * Wp + 4, Hp - 0.5), np.arange(-1.25, Hp + 1, 0.5)])
+        xy = torch.from_numpy(np.stack([(2 * gx + 1) / Wp - 1, (2 * gy + 1) / Hp - 1], -1).astype(np.float32))
+        xy = torch.cat([xy, torch.tensor([[-3.0, -3.0], [3.0, 3.0], [-1.0, -1.0], [1.0, 1.0], [0.0, 0.0], [-1.0 - 1.0 / Wp, 0.0]])])
+        bad = fm.clone()
+        bad[0, 0, 0] = float("nan")
+        bad[0, Hp - 1, Wp - 1] = float("inf")
+        bad[0, Hp // 2, Wp // 2, 0] = float("nan")
+        for m in (fm, bad):
+            got = O.sample_features_at_points(m, xy)
+            assert_same_with_nans(got, grid_sample64(m, xy), 1e-5)       # the oracle's unnormalisation and weights round in fp32
+        got = O.sample_features_at_points(bad, xy)
+        assert np.isnan(got.numpy()).any() and bool((got[-6] == 0).all()) and bool((got[-5] == 0).all())   # NaN reaches on-map taps only
+
+
+def test_dino_views_poisoned_fetch_golden(golden):
+    """The reference's fetch (F.grid_sample) on the fixture's map with NaN at texel (0, 0), +Inf at (Hp-1, Wp-1) and NaN at an interior
+    texel, at points around and on them: the oracle reproduces it, NaN and Inf positions included."""
+    g = golden("dino_views")
+    bad = g["map64"].copy()
+    for i, (y, x) in enumerate(g["bad_texels"]):
+        bad[0, y, x] = np.inf if i == 1 else np.nan
+    want = g["fetch_poisoned"]
+    got = O.sample_features_at_points(T(bad), T(g["fetch_xy"]))
+    assert_same_with_nans(got, want, 1e-6)
+    rows_nan = np.isnan(want).any(1)
+    assert 0.02 < rows_nan.mean() < 0.5 and (want == 0).all(1).mean() > 0.1 and np.isinf(want).any()
+
+
 def test_composite_golden(golden):
     g = golden("composite")
     c, d, w = O.volume_render(T(g["rgb_in"]), T(g["sigma_in"]), T(g["z"]), T(g["rays_d"]))
