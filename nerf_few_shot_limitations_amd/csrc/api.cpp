@@ -492,79 +492,73 @@ int64_t nrf_train_context_bytes(nrf_model* m, int mma_mode, int64_t n) {
     return nrf::train_ctx_bytes(m->train, mma_mode, n);
 }
 
-int nrf_mlp_forward_train_v1(nrf_model* m, int mma_mode, const float* x_enc, int64_t n, float* out4, void* ctx, int64_t ctx_bytes,
-                             void* stream) {
+extern "C++" {
+namespace {
+
+// The prologue of the four training entries, in this order: the model, n and the mode, nothing to do (n == 0), null pointers,
+// the entry's family check `wrong` (an error text or NULL), the device, the training set-up, the context size and, before a
+// dZ chain, the freshness of the transposed weights; then launch(err).
+template <class Wrong, class Launch>
+int train_entry(nrf_model* m, int mma_mode, int64_t n, bool null_ptr, int64_t ctx_bytes, bool backward, Wrong&& wrong, Launch&& launch) {
     if (!m) return fail(NRF_EINVAL, "model is NULL");
     if (n < 0 || mma_mode < 0 || mma_mode > 2) return fail(NRF_EINVAL, "bad n / mma_mode (the training path is built for bf16, f16 and f32)");
     if (n == 0) return NRF_OK;
-    if (!x_enc || !out4 || !ctx) return fail(NRF_EINVAL, "null pointer");
+    if (null_ptr) return fail(NRF_EINVAL, "null pointer");
+    if (const char* w = wrong()) return fail(NRF_EINVAL, w);
     DeviceGuard guard(m->device);
     if (!guard.ok) return fail(NRF_EHIP, "cannot select the model's device");
     const int rc = ensure_train(m);
     if (rc != NRF_OK) return rc;
     if (ctx_bytes < nrf::train_ctx_bytes(m->train, mma_mode, n)) return fail(NRF_EINVAL, "context buffer smaller than nrf_train_context_bytes");
+    if (backward && !m->bfresh[mma_mode])
+        return fail(NRF_EINVAL, "backward weights of this mode are older than the parameters: call nrf_model_update_device (with this mode) first");
     std::string err;
-    const int r = nrf::launch_train_forward(m->net, m->train, mma_mode, x_enc, n, out4, ctx, (hipStream_t)stream, err);
+    const int r = launch(err);
     return r == NRF_OK ? NRF_OK : fail(r, err);
+}
+
+const char* any_family() { return nullptr; }      // the V1 entries: the launcher checks the family
+
+}  // namespace
+}  // extern "C++"
+
+int nrf_mlp_forward_train_v1(nrf_model* m, int mma_mode, const float* x_enc, int64_t n, float* out4, void* ctx, int64_t ctx_bytes,
+                             void* stream) {
+    return train_entry(m, mma_mode, n, !x_enc || !out4 || !ctx, ctx_bytes, false, any_family, [&](std::string& err) {
+        return nrf::launch_train_forward(m->net, m->train, mma_mode, x_enc, n, out4, ctx, (hipStream_t)stream, err);
+    });
 }
 
 int nrf_mlp_backward_v1(nrf_model* m, int mma_mode, const float* out4, const float* g_out4, int64_t n, void* ctx, int64_t ctx_bytes,
                         float* flat_grad, void* stream) {
-    if (!m) return fail(NRF_EINVAL, "model is NULL");
-    if (n < 0 || mma_mode < 0 || mma_mode > 2) return fail(NRF_EINVAL, "bad n / mma_mode (the training path is built for bf16, f16 and f32)");
-    if (n == 0) return NRF_OK;
-    if (!out4 || !g_out4 || !ctx || !flat_grad) return fail(NRF_EINVAL, "null pointer");
-    DeviceGuard guard(m->device);
-    if (!guard.ok) return fail(NRF_EHIP, "cannot select the model's device");
-    const int rc = ensure_train(m);
-    if (rc != NRF_OK) return rc;
-    if (ctx_bytes < nrf::train_ctx_bytes(m->train, mma_mode, n)) return fail(NRF_EINVAL, "context buffer smaller than nrf_train_context_bytes");
-    if (!m->bfresh[mma_mode])
-        return fail(NRF_EINVAL, "backward weights of this mode are older than the parameters: call nrf_model_update_device (with this mode) first");
-    std::string err;
-    const int r = nrf::launch_train_backward(m->net, m->train, mma_mode, out4, g_out4, n, ctx, flat_grad, (hipStream_t)stream, err);
-    return r == NRF_OK ? NRF_OK : fail(r, err);
+    return train_entry(m, mma_mode, n, !out4 || !g_out4 || !ctx || !flat_grad, ctx_bytes, true, any_family, [&](std::string& err) {
+        return nrf::launch_train_backward(m->net, m->train, mma_mode, out4, g_out4, n, ctx, flat_grad, (hipStream_t)stream, err);
+    });
 }
 
 int nrf_mlp_forward_train(nrf_model* m, int mma_mode, const float* positions, const float* directions, const float* dino, int64_t n, float* rgb,
                           float* density, void* ctx, int64_t ctx_bytes, void* stream) {
-    if (!m) return fail(NRF_EINVAL, "model is NULL");
-    if (n < 0 || mma_mode < 0 || mma_mode > 2) return fail(NRF_EINVAL, "bad n / mma_mode (the training path is built for bf16, f16 and f32)");
-    if (n == 0) return NRF_OK;
-    if (!positions || !directions || !rgb || !density || !ctx) return fail(NRF_EINVAL, "null pointer");
-    if (m->arch.net == NRF_NET_V1) return fail(NRF_EINVAL, "V1 models take encoded inputs: nrf_mlp_forward_train_v1");
-    if (m->arch.net == NRF_NET_V3 && !dino) return fail(NRF_EINVAL, "V3 needs per-sample dino features");
-    DeviceGuard guard(m->device);
-    if (!guard.ok) return fail(NRF_EHIP, "cannot select the model's device");
-    const int rc = ensure_train(m);
-    if (rc != NRF_OK) return rc;
-    if (ctx_bytes < nrf::train_ctx_bytes(m->train, mma_mode, n)) return fail(NRF_EINVAL, "context buffer smaller than nrf_train_context_bytes");
-    std::string err;
-    const int r = m->arch.net == NRF_NET_V3
-        ? nrf::launch_train_forward_v3(m->net, m->train, mma_mode, positions, directions, dino, n, rgb, density, ctx, (hipStream_t)stream, err)
-        : nrf::launch_train_forward_v2(m->net, m->train, mma_mode, positions, directions, n, rgb, density, ctx, (hipStream_t)stream, err);
-    return r == NRF_OK ? NRF_OK : fail(r, err);
+    auto wrong = [&]() -> const char* {
+        if (m->arch.net == NRF_NET_V1) return "V1 models take encoded inputs: nrf_mlp_forward_train_v1";
+        if (m->arch.net == NRF_NET_V3 && !dino) return "V3 needs per-sample dino features";
+        return nullptr;
+    };
+    return train_entry(m, mma_mode, n, !positions || !directions || !rgb || !density || !ctx, ctx_bytes, false, wrong, [&](std::string& err) {
+        return m->arch.net == NRF_NET_V3
+            ? nrf::launch_train_forward_v3(m->net, m->train, mma_mode, positions, directions, dino, n, rgb, density, ctx, (hipStream_t)stream, err)
+            : nrf::launch_train_forward_v2(m->net, m->train, mma_mode, positions, directions, n, rgb, density, ctx, (hipStream_t)stream, err);
+    });
 }
 
 int nrf_mlp_backward(nrf_model* m, int mma_mode, const float* rgb, const float* density, const float* g_rgb, const float* g_density, int64_t n,
                      void* ctx, int64_t ctx_bytes, float* flat_grad, void* stream) {
-    if (!m) return fail(NRF_EINVAL, "model is NULL");
-    if (n < 0 || mma_mode < 0 || mma_mode > 2) return fail(NRF_EINVAL, "bad n / mma_mode (the training path is built for bf16, f16 and f32)");
-    if (n == 0) return NRF_OK;
-    if (!rgb || !density || !g_rgb || !g_density || !ctx || !flat_grad) return fail(NRF_EINVAL, "null pointer");
-    if (m->arch.net == NRF_NET_V1) return fail(NRF_EINVAL, "V1 models: nrf_mlp_backward_v1");
-    DeviceGuard guard(m->device);
-    if (!guard.ok) return fail(NRF_EHIP, "cannot select the model's device");
-    const int rc = ensure_train(m);
-    if (rc != NRF_OK) return rc;
-    if (ctx_bytes < nrf::train_ctx_bytes(m->train, mma_mode, n)) return fail(NRF_EINVAL, "context buffer smaller than nrf_train_context_bytes");
-    if (!m->bfresh[mma_mode])
-        return fail(NRF_EINVAL, "backward weights of this mode are older than the parameters: call nrf_model_update_device (with this mode) first");
-    std::string err;
-    const int r = m->arch.net == NRF_NET_V3
-        ? nrf::launch_train_backward_v3(m->net, m->train, mma_mode, rgb, density, g_rgb, g_density, n, ctx, flat_grad, (hipStream_t)stream, err)
-        : nrf::launch_train_backward_v2(m->net, m->train, mma_mode, rgb, density, g_rgb, g_density, n, ctx, flat_grad, (hipStream_t)stream, err);
-    return r == NRF_OK ? NRF_OK : fail(r, err);
+    auto wrong = [&]() -> const char* { return m->arch.net == NRF_NET_V1 ? "V1 models: nrf_mlp_backward_v1" : nullptr; };
+    return train_entry(m, mma_mode, n, !rgb || !density || !g_rgb || !g_density || !ctx || !flat_grad, ctx_bytes, true, wrong,
+                       [&](std::string& err) {
+        return m->arch.net == NRF_NET_V3
+            ? nrf::launch_train_backward_v3(m->net, m->train, mma_mode, rgb, density, g_rgb, g_density, n, ctx, flat_grad, (hipStream_t)stream, err)
+            : nrf::launch_train_backward_v2(m->net, m->train, mma_mode, rgb, density, g_rgb, g_density, n, ctx, flat_grad, (hipStream_t)stream, err);
+    });
 }
 
 int nrf_composite_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals, const float* rays_d,

@@ -6,6 +6,7 @@
 
 #include "feature_map.hpp"
 #include "stream_config.hpp"
+#include "train_slots.hpp"
 
 namespace nrf {
 
@@ -340,7 +341,7 @@ PackedStream pack_stream(const NetPlan& plan, const std::vector<HostLinear>& lin
 // ---------------------------------------------------------------------------
 // training path
 // ---------------------------------------------------------------------------
-// Saved-tensor slots: train_impl.hpp (V1), train_v2_impl.hpp (V2).
+// Saved-tensor slots: train_slots.hpp.
 bool make_backward_plan(const nrf_arch& a, const std::vector<HostLinear>& lin, NetPlan& plan, std::string& err) {
     plan = NetPlan();
     if (a.net != NRF_NET_V1 && a.net != NRF_NET_V2 && a.net != NRF_NET_V3) { err = "unknown network family"; return false; }
@@ -416,53 +417,54 @@ bool make_train_plan(const nrf_arch& a, const NetPlan& fwd, const ParamLayout& l
         J.col.assign(L.col.begin() + 32 * x_first, L.col.begin() + 32 * (x_first + KT));
         tp.jobs.push_back(std::move(J));
     };
+    // the colour branch of V2 and V3: slot sizes, and the jobs of the forward plan's layers first .. first+4 (density_head,
+    // feature_head, color_layers.0 / .2 / .4) fed by the trunk output `top`
+    auto colour = [&](const ColourSlots& cs, int first, int top) {
+        tp.slot_tiles[cs.in()] = 9; tp.slot_tiles[cs.c0()] = 4; tp.slot_tiles[cs.c2()] = 2;
+        tp.slot_tiles[cs.dz_density()] = 1; tp.slot_tiles[cs.dz_c0()] = 4; tp.slot_tiles[cs.dz_c2()] = 2; tp.slot_tiles[cs.d_logits()] = 1;
+        add_job(fwd.layers[first], top, cs.dz_density(), 0, 8, true);              // density_head
+        add_job(fwd.layers[first + 1], top, cs.d_feature(), 0, 8, true);          // feature_head
+        add_job(fwd.layers[first + 2], cs.in(), cs.dz_c0(), 0, 8, true);          // color_layers.0, feature columns
+        add_job(fwd.layers[first + 2], cs.in(), cs.dz_c0(), 8, 1, false);         // color_layers.0, direction-encoding columns (bias counted above)
+        add_job(fwd.layers[first + 3], cs.c0(), cs.dz_c2(), 0, 4, true);          // color_layers.2
+        add_job(fwd.layers[first + 4], cs.c2(), cs.d_logits(), 0, 2, true);       // color_layers.4
+    };
     if (a.net == NRF_NET_V1) {
-        tp.slot_tiles.assign(2 * n + 2, 8);
-        tp.slot_tiles[0] = fwd.layers[0].KT;
-        tp.slot_tiles[2 * n + 1] = 1;
-        tp.n_mask_slots = n;                                       // plane l: ReLU of layers.{l}
-        for (int l = 0; l <= n; ++l) add_job(fwd.layers[l], l, l < n ? n + 1 + l : 2 * n + 1, 0, fwd.layers[l].KT, true);
+        const SlotsV1 S{n};
+        tp.slot_tiles.assign(S.count(), 8);
+        tp.slot_tiles[S.input()] = fwd.layers[0].KT;
+        tp.slot_tiles[S.dz_head()] = 1;
+        tp.n_mask_slots = S.planes();
+        for (int l = 0; l < n; ++l) add_job(fwd.layers[l], l ? S.trunk(l - 1) : S.input(), S.dz_trunk(l), 0, fwd.layers[l].KT, true);
+        add_job(fwd.layers[n], S.trunk(n - 1), S.dz_head(), 0, fwd.layers[n].KT, true);
         return true;
     }
     if (a.net == NRF_NET_V3) {
-        // slots and planes: train_v3_impl.hpp.  Forward plan layers: 0 F0, 1 F1, 2 A0, 3 A2, 4 F0 (second pass), 5 F1, 6 proj,
-        // 7.. trunk, then density_head, feature_head, colour layers.
-        const int KT0 = fwd.layers[0].KT, D = 11 + n;
-        tp.slot_tiles.assign(23 + 2 * n, 8);
-        tp.slot_tiles[0] = KT0; tp.slot_tiles[3] = 2; tp.slot_tiles[4] = KT0;
-        tp.slot_tiles[8 + n] = 9; tp.slot_tiles[9 + n] = 4; tp.slot_tiles[10 + n] = 2;
-        tp.slot_tiles[D + 2] = 2; tp.slot_tiles[D + 3] = 1;
-        tp.slot_tiles[D + 7 + n] = 1; tp.slot_tiles[D + 9 + n] = 4; tp.slot_tiles[D + 10 + n] = 2; tp.slot_tiles[D + 11 + n] = 1;
-        tp.n_mask_slots = 7 + n;
+        // forward plan layers: 0 F0, 1 F1, 2 A0, 3 A2, 4 F0 (second pass), 5 F1, 6 proj, 7.. trunk, then the colour branch
+        const SlotsV3 S{n};
+        const int KT0 = fwd.layers[0].KT;
+        tp.slot_tiles.assign(S.count(), 8);
+        tp.slot_tiles[S.input(0)] = KT0; tp.slot_tiles[S.attention0()] = 2; tp.slot_tiles[S.input(1)] = KT0;
+        tp.slot_tiles[S.dz_attention0()] = 2; tp.slot_tiles[S.d_gate()] = 1;
+        tp.n_mask_slots = S.planes();
         tp.aux_floats = 2;                                           // the gate (w0, w1) per sample
-        add_job(fwd.layers[0], 0, D + 0, 0, KT0, true);              // fusion.0, first pass
-        add_job(fwd.layers[4], 4, D + 4, 0, KT0, true);              // fusion.0, second pass (same weights: the sums add up)
-        add_job(fwd.layers[1], 1, D + 1, 0, 8, true);                // fusion.2, first pass
-        add_job(fwd.layers[5], 5, D + 5, 0, 8, true);                // fusion.2, second pass
-        add_job(fwd.layers[2], 2, D + 2, 0, 8, true);                // attention.0
-        add_job(fwd.layers[3], 3, D + 3, 0, 2, true);                // attention.2
-        add_job(fwd.layers[6], 6, D + 6, 0, 8, true);                // output_proj
-        for (int l = 0; l < n; ++l) add_job(fwd.layers[7 + l], 7 + l, D + 7 + l, 0, 8, true);
-        add_job(fwd.layers[7 + n], 7 + n, D + 7 + n, 0, 8, true);    // density_head
-        add_job(fwd.layers[8 + n], 7 + n, D + 8 + n, 0, 8, true);    // feature_head
-        add_job(fwd.layers[9 + n], 8 + n, D + 9 + n, 0, 8, true);    // color_layers.0, feature columns
-        add_job(fwd.layers[9 + n], 8 + n, D + 9 + n, 8, 1, false);   // color_layers.0, direction columns
-        add_job(fwd.layers[10 + n], 9 + n, D + 10 + n, 0, 4, true);  // color_layers.2
-        add_job(fwd.layers[11 + n], 10 + n, D + 11 + n, 0, 2, true); // color_layers.4
+        add_job(fwd.layers[0], S.input(0), S.dz_fusion0(0), 0, KT0, true);          // fusion.0, first pass
+        add_job(fwd.layers[4], S.input(1), S.dz_fusion0(1), 0, KT0, true);          // fusion.0, second pass (same weights: the sums add up)
+        add_job(fwd.layers[1], S.fusion0(0), S.dz_fusion2(0), 0, 8, true);          // fusion.2, first pass
+        add_job(fwd.layers[5], S.fusion0(1), S.dz_fusion2(1), 0, 8, true);          // fusion.2, second pass
+        add_job(fwd.layers[2], S.fusion2(0), S.dz_attention0(), 0, 8, true);        // attention.0
+        add_job(fwd.layers[3], S.attention0(), S.d_gate(), 0, 2, true);             // attention.2
+        add_job(fwd.layers[6], S.fusion2(1), S.dz_proj(), 0, 8, true);              // output_proj
+        for (int l = 0; l < n; ++l) add_job(fwd.layers[7 + l], l ? S.trunk(l - 1) : S.proj(), S.dz_trunk(l), 0, 8, true);
+        colour(S.colour(), 7 + n, S.trunk(n - 1));
         return true;
     }
-    tp.slot_tiles.assign(2 * n + 9, 8);
-    tp.slot_tiles[0] = fwd.layers[0].KT;
-    tp.slot_tiles[n + 1] = 9; tp.slot_tiles[n + 2] = 4; tp.slot_tiles[n + 3] = 2;
-    tp.n_mask_slots = n + 2;                                       // trunk planes 0..n-1, colour layer 0 (n), colour layer 2 (n+1)
-    tp.slot_tiles[2 * n + 4] = 1; tp.slot_tiles[2 * n + 6] = 4; tp.slot_tiles[2 * n + 7] = 2; tp.slot_tiles[2 * n + 8] = 1;
-    for (int l = 0; l < n; ++l) add_job(fwd.layers[l], l, n + 4 + l, 0, fwd.layers[l].KT, true);
-    add_job(fwd.layers[n], n, 2 * n + 4, 0, 8, true);              // density_head
-    add_job(fwd.layers[n + 1], n, 2 * n + 5, 0, 8, true);          // feature_head
-    add_job(fwd.layers[n + 2], n + 1, 2 * n + 6, 0, 8, true);      // color_layers.0, feature columns
-    add_job(fwd.layers[n + 2], n + 1, 2 * n + 6, 8, 1, false);     // color_layers.0, direction-encoding columns (bias counted above)
-    add_job(fwd.layers[n + 3], n + 2, 2 * n + 7, 0, 4, true);      // color_layers.2
-    add_job(fwd.layers[n + 4], n + 3, 2 * n + 8, 0, 2, true);      // color_layers.4
+    const SlotsV2 S{n};
+    tp.slot_tiles.assign(S.count(), 8);
+    tp.slot_tiles[S.input()] = fwd.layers[0].KT;
+    tp.n_mask_slots = S.planes();
+    for (int l = 0; l < n; ++l) add_job(fwd.layers[l], l ? S.trunk(l - 1) : S.input(), S.dz_trunk(l), 0, fwd.layers[l].KT, true);
+    colour(S.colour(), n, S.trunk(n - 1));
     return true;
 }
 

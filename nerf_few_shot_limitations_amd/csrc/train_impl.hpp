@@ -11,6 +11,9 @@
 //   repack_kernel          flat fp32 parameters -> the packed operand streams (after every optimizer step);
 //   adam_kernel            torch.optim.Adam's update on the flat vectors (train.py:113-118).
 //
+// The chain kernels of every family are written with ChainTile's blocks inside chain_kernel's frame, and index the saved
+// tensors through train_slots.hpp.
+//
 // LANE <-> SAMPLE here (not ray): a training batch is a few thousand rays (baseline.yaml:32), so the sample
 // axis, not the ray axis, has to fill the chip; compositing and its backward are the staged kernels.
 #pragma once
@@ -18,6 +21,7 @@
 
 #include "fused_impl.hpp"
 #include "train_core.hpp"
+#include "train_slots.hpp"
 
 namespace nrf {
 
@@ -153,32 +157,248 @@ __device__ __forceinline__ char* tile_ptr(const TrainKArgs& P, int slot, int64_t
 }
 
 // ---------------------------------------------------------------------------------------------
-// forward
+// the chain kernels' building blocks (slots and planes: train_slots.hpp)
 // ---------------------------------------------------------------------------------------------
-template <class Mode, int WAVES, int LP>
-__global__ void __launch_bounds__(WAVES * 64) train_forward_kernel(const TrainKArgs P) {
+// One wave's 32-sample tile of a chain kernel.  `bias` is the bias table in the saving forward chains and 32 * 8 zeros in the
+// dZ chains, which have no bias (their accumulators start at 0, boff stays 0).
+template <class Mode, int WAVES>
+struct ChainTile {
+    typedef typename Mode::Act Act;
+    typedef ActIO<Mode> IO;
+    typedef Act Tiles[8][1];              // 256 features
+    const TrainKArgs& P;
+    Pipe<WAVES>& pipe;
+    const NRF_LDS float* bias;
+    const int lane, c, h;
+    const int64_t st, raw, sid;           // sample tile; this lane's sample; the sample it reads (past the end: the last one)
+    // dZ chains: ReLU' of the layer being produced, from the forward's bit planes (train_core.hpp), and that of the layer after
+    // it, loaded one layer ahead of its use
+    i32x4 mcur, mnext;
+
+    __device__ __forceinline__ ChainTile(const TrainKArgs& P_, Pipe<WAVES>& pipe_, const NRF_LDS float* bias_, int lane_, int c_, int h_,
+                                         int64_t st_)
+        : P(P_), pipe(pipe_), bias(bias_), lane(lane_), c(c_), h(h_), st(st_), raw(st_ * 32 + c_), sid(raw < P_.n ? raw : P_.n - 1) {}
+
+    __device__ __forceinline__ void save(int slot, int t, const Act& a) const { IO::store_g(tile_ptr<Mode>(P, slot, st, t, lane), a); }
+    __device__ __forceinline__ i32x4 bits(int plane) const { return *mask_ptr(P, plane, st, lane); }
+
+    // Linear + ReLU: out = relu(W in + b), saved into `slot`, its ReLU bits into `plane`
+    template <int KT, int MT>
+    __device__ __forceinline__ void relu_layer(const Act (&in)[KT][1], Act (&out)[MT][1], int slot, int plane, int boff) {
+        i32x4 mw = {};
+        dense<Mode, KT, MT, 1>(pipe, bias + boff, h, in, [&](auto m_, f32x16(&acc)[1]) {
+            constexpr int m = decltype(m_)::value;
+            out[m][0] = Mode::template to_act<true>(acc[0]);
+            __builtin_amdgcn_sched_barrier(0);   // relu_bits is inline asm: it must come after a compiler-visible read of the accumulators (MFMA -> VALU hazard)
+            put_bits<m>(mw, relu_bits(acc[0]));
+            save(slot, m, out[m][0]);
+            if constexpr (m == MT - 1) *mask_ptr(P, plane, st, lane) = mw;
+        });
+    }
+    // Linear without activation (feature_head, output_proj; in the dZ chains: the transpose of a layer that had none),
+    // MT output tiles into out[0 .. MT-1], saved into `slot`
+    template <int MT, int KT, int NO>
+    __device__ __forceinline__ void linear(const Act (&in)[KT][1], Act (&out)[NO][1], int slot, int boff) {
+        dense<Mode, KT, MT, 1>(pipe, bias + boff, h, in, [&](auto m_, f32x16(&acc)[1]) {
+            constexpr int m = decltype(m_)::value;
+            out[m][0] = Mode::template to_act<false>(acc[0]);
+            save(slot, m, out[m][0]);
+        });
+    }
+    // dZ chain: dZ = (W^T in) under the ReLU bits in mcur, saved into `slot`
+    template <int KT, int MT>
+    __device__ __forceinline__ void masked_layer(const Act (&in)[KT][1], Act (&out)[MT][1], int slot) {
+        dense<Mode, KT, MT, 1>(pipe, bias, h, in, [&](auto m_, f32x16(&acc)[1]) {
+            constexpr int m = decltype(m_)::value;
+            out[m][0] = masked_act<Mode, m>(acc[0], mcur);
+            save(slot, m, out[m][0]);
+        });
+    }
+
+    // Forward trunk: layers j .. end-1 (8 -> 8 tiles, Linear + ReLU, bias at boff, which moves past them), ping-ponging
+    // between A and B from A, each saved into s.trunk(j) / s.plane(j).  then(X) continues on the buffer holding the last
+    // output: a compile-time choice, so that neither buffer is indexed at run time.
+    template <class S, class Then>
+    __device__ __forceinline__ void trunk_forward(const S& s, int j, int end, Tiles& A, Tiles& B, int& boff, Then&& then) {
+        auto layer = [&](const Tiles& in, Tiles& out) {
+            relu_layer(in, out, s.trunk(j), s.plane(j), boff);
+            ++j;
+            boff += 32 * 8;
+        };
+        const int count = end - j;
+        for (int p = 0; p < count / 2; ++p) {
+            layer(A, B);
+            layer(B, A);
+        }
+        if (count & 1) {
+            layer(A, B);
+            then(B);
+        } else {
+            then(A);
+        }
+    }
+    // dZ chain through the trunk of n layers: top (head^T, or [feature_head | density_head]^T) -> dZ of layer n-1 into A under
+    // mcur, then layer j^T -> dZ of layer j-1 down to dZ of layer 0, each under bits loaded while the layer before runs.
+    // then(X, Y): X holds dZ of layer 0, Y is the other buffer (compile-time choice, as in trunk_forward).
+    template <class S, int KT, class Then>
+    __device__ __forceinline__ void trunk_backward(const S& s, int n, const Act (&top)[KT][1], Tiles& A, Tiles& B, Then&& then) {
+        int below = n - 2;                // trunk layer whose bits come next
+        auto prefetch = [&]() { if (below >= 0) mnext = bits(s.plane(below)); --below; };
+        prefetch();
+        masked_layer(top, A, s.dz_trunk(n - 1));
+        mcur = mnext;
+        const int hidden = n - 1;
+        int j = n - 2;                    // the layer whose dZ is produced
+        auto layer = [&](const Tiles& in, Tiles& out) {
+            prefetch();
+            masked_layer(in, out, s.dz_trunk(j));
+            mcur = mnext;
+            --j;
+        };
+        for (int p = 0; p < hidden / 2; ++p) {
+            layer(A, B);
+            layer(B, A);
+        }
+        if (hidden & 1) {
+            masked_layer(A, B, s.dz_trunk(j));
+            then(B, A);
+        } else {
+            then(A, B);
+        }
+    }
+
+    // V2 / V3 colour branch on the trunk output X (nets.hpp:NetV2::tail with stores): density_head, feature_head, PE(dir),
+    // colour layers 0 / 2 / 4, with the bias of density_head at boff; write_rgb_density() stores the results.
+    template <int LD>
+    __device__ __forceinline__ void colour_forward(const ColourSlots& cs, const Tiles& X, int boff, float& dens_raw, float (&logit)[3]) {
+        {
+            f32x16 dens[1];
+            dense_head<Mode, 8, 1>(pipe, bias + boff, h, X, dens);
+            dens_raw = dens[0][0];
+        }
+        Act in9[9][1];
+        linear<8>(X, in9, cs.in(), boff + 32);
+        {
+            float dd[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) dd[k] = P.dir[sid * 3 + k];
+            Act t1[pe_tiles(LD)];
+            encode3<Mode, LD>(dd, h, t1);
+            in9[8][0] = t1[0];
+            save(cs.in(), 8, t1[0]);
+        }
+        Act c0[4][1], c1[2][1];
+        relu_layer(in9, c0, cs.c0(), cs.plane_c0(), boff + 32 + 32 * 8);
+        relu_layer(c0, c1, cs.c2(), cs.plane_c2(), boff + 32 + 32 * 8 + 16 * 8);
+        f32x16 rgb[1];
+        dense_head<Mode, 2, 1>(pipe, bias + boff + 32 + 32 * 8 + 16 * 8 + 8 * 8, h, c1, rgb);
+        logit[0] = rgb[0][0]; logit[1] = rgb[0][1]; logit[2] = rgb[0][2];
+    }
+    __device__ __forceinline__ void write_rgb_density(float dens_raw, const float (&logit)[3]) const {
+        if (h == 0 && raw < P.n) {
+            P.rgb[raw * 3 + 0] = sigmoid_sel<Mode::FAST_EXP>(logit[0]);
+            P.rgb[raw * 3 + 1] = sigmoid_sel<Mode::FAST_EXP>(logit[1]);
+            P.rgb[raw * 3 + 2] = sigmoid_sel<Mode::FAST_EXP>(logit[2]);
+            P.density[raw] = fmaxf(dens_raw, 0.0f);                                 // nerf_mlp.py:63
+        }
+    }
+    // V2 / V3 colour branch, dZ chain: d rgb -> d logits (sigmoid'), relu' of density_head, colour layers 4^T and 2^T under
+    // their bits, 0^T (feature columns) without: feature_vec has no activation.  Leaves in9 = [d feature_vec | dZ density_head],
+    // the operand of the trunk's top layer, and mcur = the bits of trunk plane top_plane.
+    __device__ __forceinline__ void colour_backward(const ColourSlots& cs, int top_plane, Act (&in9)[9][1]) {
+        mcur = bits(cs.plane_c2());
+        mnext = bits(cs.plane_c0());
+        Act G[1][1], d1[2][1], d0[4][1];
+        {
+            f32x16 e = {};
+            float ds = 0.0f;
+            if (h == 0 && raw < P.n) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float o = P.rgb[raw * 3 + k];
+                    e[k] = P.g_rgb[raw * 3 + k] * o * (1.0f - o);
+                }
+                ds = P.density[raw] > 0.0f ? P.g_density[raw] : 0.0f;          // relu' of density_head (nerf_mlp.py:63)
+            }
+            G[0][0] = Mode::template to_act<false>(e);
+            save(cs.d_logits(), 0, G[0][0]);
+            f32x16 e2 = {};
+            e2[0] = ds;
+            in9[8][0] = Mode::template to_act<false>(e2);
+            save(cs.dz_density(), 0, in9[8][0]);
+        }
+        masked_layer(G, d1, cs.dz_c2());
+        mcur = mnext;
+        mnext = bits(top_plane);
+        masked_layer(d1, d0, cs.dz_c0());
+        mcur = mnext;
+        linear<8>(d0, in9, cs.d_feature(), 0);
+    }
+};
+
+// The frame of every chain kernel: the LDS carve-out, the bias table (FORWARD) or the zero bias of the dZ chains, the weight
+// pipe, and the persistent walk over this workgroup's tiles; body(T) runs one tile of this wave (a ChainTile).
+template <class Mode, int WAVES, bool FORWARD, class Body>
+__device__ __forceinline__ void chain_kernel(const TrainKArgs& P, Body&& body) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     NRF_LDS char* lds = (NRF_LDS char*)smem;
     NRF_LDS float* bias = (NRF_LDS float*)(lds + kLdsRing);
-    typedef typename Mode::Act Act;
-    typedef ActIO<Mode> IO;
-    constexpr int KT0 = pe_tiles(LP), HT = 8, PE = pe_dim(LP);
-
     const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    load_bias_table(bias, P.net.bias, P.net.n_bias);
+    if constexpr (FORWARD) {
+        load_bias_table(bias, P.net.bias, P.net.n_bias);
+    } else {
+        for (int i = threadIdx.x; i < 32 * 8; i += blockDim.x) bias[i] = 0.0f;
+        __syncthreads();
+    }
     Pipe<WAVES> pipe;
     pipe.init(P.net.stream, P.net.n_chunks, lds);
     pipe.start();
-
     for (int64_t tile = blockIdx.x; tile < P.n_tiles; tile += gridDim.x) {
-        const int64_t st = tile * WAVES + wave;                  // this wave's 32-sample tile
-        const int64_t raw = st * 32 + c;
-        const int64_t sid = raw < P.n ? raw : P.n - 1;
-        Act A[HT][1], B[HT][1];
+        ChainTile<Mode, WAVES> T(P, pipe, bias, lane, c, h, tile * WAVES + wave);
+        body(T);
+    }
+    pipe.drain();
+}
+
+namespace {
+
+// The launch body of every family's chain launchers (train_v*.hip): F::check, then the chain kernel
+// F::forward<ChainGeo> / F::backward<ChainGeo> at the mode's geometry; the dZ chains stream the transposed weights and are
+// followed by the weight gradients.
+template <class F, bool FORWARD>
+int run_chain(const DeviceNet& net, const TrainDev& t, int mode, TrainKArgs k, float* grad, hipStream_t s, std::string& err) {
+    if (!F::check(net, t, mode, err)) return NRF_EINVAL;
+    const int64_t n = k.n;
+    if (n <= 0) return NRF_OK;
+    if (!fill_slots(t, mode, n, k, err)) return NRF_EINVAL;
+    const int r = dispatch_chain(net, mode, n, [&](auto g) {
+        typedef decltype(g) G;
+        if constexpr (FORWARD)
+            return launch_persistent<F::template forward<G>, G::kWaves>(net, net_args(net, mode), k, tiles32(n) / G::kWaves, s, "train forward", err);
+        else
+            return launch_persistent<F::template backward<G>, G::kWaves>(net, backward_net_args(net, t, mode), k, tiles32(n) / G::kWaves, s,
+                                                                         "train backward", err);
+    });
+    if (FORWARD || r != NRF_OK) return r;
+    return launch_weight_grad(net, t, mode, k, grad, s, err);
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
+// V1 forward
+// ---------------------------------------------------------------------------------------------
+template <class Mode, int WAVES, int LP>
+__global__ void __launch_bounds__(WAVES * 64) train_forward_kernel(const TrainKArgs P) {
+    typedef typename Mode::Act Act;
+    constexpr int KT0 = pe_tiles(LP), PE = pe_dim(LP);
+    chain_kernel<Mode, WAVES, true>(P, [&](ChainTile<Mode, WAVES>& T) {
+        const int h = T.h;
+        Act A[8][1], B[8][1];
         {
             Act enc[KT0][1];
-            const float* xin = P.x_enc + sid * PE;
+            const float* xin = P.x_enc + T.sid * PE;
             f32x16 e[KT0];
             static_for<16 * KT0>([&](auto u_) {                  // positional_encoding.py order -> operand order (feature_map.hpp)
                 constexpr int u = decltype(u_)::value;
@@ -192,122 +412,48 @@ __global__ void __launch_bounds__(WAVES * 64) train_forward_kernel(const TrainKA
 #pragma unroll
             for (int t = 0; t < KT0; ++t) {
                 enc[t][0] = Mode::template to_act<false>(e[t]);
-                IO::store_g(tile_ptr<Mode>(P, 0, st, t, lane), enc[t][0]);
+                T.save(SlotsV1::input(), t, enc[t][0]);
             }
-            i32x4 mw;
-            dense<Mode, KT0, HT, 1>(pipe, bias, h, enc, [&](auto m_, f32x16(&acc)[1]) {
-                constexpr int m = decltype(m_)::value;                A[m][0] = Mode::template to_act<true>(acc[0]);
-                __builtin_amdgcn_sched_barrier(0);   // relu_bits is inline asm: it must come after a compiler-visible read of the accumulators (MFMA -> VALU hazard)
-
-                put_bits<m>(mw, relu_bits(acc[0]));
-                IO::store_g(tile_ptr<Mode>(P, 1, st, m, lane), A[m][0]);
-                if constexpr (m == HT - 1) *mask_ptr(P, 0, st, lane) = mw;
-            });
+            T.relu_layer(enc, A, SlotsV1::trunk(0), SlotsV1::plane(0), 0);
         }
-        // trunk layer writing activation slot `slot` (and the mask plane slot - 1)
-        auto layer = [&](const Act (&in)[HT][1], Act (&out)[HT][1], int slot, int boff) {
-            i32x4 mw;
-            dense<Mode, HT, HT, 1>(pipe, bias + boff, h, in, [&](auto m_, f32x16(&acc)[1]) {
-                constexpr int m = decltype(m_)::value;                out[m][0] = Mode::template to_act<true>(acc[0]);
-                __builtin_amdgcn_sched_barrier(0);   // relu_bits is inline asm: it must come after a compiler-visible read of the accumulators (MFMA -> VALU hazard)
-
-                put_bits<m>(mw, relu_bits(acc[0]));
-                IO::store_g(tile_ptr<Mode>(P, slot, st, m, lane), out[m][0]);
-                if constexpr (m == HT - 1) *mask_ptr(P, slot - 1, st, lane) = mw;
-            });
-        };
-        int boff = 32 * HT, slot = 2;
-        const int hidden = P.net.n_layers - 1;
-        for (int p = 0; p < hidden / 2; ++p) {
-            layer(A, B, slot++, boff); boff += 32 * HT;
-            layer(B, A, slot++, boff); boff += 32 * HT;
-        }
+        const SlotsV1 S{P.net.n_layers};
+        int boff = 32 * 8;
         f32x16 head[1];
-        if (hidden & 1) {
-            layer(A, B, slot++, boff); boff += 32 * HT;
-            dense_head<Mode, HT, 1>(pipe, bias + boff, h, B, head);
-        } else {
-            dense_head<Mode, HT, 1>(pipe, bias + boff, h, A, head);
-        }
-        if (h == 0 && raw < P.n) {
+        T.trunk_forward(S, 1, S.n, A, B, boff, [&](const Act (&X)[8][1]) { dense_head<Mode, 8, 1>(T.pipe, T.bias + boff, h, X, head); });
+        if (h == 0 && T.raw < P.n) {
             const float r = sigmoid_sel<Mode::FAST_EXP>(head[0][0]), g = sigmoid_sel<Mode::FAST_EXP>(head[0][1]),
                         b = sigmoid_sel<Mode::FAST_EXP>(head[0][2]);
-            *(float4*)(P.out4 + raw * 4) = make_float4(r, g, b, head[0][3]);      // nerf_model.py:22-24
+            *(float4*)(P.out4 + T.raw * 4) = make_float4(r, g, b, head[0][3]);      // nerf_model.py:22-24
         }
-    }
-    pipe.drain();
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
-// backward chain
+// V1 backward chain
 // ---------------------------------------------------------------------------------------------
-// ReLU' comes from the forward's bit planes (train_core.hpp), 16 B per lane and layer, loaded one layer ahead
 template <class Mode, int WAVES, int LP>
 __global__ void __launch_bounds__(WAVES * 64) train_backward_kernel(const TrainKArgs P) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    NRF_LDS char* lds = (NRF_LDS char*)smem;
-    NRF_LDS float* zero_bias = (NRF_LDS float*)(lds + kLdsRing);
     typedef typename Mode::Act Act;
-    typedef ActIO<Mode> IO;
-    constexpr int HT = 8;
-
-    const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (int i = threadIdx.x; i < 32 * HT; i += blockDim.x) zero_bias[i] = 0.0f;     // the chain has no bias: accumulators start at 0
-    __syncthreads();
-    Pipe<WAVES> pipe;
-    pipe.init(P.net.stream, P.net.n_chunks, lds);
-    pipe.start();
-    const int n = P.net.n_layers;
-
-    for (int64_t tile = blockIdx.x; tile < P.n_tiles; tile += gridDim.x) {
-        const int64_t st = tile * WAVES + wave;
-        const int64_t raw = st * 32 + c;
-        // ReLU' bits of trunk layer L (mask plane L - 1), loaded one layer ahead of their use
-        i32x4 mcur = *mask_ptr(P, n - 1, st, lane), mnext = mcur;
-
+    chain_kernel<Mode, WAVES, false>(P, [&](ChainTile<Mode, WAVES>& T) {
+        const SlotsV1 S{P.net.n_layers};
+        T.mcur = T.mnext = T.bits(S.plane(S.n - 1));
         Act G[1][1];
         {   // d out4 -> d [rgb logits, sigma]: rows 0..3 of one operand tile (registers 0..3 of lane half 0)
             f32x16 e = {};
-            if (h == 0 && raw < P.n) {
-                const float4 o = *(const float4*)(P.out4 + raw * 4);
-                const float4 g = *(const float4*)(P.g_out4 + raw * 4);
+            if (T.h == 0 && T.raw < P.n) {
+                const float4 o = *(const float4*)(P.out4 + T.raw * 4);
+                const float4 g = *(const float4*)(P.g_out4 + T.raw * 4);
                 e[0] = g.x * o.x * (1.0f - o.x);                                    // sigmoid'
                 e[1] = g.y * o.y * (1.0f - o.y);
                 e[2] = g.z * o.z * (1.0f - o.z);
                 e[3] = g.w;                                                         // sigma_out has no activation
             }
             G[0][0] = Mode::template to_act<false>(e);
-            IO::store_g(tile_ptr<Mode>(P, 2 * n + 1, st, 0, lane), G[0][0]);
+            T.save(S.dz_head(), 0, G[0][0]);
         }
-        Act A[HT][1], B[HT][1];
-        auto epilogue = [&](auto m_, f32x16(&acc)[1], Act (&out)[HT][1], int slot_dz) {
-            constexpr int m = decltype(m_)::value;
-            out[m][0] = masked_act<Mode, m>(acc[0], mcur);
-            IO::store_g(tile_ptr<Mode>(P, slot_dz, st, m, lane), out[m][0]);
-        };
-        int below = n - 2;            // mask plane of the layer under the one being produced
-        auto prefetch = [&]() { if (below >= 0) mnext = *mask_ptr(P, below, st, lane); --below; };
-        // head^T -> dZ of layers.{n-1}
-        prefetch();
-        dense<Mode, 1, HT, 1>(pipe, zero_bias, h, G, [&](auto m_, f32x16(&acc)[1]) { epilogue(m_, acc, A, 2 * n); });
-        mcur = mnext;
-        // layers.l^T, l = n-1 .. 1: dZ_l -> dZ_{l-1}
-        const int hidden = n - 1;
-        int slot = 2 * n - 1;
-        for (int p = 0; p < hidden / 2; ++p) {
-            prefetch();
-            dense<Mode, HT, HT, 1>(pipe, zero_bias, h, A, [&](auto m_, f32x16(&acc)[1]) { epilogue(m_, acc, B, slot); });
-            mcur = mnext; --slot;
-            prefetch();
-            dense<Mode, HT, HT, 1>(pipe, zero_bias, h, B, [&](auto m_, f32x16(&acc)[1]) { epilogue(m_, acc, A, slot); });
-            mcur = mnext; --slot;
-        }
-        if (hidden & 1) {
-            dense<Mode, HT, HT, 1>(pipe, zero_bias, h, A, [&](auto m_, f32x16(&acc)[1]) { epilogue(m_, acc, B, slot); });
-        }
-    }
-    pipe.drain();
+        Act A[8][1], B[8][1];
+        T.trunk_backward(S, S.n, G, A, B, [](const Act (&)[8][1], const Act (&)[8][1]) {});
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
