@@ -155,6 +155,49 @@ int nrf_render_cameras_tiles(const nrf_model* m, int H, int W, float focal, cons
                              const nrf_render_opts* opts,
                              float* rgb, float* depth, float* weights, float* z_vals, void* stream);
 
+/* ---- tail mode: a 16-bit render whose last sample is evaluated in split-f16 -------------
+ *
+ * The reference composites a ray's last sample with dists[-1] = 1e10 (nerf_mlp.py:182): its
+ * opacity is 1 if sigma_last > 0 and 0 otherwise, so on a ray whose last density is ~ 0 any
+ * rounding of the network flips a weight of size T_last.  That one rule is the source of every
+ * large single-pixel error of NRF_MMA_BF16 / NRF_MMA_F16.  The *_tail entry points march samples
+ * 0 .. S-2 exactly as the plain call in opts->mma_mode (bf16 or f16) does -- weights[:, :S-1] and
+ * z_vals are its bits -- and evaluate sample S-1 (encoding, network, sigmoid / exp of the
+ * compositor step) with the arithmetic of NRF_MMA_F16X3, then run the plain epilogue.  With
+ * n_samples == 1 the result is the NRF_MMA_F16X3 render's, bit for bit.
+ *
+ * Two launches on the caller's stream (one when n_samples == 1); between them the six compositor
+ * floats of every ray (T, r, g, b, depth, acc) rest in the caller's `workspace`.  The library
+ * still allocates nothing.  A tail render READS TWO WEIGHT STREAMS of the model: the one of
+ * opts->mma_mode and the one of NRF_MMA_F16X3 -- after nrf_model_update_device both bits must
+ * have been in a mode_mask since the parameters last changed.
+ *
+ * Refused with NRF_EINVAL: tail == NULL, a tail mode other than NRF_MMA_F16X3, a base mode other
+ * than NRF_MMA_BF16 / NRF_MMA_F16, a workspace that is NULL, smaller than nrf_render_tail_bytes
+ * or not 16-byte aligned, and ert_eps > 0: the ray-queue kernel is deliberately not part of this
+ * mode (a ray that terminated early has, by construction, a tail worth less than eps). */
+typedef struct nrf_tail {
+    int32_t mode;             /* arithmetic of the last sample: NRF_MMA_F16X3 */
+    void*   workspace;        /* device, 16-byte aligned, written and read by the call */
+    int64_t workspace_bytes;  /* >= nrf_render_tail_bytes of the call's ray count */
+} nrf_tail;
+
+/* Bytes of workspace a tail render of n_rays rays needs (24 per ray, rounded up to 16); -1 if n_rays < 0.
+ * For nrf_render_cameras_tiles_tail n_rays = n_cams * n_tiles * tile_rays. */
+int64_t nrf_render_tail_bytes(int64_t n_rays);
+
+/* nrf_render_rays / nrf_render_camera / nrf_render_cameras_tiles with a tail: same arguments, same outputs. */
+int nrf_render_rays_tail(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays,
+                         const nrf_render_opts* opts, const nrf_tail* tail,
+                         float* rgb, float* depth, float* weights, float* z_vals, void* stream);
+int nrf_render_camera_tail(const nrf_model* m, int H, int W, float focal, const float c2w[12],
+                           int64_t ray_begin, int64_t ray_end, const nrf_render_opts* opts, const nrf_tail* tail,
+                           float* rgb, float* depth, float* weights, float* z_vals, void* stream);
+int nrf_render_cameras_tiles_tail(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams,
+                                  int64_t tile_rays, int64_t first_tile, int64_t tile_step, int64_t n_tiles,
+                                  const nrf_render_opts* opts, const nrf_tail* tail,
+                                  float* rgb, float* depth, float* weights, float* z_vals, void* stream);
+
 /* ---- staged entry points (one reference leaf each; used by the drop-in
  *      Python surface and by the stage-wise parity tests) ------------------- */
 
@@ -221,7 +264,7 @@ int nrf_debug_train_plan(const nrf_arch* arch, const nrf_linear* linears, int n_
 const char* nrf_last_error(void);
 int nrf_abi_version(void);
 /* sizeof() of the ABI structs as this library was compiled (0: nrf_arch, 1: nrf_linear, 2: nrf_dino,
- * 3: nrf_render_opts; -1 otherwise): lets a binding check its struct declarations before the first call. */
+ * 3: nrf_render_opts, 4: nrf_tail; -1 otherwise): lets a binding check its struct declarations before the first call. */
 int nrf_abi_sizeof(int which);
 /* name / average duration bookkeeping is the caller's business: the library never times anything. */
 
@@ -245,7 +288,10 @@ int64_t nrf_param_count(const nrf_model* m);
  * mode_mask (bit NRF_MMA_*) from flat_params, plus the bias table.  Enqueued on
  * `stream`; a single mode is one kernel launch.  The streams of the modes NOT in the
  * mask keep the previous parameters (a later render / backward in such a mode needs
- * its own update; nrf_mlp_backward* refuses stale backward weights). */
+ * its own update; nrf_mlp_backward* refuses stale backward weights).  A tail render
+ * (nrf_render_*_tail) reads two streams: put the base mode's bit and NRF_MMA_F16X3's into
+ * ONE mask -- a second call for the other mode would mark the first one's backward weights
+ * stale. */
 int nrf_model_update_device(nrf_model* m, const float* flat_params, int mode_mask, void* stream);
 
 /* Bytes of saved tensors ("context") a forward_train/backward pair needs for n

@@ -18,6 +18,9 @@ NRF_NET_V1, NRF_NET_V2, NRF_NET_V3 = 1, 2, 3
 MMA_MODES = {"bf16": 0, "f16": 1, "f32": 2, "f16x3": 3}
 # the training kernels are built for the first three; a module in the split mode (fp32-class results) trains in exact fp32
 TRAIN_MODE = {"bf16": "bf16", "f16": "f16", "f32": "f32", "f16x3": "f32"}
+# tail mode (nerfhip.h: nrf_tail): the arithmetic of a 16-bit render's last sample, and the base modes that take one
+TAIL_MODES = {"f16x3": 3}
+TAIL_BASE_MODES = ("bf16", "f16")
 ERRORS = {-1: "NRF_EINVAL", -2: "NRF_EUNSUPPORTED", -3: "NRF_EHIP", -4: "NRF_ENOMEM"}
 
 c_float_p = C.POINTER(C.c_float)
@@ -49,6 +52,10 @@ class nrf_render_opts(C.Structure):
                 ("white_bkgd", C.c_int32), ("mma_mode", C.c_int32), ("dino", C.POINTER(nrf_dino)), ("out_rgbd", C.c_int32)]
 
 
+class nrf_tail(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 # name -> (restype, argtypes); tests/test_packing_emulation.py checks this table against include/nerfhip.h
 SIGNATURES = {
     "nrf_abi_version": (C.c_int, []),
@@ -64,6 +71,14 @@ SIGNATURES = {
                                     C.POINTER(nrf_render_opts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_render_cameras_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                            C.c_int64, C.POINTER(nrf_render_opts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_render_tail_bytes": (C.c_int64, [C.c_int64]),
+    "nrf_render_rays_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(nrf_render_opts), C.POINTER(nrf_tail),
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_render_camera_tail": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float * 12, C.c_int64, C.c_int64,
+                                         C.POINTER(nrf_render_opts), C.POINTER(nrf_tail), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_render_cameras_tiles_tail": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                                C.c_int64, C.POINTER(nrf_render_opts), C.POINTER(nrf_tail), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
     "nrf_get_rays": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float * 12, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_sample_along_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -121,7 +136,7 @@ def lib() -> C.CDLL:
                 fn.restype, fn.argtypes = res, args
             if handle.nrf_abi_version() != 5:
                 raise RuntimeError("libnerfhip.so ABI version mismatch")
-            for which, st in enumerate((nrf_arch, nrf_linear, nrf_dino, nrf_render_opts)):
+            for which, st in enumerate((nrf_arch, nrf_linear, nrf_dino, nrf_render_opts, nrf_tail)):
                 if handle.nrf_abi_sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libnerfhip.so: sizeof({st.__name__}) differs from the ctypes declaration")
             _lib = handle
@@ -187,6 +202,30 @@ def require_gpu():
 
 _ladders = {}
 _u_rows = {}
+_tail_ws = {}
+
+
+def tail_arg(tail_mode, mma_mode, n_rays, device):
+    """The `const nrf_tail*` of a *_tail entry point for a render of n_rays rays in `mma_mode` on `device`, or None for
+    tail_mode=None.  The carry workspace (24 bytes per ray) is cached per (device, ray count, stream) like the ladders: the two
+    launches of a render and the renders that follow on the same stream use it in order.  Call with `device` current.
+    Returns (nrf_tail struct, workspace tensor to keep alive)."""
+    if tail_mode is None:
+        return None, None
+    if tail_mode not in TAIL_MODES:
+        raise ValueError(f"tail_mode must be None or one of {sorted(TAIL_MODES)}, got {tail_mode!r}")
+    if mma_mode not in TAIL_BASE_MODES:
+        raise ValueError(f"tail_mode needs a 16-bit mma_mode {TAIL_BASE_MODES}, got {mma_mode!r}")
+    key = (str(device), int(n_rays), stream_ptr())
+    ws = _tail_ws.get(key)
+    if ws is None:
+        nbytes = lib().nrf_render_tail_bytes(int(n_rays))
+        ws = torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=device)
+        if len(_tail_ws) > 16:
+            _tail_ws.clear()
+        _tail_ws[key] = ws
+    t = nrf_tail(TAIL_MODES[tail_mode], ws.data_ptr(), ws.numel() * 4)
+    return t, ws
 
 
 def u_row(n_importance, device):

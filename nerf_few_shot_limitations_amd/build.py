@@ -26,7 +26,9 @@ INCLUDE = os.path.join(os.path.dirname(PKG), "include")
 HALF16 = ["-DNRF_TU_HALF=16", "-DNRF_ACT_AGPR=1", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 HALF32 = ["-DNRF_TU_HALF=32"]
 FUSED = [(f"fused_{fam}.hip", f"fused_{fam}_{half}", flags) for fam in ("v1", "v2", "v3", "v3w") for half, flags in (("16", HALF16), ("32", HALF32))]
-SOURCES = FUSED + [(f, os.path.splitext(f)[0], []) for f in
+# tail mode (fused_impl.hpp: render_march): the last-sample kernels of all four families, split-f16 only
+TAIL = [("fused_tail.hip", "fused_tail", HALF32)]
+SOURCES = FUSED + TAIL + [(f, os.path.splitext(f)[0], []) for f in
                    ("fused_kernels.hip", "train_shared.hip", "train_v1.hip", "train_v2.hip", "train_v3.hip", "staged_kernels.hip", "api.cpp",
                     "packing.cpp")]
 # -Rpass-analysis=kernel-resource-usage: the backend reports every kernel's registers / spills / scratch; kept beside the object

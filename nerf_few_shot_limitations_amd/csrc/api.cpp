@@ -233,6 +233,34 @@ void fill_common(nrf::RenderArgs& a, const nrf_render_opts* o, float* rgb, float
     a.rgb = rgb; a.depth = depth; a.weights = weights; a.z_vals = z_vals;
 }
 
+// the tail description of a *_tail entry point against the call's options and ray count (nerfhip.h: nrf_tail)
+int check_tail(const nrf_render_opts* o, const nrf_tail* t, int64_t n_rays) {
+    if (!t) return fail(NRF_EINVAL, "tail is NULL");
+    if (t->mode != NRF_MMA_F16X3) return fail(NRF_EINVAL, "tail mode must be NRF_MMA_F16X3");
+    if (o->mma_mode != NRF_MMA_BF16 && o->mma_mode != NRF_MMA_F16)
+        return fail(NRF_EINVAL, "a tail render needs a 16-bit base mode (NRF_MMA_BF16 or NRF_MMA_F16): the parity modes have no last-sample flips to repair");
+    if (o->ert_eps > 0.0f) return fail(NRF_EINVAL, "a tail render takes ert_eps == 0: the ray-queue kernel is not part of the tail mode");
+    if (!t->workspace) return fail(NRF_EINVAL, "tail workspace is NULL");
+    if ((reinterpret_cast<uintptr_t>(t->workspace) & 15u) != 0) return fail(NRF_EINVAL, "tail workspace must be 16-byte aligned");
+    if (t->workspace_bytes < nrf_render_tail_bytes(n_rays)) return fail(NRF_EINVAL, "tail workspace smaller than nrf_render_tail_bytes");
+    return NRF_OK;
+}
+
+// the launch of a render entry point: plain, or prefix + tail through the caller's workspace
+int launch_any(const nrf_model* m, const nrf_render_opts* opts, const nrf_tail* tail, const nrf::RenderArgs& a, void* stream, std::string& err) {
+    if (tail) return nrf::launch_render_tail(m->net, opts->mma_mode, a, static_cast<float*>(tail->workspace), (hipStream_t)stream, err);
+    return nrf::launch_render(m->net, opts->mma_mode, a, (hipStream_t)stream, err);
+}
+
+int render_rays_any(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays, const nrf_render_opts* opts,
+                    const nrf_tail* tail, bool tailed, float* rgb, float* depth, float* weights, float* z_vals, void* stream);
+int render_camera_any(const nrf_model* m, int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
+                      const nrf_render_opts* opts, const nrf_tail* tail, bool tailed, float* rgb, float* depth, float* weights, float* z_vals,
+                      void* stream);
+int render_cameras_tiles_any(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams, int64_t tile_rays,
+                             int64_t first_tile, int64_t tile_step, int64_t n_tiles, const nrf_render_opts* opts, const nrf_tail* tail,
+                             bool tailed, float* rgb, float* depth, float* weights, float* z_vals, void* stream);
+
 }  // namespace
 
 extern "C" {
@@ -245,6 +273,7 @@ int nrf_abi_sizeof(int which) {
         case 1: return (int)sizeof(nrf_linear);
         case 2: return (int)sizeof(nrf_dino);
         case 3: return (int)sizeof(nrf_render_opts);
+        case 4: return (int)sizeof(nrf_tail);
         default: return -1;
     }
 }
@@ -312,8 +341,48 @@ void nrf_model_destroy(nrf_model* m) {
 
 int64_t nrf_model_flops_per_sample(const nrf_model* m) { return m ? m->plan.flops_per_sample : 0; }
 
+int64_t nrf_render_tail_bytes(int64_t n_rays) {
+    if (n_rays < 0) { (void)fail(NRF_EINVAL, "nrf_render_tail_bytes: n_rays < 0"); return -1; }
+    return (nrf::render_tail_floats(n_rays) * (int64_t)sizeof(float) + 15) & ~(int64_t)15;
+}
+
 int nrf_render_rays(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays, const nrf_render_opts* opts,
                     float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
+    return render_rays_any(m, rays_o, rays_d, n_rays, opts, nullptr, false, rgb, depth, weights, z_vals, stream);
+}
+int nrf_render_rays_tail(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays, const nrf_render_opts* opts,
+                         const nrf_tail* tail, float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
+    return render_rays_any(m, rays_o, rays_d, n_rays, opts, tail, true, rgb, depth, weights, z_vals, stream);
+}
+int nrf_render_camera(const nrf_model* m, int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
+                      const nrf_render_opts* opts, float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
+    return render_camera_any(m, H, W, focal, c2w, ray_begin, ray_end, opts, nullptr, false, rgb, depth, weights, z_vals, stream);
+}
+int nrf_render_camera_tail(const nrf_model* m, int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
+                           const nrf_render_opts* opts, const nrf_tail* tail, float* rgb, float* depth, float* weights, float* z_vals,
+                           void* stream) {
+    return render_camera_any(m, H, W, focal, c2w, ray_begin, ray_end, opts, tail, true, rgb, depth, weights, z_vals, stream);
+}
+int nrf_render_cameras_tiles(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams, int64_t tile_rays,
+                             int64_t first_tile, int64_t tile_step, int64_t n_tiles, const nrf_render_opts* opts, float* rgb, float* depth,
+                             float* weights, float* z_vals, void* stream) {
+    return render_cameras_tiles_any(m, H, W, focal, c2w, n_cams, tile_rays, first_tile, tile_step, n_tiles, opts, nullptr, false, rgb, depth,
+                                    weights, z_vals, stream);
+}
+int nrf_render_cameras_tiles_tail(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams, int64_t tile_rays,
+                                  int64_t first_tile, int64_t tile_step, int64_t n_tiles, const nrf_render_opts* opts, const nrf_tail* tail,
+                                  float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
+    return render_cameras_tiles_any(m, H, W, focal, c2w, n_cams, tile_rays, first_tile, tile_step, n_tiles, opts, tail, true, rgb, depth,
+                                    weights, z_vals, stream);
+}
+
+extern "C++" {
+namespace {
+
+// The three render entry points, plain (tailed == false) and with a tail (nerfhip.h: nrf_tail), which is checked once the call's
+// ray count is known.
+int render_rays_any(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays, const nrf_render_opts* opts,
+                    const nrf_tail* tail, bool tailed, float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
     if (rgbd_misaligned(opts, rgb)) return fail(NRF_EINVAL, kRgbdAlign);
     if (!m) return fail(NRF_EINVAL, "model is NULL");
     if (n_rays < 0) return fail(NRF_EINVAL, "n_rays < 0");
@@ -322,6 +391,7 @@ int nrf_render_rays(const nrf_model* m, const float* rays_o, const float* rays_d
     if (rc != NRF_OK) return rc;
     if (!rays_o || !rays_d || !rgb || (!depth && !opts->out_rgbd)) return fail(NRF_EINVAL, "nrf_render_rays: null ray or output pointer");
     if ((int64_t)opts->n_samples * n_rays > (int64_t)1 << 40) return fail(NRF_EINVAL, "ray-sample count too large");
+    if (tailed && check_tail(opts, tail, n_rays) != NRF_OK) return NRF_EINVAL;
     nrf::RenderArgs a{};
     a.rays_o = rays_o; a.rays_d = rays_d; a.camera_mode = 0; a.ray_begin = 0; a.n_rays = n_rays;
     a.n_cams = 1; a.rays_per_cam = n_rays; a.tile_rays = n_rays; a.tile_stride = 0;
@@ -330,12 +400,13 @@ int nrf_render_rays(const nrf_model* m, const float* rays_o, const float* rays_d
     if (m->arch.net == NRF_NET_V3 && !make_dino(opts->dino, m->arch.dino_dim, a.dino, err)) return fail(NRF_EINVAL, err);
     DeviceGuard guard(m->device);
     if (!guard.ok) return fail(NRF_EHIP, "cannot select the model's device");
-    const int r = nrf::launch_render(m->net, opts->mma_mode, a, (hipStream_t)stream, err);
+    const int r = launch_any(m, opts, tail, a, stream, err);
     return r == NRF_OK ? NRF_OK : fail(r, err);
 }
 
-int nrf_render_camera(const nrf_model* m, int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
-                      const nrf_render_opts* opts, float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
+int render_camera_any(const nrf_model* m, int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
+                      const nrf_render_opts* opts, const nrf_tail* tail, bool tailed, float* rgb, float* depth, float* weights, float* z_vals,
+                      void* stream) {
     if (rgbd_misaligned(opts, rgb)) return fail(NRF_EINVAL, kRgbdAlign);
     if (!m) return fail(NRF_EINVAL, "model is NULL");
     if (H < 1 || W < 1 || !(focal > 0.0f) || !c2w) return fail(NRF_EINVAL, "bad camera");
@@ -344,6 +415,7 @@ int nrf_render_camera(const nrf_model* m, int H, int W, float focal, const float
     const int rc = check_opts(opts);
     if (rc != NRF_OK) return rc;
     if (!rgb || (!depth && !opts->out_rgbd)) return fail(NRF_EINVAL, "nrf_render_camera: null output pointer");
+    if (tailed && check_tail(opts, tail, ray_end - ray_begin) != NRF_OK) return NRF_EINVAL;
     nrf::RenderArgs a{};
     a.camera_mode = 1; a.n_cams = 1; a.cams[0] = make_camera(H, W, focal, c2w); a.ray_begin = ray_begin; a.n_rays = ray_end - ray_begin;
     a.rays_per_cam = a.n_rays; a.tile_rays = a.n_rays; a.tile_stride = 0;
@@ -352,13 +424,13 @@ int nrf_render_camera(const nrf_model* m, int H, int W, float focal, const float
     if (m->arch.net == NRF_NET_V3 && !make_dino(opts->dino, m->arch.dino_dim, a.dino, err)) return fail(NRF_EINVAL, err);
     DeviceGuard guard(m->device);
     if (!guard.ok) return fail(NRF_EHIP, "cannot select the model's device");
-    const int r = nrf::launch_render(m->net, opts->mma_mode, a, (hipStream_t)stream, err);
+    const int r = launch_any(m, opts, tail, a, stream, err);
     return r == NRF_OK ? NRF_OK : fail(r, err);
 }
 
-int nrf_render_cameras_tiles(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams, int64_t tile_rays,
-                             int64_t first_tile, int64_t tile_step, int64_t n_tiles, const nrf_render_opts* opts, float* rgb, float* depth,
-                             float* weights, float* z_vals, void* stream) {
+int render_cameras_tiles_any(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams, int64_t tile_rays,
+                             int64_t first_tile, int64_t tile_step, int64_t n_tiles, const nrf_render_opts* opts, const nrf_tail* tail,
+                             bool tailed, float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
     if (rgbd_misaligned(opts, rgb)) return fail(NRF_EINVAL, kRgbdAlign);
     if (!m) return fail(NRF_EINVAL, "model is NULL");
     if (H < 1 || W < 1 || !(focal > 0.0f) || !c2w) return fail(NRF_EINVAL, "bad camera");
@@ -370,6 +442,7 @@ int nrf_render_cameras_tiles(const nrf_model* m, int H, int W, float focal, cons
     if (rc != NRF_OK) return rc;
     if (!rgb || (!depth && !opts->out_rgbd)) return fail(NRF_EINVAL, "nrf_render_cameras_tiles: null output pointer");
     if (opts->t_rand || opts->z_in) return fail(NRF_EINVAL, "tile rendering takes no per-ray inputs (t_rand and z_in must be NULL)");
+    if (tailed && check_tail(opts, tail, n_tiles * tile_rays * n_cams) != NRF_OK) return NRF_EINVAL;
     nrf::RenderArgs a{};
     a.camera_mode = 1; a.n_cams = n_cams;
     for (int c = 0; c < n_cams; ++c) a.cams[c] = make_camera(H, W, focal, c2w + 12 * c);
@@ -380,9 +453,12 @@ int nrf_render_cameras_tiles(const nrf_model* m, int H, int W, float focal, cons
     if (m->arch.net == NRF_NET_V3 && !make_dino(opts->dino, m->arch.dino_dim, a.dino, err)) return fail(NRF_EINVAL, err);
     DeviceGuard guard(m->device);
     if (!guard.ok) return fail(NRF_EHIP, "cannot select the model's device");
-    const int r = nrf::launch_render(m->net, opts->mma_mode, a, (hipStream_t)stream, err);
+    const int r = launch_any(m, opts, tail, a, stream, err);
     return r == NRF_OK ? NRF_OK : fail(r, err);
 }
+
+}  // namespace
+}  // extern "C++"
 
 int nrf_get_rays(int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end, float* rays_o, float* rays_d,
                  void* stream) {

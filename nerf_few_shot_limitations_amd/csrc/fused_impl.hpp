@@ -35,6 +35,7 @@ struct RenderKArgs {
     NetArgs net;
     RenderArgs a;
     int64_t n_tiles;
+    float* carry = nullptr;  // tail mode: six rows of a.n_rays floats [T | r | g | b | depth | acc] between the prefix and the tail launch
 };
 
 struct ForwardKArgs {
@@ -93,8 +94,19 @@ __device__ __forceinline__ int64_t global_ray(const RenderArgs& a, int64_t i, in
 enum { F_OX, F_OY, F_OZ, F_DX, F_DY, F_DZ, F_NORM, F_Z, F_T, F_R, F_G, F_B, F_DEPTH, F_ACC, kFields };
 constexpr int kLdsState = kLdsRing + kBiasMaxFloats * 4 + 64 + kLadderLds * 4;     // byte offset of the state rows
 
-template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
-__global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P) {
+// Tail mode (nerfhip.h: nrf_tail) cuts the march in two launches of this one body.  A ray's last sample is composited with
+// dist = 1e10 |d|: its opacity is a step function of its density, and a 16-bit network flips it on rays whose last density is ~ 0.
+//   kWhole : samples 0 .. S-1, the image (render_kernel);
+//   kPrefix: samples 0 .. S-2 of the SAME ladder of S depths (the dist of sample S-2 needs z_{S-1}), never the `last` branch; the
+//            six compositor floats go to P.carry instead of the image (render_hold_kernel, 16-bit modes);
+//   kTail  : sample S-1 alone on a state read back from P.carry (S == 1: the reset state), one network pass per 128 rays in the
+//            split-f16 geometry, then the epilogue (render_tail_kernel).
+// Every sample is still composited by the operations of the whole march in the same order: weights[:, :S-1] and z_vals of
+// prefix + tail are the plain render's bits, and with S == 1 the tail alone is the split-f16 render.
+enum { kWhole = 0, kPrefix = 1, kTail = 2 };
+
+template <class Net, class Mode, int NT, int WAVES, int LP, int LD, int PART>
+__device__ __forceinline__ void render_march(const RenderKArgs& P) {
     static_assert(NT == 1 || NT == 2, "a wave marches 32 or 64 sample columns");
     constexpr int COLS = 32 * NT;                  // sample columns of a wave: column q = c + 32 n sits on lanes c, c + 32 of operand tile n
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -139,11 +151,13 @@ __global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P)
     // on NT.  The state rows of a lane >= RPW mirror ray (lane mod RPW): column q's origin / direction are read from thread q's rows.
     // What SPW buys: frames whose ray count does not fill whole rounds of 256-ray tiles over the CUs (400x400; an 80 000-ray
     // shard) are cut into 2x / 4x as many, shorter, work items.
-    const int spw_log2 = a.spw_log2;
+    const int spw_log2 = PART == kTail ? 0 : a.spw_log2;         // the tail is one sample per ray: one pass of COLS rays per wave
     const int rpw_log2 = (NT == 2 ? 6 : 5) - spw_log2;
     const int SPW = 1 << spw_log2, RPW = COLS >> spw_log2;
     const int64_t tile_rays = (int64_t)WAVES * RPW;
-    const int n_pass = (S + SPW - 1) >> spw_log2;
+    const int SM = PART == kPrefix ? S - 1 : S;                   // samples [s_begin, SM) are marched
+    const int s_begin = PART == kTail ? S - 1 : 0;
+    const int n_pass = PART == kTail ? 1 : (SM + SPW - 1) >> spw_log2;
 
     auto z_ray = [&](int64_t ray, int s) -> float {
         if (a.z_in) return a.z_in[ray * S + s];
@@ -183,10 +197,16 @@ __global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P)
             ST(F_OX) = o[0]; ST(F_OY) = o[1]; ST(F_OZ) = o[2];
             ST(F_DX) = d[0]; ST(F_DY) = d[1]; ST(F_DZ) = d[2];
             ST(F_NORM) = ray_norm(d);
-            int s_first = 0;                         // opaque: z_0 (and the z_1 of its jitter interval) as compile-time constants of the ladder
+            int s_first = s_begin;                   // opaque: z_0 (and the z_1 of its jitter interval) as compile-time constants of the ladder
             asm volatile("" : "+s"(s_first));        // formula were hoisted out of the tile loop into VGPRs and spilled across the network walk
             ST(F_Z) = z_ray(rid, s_first);           // depth of the ray's next sample to composite
-            ST(F_T) = 1.0f; ST(F_R) = 0.0f; ST(F_G) = 0.0f; ST(F_B) = 0.0f; ST(F_DEPTH) = 0.0f; ST(F_ACC) = 0.0f;
+            if (PART == kTail && S > 1) {            // the state the prefix launch left: six coalesced loads (lanes of a wave: consecutive rays)
+                const float* cy = P.carry + rid;
+                ST(F_T) = cy[0]; ST(F_R) = cy[a.n_rays]; ST(F_G) = cy[2 * a.n_rays]; ST(F_B) = cy[3 * a.n_rays];
+                ST(F_DEPTH) = cy[4 * a.n_rays]; ST(F_ACC) = cy[5 * a.n_rays];
+            } else {
+                ST(F_T) = 1.0f; ST(F_R) = 0.0f; ST(F_G) = 0.0f; ST(F_B) = 0.0f; ST(F_DEPTH) = 0.0f; ST(F_ACC) = 0.0f;
+            }
         }
 
         for (int p = 0; p < n_pass; ++p) {
@@ -268,8 +288,8 @@ __global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P)
             float zo = ST(F_Z);
             const float norm = ST(F_NORM);
             if (SPW == 1) {
-                const int s = p;
-                const bool last = (s + 1 == S);
+                const int s = PART == kTail ? S - 1 : p;
+                const bool last = PART == kTail || (PART == kWhole && s + 1 == S);
                 float v[4];
                 // NT == 2: lane L owns column L = tile h, column c -- and holds that tile's head rows itself
 #pragma unroll
@@ -294,8 +314,8 @@ __global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P)
                 const int q = NT == 2 ? lane : c;
                 const int sq = p * SPW + (q >> rpw_log2);
                 float ca = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f, cz = 0.0f;
-                if (sq < S) {
-                    const bool last = (sq + 1 == S);
+                if (sq < SM) {
+                    const bool last = PART == kWhole && (sq + 1 == S);
                     float v[4];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) v[k] = NT == 2 ? pick_reg(out4[0][k], out4[NT - 1][k], h != 0) : out4[0][k];
@@ -307,7 +327,7 @@ __global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P)
                 }
                 for (int j = 0; j < SPW; ++j) {
                     const int s = p * SPW + j;
-                    if (s >= S) break;
+                    if (s >= SM) break;
                     const int qj = lane + (j << rpw_log2);                       // the column of sample s of this (owner) lane's ray
                     const int src = (NT == 2 ? (qj & 63) : ((lane & 32) | (qj & 31))) << 2;
                     auto from = [&](float x) { return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src, __builtin_bit_cast(int, x))); };
@@ -325,7 +345,13 @@ __global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P)
 
         {
             const int64_t raw = tile * tile_rays + wave * RPW + (lane & (RPW - 1));
-            if (lane < RPW && raw < a.n_rays) {
+            if (PART == kPrefix) {
+                if (lane < RPW && raw < a.n_rays) {                      // hold the state for the tail launch: six coalesced stores
+                    float* cy = P.carry + raw;
+                    cy[0] = ST(F_T); cy[a.n_rays] = ST(F_R); cy[2 * a.n_rays] = ST(F_G); cy[3 * a.n_rays] = ST(F_B);
+                    cy[4 * a.n_rays] = ST(F_DEPTH); cy[5 * a.n_rays] = ST(F_ACC);
+                }
+            } else if (lane < RPW && raw < a.n_rays) {
                 float r = ST(F_R), g = ST(F_G), b = ST(F_B);
                 if (a.white_bkgd) {                                      // nerf_mlp.py:209-212
                     const float bg = __fsub_rn(1.0f, ST(F_ACC));
@@ -343,6 +369,19 @@ __global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P)
         }
     }
     pipe.drain();
+}
+
+template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
+__global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P) {
+    render_march<Net, Mode, NT, WAVES, LP, LD, kWhole>(P);
+}
+template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
+__global__ void __launch_bounds__(WAVES * 64) render_hold_kernel(const RenderKArgs P) {
+    render_march<Net, Mode, NT, WAVES, LP, LD, kPrefix>(P);
+}
+template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
+__global__ void __launch_bounds__(WAVES * 64) render_tail_kernel(const RenderKArgs P) {
+    render_march<Net, Mode, NT, WAVES, LP, LD, kTail>(P);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -765,6 +804,31 @@ int run_render_v(const DeviceNet& net, int mode, const RenderArgs& a, hipStream_
                                                                                                  s, "render", err);
 }
 
+// tail mode, first launch (16-bit geometry): samples 0 .. S-2 of every ray, compositor state -> carry.  The split is picked for the
+// S-1 samples this launch marches.
+template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
+int run_render_hold(const DeviceNet& net, int mode, const RenderArgs& a, float* carry, hipStream_t s, std::string& err) {
+    RenderKArgs k;
+    k.a = a;
+    k.carry = carry;
+    k.a.spw_log2 = pick_spw_log2(a.n_rays, a.n_samples - 1, WAVES, 32 * NT, net.cu_count);
+    const int64_t tile = (int64_t)WAVES * ((32 * NT) >> k.a.spw_log2);
+    return launch_persistent<render_hold_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, (a.n_rays + tile - 1) / tile,
+                                                                                                      s, "render (tail mode, prefix)", err);
+}
+
+// tail mode, second launch (split-f16 geometry): sample S-1 of every ray on the carried state, 128 rays per workgroup and pass
+template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
+int run_render_tail(const DeviceNet& net, int mode, const RenderArgs& a, float* carry, hipStream_t s, std::string& err) {
+    RenderKArgs k;
+    k.a = a;
+    k.carry = carry;
+    k.a.spw_log2 = 0;
+    const int64_t tile = (int64_t)WAVES * 32 * NT;
+    return launch_persistent<render_tail_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, (a.n_rays + tile - 1) / tile,
+                                                                                                      s, "render (tail mode, last sample)", err);
+}
+
 template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
 int run_render_queue(const DeviceNet& net, int mode, RenderArgs a, hipStream_t s, std::string& err) {
     auto kernel = render_queue_kernel<Net, Mode, NT, WAVES, LP, LD>;
@@ -834,7 +898,13 @@ bool check_net(const DeviceNet& net, int mode, std::string& err) {
         case NRF_MMA_BF16: return FN<NETT(ModeBF16, 2), ModeBF16, 2, 4, LP, 4>(__VA_ARGS__);          \
         default:           return FN<NETT(ModeF16, 2), ModeF16, 2, 4, LP, 4>(__VA_ARGS__);            \
     }
+// the tail mode's prefix launch exists in the 16-bit half only
+#define NRF_DEFINE_HOLD(fam, NETT, LP)                                                                                              \
+    int render_hold_##fam##_16(const DeviceNet& net, int mode, const RenderArgs& a, float* carry, hipStream_t s, std::string& err) { \
+        NRF_DISPATCH_MODE(run_render_hold, NETT, LP, net, mode, a, carry, s, err)                                                   \
+    }
 #else
+#define NRF_DEFINE_HOLD(fam, NETT, LP)
 #define NRF_TU_NAME(f) f##_32
 #define NRF_DISPATCH_MODE(FN, NETT, LP, ...)                                                         \
     switch (mode) {                                                                                   \
@@ -853,6 +923,9 @@ bool check_net(const DeviceNet& net, int mode, std::string& err) {
     int render_##fam##_32(const DeviceNet& net, int mode, const RenderArgs& a, hipStream_t s, std::string& err);           \
     int forward_##fam##_16(const DeviceNet& net, int mode, ForwardKArgs k, hipStream_t s, std::string& err);               \
     int forward_##fam##_32(const DeviceNet& net, int mode, ForwardKArgs k, hipStream_t s, std::string& err);               \
+    /* tail mode: the prefix in the 16-bit half of the family's unit, the split-f16 last sample in fused_tail.hip */       \
+    int render_hold_##fam##_16(const DeviceNet& net, int mode, const RenderArgs& a, float* carry, hipStream_t s, std::string& err); \
+    int render_tail_##fam(const DeviceNet& net, const RenderArgs& a, float* carry, hipStream_t s, std::string& err);       \
     inline int render_##fam(const DeviceNet& net, int mode, const RenderArgs& a, hipStream_t s, std::string& err) {        \
         return (mode == NRF_MMA_BF16 || mode == NRF_MMA_F16) ? render_##fam##_16(net, mode, a, s, err) : render_##fam##_32(net, mode, a, s, err); \
     }                                                                                                                      \

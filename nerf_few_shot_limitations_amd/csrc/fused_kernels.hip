@@ -14,6 +14,31 @@ int launch_render(const DeviceNet& net, int mode, const RenderArgs& a, hipStream
     return NRF_EUNSUPPORTED;
 }
 
+int launch_render_tail(const DeviceNet& net, int base_mode, const RenderArgs& a, float* carry, hipStream_t s, std::string& err) {
+    if (!check_net(net, base_mode, err) || !check_net(net, NRF_MMA_F16X3, err)) return NRF_EINVAL;
+    if (a.n_rays <= 0) return NRF_OK;
+    const bool prefix = a.n_samples > 1;       // n_samples == 1: the state is the reset state and the render is the tail launch alone
+    int rc = NRF_OK;
+    if (net.arch.net == NRF_NET_V1 && net.arch.pos_freq == 10) {
+        if (prefix) rc = render_hold_v1_16(net, base_mode, a, carry, s, err);
+        return rc != NRF_OK ? rc : render_tail_v1(net, a, carry, s, err);
+    }
+    if (net.arch.net == NRF_NET_V2 && net.arch.pos_freq == 10) {
+        if (prefix) rc = render_hold_v2_16(net, base_mode, a, carry, s, err);
+        return rc != NRF_OK ? rc : render_tail_v2(net, a, carry, s, err);
+    }
+    if (net.arch.net == NRF_NET_V3 && net.arch.pos_freq == 12 && net.arch.dino_dim == 64) {
+        if (prefix) rc = render_hold_v3_16(net, base_mode, a, carry, s, err);
+        return rc != NRF_OK ? rc : render_tail_v3(net, a, carry, s, err);
+    }
+    if (net.arch.net == NRF_NET_V3 && net.arch.pos_freq == 12 && net.arch.dino_dim == 128) {
+        if (prefix) rc = render_hold_v3w_16(net, base_mode, a, carry, s, err);
+        return rc != NRF_OK ? rc : render_tail_v3w(net, a, carry, s, err);
+    }
+    err = "no fused renderer built for this (net, pos_freq): see nrf_render_rays";
+    return NRF_EUNSUPPORTED;
+}
+
 int launch_forward_v1(const DeviceNet& net, int mode, const float* x_enc, int64_t n, float* out4, hipStream_t s, std::string& err) {
     if (!check_net(net, mode, err)) return NRF_EINVAL;
     if (net.arch.net != NRF_NET_V1) { err = "nrf_mlp_forward_v1 needs a V1 model"; return NRF_EINVAL; }

@@ -70,6 +70,11 @@ struct RenderArgs {
 };
 
 int launch_render(const DeviceNet& net, int mma_mode, const RenderArgs& a, hipStream_t s, std::string& err);
+// Tail mode: samples 0 .. S-2 in base_mode (bf16 / f16), compositor state through `carry` (render_tail_floats(n_rays) floats), sample
+// S-1 in split-f16; two launches on s (one when n_samples == 1).  Reads the streams of base_mode AND of NRF_MMA_F16X3.
+constexpr int kCarryRows = 6;       // T, r, g, b, depth, acc: one row of n_rays floats each
+inline int64_t render_tail_floats(int64_t n_rays) { return kCarryRows * n_rays; }
+int launch_render_tail(const DeviceNet& net, int base_mode, const RenderArgs& a, float* carry, hipStream_t s, std::string& err);
 int launch_forward_v1(const DeviceNet& net, int mma_mode, const float* x_enc, int64_t n, float* out4, hipStream_t s, std::string& err);
 int launch_forward(const DeviceNet& net, int mma_mode, const float* pos, const float* dir, const float* dino, int64_t n,
                    float* rgb, float* density, hipStream_t s, std::string& err);

@@ -30,6 +30,8 @@ def main(argv=None):
     ap.add_argument("--out", default=None)
     ap.add_argument("--mode", default="f16x3", choices=["f16x3", "f32", "f16", "bf16"],
                     help="f16x3 / f32: parity-grade (1e-4 of the reference); f16 / bf16: full MFMA rate")
+    ap.add_argument("--tail-mode", default=None, choices=["f16x3"],
+                    help="with --mode f16 / bf16: evaluate every ray's last sample (composited with dist = 1e10) in split-f16")
     ap.add_argument("--max-views", type=int, default=None)
     ap.add_argument("--ert", type=float, default=0.0)
     ap.add_argument("--dino-map", default=None)
@@ -65,9 +67,11 @@ def main(argv=None):
     model = model.cuda().eval()
     targets = images.permute(0, 2, 3, 1).contiguous()
     res = evaluate_views(model, poses, H, W, focal, rs["near"], rs["far"], rs["n_samples"], targets=targets, out_dir=args.out,
-                         white_bkgd=rs["white_bkgd"], mma_mode=args.mode, ert_eps=args.ert, dino=dino)
+                         white_bkgd=rs["white_bkgd"], mma_mode=args.mode, ert_eps=args.ert, dino=dino, tail_mode=args.tail_mode)
     metrics = {"psnr": res["psnr"], "ssim": res["ssim"], "views": len(res["per_view"]), "per_view": res["per_view"],
                "H": H, "W": W, "n_samples": rs["n_samples"], "mode": args.mode}
+    if args.tail_mode:
+        metrics["tail_mode"] = args.tail_mode
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         with open(os.path.join(args.out, "metrics.json"), "w") as f:

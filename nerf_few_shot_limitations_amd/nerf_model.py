@@ -166,10 +166,12 @@ class NeRFMLP(nn.Module):
         ok = all(p.data_ptr() == base + 4 * off for p, off in zip(fp.params(), fp.offsets))
         return fp.flat if ok else None
 
-    def handle(self, device=None, mma_mode=None):
+    def handle(self, device=None, mma_mode=None, also=None):
         """The nrf_model* for this module on `device`, (re)packed if the parameters changed.  `mma_mode`: the arithmetic
         mode the caller is about to run (default: the module's own) -- after a device-side re-pack only the modes that
-        were asked for hold the current parameters."""
+        were asked for hold the current parameters.  `also`: a second mode the same call reads (a tail render: the base
+        mode's and the split-f16 stream); both are brought up to date by ONE nrf_model_update_device call, which is what
+        keeps the base mode's backward weights marked current for the next training step."""
         L.require_gpu()
         if device is None:
             p = next(self.parameters())
@@ -178,15 +180,16 @@ class NeRFMLP(nn.Module):
         idx = device.index if device.index is not None else torch.cuda.current_device()
         ver = self._versions()
         mode = L.MMA_MODES[mma_mode or self.mma_mode]
+        modes = {mode} if also is None else {mode, L.MMA_MODES[also]}
         same = self._handle is not None and self._handle_dev == idx
-        if same and self._packed == ver and (self._packed_modes is None or mode in self._packed_modes):
+        if same and self._packed == ver and (self._packed_modes is None or modes <= self._packed_modes):
             return self._handle
         flat = self._flat_on(idx) if same else None
         if flat is not None:
-            # parameters live in the flat device vector (training): re-pack this mode's streams on the device
+            # parameters live in the flat device vector (training): re-pack the asked-for modes' streams on the device
             with torch.cuda.device(idx):
-                L.check(L.lib().nrf_model_update_device(self._handle, L.ptr(flat), 1 << mode, L.stream_ptr()))
-            self._packed_modes = ({mode} if self._packed != ver or self._packed_modes is None else self._packed_modes | {mode})
+                L.check(L.lib().nrf_model_update_device(self._handle, L.ptr(flat), sum(1 << k for k in modes), L.stream_ptr()))
+            self._packed_modes = (modes if self._packed != ver or self._packed_modes is None else self._packed_modes | modes)
             self._packed = ver
             return self._handle
         arr, n, keep = self._host_linears()

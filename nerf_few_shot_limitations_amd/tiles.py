@@ -70,7 +70,7 @@ class TileJob:
     `launch()` enqueues exactly the render kernel(s), which write rgb+depth rows straight into the gather buffer `buf`."""
 
     def __init__(self, model, H, W, focal, c2w, near, far, N_samples, rank, world, tile_rays, perturb=False, seed=0, lindisp=False,
-                 ert_eps=0.0, white_bkgd=False, mma_mode: Optional[str] = None, dino=None, device=None):
+                 ert_eps=0.0, white_bkgd=False, mma_mode: Optional[str] = None, dino=None, device=None, tail_mode: Optional[str] = None):
         from .renderer import _opts, make_dino
         L.require_gpu()
         self.H, self.W, self.focal = int(H), int(W), float(focal)
@@ -85,6 +85,7 @@ class TileJob:
         if model.net == L.NRF_NET_V3:
             self._dn, self._keep = make_dino(**dino)
         self.mma_mode = mma_mode or model.mma_mode
+        self.tail_mode = tail_mode                                           # renderer.render_rays: every ray's last sample in split-f16
         self.opts = _opts(near, far, N_samples, perturb, None, seed, lindisp, ert_eps, white_bkgd, self.mma_mode,
                           self._dn, self.device)
         self.model = model
@@ -116,7 +117,8 @@ class TileJob:
         """Enqueue the render kernel(s): they write this rank's tiles straight into the gather buffer `self.buf`
         (V, per_rank*tile_rays, 4).  One launch per 8 views when the tiles deal evenly (every rank's buffer is all real tiles);
         otherwise one launch per view, each into the real-tile prefix of that view's rows (the padding rows stay zero)."""
-        h = self.model.handle(self.device, self.mma_mode)
+        from .renderer import _handle
+        h = _handle(self.model, self.device, self.mma_mode, self.tail_mode)
         n = self.n_real * self.tile_rays
         if n == 0:
             return
@@ -132,9 +134,15 @@ class TileJob:
                     # the kernel keys a view's jitter by seed + (camera index inside the launch) * 0x51ED27: offset the seed by the
                     # launch's first view so that the pattern is a function of the GLOBAL view index, however the views are batched
                     self.opts.rng_seed = (seed0 + v0 * 0x51ED27) & 0xFFFFFFFFFFFFFFFF
-                    L.check(L.lib().nrf_render_cameras_tiles(h, self.H, self.W, self.focal, C.cast(sub, C.c_void_p), nv, self.tile_rays,
-                                                             self.rank, self.world, self.n_real, C.byref(self.opts),
-                                                             L.ptr(out), None, None, None, L.stream_ptr()))
+                    tail, ws = L.tail_arg(self.tail_mode, self.mma_mode, nv * n, self.device)
+                    if tail is None:
+                        L.check(L.lib().nrf_render_cameras_tiles(h, self.H, self.W, self.focal, C.cast(sub, C.c_void_p), nv, self.tile_rays,
+                                                                 self.rank, self.world, self.n_real, C.byref(self.opts),
+                                                                 L.ptr(out), None, None, None, L.stream_ptr()))
+                    else:
+                        L.check(L.lib().nrf_render_cameras_tiles_tail(h, self.H, self.W, self.focal, C.cast(sub, C.c_void_p), nv, self.tile_rays,
+                                                                      self.rank, self.world, self.n_real, C.byref(self.opts), C.byref(tail),
+                                                                      L.ptr(out), None, None, None, L.stream_ptr()))
         finally:
             self.opts.rng_seed = seed0
 

@@ -354,12 +354,16 @@ _encoders = {}
 
 
 def render_rays_train(module, rays_o, rays_d, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False,
-                      white_bkgd=False, dino=None, z_in=None, mma_mode=None):
+                      white_bkgd=False, dino=None, z_in=None, mma_mode=None, tail_mode=None):
     """renderer.render_rays when grad is enabled: the reference's own sequence (train.py:188-242) -- stratified samples,
     [project + fetch DINO features,] NeRFMLP, VolumeRenderer -- returning {'rgb','depth','weights','z_vals'} that carry a grad_fn.
     Gradients reach the parameters only (rays, depths and features are data: a tensor that requires grad is refused).
     The arithmetic mode is `mma_mode` (default: the module's own) mapped to a training mode (_lib.TRAIN_MODE: the split mode
-    trains in exact fp32); early ray termination does not apply."""
+    trains in exact fp32); early ray termination does not apply.  A `tail_mode` (renderer.render_rays) is refused: the training
+    kernels have no split-f16 mode, and a silently different forward would be worse than a refusal."""
+    if tail_mode is not None:
+        raise ValueError("tail_mode is an inference option: the training kernels have no split-f16 mode (render under "
+                         "torch.no_grad() or model.eval())")
     from .ray_sampler import sample_points_along_rays
     o = L.dev_f32(L.refuse_grad(rays_o, "render_rays(rays_o)")).reshape(-1, 3)
     d = L.dev_f32(L.refuse_grad(rays_d, "render_rays(rays_d)"), o.device).reshape(-1, 3)

@@ -28,6 +28,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import synthetic_scene  # noqa: E402
 
 MODES = ("f32", "f16x3", "f16", "bf16")
+# the 16-bit modes with every ray's last sample in split-f16 (render_rays' tail_mode): reported by the command line beside MODES
+TAIL_MODES = ("f16+tail", "bf16+tail")
 
 
 def config(size, views, epochs):
@@ -148,14 +150,16 @@ def compare_modes(model, scene_dir, size, views, modes=MODES, n_samples=64, dino
         gt = images.permute(0, 2, 3, 1).contiguous().to(dev)
         res = {}
         for mode in modes:
+            tail = dict(tail_mode="f16x3") if mode.endswith("+tail") else {}
+            mma = mode.split("+")[0]
             with torch.no_grad():
                 if dino is None:
-                    r = N.evaluate_views(model, poses, H, W, focal, 2.0, 6.0, n_samples, targets=None, mma_mode=mode)
+                    r = N.evaluate_views(model, poses, H, W, focal, 2.0, 6.0, n_samples, targets=None, mma_mode=mma, **tail)
                     img, dep = r["images"], r["depth"]
                 else:
                     # train views: each with its own feature map (as trained); test views: view 0's map, as the reference evaluates
-                    per = [N.evaluate_views(model, poses[v:v + 1], H, W, focal, 2.0, 6.0, n_samples, targets=None, mma_mode=mode,
-                                            dino=dino[v] if split == "train" else dino[0]) for v in range(poses.shape[0])]
+                    per = [N.evaluate_views(model, poses[v:v + 1], H, W, focal, 2.0, 6.0, n_samples, targets=None, mma_mode=mma,
+                                            dino=dino[v] if split == "train" else dino[0], **tail) for v in range(poses.shape[0])]
                     img, dep = torch.cat([x["images"] for x in per]), torch.cat([x["depth"] for x in per])
             res[mode] = (img, dep, N.psnr(img, gt))
         ref = res["f32"] if "f32" in res else res[modes[0]]
@@ -200,5 +204,7 @@ if __name__ == "__main__":
     ap.add_argument("--v1-batch", type=int, default=None)
     ap.add_argument("--lr", type=float, default=None)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--no-tail", action="store_true", help="report the plain modes only")
     a = ap.parse_args()
-    print(json.dumps(run(a.net, a.train_mode, a.epochs, a.views, a.size, seed=a.seed, sigma_bias=None if a.sigma_bias < 0 else a.sigma_bias, v1_batch=a.v1_batch, lr=a.lr)))
+    print(json.dumps(run(a.net, a.train_mode, a.epochs, a.views, a.size, seed=a.seed, modes=MODES if a.no_tail else MODES + TAIL_MODES,
+                         sigma_bias=None if a.sigma_bias < 0 else a.sigma_bias, v1_batch=a.v1_batch, lr=a.lr)))
