@@ -360,6 +360,57 @@ int nrf_adam_step_loss(float* params, const float* grads, float* exp_avg, float*
                        float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                        const float* ray_loss, int64_t n_rays, float loss_weight, float* loss, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The multiscale trainer's step (src/training/train_multiscale.py:207-211,249-266):
+ * nerf_mlp.NeRFLoss on a VolumeRenderer in train() mode, clip_grad_norm_, optim.AdamW.  Additive to ABI 5: the
+ * struct carries its own size, nrf_abi_sizeof knows nothing of it.
+ * ------------------------------------------------------------------------ */
+typedef struct nrf_loss_opts {
+    int32_t      struct_bytes;  /* sizeof(nrf_loss_opts): checked by the library */
+    float        rgb_weight;    /* nerf_mlp.py:219-223; all three >= 0 */
+    float        reg_weight;    /* * mean(weights^2) */
+    float        depth_weight;  /* * l1(depth, target_depth); inert without target_depth */
+    const float* target_depth;  /* device, (n_rays), or NULL: no depth term */
+    float        noise_std;     /* >= 0; nerf_mlp.py:188-190: density + noise * noise_std in front of the compositor's ReLU */
+    const float* noise;         /* device, (n_rays, n_samples) standard normals (the parity route), or NULL: the in-kernel
+                                   counter RNG (two uniforms -> Box-Muller) keyed by (rng_seed, ray index in the call, sample) */
+    uint64_t     rng_seed;
+} nrf_loss_opts;
+
+/* nrf_composite_mse_backward generalised to the three-term loss, still ONE launch: composites sigma + noise_std * n, forms
+ *   g_rgb = 2 rgb_weight (pred - target) / (3 R),  g_depth = depth_weight sign(depth - target_depth) / R,
+ *   g_w[i] = 2 reg_weight w_i / (R S)   (in registers)
+ * and runs the compositor backward with them; the ReLU mask of d_sigma is [sigma + noise_std * n > 0].  With
+ * noise_std == 0, reg_weight == 0 and no target_depth, d_rgb / d_sigma / pred / ray_terms[0..n_rays) are
+ * nrf_composite_mse_backward's bits.
+ *   ray_terms : 3 * n_rays floats: every ray's squared rgb error | sum of w^2 | |depth - target_depth|
+ *               (nrf_adamw_step_loss adds them up in a fixed order as a side job of its launch). */
+int nrf_composite_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride,
+                                const float* z_vals, const float* rays_d, int64_t n_rays, int n_samples, int white_bkgd,
+                                const float* target, const nrf_loss_opts* loss, float* pred,
+                                float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride,
+                                float* ray_terms, float* zero_buf, int64_t zero_n, void* stream);
+
+/* Global L2 norm of a flat gradient vector for clip_grad_norm_, without a read-back: this launch leaves at most 1024 partial
+ * sums of squares in `workspace` (nrf_grad_sqnorm_workspace_bytes(n) bytes, device, 4-byte aligned); nrf_adamw_step_loss adds
+ * them up.  Fixed summation order, no atomics: bit-reproducible.  Data parallel: call after the gradient all-reduce. */
+int64_t nrf_grad_sqnorm_workspace_bytes(int64_t n);
+int nrf_grad_sqnorm_partials(const float* grads, int64_t n, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* nrf_adam_step_loss with clipping and the choice of decay:
+ *   max_norm > 0 : g is scaled on load by min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_), norm from
+ *                  `sqnorm_partials` (the workspace nrf_grad_sqnorm_partials filled for the same n); <= 0: no clipping;
+ *   decoupled    : 0 = torch.optim.Adam (weight_decay * p added to the gradient), 1 = torch.optim.AdamW
+ *                  (p *= 1 - lr * weight_decay in front of the moment update);
+ *   grad_norm    : optional device float, receives the pre-clip norm (needs sqnorm_partials);
+ *   ray_terms / losses : both or neither; losses[4] = total, rgb (mse), depth (l1), reg (mean w^2) with
+ *                  total = rgb_weight rgb + depth_weight depth + reg_weight reg (nerf_mlp.py:249-257). */
+int nrf_adamw_step_loss(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
+                        float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                        int decoupled, float max_norm, const float* sqnorm_partials, float* grad_norm,
+                        const float* ray_terms, int64_t n_rays, int n_samples,
+                        float rgb_weight, float depth_weight, float reg_weight, float* losses, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

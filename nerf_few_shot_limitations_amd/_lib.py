@@ -56,6 +56,17 @@ class nrf_tail(C.Structure):
     _fields_ = [("mode", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class nrf_loss_opts(C.Structure):
+    """The multi-term loss of nrf_composite_loss_backward; struct_bytes is filled in by loss_opts()."""
+    _fields_ = [("struct_bytes", C.c_int32), ("rgb_weight", C.c_float), ("reg_weight", C.c_float), ("depth_weight", C.c_float),
+                ("target_depth", C.c_void_p), ("noise_std", C.c_float), ("noise", C.c_void_p), ("rng_seed", C.c_uint64)]
+
+
+def loss_opts(rgb_weight=1.0, reg_weight=0.0, depth_weight=0.0, target_depth=None, noise_std=0.0, noise=None, rng_seed=0):
+    """nrf_loss_opts with its size field set; target_depth / noise are device pointers (ints) or None."""
+    return nrf_loss_opts(C.sizeof(nrf_loss_opts), rgb_weight, reg_weight, depth_weight, target_depth, noise_std, noise, int(rng_seed) & (2 ** 64 - 1))
+
+
 # name -> (restype, argtypes); tests/test_packing_emulation.py checks this table against include/nerfhip.h
 SIGNATURES = {
     "nrf_abi_version": (C.c_int, []),
@@ -114,6 +125,15 @@ SIGNATURES = {
                                 C.c_float, C.c_int, C.c_void_p]),
     "nrf_adam_step_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                      C.c_float, C.c_int, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
+    # the multiscale trainer's step: three-term loss, gradient clipping, AdamW
+    "nrf_composite_loss_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                              C.c_void_p, C.POINTER(nrf_loss_opts), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "nrf_grad_sqnorm_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "nrf_grad_sqnorm_partials": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "nrf_adamw_step_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
+                                      C.c_float, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                      C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

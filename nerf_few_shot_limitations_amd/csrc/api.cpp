@@ -694,6 +694,65 @@ int nrf_adam_step_loss(float* params, const float* grads, float* exp_avg, float*
     return r == NRF_OK ? NRF_OK : fail(r, "adam launch failed");
 }
 
+int nrf_composite_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals, const float* rays_d,
+                                int64_t n_rays, int n_samples, int white_bkgd, const float* target, const nrf_loss_opts* loss, float* pred,
+                                float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf,
+                                int64_t zero_n, void* stream) {
+    if (!loss) return fail(NRF_EINVAL, "nrf_composite_loss_backward: loss is NULL");
+    if (loss->struct_bytes != (int32_t)sizeof(nrf_loss_opts)) return fail(NRF_EINVAL, "nrf_loss_opts.struct_bytes is not sizeof(nrf_loss_opts)");
+    if (!(loss->rgb_weight >= 0.0f) || !(loss->reg_weight >= 0.0f) || !(loss->depth_weight >= 0.0f) || !std::isfinite(loss->rgb_weight) ||
+        !std::isfinite(loss->reg_weight) || !std::isfinite(loss->depth_weight))
+        return fail(NRF_EINVAL, "loss weights must be finite and >= 0");
+    if (!(loss->noise_std >= 0.0f) || !std::isfinite(loss->noise_std)) return fail(NRF_EINVAL, "noise_std must be finite and >= 0");
+    if (n_rays <= 0 || n_rays > ((int64_t)1 << 30) || n_samples < 1 || n_samples > 4096) return fail(NRF_EINVAL, "nrf_composite_loss_backward: bad sizes");
+    if (rgb_stride < 3 || sigma_stride < 1 || d_rgb_stride < 3 || d_sigma_stride < 1) return fail(NRF_EINVAL, "bad strides");
+    if (!rgb || !sigma || !z_vals || !rays_d || !target || !d_rgb || !d_sigma || !ray_terms) return fail(NRF_EINVAL, "null pointer");
+    if (zero_n < 0 || (zero_n > 0 && !zero_buf)) return fail(NRF_EINVAL, "zero_buf is NULL");
+    nrf::LossTerms lt{};
+    lt.rgb_weight = loss->rgb_weight; lt.reg_weight = loss->reg_weight; lt.depth_weight = loss->depth_weight;
+    lt.target_depth = loss->target_depth; lt.noise_std = loss->noise_std; lt.noise = loss->noise; lt.rng_seed = loss->rng_seed;
+    const int r = nrf::launch_composite_loss_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, lt,
+                                                      pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n,
+                                                      (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "composite + loss + backward launch failed");
+}
+
+int64_t nrf_grad_sqnorm_workspace_bytes(int64_t n) {
+    if (n <= 0) { (void)fail(NRF_EINVAL, "nrf_grad_sqnorm_workspace_bytes: n must be positive"); return -1; }
+    return 4 * (int64_t)nrf::sqnorm_partials(n);
+}
+
+int nrf_grad_sqnorm_partials(const float* grads, int64_t n, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (n <= 0) return fail(NRF_EINVAL, "nrf_grad_sqnorm_partials: n must be positive");
+    if (!grads) return fail(NRF_EINVAL, "null pointer");
+    if (!workspace) return fail(NRF_EINVAL, "norm workspace is NULL");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 3u) != 0) return fail(NRF_EINVAL, "norm workspace must be 4-byte aligned");
+    if (workspace_bytes < 4 * (int64_t)nrf::sqnorm_partials(n)) return fail(NRF_EINVAL, "norm workspace smaller than nrf_grad_sqnorm_workspace_bytes");
+    const int r = nrf::launch_grad_sqnorm_partials(grads, n, (float*)workspace, (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "norm partials launch failed");
+}
+
+int nrf_adamw_step_loss(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, int step, int decoupled, float max_norm, const float* sqnorm_partials, float* grad_norm,
+                        const float* ray_terms, int64_t n_rays, int n_samples, float rgb_weight, float depth_weight, float reg_weight,
+                        float* losses, void* stream) {
+    if (n <= 0 || step < 1) return fail(NRF_EINVAL, "bad n / step");
+    if (!params || !grads || !exp_avg || !exp_avg_sq) return fail(NRF_EINVAL, "null pointer");
+    if (!(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f) || !(eps >= 0.0f)) return fail(NRF_EINVAL, "bad Adam constants");
+    if (std::isnan(max_norm)) return fail(NRF_EINVAL, "max_norm is NaN");
+    if (max_norm > 0.0f && !sqnorm_partials) return fail(NRF_EINVAL, "max_norm > 0 needs the partial sums of nrf_grad_sqnorm_partials");
+    if (grad_norm && !sqnorm_partials) return fail(NRF_EINVAL, "grad_norm needs the partial sums of nrf_grad_sqnorm_partials");
+    if ((ray_terms == nullptr) != (losses == nullptr)) return fail(NRF_EINVAL, "nrf_adamw_step_loss: ray_terms and losses go together");
+    if (ray_terms && (n_rays <= 0 || n_samples < 1)) return fail(NRF_EINVAL, "nrf_adamw_step_loss: bad n_rays / n_samples");
+    if (ray_terms && (!(rgb_weight >= 0.0f) || !(depth_weight >= 0.0f) || !(reg_weight >= 0.0f))) return fail(NRF_EINVAL, "loss weights must be >= 0");
+    nrf::AdamExt e{};
+    e.decoupled = decoupled ? 1 : 0; e.max_norm = max_norm; e.partials = sqnorm_partials; e.grad_norm = grad_norm;
+    e.ray_terms = ray_terms; e.n_rays = n_rays; e.n_samples = n_samples;
+    e.rgb_weight = rgb_weight; e.depth_weight = depth_weight; e.reg_weight = reg_weight; e.losses = losses;
+    const int r = nrf::launch_adamw(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, e, (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "adamw launch failed");
+}
+
 int nrf_sample_pdf(const float* z_vals, const float* weights, int64_t n_rays, int n_samples, int n_importance, const float* u, int64_t u_ray_stride,
                    float* samples, float* z_union, void* stream) {
     if (n_rays < 0 || n_samples < 2 || n_importance < 1) return fail(NRF_EINVAL, "bad sizes");

@@ -97,13 +97,27 @@ __device__ __forceinline__ float ladder_z_jitter(const DepthLadder& L, int s, fl
 
 // counter-based uniform [0,1) for the in-kernel jitter (only distribution-tested: the reference
 // uses torch.rand, ray_utils.py:78, whose stream cannot be reproduced on a GPU)
-__device__ __forceinline__ float counter_uniform(uint64_t seed, uint64_t ray, uint32_t s) {
+__device__ __forceinline__ uint64_t counter_bits(uint64_t seed, uint64_t ray, uint32_t s) {
     uint64_t x = seed ^ (ray * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)s << 40);
     x += 0x9E3779B97F4A7C15ull;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
     x ^= x >> 31;
-    return (float)(x >> 40) * (1.0f / 16777216.0f);
+    return x;
+}
+__device__ __forceinline__ float counter_uniform(uint64_t seed, uint64_t ray, uint32_t s) {
+    return (float)(counter_bits(seed, ray, s) >> 40) * (1.0f / 16777216.0f);
+}
+
+// counter-based standard normal for the in-kernel density noise (nerf_mlp.py:188-190 draws torch.randn_like; only distribution-
+// tested, as the jitter): the two 24-bit halves of one counter word are two uniforms, u1 in (0,1] and u2 in [0,1), and Box-Muller
+// makes one normal of them, sqrt(-2 ln u1) cos(2 pi u2).  |n| <= sqrt(48 ln 2) = 5.77.  A pure function of (seed, ray, sample):
+// every pass over a ray sees the same draw, whatever the grid.
+__device__ __forceinline__ float counter_normal(uint64_t seed, uint64_t ray, uint32_t s) {
+    const uint64_t x = counter_bits(seed ^ 0xD1B54A32D192ED03ull, ray, s);      // a stream of its own: not the jitter's under one seed
+    const float u1 = (float)((uint32_t)(x >> 40) + 1u) * (1.0f / 16777216.0f);
+    const float u2 = (float)((uint32_t)(x >> 16) & 0xFFFFFFu) * (1.0f / 16777216.0f);
+    return __fmul_rn(sqrtf(__fmul_rn(-2.0f, logf(u1))), cospif(__fmul_rn(2.0f, u2)));
 }
 
 // pts = o + d*z, product rounded before the add (ray_utils.py:82)

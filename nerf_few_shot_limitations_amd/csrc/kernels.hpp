@@ -120,6 +120,39 @@ int launch_composite_mse_backward(const float* rgb, int rgb_stride, const float*
                                   int64_t n_rays, int S, int white_bkgd, const float* target, float weight, float* pred, float* d_rgb,
                                   int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_loss, float* zero_buf,
                                   int64_t zero_n, hipStream_t s);
+// The multiscale trainer's step (train_multiscale.py:207-211,249-266): nerf_mlp.NeRFLoss on a VolumeRenderer in train() mode,
+// clip_grad_norm_, AdamW
+struct LossTerms {
+    float rgb_weight, reg_weight, depth_weight;
+    const float* target_depth;      // (R) or NULL
+    float noise_std;
+    const float* noise;             // (R,S) standard normals, or NULL: in-kernel counter RNG
+    uint64_t rng_seed;
+};
+// ray_terms (3,R): squared rgb error | sum of w^2 | |depth - target_depth|
+int launch_composite_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
+                                   int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, float* pred, float* d_rgb,
+                                   int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n,
+                                   hipStream_t s);
+// partial sums of squares of a flat vector (one float per workgroup, fixed order); the optimiser launch adds them up
+constexpr int kMaxSqnormPartials = 1024;
+inline int sqnorm_partials(int64_t n) {
+    const int64_t p = (n + 1023) / 1024;
+    return (int)(p < 1 ? 1 : (p > kMaxSqnormPartials ? kMaxSqnormPartials : p));
+}
+int launch_grad_sqnorm_partials(const float* g, int64_t n, float* partials, hipStream_t s);
+struct AdamExt {
+    int decoupled;                  // torch.optim.AdamW: p *= 1 - lr wd in front of the moment update, no decay in the gradient
+    float max_norm;                 // > 0: clip_grad_norm_(max_norm) applied to g on load
+    const float* partials;          // sqnorm_partials(n) floats of launch_grad_sqnorm_partials (max_norm > 0 or grad_norm)
+    float* grad_norm;               // optional: receives the (pre-clip) L2 norm
+    const float* ray_terms;         // optional (3,R) of launch_composite_loss_backward, with losses[4] = total, rgb, depth, reg
+    int64_t n_rays; int n_samples;
+    float rgb_weight, depth_weight, reg_weight;
+    float* losses;
+};
+int launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd, int step,
+                 const AdamExt& ext, hipStream_t s);
 int launch_repack3(const float* flat, const int32_t* const src[3], const int64_t n_elems[3], const int modes[3], void* const out[3], hipStream_t s);
 int launch_composite_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
                               int64_t n_rays, int S, int white_bkgd, const float* g_rgb, const float* g_depth, const float* g_w,

@@ -98,15 +98,30 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// Density noise of a training render (nerf_mlp.py:188-190: density + randn_like(density) * noise_std in front of the ReLU): the
+// caller's (R,S) standard normals, or -- n == NULL -- the counter RNG keyed by (seed, ray index in the call, sample).
+struct NoiseSrc { float std; const float* n; uint64_t seed; };
+// EXT = false: the density as it is (every caller but the multi-term loss kernel; these instantiations are the code the kernels
+// had before the noise existed)
+template <bool EXT>
+__device__ __forceinline__ float sigma_eff(float sigma, const NoiseSrc& ns, int64_t i, int64_t r, int s) {
+    if constexpr (EXT) {
+        if (ns.std > 0.0f) return __fadd_rn(sigma, __fmul_rn(ns.n ? ns.n[i] : counter_normal(ns.seed, (uint64_t)r, (uint32_t)s), ns.std));
+    }
+    return sigma;
+}
+
 // One ray on one wave (LANE <-> sample, 64-sample segments front to back): every lane returns the ray's sums
-struct RaySums { float r, g, b, depth, acc; };
+// (w2 = sum of squared weights, the regulariser of nerf_mlp.py:245: EXT only)
+struct RaySums { float r, g, b, depth, acc, w2; };
+template <bool EXT = false>
 __device__ __forceinline__ RaySums composite_ray(const float* __restrict__ rgb, int rgb_stride, const float* __restrict__ sigma, int sigma_stride,
                                                  const float* __restrict__ z, const float* __restrict__ rays_d, int64_t r, int S, int lane,
-                                                 float* __restrict__ out_w) {
+                                                 float* __restrict__ out_w, const NoiseSrc ns = NoiseSrc{}) {
     const float d[3] = {rays_d[r * 3], rays_d[r * 3 + 1], rays_d[r * 3 + 2]};
     const float norm = ray_norm(d);
     float T_in = 1.0f;                                   // transmittance entering this 64-sample segment
-    float sr = 0.0f, sg = 0.0f, sb = 0.0f, sd = 0.0f, sa = 0.0f;
+    float sr = 0.0f, sg = 0.0f, sb = 0.0f, sd = 0.0f, sa = 0.0f, sw2 = 0.0f;
     for (int s0 = 0; s0 < S; s0 += 64) {
         const int s = s0 + lane;
         const bool valid = s < S;
@@ -117,7 +132,7 @@ __device__ __forceinline__ RaySums composite_ray(const float* __restrict__ rgb, 
         const bool last = (s + 1 == S);
         const float dist = last ? __fmul_rn(1e10f, norm) : __fmul_rn(__fsub_rn(zn, zc), norm);
         float alpha = 0.0f;
-        if (valid) alpha = __fsub_rn(1.0f, expf(__fmul_rn(-fmaxf(sigma[i * sigma_stride], 0.0f), dist)));
+        if (valid) alpha = __fsub_rn(1.0f, expf(__fmul_rn(-fmaxf(sigma_eff<EXT>(sigma[i * sigma_stride], ns, i, r, s), 0.0f), dist)));
         const float f = valid ? __fadd_rn(__fsub_rn(1.0f, alpha), 1e-10f) : 1.0f;
         const float incl = wave_incl_prod(f, lane);
         float excl = __shfl_up(incl, 1, 64);
@@ -130,11 +145,13 @@ __device__ __forceinline__ RaySums composite_ray(const float* __restrict__ rgb, 
             sb = __fadd_rn(sb, __fmul_rn(w, rgb[i * rgb_stride + 2]));
             sd = __fadd_rn(sd, __fmul_rn(w, zc));
             sa = __fadd_rn(sa, w);
+            if constexpr (EXT) sw2 = __fadd_rn(sw2, __fmul_rn(w, w));
         }
         T_in = __fmul_rn(T_in, __shfl(incl, 63, 64));
     }
     RaySums o;
     o.r = wave_sum(sr); o.g = wave_sum(sg); o.b = wave_sum(sb); o.depth = wave_sum(sd); o.acc = wave_sum(sa);
+    o.w2 = EXT ? wave_sum(sw2) : 0.0f;
     return o;
 }
 
@@ -163,6 +180,7 @@ __global__ void __launch_bounds__(kBlock) composite_kernel(const float* __restri
 //   dL/dc_i     = w_i * g_rgb
 //   dL/dalpha_i = T_i * v_i - (sum_{j>i} w_j v_j) / (1 - alpha_i + 1e-10)
 //   dL/dsigma_i = dL/dalpha_i * dist_i * exp(-relu(sigma_i) dist_i) * [sigma_i > 0]
+// (under density noise sigma_i stands for sigma_i + noise_std * n_i throughout: the compositor's ReLU acts on the noisy density)
 // The suffix sum is a true reverse scan (segments walked back to front): "total - prefix" would lose every digit behind
 // an opaque sample, where the reference's +1e-10 makes the divisor 1e-10.  One WAVE per ray, LANE <-> sample.
 __device__ __forceinline__ float wave_incl_sum_rev(float v, int lane) {
@@ -177,17 +195,20 @@ __device__ __forceinline__ float wave_incl_sum_rev(float v, int lane) {
 constexpr int kMaxSegments = 64;     // S <= 4096
 
 // One ray on one wave; gr, gg, gb, gd = dL/d rgb_map, dL/d depth of the ray (wave-uniform), g_w = dL/d weights or NULL;
-// seg_T = the wave's LDS row of kMaxSegments floats
+// seg_T = the wave's LDS row of kMaxSegments floats.  EXT: the density noise `ns`, and the regulariser's dL/d weights formed in
+// registers, g_w[i] = gw_scale * w_i (no (R,S) tensor)
+template <bool EXT = false>
 __device__ __forceinline__ void composite_backward_ray(const float* __restrict__ rgb, int rgb_stride, const float* __restrict__ sigma,
                                                        int sigma_stride, const float* __restrict__ z, const float* __restrict__ rays_d,
                                                        int64_t r, int S, int lane, int white_bkgd, float gr, float gg, float gb, float gd,
                                                        const float* __restrict__ g_w, float* __restrict__ d_rgb, int d_rgb_stride,
-                                                       float* __restrict__ d_sigma, int d_sigma_stride, float* seg_T) {
+                                                       float* __restrict__ d_sigma, int d_sigma_stride, float* seg_T,
+                                                       const NoiseSrc ns = NoiseSrc{}, float gw_scale = 0.0f) {
     const int n_seg = (S + 63) / 64;
     const float d[3] = {rays_d[r * 3], rays_d[r * 3 + 1], rays_d[r * 3 + 2]};
     const float norm = ray_norm(d);
     const float bg = white_bkgd ? __fadd_rn(__fadd_rn(gr, gg), gb) : 0.0f;
-    auto sample = [&](int s0, float& alpha, float& e, float& dist, float& f, float& zc, bool& valid, int64_t& i) {
+    auto sample = [&](int s0, float& alpha, float& e, float& dist, float& f, float& zc, bool& valid, int64_t& i, float& sg) {
         const int s = s0 + lane;
         valid = s < S;
         i = r * S + (valid ? s : S - 1);
@@ -196,15 +217,16 @@ __device__ __forceinline__ void composite_backward_ray(const float* __restrict__
         if (lane == 63 && s + 1 < S) zn = z[i + 1];
         const bool last = (s + 1 == S);
         dist = last ? __fmul_rn(1e10f, norm) : __fmul_rn(__fsub_rn(zn, zc), norm);
-        e = valid ? expf(__fmul_rn(-fmaxf(sigma[i * sigma_stride], 0.0f), dist)) : 1.0f;
+        sg = sigma_eff<EXT>(sigma[i * sigma_stride], ns, i, r, s);
+        e = valid ? expf(__fmul_rn(-fmaxf(sg, 0.0f), dist)) : 1.0f;
         alpha = valid ? __fsub_rn(1.0f, e) : 0.0f;
         f = valid ? __fadd_rn(__fsub_rn(1.0f, alpha), 1e-10f) : 1.0f;
     };
     // pass 1, front to back: transmittance entering every 64-sample segment
     float T_in = 1.0f;
     for (int k = 0; k < n_seg; ++k) {
-        float alpha, e, dist, f, zc; bool valid; int64_t i;
-        sample(64 * k, alpha, e, dist, f, zc, valid, i);
+        float alpha, e, dist, f, zc, sg; bool valid; int64_t i;
+        sample(64 * k, alpha, e, dist, f, zc, valid, i, sg);
         if (lane == 0) seg_T[k] = T_in;
         const float incl = wave_incl_prod(f, lane);
         T_in = __fmul_rn(T_in, __shfl(incl, 63, 64));
@@ -212,8 +234,8 @@ __device__ __forceinline__ void composite_backward_ray(const float* __restrict__
     // pass 2, back to front
     float carry = 0.0f;                                  // sum of w_j v_j over all later segments
     for (int k = n_seg - 1; k >= 0; --k) {
-        float alpha, e, dist, f, zc; bool valid; int64_t i;
-        sample(64 * k, alpha, e, dist, f, zc, valid, i);
+        float alpha, e, dist, f, zc, sg; bool valid; int64_t i;
+        sample(64 * k, alpha, e, dist, f, zc, valid, i, sg);
         const float incl = wave_incl_prod(f, lane);
         float excl = __shfl_up(incl, 1, 64);
         if (lane == 0) excl = 1.0f;
@@ -225,6 +247,7 @@ __device__ __forceinline__ void composite_backward_ray(const float* __restrict__
             v = __fadd_rn(__fadd_rn(__fmul_rn(gr, cr), __fmul_rn(gg, cg)), __fmul_rn(gb, cb));
             v = __fadd_rn(v, __fmul_rn(gd, zc));
             if (g_w) v = __fadd_rn(v, g_w[i]);
+            if constexpr (EXT) v = __fadd_rn(v, __fmul_rn(gw_scale, w));
             v = __fsub_rn(v, bg);
         }
         const float wv_ = valid ? __fmul_rn(w, v) : 0.0f;
@@ -233,7 +256,6 @@ __device__ __forceinline__ void composite_backward_ray(const float* __restrict__
         carry = __fadd_rn(carry, __shfl(incl_rev, 0, 64));
         if (valid) {
             const float d_alpha = __fsub_rn(__fmul_rn(T, v), suffix / f);
-            const float sg = sigma[i * sigma_stride];
             d_sigma[i * d_sigma_stride] = sg > 0.0f ? __fmul_rn(__fmul_rn(d_alpha, dist), e) : 0.0f;
             d_rgb[i * d_rgb_stride] = __fmul_rn(w, gr);
             d_rgb[i * d_rgb_stride + 1] = __fmul_rn(w, gg);
@@ -260,21 +282,34 @@ __global__ void __launch_bounds__(kBlock) composite_backward_kernel(const float*
     }
 }
 
-// The three launches between the network's forward and its backward in a FusedStep -- compositor, `rgb_weight * nn.MSELoss()` with
-// its gradient, compositor backward (train.py:236,36-44,285) -- as ONE: the loss gradient of a ray needs nothing but the ray's own
-// prediction and target, d loss / d pred = 2 w (pred - target) / (3 R).  Same per-ray arithmetic as the three kernels (the two bodies
-// above), so d_rgb / d_sigma are bit-equal to the staged sequence.  The loss VALUE needs all rays: every ray leaves its squared error
-// in `ray_loss` and a later launch adds them up in a fixed order (adam_kernel's side job, train_shared.hip) -- a device-wide
-// "last workgroup sums" inside this kernel costs a release fence (an L2 write-back on this chip) per workgroup: measured 53 us
-// against 16 us for the three separate launches.  Side job: `zero_buf` (the caller's flat gradient vector, which the
-// weight-gradient reduction adds into) is cleared by the same launch.
-__global__ void __launch_bounds__(kBlock) composite_mse_backward_kernel(const float* __restrict__ rgb, int rgb_stride,
-                                                                        const float* __restrict__ sigma, int sigma_stride,
-                                                                        const float* __restrict__ z, const float* __restrict__ rays_d,
-                                                                        int64_t n_rays, int S, int white_bkgd, const float* __restrict__ target,
-                                                                        float weight, float* __restrict__ pred, float* __restrict__ d_rgb,
-                                                                        int d_rgb_stride, float* __restrict__ d_sigma, int d_sigma_stride,
-                                                                        float* __restrict__ ray_loss, float* __restrict__ zero_buf, int64_t zero_n) {
+// The three launches between the network's forward and its backward in a FusedStep -- compositor, loss with its gradient,
+// compositor backward -- as ONE: the loss gradient of a ray needs nothing but the ray's own outputs and targets.  Same per-ray
+// arithmetic as the three kernels (the two bodies above), so d_rgb / d_sigma are bit-equal to the staged sequence.  The loss VALUE
+// needs all rays: every ray leaves its terms in `ray_loss` and a later launch adds them up in a fixed order (adam_kernel's side
+// job, train_shared.hip) -- a device-wide "last workgroup sums" inside this kernel costs a release fence (an L2 write-back on this
+// chip) per workgroup: measured 53 us against 16 us for the three separate launches.  Side job: `zero_buf` (the caller's flat
+// gradient vector, which the weight-gradient reduction adds into) is cleared by the same launch.
+//   EXT = false: `rgb_weight * nn.MSELoss()` (train.py:236,36-44,285), d loss / d pred = 2 w (pred - target) / (3 R); ray_loss
+//                (R) = the rays' squared errors.  nrf_composite_mse_backward.
+//   EXT = true:  nerf_mlp.NeRFLoss on a VolumeRenderer in train() mode (nerf_mlp.py:188-190,217-258; train_multiscale.py:207-211):
+//                density noise in front of the compositor's ReLU, + depth_weight * l1(depth, target_depth) + reg_weight *
+//                mean(weights^2); ray_loss (3,R) = squared rgb error | sum of w^2 | |depth - target_depth|.  With every option off
+//                its d_rgb / d_sigma / pred / ray_loss[0:R] are the EXT = false kernel's bits.
+struct LossExt {
+    NoiseSrc noise;
+    const float* target_depth;        // (R) or NULL
+    float gd_scale;                   // depth_weight / R
+    float gw_scale;                   // 2 reg_weight / (R S)
+};
+template <bool EXT>
+__global__ void __launch_bounds__(kBlock) composite_loss_backward_kernel(const float* __restrict__ rgb, int rgb_stride,
+                                                                         const float* __restrict__ sigma, int sigma_stride,
+                                                                         const float* __restrict__ z, const float* __restrict__ rays_d,
+                                                                         int64_t n_rays, int S, int white_bkgd, const float* __restrict__ target,
+                                                                         float weight, float* __restrict__ pred, float* __restrict__ d_rgb,
+                                                                         int d_rgb_stride, float* __restrict__ d_sigma, int d_sigma_stride,
+                                                                         float* __restrict__ ray_loss, float* __restrict__ zero_buf, int64_t zero_n,
+                                                                         const LossExt ext) {
     __shared__ float seg_T[kBlock / 64][kMaxSegments];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t gtid = blockIdx.x * (int64_t)kBlock + threadIdx.x, n_threads = (int64_t)gridDim.x * kBlock;
@@ -282,18 +317,24 @@ __global__ void __launch_bounds__(kBlock) composite_mse_backward_kernel(const fl
     const float count = 3.0f * (float)n_rays;
     const float scale = 2.0f * weight / count;
     for (int64_t r = gtid >> 6; r < n_rays; r += n_threads >> 6) {
-        RaySums o = composite_ray(rgb, rgb_stride, sigma, sigma_stride, z, rays_d, r, S, lane, nullptr);
+        RaySums o = composite_ray<EXT>(rgb, rgb_stride, sigma, sigma_stride, z, rays_d, r, S, lane, nullptr, ext.noise);
         if (white_bkgd) {
             const float bg = __fsub_rn(1.0f, o.acc);
             o.r = __fadd_rn(o.r, bg); o.g = __fadd_rn(o.g, bg); o.b = __fadd_rn(o.b, bg);
         }
         const float dr = o.r - target[r * 3], dg = o.g - target[r * 3 + 1], db = o.b - target[r * 3 + 2];
+        float gd = 0.0f;
+        if constexpr (EXT) {
+            const float dd = ext.target_depth ? __fsub_rn(o.depth, ext.target_depth[r]) : 0.0f;
+            gd = dd > 0.0f ? ext.gd_scale : (dd < 0.0f ? -ext.gd_scale : 0.0f);          // l1_loss: sign(0) = 0
+            if (lane == 0) { ray_loss[n_rays + r] = o.w2; ray_loss[2 * n_rays + r] = fabsf(dd); }
+        }
         if (lane == 0) {
             if (pred) { pred[r * 3] = o.r; pred[r * 3 + 1] = o.g; pred[r * 3 + 2] = o.b; }
             ray_loss[r] = dr * dr + dg * dg + db * db;
         }
-        composite_backward_ray(rgb, rgb_stride, sigma, sigma_stride, z, rays_d, r, S, lane, white_bkgd, scale * dr, scale * dg, scale * db, 0.0f,
-                               nullptr, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, seg_T[wv]);
+        composite_backward_ray<EXT>(rgb, rgb_stride, sigma, sigma_stride, z, rays_d, r, S, lane, white_bkgd, scale * dr, scale * dg, scale * db, gd,
+                                    nullptr, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, seg_T[wv], ext.noise, ext.gw_scale);
     }
 }
 
@@ -595,9 +636,26 @@ int launch_composite_mse_backward(const float* rgb, int rgb_stride, const float*
                                   int64_t zero_n, hipStream_t s) {
     if (n_rays <= 0 || S > 64 * kMaxSegments) return NRF_EINVAL;
     const int64_t work = std::max(n_rays * 64, (zero_n + 3) / 4);
-    hipLaunchKernelGGL(composite_mse_backward_kernel, dim3(grid_for(work, kBlock, 16384)), dim3(kBlock), 0, s, rgb, rgb_stride, sigma,
+    hipLaunchKernelGGL(composite_loss_backward_kernel<false>, dim3(grid_for(work, kBlock, 16384)), dim3(kBlock), 0, s, rgb, rgb_stride, sigma,
                        sigma_stride, z, rays_d, n_rays, S, white_bkgd, target, weight, pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_loss,
-                       zero_buf, zero_n);
+                       zero_buf, zero_n, LossExt{});
+    return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
+}
+
+int launch_composite_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
+                                   int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, float* pred, float* d_rgb,
+                                   int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n,
+                                   hipStream_t s) {
+    if (n_rays <= 0 || S > 64 * kMaxSegments) return NRF_EINVAL;
+    LossExt ext{};
+    ext.noise.std = lt.noise_std; ext.noise.n = lt.noise; ext.noise.seed = lt.rng_seed;
+    ext.target_depth = lt.target_depth;
+    ext.gd_scale = lt.target_depth ? lt.depth_weight / (float)n_rays : 0.0f;
+    ext.gw_scale = 2.0f * lt.reg_weight / ((float)n_rays * (float)S);
+    const int64_t work = std::max(n_rays * 64, (zero_n + 3) / 4);
+    hipLaunchKernelGGL(composite_loss_backward_kernel<true>, dim3(grid_for(work, kBlock, 16384)), dim3(kBlock), 0, s, rgb, rgb_stride, sigma,
+                       sigma_stride, z, rays_d, n_rays, S, white_bkgd, target, lt.rgb_weight, pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride,
+                       ray_terms, zero_buf, zero_n, ext);
     return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
 }
 

@@ -1,5 +1,6 @@
 """python -m nerf_few_shot_limitations_amd.train_cli --config experiments/baseline.yaml --data data/nerf_synthetic/lego \\
-        [--epochs N] [--mode bf16|f16|f32] [--eval-mode f16] [--out DIR] [--checkpoint CKPT] [--dino-weights DIR | --dino-maps maps.pt] [--seed 0]
+        [--recipe train|multiscale] [--epochs N] [--mode bf16|f16|f32] [--eval-mode f16] [--out DIR] [--checkpoint CKPT]
+        [--dino-weights DIR | --dino-maps maps.pt] [--seed 0]
 
 The training run of `NeRFDINOTrainer` (src/training/train.py:244-292 `train_step`, :344-372 `train`) as a command on the
 HIP path: the YAML loads unchanged; per epoch and training view the rays are cast at the progressive schedule's
@@ -9,10 +10,16 @@ rgb_weight * mse -> backward -> Adam(lr, weight_decay) -- with MultiStepLR betwe
 `output.val_freq` epochs on the fused renderer (`evaluate_views`) and checkpoints under the reference's key names
 (:374-389, readable by evaluate.py:22-33 and by evaluate_cli).
 
-Objective.  The step minimises `loss.rgb_weight * mse(rgb, target)` -- exactly what the reference's training loss returns:
-train.py:27-44 (the `NeRFLoss` class train.py defines and uses) computes only that term; `loss.depth_weight` /
-`loss.reg_weight` of the YAMLs are read into the constructor and never used there.  (nerf_mlp.NeRFLoss, a different class the
-trainer does not import, adds mean(weights^2); tests/test_gpu_training.py covers it through the autograd route.)
+Objective.  --recipe train (the default) minimises `loss.rgb_weight * mse(rgb, target)` with Adam -- exactly what train.py
+does: train.py:27-44 (the `NeRFLoss` class train.py defines and uses) computes only that term; `loss.depth_weight` /
+`loss.reg_weight` of the YAMLs are read into the constructor and never used there.
+--recipe multiscale is the step of the reference's other trainer, src/training/train_multiscale.py:207-211,249-266 (the one
+behind experiments/multiscale.yaml), still one `FusedStep`: density noise `rendering.noise_std` in front of the compositor's
+ReLU, nerf_mlp.NeRFLoss = rgb_weight * mse + `loss.reg_weight` * mean(weights^2) (`loss.depth_weight` is read and inert, as
+there: its targets carry no depth), clip_grad_norm_(max_norm=1.0) and optim.AdamW(lr, weight_decay); its checkpoints carry
+`nerf_state_dict` (train_multiscale.py:368-376) next to `nerf_model_state_dict`.  The ray batches, schedule, validation and
+LR steps stay this command's (the two trainers agree on them); the DINO-feature mean substitution of
+train_multiscale.py:190-197 (its mask is always false) is not part of it, and the extractor receives no gradient in either recipe.
 
 use_dino configs condition on the DINOv2 feature map of every training view.  As in train.py:158-169 the maps are computed ONCE,
 under no_grad, by the extractor the config names (config.dino_model_from_config: SpatialDINOFeatures or
@@ -116,13 +123,29 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
     return (float(total) / max(n_batches, 1)) if total is not None else 0.0, samples
 
 
-def save_checkpoint(path, model, step, epoch, best_psnr, cfg):
-    """train.py:374-389's dictionary: `nerf_model_state_dict` is what evaluate.py:27 / load_checkpoint_into read."""
+def step_options(cfg, recipe="train"):
+    """FusedStep's keyword arguments for a config under a recipe.  'train': train.py:36-44,113-118 (rgb_weight * mse, Adam with
+    weight decay in the gradient).  'multiscale': train_multiscale.py:41-45,61-65,207-211,259-264 (NeRFLoss with the
+    regulariser, density noise, clip_grad_norm_ at 1.0, AdamW)."""
+    o, lw, r = cfg["optimizer"], cfg.get("loss", {}) or {}, cfg.get("rendering", {}) or {}
+    kw = dict(lr=float(o["lr"]), weight_decay=float(o["weight_decay"]), rgb_weight=float(lw.get("rgb_weight", 1.0)))
+    if recipe == "multiscale":
+        kw.update(reg_weight=float(lw.get("reg_weight", 0.01)), depth_weight=float(lw.get("depth_weight", 0.1)),
+                  noise_std=float(r.get("noise_std", 0.0)), max_grad_norm=1.0, decoupled_weight_decay=True)
+    elif recipe != "train":
+        raise ValueError(f"unknown recipe {recipe!r}")
+    return kw
+
+
+def save_checkpoint(path, model, step, epoch, best_psnr, cfg, recipe="train"):
+    """train.py:374-389's dictionary: `nerf_model_state_dict` is what evaluate.py:27 / load_checkpoint_into read; the multiscale
+    recipe adds train_multiscale.py:368-376's `nerf_state_dict` (the same tensors)."""
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     opt = step.opt
     o = cfg["optimizer"]
+    sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
     torch.save({"epoch": epoch, "best_psnr": best_psnr,
-                "nerf_model_state_dict": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
+                "nerf_model_state_dict": sd, **({"nerf_state_dict": sd} if recipe == "multiscale" else {}),
                 # flat-vector Adam state (training.Adam; layout = include/nerfhip.h's flat parameter order), restored by --checkpoint
                 "optimizer_state_dict": {"step": opt.step_count, "exp_avg": None if opt.exp_avg is None else opt.exp_avg.cpu(),
                                          "exp_avg_sq": None if opt.exp_avg_sq is None else opt.exp_avg_sq.cpu(), "lr": opt.lr},
@@ -150,6 +173,9 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", required=True)
     ap.add_argument("--data", required=True, help="dataset directory holding transforms_train.json / transforms_test.json")
+    ap.add_argument("--recipe", default="train", choices=["train", "multiscale"],
+                    help="the optimisation step: train.py's (rgb_weight * mse, Adam) or train_multiscale.py's (density noise, NeRFLoss with "
+                         "the weights regulariser, gradient clipping at 1.0, AdamW)")
     ap.add_argument("--epochs", type=int, default=None, help="default: training.epochs of the config")
     ap.add_argument("--mode", default="bf16", choices=["bf16", "f16", "f32"],
                     help="arithmetic of the TRAINING kernels (bf16: its exponent range suits the unscaled gradients)")
@@ -220,9 +246,8 @@ def main(argv=None):
     if ckpt is not None:
         load_checkpoint_into(model, ckpt)
     model = model.to(dev).train()
-    o, lw = cfg["optimizer"], cfg.get("loss", {})
-    step = FusedStep(model, lr=float(o["lr"]), weight_decay=float(o["weight_decay"]), rgb_weight=float(lw.get("rgb_weight", 1.0)),
-                     white_bkgd=rs["white_bkgd"], data_parallel=world > 1)
+    step = FusedStep(model, white_bkgd=rs["white_bkgd"], data_parallel=world > 1, **step_options(cfg, args.recipe),
+                     **({"seed": args.seed} if args.recipe == "multiscale" else {}))
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed)
     best, log, first_epoch = 0.0, [], 0
@@ -247,9 +272,9 @@ def main(argv=None):
             rec.update(psnr=m["psnr"], ssim=m["ssim"])
             if m["psnr"] > best:
                 best = m["psnr"]
-                save_checkpoint(os.path.join(out_dir, f"best_{name}.pth"), model, step, epoch, best, cfg)
+                save_checkpoint(os.path.join(out_dir, f"best_{name}.pth"), model, step, epoch, best, cfg, args.recipe)
         if (epoch + 1) % int(cfg["output"]["save_freq"]) == 0:
-            save_checkpoint(os.path.join(out_dir, f"epoch_{epoch + 1}.pth"), model, step, epoch, best, cfg)
+            save_checkpoint(os.path.join(out_dir, f"epoch_{epoch + 1}.pth"), model, step, epoch, best, cfg, args.recipe)
         log.append(rec)
         print(json.dumps(rec), flush=True)
     if rank == 0:

@@ -7,8 +7,10 @@
   * `composite`      nerf_mlp.VolumeRenderer / volume_render_radiance with grad enabled;
   * `FlatParams`     the module's parameters as views into one flat fp32 vector, so that an
                      optimizer step is visible to the kernels without leaving the device;
-  * `Adam`           torch.optim.Adam's update as one kernel on the flat vectors (train.py:113-118);
-  * `FusedStep`      the whole optimisation step of the reference's loop as a fixed sequence of library calls;
+  * `Adam`           torch.optim.Adam's update as one kernel on the flat vectors (train.py:113-118); optionally torch.optim.AdamW's
+                     decoupled decay and clip_grad_norm_ without its host read-back (train_multiscale.py:259-266);
+  * `FusedStep`      the whole optimisation step of the reference's loop as a fixed sequence of library calls: train.py's
+                     (rgb_weight * mse, Adam) or train_multiscale.py's (density noise, nerf_mlp.NeRFLoss, clipping, AdamW);
   * `all_reduce_gradients`   data-parallel training: ONE collective per step on the flat gradient vector.
 
 There is no PyTorch fallback: without libnerfhip.so / a gfx950 GPU every call raises.
@@ -404,11 +406,21 @@ def render_rays_train(module, rays_o, rays_d, near, far, n_samples, perturb=True
 # ---------------------------------------------------------------------------------------------
 class Adam:
     """torch.optim.Adam(params, lr, betas, eps, weight_decay) for a NeRFMLP whose parameters live in a FlatParams
-    vector: one kernel per step.  Same update rule and defaults as the reference's optimizer (train.py:113-118)."""
+    vector: one kernel per step.  Same update rule and defaults as the reference's optimizer (train.py:113-118).
+    decoupled=True is torch.optim.AdamW's rule (p *= 1 - lr * weight_decay in front of the moment update); max_grad_norm=c
+    clips the gradients as torch.nn.utils.clip_grad_norm_(params, c) in front of the step would, on the device: one small
+    launch leaves partial sums of squares, the update kernel forms the coefficient -- no read-back, no sync.  The pre-clip
+    norm of the last step stays in `last_grad_norm` (a device scalar)."""
 
-    def __init__(self, module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    def __init__(self, module, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False, max_grad_norm=None):
         self.module = module
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.decoupled = bool(decoupled)
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be positive (None: no clipping)")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm = None
+        self._norm_ws = None
         self.step_count = 0
         self.exp_avg = None
         self.exp_avg_sq = None
@@ -421,6 +433,27 @@ class Adam:
             self.exp_avg = torch.zeros_like(flat)
             self.exp_avg_sq = torch.zeros_like(flat)
         return fp, flat
+
+    @property
+    def extended(self):
+        """True when the step needs the clipped / decoupled kernel (nrf_adamw_step_loss) instead of nrf_adam_step[_loss]."""
+        return self.decoupled or self.max_grad_norm is not None
+
+    def _update(self, flat, g, terms=None, R=0, S=1, weights=(0.0, 0.0, 0.0), losses=None):
+        """The extended update on the flat vectors (call with the device current): [norm partials ->] clipped Adam / AdamW,
+        with the loss side job when `terms` (3,R) / `losses` (4) are given."""
+        lib, st, n = L.lib(), L.stream_ptr(), flat.numel()
+        ws = norm = None
+        if self.max_grad_norm is not None:
+            ws = self._norm_ws
+            if ws is None or ws.device != flat.device or ws.numel() * 4 < lib.nrf_grad_sqnorm_workspace_bytes(n):
+                ws = self._norm_ws = torch.empty(lib.nrf_grad_sqnorm_workspace_bytes(n) // 4, dtype=torch.float32, device=flat.device)
+            norm = torch.empty((), dtype=torch.float32, device=flat.device)
+            L.check(lib.nrf_grad_sqnorm_partials(L.ptr(g), n, L.ptr(ws), ws.numel() * 4, st))
+        L.check(lib.nrf_adamw_step_loss(L.ptr(flat), L.ptr(g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), n, self.lr, self.betas[0],
+                                        self.betas[1], self.eps, self.weight_decay, self.step_count, int(self.decoupled),
+                                        self.max_grad_norm or 0.0, L.ptr(ws), L.ptr(norm), L.ptr(terms), R, S, *weights, L.ptr(losses), st))
+        self.last_grad_norm = norm
 
     @staticmethod
     def _flat_grad_of(ps, fp, flat):
@@ -461,8 +494,11 @@ class Adam:
                         v.copy_(p.grad)
         self.step_count += 1
         with torch.no_grad(), torch.cuda.device(flat.device):
-            L.check(L.lib().nrf_adam_step(L.ptr(flat), L.ptr(g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), flat.numel(), self.lr,
-                                          self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count, L.stream_ptr()))
+            if self.extended:
+                self._update(flat, g)
+            else:
+                L.check(L.lib().nrf_adam_step(L.ptr(flat), L.ptr(g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), flat.numel(), self.lr,
+                                              self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count, L.stream_ptr()))
         self.module._gen += 1            # the packed streams are now older than the parameters
 
 
@@ -513,22 +549,51 @@ class FusedStep:
         loss = step(points, z_vals, rays_d, target)               # V1: points = encoded (R*S, 63)
         loss = step(points, z_vals, rays_d, target, dirs=dirs)    # V2: points (R*S, 3), dirs (R*S, 3)
         loss = step(points, z_vals, rays_d, target, dirs=dirs, dino=feats)    # V3: + per-sample DINO features (R*S, C)
+
+    The multiscale trainer's step (train_multiscale.py:207-211,249-266) is the same sequence with its options switched on --
+    density noise in front of the compositor's ReLU, nerf_mlp.NeRFLoss (rgb_weight * mse + depth_weight * l1(depth,
+    target_depth) + reg_weight * mean(weights^2)), clip_grad_norm_, AdamW:
+
+        step = FusedStep(model, lr=2e-4, weight_decay=1e-6, reg_weight=1e-4, noise_std=0.1, max_grad_norm=1.0,
+                         decoupled_weight_decay=True)
+
+    The general compositor/loss kernel stands in for the mse one and the clipped optimiser for Adam; the only additional launch
+    is the norm's partial sums (with max_grad_norm).  The returned value is the total loss; `last_losses` holds the components
+    ({'total', 'rgb', 'depth', 'reg'}: device scalars, the reference's `losses` dict) and `last_grad_norm` the pre-clip norm
+    (device scalar, None without clipping).  Nothing synchronises.
     """
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rgb_weight=1.0, white_bkgd=False,
-                 process_group=None, data_parallel=False):
+                 process_group=None, data_parallel=False, reg_weight=0.0, depth_weight=0.0, noise_std=0.0, max_grad_norm=None,
+                 decoupled_weight_decay=False, seed=None):
         """data_parallel=True (inside an initialised torch.distributed job): every rank passes ITS shard of the ray batch
-        (equal sizes), the flat gradient vector is averaged over the ranks with one all-reduce before Adam, and the
-        returned loss is this rank's."""
+        (equal sizes), the flat gradient vector is averaged over the ranks with one all-reduce before Adam (the norm of
+        max_grad_norm is taken behind it, so all ranks clip alike), and the returned loss is this rank's.
+        seed: of the in-kernel density noise (noise_std > 0 and no `noise` tensor passed to the call); step t draws from
+        seed + t, a ray's draw is keyed by its index in the call.  Default: drawn from torch's CPU generator when first needed."""
         if model.net not in (L.NRF_NET_V1, L.NRF_NET_V2, L.NRF_NET_V3):
             raise NotImplementedError("FusedStep: unknown network family")
+        if min(float(rgb_weight), float(reg_weight), float(depth_weight), float(noise_std)) < 0.0:
+            raise ValueError("FusedStep: loss weights and noise_std must be >= 0")
         self.model = model
         self.data_parallel = bool(data_parallel)
         self.group = process_group
-        self.opt = Adam(model, lr, betas, eps, weight_decay)
+        self.opt = Adam(model, lr, betas, eps, weight_decay, decoupled=decoupled_weight_decay, max_grad_norm=max_grad_norm)
         self.rgb_weight = float(rgb_weight)
+        self.reg_weight, self.depth_weight, self.noise_std = float(reg_weight), float(depth_weight), float(noise_std)
+        self.seed = None if seed is None else int(seed)
         self.white = int(bool(white_bkgd))
+        self._loss_vec, self.last_grad_norm = None, None
         self._key = None
+
+    @property
+    def last_losses(self):
+        """The last step's loss terms as device scalars (no sync): {'total'} of the plain step, {'total', 'rgb', 'depth', 'reg'}
+        (nerf_mlp.NeRFLoss's dict, unweighted components) of the multi-term one; None before the first step."""
+        v = self._loss_vec
+        if v is None:
+            return None
+        return {"total": v} if v.dim() == 0 else {"total": v[0], "rgb": v[1], "depth": v[2], "reg": v[3]}
 
     def _buffers(self, n, R, S, dev, h, mode):
         key = (n, R, S, str(dev), mode)
@@ -541,12 +606,14 @@ class FusedStep:
             self.nbytes = nbytes
             self.out4, self.d_out4 = f(n, 4), f(n, 4)                 # V1: [rgb, sigma] rows; V2: rgb | density packed in the same rows
             self.pred = f(R, 3)
-            self.ray_loss = f(R)
+            self.ray_loss = f(3, R)              # row 0: squared rgb errors; rows 1, 2 (multi-term loss): sum of w^2, |depth error|
             self.grad = torch.zeros(self.model.flat_params().flat.numel(), dtype=torch.float32, device=dev)
             self._key = key
 
     @torch.no_grad()
-    def __call__(self, points, z_vals, rays_d, target, dirs=None, dino=None):
+    def __call__(self, points, z_vals, rays_d, target, dirs=None, dino=None, target_depth=None, noise=None):
+        """target_depth (R): switches the depth term on (with depth_weight); noise (R,S): the standard normals of the density noise
+        (with noise_std) instead of the in-kernel RNG -- what torch.randn_like would have drawn, for parity runs."""
         m = self.model
         pts = L.dev_f32(points)
         dev = pts.device
@@ -579,21 +646,44 @@ class FusedStep:
                 d_heads = (L.ptr(d4), 4, C.c_void_p(d4.data_ptr() + 12), 4)
             # compositor -> d loss / d pred = 2 w (pred - target) / (3 R) -> compositor backward, and the flat gradient vector cleared:
             # one launch (a ray's loss gradient needs only its own prediction); the rays' squared errors stay in ray_loss
-            loss = torch.empty((), dtype=torch.float32, device=dev)
-            L.check(lib.nrf_composite_mse_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), self.rgb_weight, L.ptr(self.pred),
-                                                   *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
+            opt = self.opt
+            multi = (self.reg_weight > 0.0 or self.depth_weight > 0.0 or self.noise_std > 0.0 or opt.extended or target_depth is not None
+                     or noise is not None)
+            if multi:
+                td = None if target_depth is None else L.dev_f32(target_depth, dev).reshape(R)
+                nz = None if noise is None or self.noise_std == 0.0 else L.dev_f32(noise, dev).reshape(R, S)
+                seed = 0
+                if self.noise_std > 0.0 and nz is None:
+                    if self.seed is None:
+                        self.seed = L.fresh_seed()
+                    seed = self.seed + opt.step_count
+                lo = L.loss_opts(self.rgb_weight, self.reg_weight, self.depth_weight, L.ptr(td), self.noise_std, L.ptr(nz), seed)
+                loss = torch.empty((4,), dtype=torch.float32, device=dev)
+                L.check(lib.nrf_composite_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), L.ptr(self.pred),
+                                                        *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
+            else:
+                loss = torch.empty((), dtype=torch.float32, device=dev)
+                L.check(lib.nrf_composite_mse_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), self.rgb_weight, L.ptr(self.pred),
+                                                       *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
             if v2:
                 L.check(lib.nrf_mlp_backward(h, mode, L.ptr(rgb), L.ptr(den), L.ptr(g_rgb), L.ptr(g_den), n, ctx, self.nbytes, L.ptr(self.grad), st))
             else:
                 L.check(lib.nrf_mlp_backward_v1(h, mode, L.ptr(o4), L.ptr(d4), n, ctx, self.nbytes, L.ptr(self.grad), st))
             if self.data_parallel:
                 _all_reduce_mean(self.grad, self.group)
-            opt = self.opt
             fp, flat = opt._buffers()
             opt.step_count += 1
-            # Adam, and as a side job of its launch the loss value: rgb_weight * sum(ray_loss) / (3 R) in a fixed order
-            L.check(lib.nrf_adam_step_loss(L.ptr(flat), L.ptr(self.grad), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq), flat.numel(), opt.lr,
-                                           opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, opt.step_count, L.ptr(self.ray_loss), R,
-                                           self.rgb_weight, L.ptr(loss), st))
+            if multi:
+                # [norm partials ->] clipped Adam / AdamW, and as a side job of its launch the loss terms summed in a fixed order
+                opt._update(flat, self.grad, self.ray_loss, R, S, (self.rgb_weight, self.depth_weight if target_depth is not None else 0.0,
+                                                                   self.reg_weight), loss)
+                self._loss_vec, self.last_grad_norm = loss, opt.last_grad_norm
+                loss = loss[0]
+            else:
+                # Adam, and as a side job of its launch the loss value: rgb_weight * sum(ray_loss) / (3 R) in a fixed order
+                L.check(lib.nrf_adam_step_loss(L.ptr(flat), L.ptr(self.grad), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq), flat.numel(), opt.lr,
+                                               opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, opt.step_count, L.ptr(self.ray_loss), R,
+                                               self.rgb_weight, L.ptr(loss), st))
+                self._loss_vec, self.last_grad_norm = loss, None
         m._gen += 1
         return loss
