@@ -241,6 +241,19 @@ int nrf_project_fetch(const nrf_dino* dino, const float* points, int64_t n, floa
  * (zeros padding, align_corners=False) of a (1,Hp,Wp,C) channel-last map at n normalised image points (n,2) -> (n,C). */
 int nrf_sample_features(const float* features, int Hp, int Wp, int C, const float* points_2d, int64_t n, float* feats, void* stream);
 
+/* The adjoints of the two fetches with respect to the map -- what autograd through F.grid_sample (dino_feature_model.py:137-143)
+ * hands to the feature extractor when its map requires grad (the LoRA matrices of lora_dino.py are in train.py:105-110's
+ * optimizer): d_map (Hp,Wp,C) = [accumulate ? d_map : 0] + sum over samples and their <= 4 on-map taps of weight * d_feats (n,C).
+ * The same tap arithmetic as the forward; no gradient with respect to the points.  No atomics: workgroups add their slab of
+ * samples, in order, into private copies of the map in `ws` (device, nrf_fetch_backward_workspace_bytes(Hp, Wp, C, n) bytes --
+ * a function of the sizes alone), which a second launch adds up in a fixed order, so d_map is bit-identical from run to run.
+ * dino->features is not read (may be NULL).  n == 0 with accumulate == 0 clears d_map. */
+int64_t nrf_fetch_backward_workspace_bytes(int Hp, int Wp, int C, int64_t n);
+int nrf_project_fetch_backward(const nrf_dino* dino, const float* points, int64_t n, const float* d_feats,
+                               float* d_map, int accumulate, void* ws, int64_t ws_bytes, void* stream);
+int nrf_sample_features_backward(int Hp, int Wp, int C, const float* points_2d, int64_t n, const float* d_feats,
+                                 float* d_map, int accumulate, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- host-only introspection (no GPU needed; used by the CPU test-suite to replay the
  *      kernel's MFMA walk over the packed stream) -------------------------------- */
 /* Packs `linears` exactly as nrf_model_create would for `mma_mode`.  stream_out / bias_out may be
@@ -259,6 +272,10 @@ int nrf_debug_pack_backward(const nrf_arch* arch, const nrf_linear* linears, int
                             uint8_t* stream_out, int64_t stream_cap, int64_t* stream_bytes);
 int nrf_debug_train_plan(const nrf_arch* arch, const nrf_linear* linears, int n_linear,
                          int32_t* out, int64_t cap, int64_t* n_ints);
+/* NRF_NET_V3, host-only: the fragment stream of nrf_mlp_backward_dino's A operand -- W0d^T, the dino_dim columns of
+ * dino_fusion.fusion.0 (lora_dino.py:156) transposed: dino_dim/32 output tiles x 8 K tiles, fragment order (m, t, s). */
+int nrf_debug_pack_dino_grad(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int mma_mode,
+                             uint8_t* stream_out, int64_t stream_cap, int64_t* stream_bytes);
 
 /* ---- misc ------------------------------------------------------------------ */
 const char* nrf_last_error(void);
@@ -324,6 +341,12 @@ int nrf_mlp_forward_train(nrf_model* m, int mma_mode, const float* positions, co
 int nrf_mlp_backward(nrf_model* m, int mma_mode, const float* rgb, const float* density,
                      const float* g_rgb, const float* g_density, int64_t n,
                      void* ctx, int64_t ctx_bytes, float* flat_grad, void* stream);
+
+/* NRF_NET_V3, after nrf_mlp_backward on the same ctx (same n and mode): d_dino (n, dino_dim) = dL/d dino, the gradient with
+ * respect to the per-sample features nrf_mlp_forward_train read (lora_dino.py:181,187-191: through both fusion passes and the
+ * gate).  One more launch over what the backward saved; nrf_train_context_bytes does not change.  d_dino is overwritten
+ * (16-byte aligned).  NRF_EINVAL for another network family, a context that is too small or stale backward weights. */
+int nrf_mlp_backward_dino(nrf_model* m, int mma_mode, int64_t n, void* ctx, int64_t ctx_bytes, float* d_dino, void* stream);
 
 /* Backward of nrf_composite (autograd through nerf_mlp.py:181-212): given
  * dL/d rgb_map (n_rays,3), optionally dL/d depth (n_rays) and dL/d weights

@@ -105,6 +105,14 @@ SIGNATURES = {
     "nrf_sample_features": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "nrf_debug_pack_backward": (C.c_int, [C.POINTER(nrf_arch), C.POINTER(nrf_linear), C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "nrf_debug_train_plan": (C.c_int, [C.POINTER(nrf_arch), C.POINTER(nrf_linear), C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    # gradients with respect to the DINO features / feature maps
+    "nrf_debug_pack_dino_grad": (C.c_int, [C.POINTER(nrf_arch), C.POINTER(nrf_linear), C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "nrf_fetch_backward_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int64]),
+    "nrf_project_fetch_backward": (C.c_int, [C.POINTER(nrf_dino), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                             C.c_void_p]),
+    "nrf_sample_features_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_int64, C.c_void_p]),
+    "nrf_mlp_backward_dino": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     # training path
     "nrf_param_count": (C.c_int64, [C.c_void_p]),
     "nrf_model_update_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),

@@ -29,7 +29,7 @@ FUSED = [(f"fused_{fam}.hip", f"fused_{fam}_{half}", flags) for fam in ("v1", "v
 # tail mode (fused_impl.hpp: render_march): the last-sample kernels of all four families, split-f16 only
 TAIL = [("fused_tail.hip", "fused_tail", HALF32)]
 SOURCES = FUSED + TAIL + [(f, os.path.splitext(f)[0], []) for f in
-                   ("fused_kernels.hip", "train_shared.hip", "train_v1.hip", "train_v2.hip", "train_v3.hip", "staged_kernels.hip", "api.cpp",
+                   ("fused_kernels.hip", "train_shared.hip", "train_v1.hip", "train_v2.hip", "train_v3.hip", "train_dino_grad.hip", "staged_kernels.hip", "api.cpp",
                     "packing.cpp")]
 # -Rpass-analysis=kernel-resource-usage: the backend reports every kernel's registers / spills / scratch; kept beside the object
 # (<name>.o.remarks, see kernel_resources()) so that a toolchain or flag change that breaks the AGPR parking or introduces

@@ -54,9 +54,22 @@ def dino_model_from_config(cfg, weights=None, backbone_config=None):
     return SpatialDINOFeatures(image_size=int(cfg["data"]["resolution"]), **kw)
 
 
-def precompute_dino_features(dino_model, images):
+def lora_trainable_parameters(dino_model):
+    """The trainable set of train.py:105-110: extractor parameters with `lora` in their name get requires_grad, everything else
+    is frozen.  Returns the list the optimizer takes."""
+    out = []
+    for name, p in dino_model.named_parameters():
+        p.requires_grad = "lora" in name
+        if p.requires_grad:
+            out.append(p)
+    return out
+
+
+def precompute_dino_features(dino_model, images, requires_grad=False):
     """train.py:158-169: one map per training view, computed once under no_grad in eval mode.  `images`: (V,3,H,W) or (V,H,W,3) in
-    [0,1]; normalised with the ImageNet statistics of train.py:128-131 -> (V,Hp,Wp,C) on the extractor's device."""
+    [0,1]; normalised with the ImageNet statistics of train.py:128-131 -> (V,Hp,Wp,C) on the extractor's device.
+    requires_grad=True: the extractor runs in its CURRENT mode under grad and the maps stay attached to it (map.backward(d_map)
+    reaches its trainable parameters) -- what a trainer that adapts the extractor calls per view."""
     import torch
     from .dino_backbone import IMAGENET_MEAN, IMAGENET_STD
     x = torch.as_tensor(images).float()
@@ -65,6 +78,9 @@ def precompute_dino_features(dino_model, images):
     dev = next(dino_model.parameters()).device
     mean = torch.tensor(IMAGENET_MEAN, device=dev).view(1, 3, 1, 1)
     std = torch.tensor(IMAGENET_STD, device=dev).view(1, 3, 1, 1)
+    if requires_grad:
+        with torch.enable_grad():
+            return torch.cat([dino_model((x[v:v + 1].to(dev) - mean) / std) for v in range(x.shape[0])], 0)
     was_training = dino_model.training
     dino_model.eval()
     maps = []

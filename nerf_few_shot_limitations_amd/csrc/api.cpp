@@ -101,7 +101,8 @@ struct nrf_model {
     bool lin_stale = false;                 // parameters were last set from a device vector: the host copy `lin` is old
     bool bfresh[3] = {false, false, false}; // backward stream of the mode matches the current parameters
     nrf::ParamLayout layout;
-    nrf::NetPlan bplan;
+    nrf::NetPlan bplan;                     // the dZ chain's layers, and behind them (V3) the feature-gradient kernel's W0d^T layer:
+    int g_frags16 = 0;                      // one device stream, one gather table, one re-pack, one freshness flag; 16-bit fragments of that layer
     nrf::TrainPlan tplan;
     nrf::TrainDev train{};
     void* d_bstream[3] = {nullptr, nullptr, nullptr};
@@ -125,7 +126,7 @@ int upload(nrf_model* m, hipStream_t s, bool allocate) {
     m->lin_stale = false;
     if (m->train_ready) {
         for (int mode = 0; mode < 3; ++mode) {
-            const nrf::PackedStream ps = nrf::pack_stream(m->bplan, m->lin, mode);
+            const nrf::PackedStream ps = nrf::pack_stream(m->bplan, m->lin, mode);      // (with the W0d^T layer: ensure_train)
             NRF_HIP(hipMemcpyAsync(m->d_bstream[mode], ps.bytes.data(), ps.bytes.size(), hipMemcpyHostToDevice, s));
             NRF_HIP(hipStreamSynchronize(s));
             m->bfresh[mode] = true;
@@ -171,12 +172,22 @@ int ensure_train(nrf_model* m) {
         return fail(NRF_EUNSUPPORTED, err);
     if ((int)m->tplan.slot_tiles.size() > nrf::kMaxSlots || (int)m->tplan.jobs.size() > nrf::kMaxJobs || m->tplan.n_mask_slots > nrf::kMaxMaskSlots)
         return fail(NRF_EUNSUPPORTED, "network too deep for the training path");
+    if (m->arch.net == NRF_NET_V3) {
+        // W0d^T (train_dino_grad_impl.hpp) rides behind the chain's layers: the chain kernels wrap at n_bchunks and never see it
+        nrf::NetPlan gplan;
+        if (!nrf::make_dino_grad_plan(m->arch, m->lin, gplan, err)) return fail(NRF_EUNSUPPORTED, err);
+        m->g_frags16 = gplan.layers[0].MT * gplan.layers[0].KT * 2;
+        m->bplan.layers.push_back(gplan.layers[0]);
+    }
     for (int mode = 0; mode < 3; ++mode) {
         const nrf::PackedStream ps = nrf::pack_stream(m->bplan, m->lin, mode);
         NRF_HIP(hipMalloc(&m->d_bstream[mode], ps.bytes.size()));
         NRF_HIP(hipMemcpy(m->d_bstream[mode], ps.bytes.data(), ps.bytes.size(), hipMemcpyHostToDevice));
+        // the layer is whole chunks: 16 fragments per chunk, DT * 16 (16-bit) or DT * 32 (fp32) fragments
+        const uint32_t g_chunks = (uint32_t)(m->g_frags16 * (mode == NRF_MMA_F32 ? 2 : 1) / 16);
         m->train.bstream[mode] = m->d_bstream[mode];
-        m->train.n_bchunks[mode] = ps.n_chunks;
+        m->train.n_bchunks[mode] = ps.n_chunks - g_chunks;
+        m->train.gstream[mode] = g_chunks ? static_cast<const char*>(m->d_bstream[mode]) + (size_t)m->train.n_bchunks[mode] * 16 * 1024 : nullptr;
         m->bfresh[mode] = !m->lin_stale;
     }
     for (int f32 = 0; f32 < 2; ++f32) {
@@ -637,6 +648,17 @@ int nrf_mlp_backward(nrf_model* m, int mma_mode, const float* rgb, const float* 
     });
 }
 
+int nrf_mlp_backward_dino(nrf_model* m, int mma_mode, int64_t n, void* ctx, int64_t ctx_bytes, float* d_dino, void* stream) {
+    auto wrong = [&]() -> const char* {
+        if (m->arch.net != NRF_NET_V3) return "nrf_mlp_backward_dino: only the V3 network has DINO feature inputs";
+        if ((reinterpret_cast<uintptr_t>(d_dino) & 15u) != 0) return "nrf_mlp_backward_dino: d_dino must be 16-byte aligned";
+        return nullptr;
+    };
+    return train_entry(m, mma_mode, n, !ctx || !d_dino, ctx_bytes, true, wrong, [&](std::string& err) {
+        return nrf::launch_dino_grad(m->net, m->train, mma_mode, n, ctx, d_dino, (hipStream_t)stream, err);
+    });
+}
+
 int nrf_composite_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals, const float* rays_d,
                            int64_t n_rays, int n_samples, int white_bkgd, const float* g_rgb, const float* g_depth, const float* g_weights,
                            float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, void* stream) {
@@ -792,6 +814,67 @@ int nrf_sample_features(const float* features, int Hp, int Wp, int C, const floa
     if (!features || !points_2d || !feats) return fail(NRF_EINVAL, "null pointer");
     const int r = nrf::launch_sample_features(features, Hp, Wp, C, points_2d, n, feats, (hipStream_t)stream);
     return r == NRF_OK ? NRF_OK : fail(r, "sample_features launch failed");
+}
+
+int64_t nrf_fetch_backward_workspace_bytes(int Hp, int Wp, int C, int64_t n) {
+    if (n < 0 || Hp < 1 || Wp < 1 || C < 1) { (void)fail(NRF_EINVAL, "nrf_fetch_backward_workspace_bytes: bad sizes"); return -1; }
+    return 4 * nrf::fetch_backward_ws_floats(Hp, Wp, C, n);
+}
+
+extern "C++" {
+namespace {
+// the checks the two fetch adjoints share; 1 = nothing to do
+int fetch_backward_check(int Hp, int Wp, int C, const void* points, int64_t n, const float* d_feats, float* d_map, int accumulate, void* ws,
+                         int64_t ws_bytes) {
+    if (n < 0 || Hp < 1 || Wp < 1 || C < 1) return fail(NRF_EINVAL, "bad sizes");
+    if (!d_map) return fail(NRF_EINVAL, "null pointer");
+    if (n == 0 && accumulate) return 1;
+    if (n > 0 && (!points || !d_feats)) return fail(NRF_EINVAL, "null pointer");
+    if (!ws) return fail(NRF_EINVAL, "fetch backward workspace is NULL");
+    if ((reinterpret_cast<uintptr_t>(ws) & 3u) != 0) return fail(NRF_EINVAL, "fetch backward workspace must be 4-byte aligned");
+    if (ws_bytes < 4 * nrf::fetch_backward_ws_floats(Hp, Wp, C, n)) return fail(NRF_EINVAL, "workspace smaller than nrf_fetch_backward_workspace_bytes");
+    return NRF_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int nrf_project_fetch_backward(const nrf_dino* dino, const float* points, int64_t n, const float* d_feats, float* d_map, int accumulate, void* ws,
+                               int64_t ws_bytes, void* stream) {
+    if (!dino) return fail(NRF_EINVAL, "dino is NULL");
+    if (dino->Hp < 1 || dino->Wp < 1 || dino->C < 1 || dino->H < 1 || dino->W < 1) return fail(NRF_EINVAL, "dino: bad map / image size");
+    const int c = fetch_backward_check(dino->Hp, dino->Wp, dino->C, points, n, d_feats, d_map, accumulate, ws, ws_bytes);
+    if (c != NRF_OK) return c == 1 ? NRF_OK : c;
+    nrf::DinoDev d{};                                       // the map itself (dino->features) is not read
+    d.Hp = dino->Hp; d.Wp = dino->Wp; d.C = dino->C;
+    std::memcpy(d.inv_pose, dino->inv_pose, sizeof(float) * 12);
+    d.focal = dino->focal; d.H = dino->H; d.W = dino->W;
+    const int r = nrf::launch_project_fetch_backward(d, points, n, d_feats, d_map, accumulate, (float*)ws, (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "project_fetch backward launch failed");
+}
+
+int nrf_sample_features_backward(int Hp, int Wp, int C, const float* points_2d, int64_t n, const float* d_feats, float* d_map, int accumulate,
+                                 void* ws, int64_t ws_bytes, void* stream) {
+    const int c = fetch_backward_check(Hp, Wp, C, points_2d, n, d_feats, d_map, accumulate, ws, ws_bytes);
+    if (c != NRF_OK) return c == 1 ? NRF_OK : c;
+    const int r = nrf::launch_sample_features_backward(Hp, Wp, C, points_2d, n, d_feats, d_map, accumulate, (float*)ws, (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "sample_features backward launch failed");
+}
+
+int nrf_debug_pack_dino_grad(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int mma_mode, uint8_t* stream_out, int64_t stream_cap,
+                             int64_t* stream_bytes) {
+    if (!arch || !linears || n_linear <= 0) return fail(NRF_EINVAL, "nrf_debug_pack_dino_grad: null argument");
+    if (mma_mode < 0 || mma_mode > 2) return fail(NRF_EINVAL, "unknown mma_mode");
+    std::string err;
+    std::vector<nrf::HostLinear> lin;
+    nrf::NetPlan plan;
+    if (!copy_linears(linears, n_linear, lin, err) || !nrf::make_dino_grad_plan(*arch, lin, plan, err)) return fail(NRF_EINVAL, err);
+    const nrf::PackedStream ps = nrf::pack_stream(plan, lin, mma_mode);
+    if (stream_bytes) *stream_bytes = (int64_t)ps.bytes.size();
+    if (stream_out) {
+        if (stream_cap < (int64_t)ps.bytes.size()) return fail(NRF_EINVAL, "stream_out too small");
+        std::memcpy(stream_out, ps.bytes.data(), ps.bytes.size());
+    }
+    return NRF_OK;
 }
 
 int nrf_debug_pack_backward(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int mma_mode, uint8_t* stream_out, int64_t stream_cap,

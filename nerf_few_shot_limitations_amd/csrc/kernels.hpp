@@ -97,6 +97,7 @@ struct TrainDev {
     int n_jobs;
     int job_x_slot[kMaxJobs], job_dz_slot[kMaxJobs], job_KT[kMaxJobs], job_MT[kMaxJobs], job_x_first[kMaxJobs];
     int64_t n_params;
+    const void* gstream[3];     // V3: the W0d^T fragments of dino_grad_kernel (train_dino_grad_impl.hpp), behind the chain's layers in bstream
 };
 
 int64_t train_ctx_bytes(const TrainDev& t, int mma_mode, int64_t n);
@@ -113,6 +114,8 @@ int launch_train_forward_v3(const DeviceNet& net, const TrainDev& t, int mma_mod
                             float* rgb, float* density, void* ctx, hipStream_t s, std::string& err);
 int launch_train_backward_v3(const DeviceNet& net, const TrainDev& t, int mma_mode, const float* rgb, const float* density,
                              const float* g_rgb, const float* g_density, int64_t n, void* ctx, float* grad, hipStream_t s, std::string& err);
+// V3, after launch_train_backward_v3 on the same context: d_dino (n, dino_dim) = dL/d per-sample DINO features
+int launch_dino_grad(const DeviceNet& net, const TrainDev& t, int mma_mode, int64_t n, void* ctx, float* d_dino, hipStream_t s, std::string& err);
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd, int step,
                 const float* ray_loss, int64_t n_rays, float loss_weight, float* loss, hipStream_t s);
 int launch_mse_grad(const float* pred, const float* target, int64_t n, float weight, float* g_pred, float* loss, hipStream_t s);
@@ -169,5 +172,12 @@ int launch_sample_pdf(const float* z, const float* w, int64_t n_rays, int S, int
                       float* z_union, hipStream_t s);
 int launch_project_fetch(const DinoDev& d, const float* points, int64_t n, float* feats, float* xy, hipStream_t s);
 int launch_sample_features(const float* features, int Hp, int Wp, int C, const float* points_2d, int64_t n, float* feats, hipStream_t s);
+// adjoints of the two fetches with respect to the map (no atomics: per-slab private copies in `ws`, fetch_backward_ws_floats(...)
+// floats, added in a fixed order): d_map (Hp,Wp,C) = [d_map +] fetch^T(d_feats (n,C)); d.features is not read
+int64_t fetch_backward_ws_floats(int Hp, int Wp, int C, int64_t n);
+int launch_project_fetch_backward(const DinoDev& d, const float* points, int64_t n, const float* d_feats, float* d_map, int accumulate, float* ws,
+                                  hipStream_t s);
+int launch_sample_features_backward(int Hp, int Wp, int C, const float* points_2d, int64_t n, const float* d_feats, float* d_map, int accumulate,
+                                    float* ws, hipStream_t s);
 
 }  // namespace nrf

@@ -392,6 +392,24 @@ bool make_backward_plan(const nrf_arch& a, const std::vector<HostLinear>& lin, N
     return true;
 }
 
+// The A operand of dino_grad_kernel (train_dino_grad_impl.hpp): W0d^T, the F0T layer above restricted to the DT DINO tiles
+// of fusion.0's input -- K = fusion.0's 256 rows, output row r = channel r of the fetched feature.
+bool make_dino_grad_plan(const nrf_arch& a, const std::vector<HostLinear>& lin, NetPlan& plan, std::string& err) {
+    plan = NetPlan();
+    if (a.net != NRF_NET_V3) { err = "the DINO feature gradient belongs to the V3 network"; return false; }
+    NetPlan fwd;
+    if (!make_plan(a, lin, fwd, err)) return false;
+    const LayerPlan& F0 = fwd.layers[0];
+    const int H = a.hidden, HT = H / 32, DT = a.dino_dim / 32, PT = F0.KT - DT;
+    LayerPlan L; L.transposed = true; L.KT = HT; L.MT = DT; L.krow.assign(32 * HT, {-1, 0});
+    for (int k = 0; k < H; ++k) L.krow[k] = {0, k};
+    L.rcol.assign(F0.col.begin() + 32 * PT, F0.col.begin() + 32 * F0.KT);
+    L.bias_off = 0;
+    plan.layers.push_back(std::move(L));
+    plan.n_bias = 32 * DT;
+    return true;
+}
+
 bool make_train_plan(const nrf_arch& a, const NetPlan& fwd, const ParamLayout& lay, TrainPlan& tp, std::string& err) {
     tp = TrainPlan();
     if (a.net != NRF_NET_V1 && a.net != NRF_NET_V2 && a.net != NRF_NET_V3) { err = "unknown network family"; return false; }

@@ -51,6 +51,9 @@ int expected_linears(const nrf_arch& arch);
 // The backward chain of a network (train_impl.hpp walks the layers in this order); V1 and V2 are built.
 bool make_backward_plan(const nrf_arch& arch, const std::vector<HostLinear>& lin, NetPlan& plan, std::string& err);
 
+// V3: the one-layer plan of W0d^T, the transposed DINO columns of fusion.0 (the feature-gradient kernel's A operand).
+bool make_dino_grad_plan(const nrf_arch& arch, const std::vector<HostLinear>& lin, NetPlan& plan, std::string& err);
+
 // Where every element of a packed stream comes from: flat-parameter offset, -1 = zero.  Elements in stream
 // order (fragment, lane, element); 512 per fragment in the 16-bit modes, 256 in the fp32 mode.  The host packer
 // and the device re-packer (after every optimizer step) are both a gather through this table.

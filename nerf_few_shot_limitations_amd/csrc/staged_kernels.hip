@@ -566,6 +566,158 @@ __global__ void __launch_bounds__(kBlock) project_fetch_kernel(DinoDev d, const 
     }
 }
 
+// Adjoint of project_fetch_kernel with respect to the map: d_map[tap] += w_tap * d_feats[sample] over the <= 4 on-map taps
+// (the same gx, gy, floorf, wx * wy and on-map test as above).  No atomics: 81 texel rows taking 4 taps from each of 10^4..10^5
+// samples is the worst contention shape there is, and the parameter gradients of this library are bit-reproducible on
+// purpose.  Slab form instead: workgroup (chunk, slab) walks ITS samples in order and adds into a private copy of ITS chunk of
+// the map in LDS -- thread <-> channel, so no two threads ever touch one address of it and the order of the
+// additions is fixed -- then leaves the copy in the workspace with plain stores; fetch_backward_reduce_kernel adds the
+// slabs' copies per element in slab order.  A chunk = kFetchLdsFloats / cw texels x cw = min(C, kFetchLdsFloats) channels: one
+// chunk for the 9 x 9 maps of the reference, 22 for a 37 x 37 x 128 one.
+constexpr int kFetchLdsFloats = 8192;        // 32 KiB
+constexpr int kFetchBatch = 8;               // samples whose gradient rows are in flight together
+constexpr int kFetchTaps = 64;               // samples whose taps are worked out together (one per thread of the first wave)
+
+struct FetchBwdGeo {
+    int cw, n_cchunks, tpc, n_tchunks, threads;
+    int64_t slabs, per_slab;
+};
+
+inline FetchBwdGeo fetch_bwd_geo(int Hp, int Wp, int C, int64_t n) {
+    FetchBwdGeo g;
+    g.cw = C < kFetchLdsFloats ? C : kFetchLdsFloats;
+    g.n_cchunks = (C + g.cw - 1) / g.cw;
+    g.tpc = kFetchLdsFloats / g.cw;
+    const int64_t texels = (int64_t)Hp * Wp;
+    if (g.tpc > texels) g.tpc = (int)texels;
+    g.n_tchunks = (int)((texels + g.tpc - 1) / g.tpc);
+    g.threads = g.cw <= 64 ? 64 : (g.cw <= 128 ? 128 : 256);
+    // ~64 samples per slab, at most ~1024 workgroups in all (a function of the sizes only: the workspace is sized without a device)
+    const int64_t chunks = (int64_t)g.n_tchunks * g.n_cchunks;
+    int64_t max_slabs = 1024 / chunks;
+    if (max_slabs < 1) max_slabs = 1;
+    int64_t slabs = (n + 63) / 64;
+    if (slabs > max_slabs) slabs = max_slabs;
+    if (slabs < 1) slabs = 1;
+    g.per_slab = (n + slabs - 1) / slabs;
+    if (g.per_slab < 1) g.per_slab = 1;
+    g.slabs = (n + g.per_slab - 1) / g.per_slab;
+    if (g.slabs < 1) g.slabs = 1;
+    return g;
+}
+
+__global__ void __launch_bounds__(256) project_fetch_backward_kernel(DinoDev d, const float* __restrict__ points, int64_t n,
+                                                                     const float* __restrict__ d_feats, float* __restrict__ ws, int points2d,
+                                                                     int cw, int n_cchunks, int tpc, int64_t per_slab) {
+    __shared__ float acc[kFetchLdsFloats];
+    __shared__ int4 s_tap[kFetchTaps];
+    __shared__ float4 s_wt[kFetchTaps];
+    const int chunk = blockIdx.x, slab = blockIdx.y;
+    const int tchunk = chunk / n_cchunks, c0 = (chunk - tchunk * n_cchunks) * cw;
+    const int64_t texels = (int64_t)d.Hp * d.Wp;
+    const int64_t t0 = (int64_t)tchunk * tpc, t1 = t0 + tpc < texels ? t0 + tpc : texels;
+    const int nt = (int)(t1 - t0);
+    const int cn = c0 + cw <= d.C ? cw : d.C - c0;          // channels of this chunk
+    for (int t = 0; t < nt; ++t)
+        for (int c = threadIdx.x; c < cn; c += blockDim.x) acc[t * cw + c] = 0.0f;
+    const int64_t s0 = slab * per_slab, s1 = s0 + per_slab < n ? s0 + per_slab : n;
+    for (int64_t sb = s0; sb < s1; sb += kFetchTaps) {
+        // the taps of the next kFetchTaps samples, one sample per thread of the first wave: texel inside the chunk (-1: off the
+        // map or in another chunk) and weight
+        __syncthreads();
+        if (threadIdx.x < kFetchTaps) {
+            const int64_t pi = sb + threadIdx.x;
+            int tp[4] = {-1, -1, -1, -1};
+            float wt[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (pi < s1) {
+                float xn, yn;
+                if (points2d) {
+                    xn = points[pi * 2]; yn = points[pi * 2 + 1];
+                } else {
+                    const float p[3] = {points[pi * 3], points[pi * 3 + 1], points[pi * 3 + 2]};
+                    project_point(d, p, xn, yn);
+                }
+                const float gx = ((xn + 1.0f) * (float)d.Wp - 1.0f) * 0.5f;
+                const float gy = ((yn + 1.0f) * (float)d.Hp - 1.0f) * 0.5f;
+                const float x0 = floorf(gx), y0 = floorf(gy);
+#pragma unroll
+                for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+                    for (int dx = 0; dx < 2; ++dx) {
+                        const float xi = x0 + dx, yi = y0 + dy;
+                        const float wx = dx ? gx - x0 : x0 + 1.0f - gx;
+                        const float wy = dy ? gy - y0 : y0 + 1.0f - gy;
+                        if (xi >= 0.0f && xi <= (float)(d.Wp - 1) && yi >= 0.0f && yi <= (float)(d.Hp - 1)) {
+                            const int64_t texel = (int64_t)yi * d.Wp + (int64_t)xi;
+                            if (texel >= t0 && texel < t1) {
+                                tp[2 * dy + dx] = (int)(texel - t0);
+                                wt[2 * dy + dx] = wx * wy;
+                            }
+                        }
+                    }
+            }
+            s_tap[threadIdx.x] = make_int4(tp[0], tp[1], tp[2], tp[3]);
+            s_wt[threadIdx.x] = make_float4(wt[0], wt[1], wt[2], wt[3]);
+        }
+        __syncthreads();
+        const int cnt = (int)(s1 - sb < kFetchTaps ? s1 - sb : kFetchTaps);
+        for (int c = threadIdx.x; c < cn; c += blockDim.x) {
+            const float* gp = d_feats + sb * d.C + c0 + c;
+            for (int u0 = 0; u0 < cnt; u0 += kFetchBatch) {      // kFetchBatch gradient rows in flight, applied in sample order
+                int4 tp[kFetchBatch];
+                float g[kFetchBatch];
+#pragma unroll
+                for (int u = 0; u < kFetchBatch; ++u) {
+                    tp[u] = u0 + u < cnt ? s_tap[u0 + u] : make_int4(-1, -1, -1, -1);
+                    const bool any = (tp[u].x & tp[u].y & tp[u].z & tp[u].w) >= 0;       // -1 = all bits set
+                    g[u] = any ? gp[(int64_t)(u0 + u) * d.C] : 0.0f;
+                }
+#pragma unroll
+                for (int u = 0; u < kFetchBatch; ++u) {
+                    if ((tp[u].x & tp[u].y & tp[u].z & tp[u].w) < 0) continue;
+                    const float4 w = s_wt[u0 + u];
+                    if (tp[u].x >= 0) acc[tp[u].x * cw + c] += g[u] * w.x;
+                    if (tp[u].y >= 0) acc[tp[u].y * cw + c] += g[u] * w.y;
+                    if (tp[u].z >= 0) acc[tp[u].z * cw + c] += g[u] * w.z;
+                    if (tp[u].w >= 0) acc[tp[u].w * cw + c] += g[u] * w.w;
+                }
+            }
+        }
+    }
+    float* out = ws + (int64_t)slab * texels * d.C;
+    for (int t = 0; t < nt; ++t)
+        for (int c = threadIdx.x; c < cn; c += blockDim.x) out[(t0 + t) * d.C + c0 + c] = acc[t * cw + c];
+}
+
+// d_map[e] = (accumulate ? d_map[e] : 0) + sum over the slabs, in slab order, of their copies' element e
+__global__ void __launch_bounds__(kBlock) fetch_backward_reduce_kernel(const float* __restrict__ ws, int64_t elems, int64_t slabs,
+                                                                       float* __restrict__ d_map, int accumulate) {
+    for (int64_t e = blockIdx.x * (int64_t)kBlock + threadIdx.x; e < elems; e += (int64_t)gridDim.x * kBlock) {
+        float s = 0.0f;
+        int64_t k = 0;
+        for (; k + 8 <= slabs; k += 8) {                     // eight loads in flight, added in order
+            float q[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) q[j] = ws[(k + j) * elems + e];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) s += q[j];
+        }
+        for (; k < slabs; ++k) s += ws[k * elems + e];
+        d_map[e] = accumulate ? d_map[e] + s : s;
+    }
+}
+
+int fetch_backward_impl(const DinoDev& d, const float* points, int points2d, int64_t n, const float* d_feats, float* d_map, int accumulate,
+                          float* ws, hipStream_t s) {
+    const FetchBwdGeo g = fetch_bwd_geo(d.Hp, d.Wp, d.C, n);
+    const int64_t elems = (int64_t)d.Hp * d.Wp * d.C;
+    hipLaunchKernelGGL(project_fetch_backward_kernel, dim3((unsigned)(g.n_tchunks * g.n_cchunks), (unsigned)g.slabs), dim3(g.threads), 0, s, d,
+                       points, n, d_feats, ws, points2d, g.cw, g.n_cchunks, g.tpc, g.per_slab);
+    if (hipGetLastError() != hipSuccess) return NRF_EHIP;
+    hipLaunchKernelGGL(fetch_backward_reduce_kernel, dim3(grid_for(elems, kBlock, 4096)), dim3(kBlock), 0, s, ws, elems, g.slabs, d_map, accumulate);
+    return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
+}
+
 }  // namespace
 
 int launch_get_rays(const Camera& cam, int64_t ray_begin, int64_t n, float* rays_o, float* rays_d, hipStream_t s) {
@@ -691,6 +843,20 @@ int launch_sample_features(const float* features, int Hp, int Wp, int C, const f
     d.features = features; d.Hp = Hp; d.Wp = Wp; d.C = C;
     hipLaunchKernelGGL(project_fetch_kernel, dim3(grid_for(n * C, kBlock, 8192)), dim3(kBlock), 0, s, d, points_2d, n, feats, (float*)nullptr, 1);
     return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
+}
+
+int64_t fetch_backward_ws_floats(int Hp, int Wp, int C, int64_t n) { return fetch_bwd_geo(Hp, Wp, C, n).slabs * (int64_t)Hp * Wp * C; }
+
+int launch_project_fetch_backward(const DinoDev& d, const float* points, int64_t n, const float* d_feats, float* d_map, int accumulate, float* ws,
+                                  hipStream_t s) {
+    return fetch_backward_impl(d, points, 0, n, d_feats, d_map, accumulate, ws, s);
+}
+
+int launch_sample_features_backward(int Hp, int Wp, int C, const float* points_2d, int64_t n, const float* d_feats, float* d_map, int accumulate,
+                                    float* ws, hipStream_t s) {
+    DinoDev d{};
+    d.Hp = Hp; d.Wp = Wp; d.C = C;
+    return fetch_backward_impl(d, points_2d, 1, n, d_feats, d_map, accumulate, ws, s);
 }
 
 }  // namespace nrf

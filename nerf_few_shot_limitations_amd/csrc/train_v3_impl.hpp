@@ -4,8 +4,8 @@
 //   fused = fusion(cat[pe, dino]);  (w0, w1) = softmax(attention(fused));
 //   x     = output_proj(fusion(cat[pe * w0, dino * w1]))          -- the SAME fusion weights, twice
 //   then DensityMLP(x) and ColorMLP as in V2.
-// No gradient with respect to positions, directions or the per-sample DINO features (the reference's feature extractor is
-// outside the path).
+// No gradient with respect to positions or directions.  The gradient with respect to the per-sample DINO features is a kernel
+// of its own behind this chain (train_dino_grad_impl.hpp), from the two dZ(fusion.0) slots and the gate saved here.
 //
 // Slots and planes: train_slots.hpp (SlotsV3).
 #pragma once

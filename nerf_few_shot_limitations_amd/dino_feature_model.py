@@ -12,8 +12,12 @@ HIP kernel (dino_features.py) instead of F.grid_sample.
 How the trainer uses them (and what that means for gradients): `NeRFDINOTrainer.precompute_dino_features` (train.py:158-169)
 and `MultiScaleNeRFDINOTrainer` (train_multiscale.py:114-120) run the extractor ONCE per training view under
 `torch.no_grad()` and keep the maps; the LoRA matrices are handed to the optimizer (train.py:105-110) but no gradient ever
-reaches them -- and with lora_B initialised to zero the wrappers add exactly 0.  The hot path therefore needs the maps as
-constants, which is what the fused renderer and NeRFMLP.forward take (SURVEY.md defect ledger: this is D13).
+reaches them -- and with lora_B initialised to zero the wrappers add exactly 0 (SURVEY.md defect ledger: D13).  That stays the
+default: the fused renderer and NeRFMLP.forward take the maps as constants.  The intent -- features adapted to the scene -- is
+opt-in: `feature_grad = True` on an extractor makes its sample_features_at_points differentiable with respect to the map,
+NeRFMLP(dino_grad=True) returns dL/d features, and config.precompute_dino_features(requires_grad=True) runs the extractor
+under grad (train_cli --train-extractor).  MultiScaleDINOFeatures keeps the reference's no_grad backbone pass
+(multi_scale_dino.py:87), so its LoRA matrices receive nothing either way.
 """
 from __future__ import annotations
 
@@ -69,13 +73,15 @@ def _pixel_values(module, images):
     return images                                                           # an already normalised (B,3,H,W) tensor (train.py:164-166)
 
 
-def _sample(features, points_2d):
+def _sample(features, points_2d, feature_grad=False):
     from .dino_features import sample_features_at_points
-    return sample_features_at_points(features, points_2d)
+    return sample_features_at_points(features, points_2d, feature_grad=feature_grad)
 
 
 class SpatialDINOFeatures(nn.Module):
     """Patch features of one DINOv2 pass + a learned (Hp*Wp, 64) position table -> 3-layer projection to 64 channels."""
+
+    feature_grad = False          # True: sample_features_at_points carries the gradient of a map that requires grad
 
     def __init__(self, model_name="facebook/dinov2-base", use_lora=True, lora_rank=16, lora_alpha=16, image_size=128, pos_embed_dim=64,
                  weights=None, config=None):
@@ -105,12 +111,14 @@ class SpatialDINOFeatures(nn.Module):
 
     def sample_features_at_points(self, features, points_2d):
         """dino_feature_model.py:114-148 on the staged HIP kernel."""
-        return _sample(features, points_2d)
+        return _sample(features, points_2d, self.feature_grad)
 
 
 class MultiScaleDINOFeatures(nn.Module):
     """DINOv2 at input scales 1, 1/2, 1/4 -> per-scale 128-d projection -> self-attention inside each scale -> bilinear
     upsampling to the finest grid -> concatenation -> 128-d projection (multi_scale_dino.py:62-154)."""
+
+    feature_grad = False          # as SpatialDINOFeatures.feature_grad (reaches the projection heads; the backbone pass is no_grad)
 
     def __init__(self, model_name="facebook/dinov2-base", use_lora=True, lora_rank=16, lora_alpha=16, weights=None, config=None):
         super().__init__()
@@ -163,4 +171,4 @@ class MultiScaleDINOFeatures(nn.Module):
 
     def sample_features_at_points(self, features, points_2d):
         """multi_scale_dino.py:156-183 on the staged HIP kernel."""
-        return _sample(features, points_2d)
+        return _sample(features, points_2d, self.feature_grad)

@@ -9,8 +9,10 @@ Two constructor forms, as the reference uses them:
             src/training/train.py:82-89,229; the module tree mirrors
             src/models/nerf_mlp.py:86-158 (NeRFWithDINO) so checkpoints load by name.
 With grad enabled every form runs the training kernels (training.py: saved activations,
-transposed-stream backward, MFMA weight gradients); gradients reach the parameters only -- a
-dino_features tensor that requires grad is refused instead of silently detached.
+transposed-stream backward, MFMA weight gradients); gradients reach the parameters and, with
+`dino_grad=True` (use_dino form), the per-sample DINO features, so that a feature extractor in front
+of the module -- the LoRA matrices of lora.yaml -- trains; by default a dino_features tensor that
+requires grad is refused instead of silently detached (the reference computes its maps under no_grad).
 """
 from __future__ import annotations
 
@@ -68,9 +70,10 @@ class _FreqBuffer(nn.Module):          # nerf_mlp.py:14-15 registers freq_bands 
 
 class NeRFMLP(nn.Module):
     def __init__(self, pos_dim=63, hidden_dim=256, n_layers=8, *, pos_freq=None, dir_freq=4, num_density_layers=None,
-                 use_dino=False, dino_dim=0, mma_mode="f32"):
+                 use_dino=False, dino_dim=0, mma_mode="f32", dino_grad=False):
         super().__init__()
         self.mma_mode = mma_mode
+        self.dino_grad = bool(dino_grad)     # opt-in: backpropagate into dino_features / feature maps that require grad
         self.hidden_dim = int(hidden_dim)
         if pos_freq is None:
             # legacy form: input is already encoded

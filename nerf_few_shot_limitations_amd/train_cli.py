@@ -1,6 +1,6 @@
 """python -m nerf_few_shot_limitations_amd.train_cli --config experiments/baseline.yaml --data data/nerf_synthetic/lego \\
         [--recipe train|multiscale] [--epochs N] [--mode bf16|f16|f32] [--eval-mode f16] [--out DIR] [--checkpoint CKPT]
-        [--dino-weights DIR | --dino-maps maps.pt] [--seed 0]
+        [--dino-weights DIR | --dino-maps maps.pt] [--train-extractor] [--seed 0]
 
 The training run of `NeRFDINOTrainer` (src/training/train.py:244-292 `train_step`, :344-372 `train`) as a command on the
 HIP path: the YAML loads unchanged; per epoch and training view the rays are cast at the progressive schedule's
@@ -19,7 +19,8 @@ ReLU, nerf_mlp.NeRFLoss = rgb_weight * mse + `loss.reg_weight` * mean(weights^2)
 there: its targets carry no depth), clip_grad_norm_(max_norm=1.0) and optim.AdamW(lr, weight_decay); its checkpoints carry
 `nerf_state_dict` (train_multiscale.py:368-376) next to `nerf_model_state_dict`.  The ray batches, schedule, validation and
 LR steps stay this command's (the two trainers agree on them); the DINO-feature mean substitution of
-train_multiscale.py:190-197 (its mask is always false) is not part of it, and the extractor receives no gradient in either recipe.
+train_multiscale.py:190-197 (its mask is always false) is not part of it, and by default the extractor receives no gradient in
+either recipe.
 
 use_dino configs condition on the DINOv2 feature map of every training view.  As in train.py:158-169 the maps are computed ONCE,
 under no_grad, by the extractor the config names (config.dino_model_from_config: SpatialDINOFeatures or
@@ -28,6 +29,18 @@ not available offline) or, to exercise the pipeline without them, --dino-random-
 (V,Hp,Wp,C) instead.  The features of a sample are fetched by projection into the view being trained on (:203-214).  Because the
 maps are constants, no gradient reaches the extractor -- in the reference too: its LoRA matrices sit in the optimizer
 (train.py:105-110) but never receive one.
+
+--train-extractor is the intent behind those LoRA matrices, restated (the reference never re-runs its extractor, so there is
+no loop to copy).  Trainable set as train.py:105-110: extractor parameters with `lora` in their name, everything else frozen, in a
+torch.optim.Adam(lr, weight_decay) of the config that follows the same lr_at(epoch).  Per epoch and view the extractor runs
+on that view under grad (train mode, train.py:246-247); the view's ray batches use the detached map as before, every FusedStep
+also writes dL/d features (`d_dino_out`), which nrf_project_fetch_backward adds into one per-view d_map; after the view's last
+batch -- also when --max-batches ends the epoch inside the view -- `map.backward(d_map)` and one extractor step.  The NeRF
+parameters step per batch as before.  Validation recomputes view 0's map under no_grad first; checkpoints add
+`dino_model_state_dict` (train.py:384) and --checkpoint restores it.  Needs --dino-weights or --dino-random-init; refused
+with --dino-maps (nothing to train), with --data-parallel (the per-view d_map would need one more all-reduce: not built) and
+for `dino_model_type: multi_scale`: MultiScaleDINOFeatures runs its backbone under no_grad (multi_scale_dino.py:87, kept), so
+its LoRA matrices would still receive nothing -- refused rather than silently training nothing.
 
 --checkpoint resumes a run: weights, Adam moments and step count, epoch counter and best PSNR (the reference's train.py saves
 these keys, :374-389, but has no resume path); the LR schedule is a function of the epoch.  wandb and LPIPS are not part of
@@ -48,7 +61,7 @@ from . import _lib as L
 from . import (dino_model_from_config, evaluate_views, get_rays, load_blender_data, load_checkpoint_into, load_config, model_from_config,
                precompute_dino_features, render_settings, sample_points_along_rays)
 from .renderer import make_dino
-from .training import FusedStep
+from .training import FusedStep, project_fetch_backward
 
 
 def schedule_for(cfg, epoch):
@@ -90,8 +103,77 @@ def fetch_features(dino_struct, pts):
     return feats
 
 
-def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, dino_maps=None, max_batches=None, rank=0, world=1):
+def extractor_args_error(args, cfg):
+    """Why --train-extractor cannot run with these arguments / this config (None: it can).  Decided before any GPU work."""
+    if not getattr(args, "train_extractor", False):
+        return None
+    model_cfg = cfg.get("model", {}) or {}
+    if not bool(model_cfg.get("use_dino", True)):
+        return "--train-extractor: this config has use_dino: false, there is no extractor"
+    if args.dino_maps:
+        return "--train-extractor needs the extractor itself (--dino-weights or --dino-random-init): --dino-maps are constants"
+    if not (args.dino_weights or args.dino_random_init):
+        return "--train-extractor needs --dino-weights <local Dinov2Model checkpoint> or --dino-random-init"
+    if args.data_parallel:
+        return "--train-extractor with --data-parallel is not built (the per-view map gradient would need its own all-reduce)"
+    if model_cfg.get("dino_model_type", "single_scale") == "multi_scale":
+        return ("--train-extractor: MultiScaleDINOFeatures runs its backbone under no_grad (multi_scale_dino.py:87), its LoRA matrices "
+                "would receive no gradient")
+    if not bool((cfg.get("dino_model", {}) or {}).get("use_lora", True)):
+        return "--train-extractor: dino_model.use_lora is false, the trainable set of train.py:105-110 is empty"
+    return None
+
+
+class ExtractorTrainer:
+    """The extractor side of --train-extractor: the LoRA parameters (config.lora_trainable_parameters) in a torch.optim.Adam, one
+    live map per view and one step per view with the map gradient summed over the view's batches."""
+
+    def __init__(self, extractor, images, lr, weight_decay):
+        from .config import lora_trainable_parameters
+        self.extractor, self.images = extractor, images                      # images: (V,H,W,3) in [0,1] on the extractor's device
+        self.params = lora_trainable_parameters(extractor)
+        if not self.params:
+            raise ValueError("the extractor has no parameter with `lora` in its name: nothing to train")
+        self.opt = torch.optim.Adam(self.params, lr=lr, weight_decay=weight_decay)
+        self.map = self.d_map = self.d_feats = None
+        self.steps = 0
+
+    def set_lr(self, lr):
+        for g in self.opt.param_groups:
+            g["lr"] = lr
+
+    def begin_view(self, v):
+        """Run the extractor on view v under grad (train mode); returns the detached (1,Hp,Wp,C) map the batches read."""
+        self.extractor.train()
+        self.map = precompute_dino_features(self.extractor, self.images[v:v + 1], requires_grad=True).float()
+        self.d_map = torch.zeros_like(self.map)
+        return self.map.detach()
+
+    def feats_grad_buffer(self, n, c):
+        if self.d_feats is None or self.d_feats.shape[0] < n or self.d_feats.shape[1] != c:
+            self.d_feats = torch.empty((n, c), dtype=torch.float32, device=self.map.device)
+        return self.d_feats[:n]
+
+    def add_batch(self, dino, pts, d_feats):
+        """d_map += the fetch adjoint of this batch's dL/d features."""
+        project_fetch_backward(dino, pts, d_feats, self.d_map, accumulate=True)
+
+    def end_view(self):
+        """map.backward(sum of the view's batches) and one extractor step."""
+        if self.map is None:
+            return
+        self.opt.zero_grad(set_to_none=True)
+        self.map.backward(self.d_map)
+        self.opt.step()
+        self.steps += 1
+        self.map = self.d_map = None
+
+
+def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, dino_maps=None, max_batches=None, rank=0, world=1,
+                extractor=None):
     """One pass of train.py:261-290 over the training views; returns (mean loss, ray-samples processed).
+    extractor: an ExtractorTrainer (--train-extractor; module docstring) -- the view's map comes from it, live, instead of
+    dino_maps[v], and it takes one step per view.
     world > 1 (data parallel, `FusedStep(data_parallel=True)`): every rank draws the SAME shuffle (same generator seed) and
     takes rays rank, rank+world, ... of each batch -- the batches are those of one process (the stratified jitter of a ray is
     keyed by its position inside the call, so the sample depths differ from a single-process run's)."""
@@ -101,7 +183,9 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
     total, n_batches, samples = None, 0, 0
     for v in range(len(images)):
         ro, rd, tgt = view_rays(images[v], poses[v], H, W, focal, Ht, Wt)
-        dino = make_dino(dino_maps[v:v + 1], poses[v], focal, H, W) if use_dino else None       # train.py:204-206: full-resolution intrinsics
+        view_map = extractor.begin_view(v) if extractor is not None else (dino_maps[v:v + 1] if use_dino else None)
+        dino = make_dino(view_map, poses[v], focal, H, W) if use_dino else None                 # train.py:204-206: full-resolution intrinsics
+        cam = dict(features=view_map, pose=poses[v], focal=focal, H=H, W=W)
         order = torch.randperm(ro.shape[0], device=ro.device, generator=gen)
         for i in range(0, order.shape[0], batch):
             idx = order[i:i + batch]
@@ -114,12 +198,21 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
             n = idx.shape[0]
             dirs = d[:, None, :].expand(n, S, 3).reshape(-1, 3)                         # train.py:225: raw ray directions per sample
             feats = fetch_features(dino, pts.reshape(-1, 3)) if use_dino else None
-            loss = step(pts.reshape(-1, 3), z, d, t, dirs=dirs, dino=feats)
+            if extractor is not None:
+                d_feats = extractor.feats_grad_buffer(n * S, feats.shape[1])
+                loss = step(pts.reshape(-1, 3), z, d, t, dirs=dirs, dino=feats, d_dino_out=d_feats)
+                extractor.add_batch(cam, pts.reshape(-1, 3), d_feats)
+            else:
+                loss = step(pts.reshape(-1, 3), z, d, t, dirs=dirs, dino=feats)
             total = loss if total is None else total + loss
             n_batches += 1
             samples += n * S
             if max_batches is not None and n_batches >= max_batches:
+                if extractor is not None:
+                    extractor.end_view()                                                # step with what has been accumulated
                 return float(total) / n_batches, samples
+        if extractor is not None:
+            extractor.end_view()
     return (float(total) / max(n_batches, 1)) if total is not None else 0.0, samples
 
 
@@ -137,9 +230,10 @@ def step_options(cfg, recipe="train"):
     return kw
 
 
-def save_checkpoint(path, model, step, epoch, best_psnr, cfg, recipe="train"):
+def save_checkpoint(path, model, step, epoch, best_psnr, cfg, recipe="train", extractor=None):
     """train.py:374-389's dictionary: `nerf_model_state_dict` is what evaluate.py:27 / load_checkpoint_into read; the multiscale
-    recipe adds train_multiscale.py:368-376's `nerf_state_dict` (the same tensors)."""
+    recipe adds train_multiscale.py:368-376's `nerf_state_dict` (the same tensors); --train-extractor adds
+    `dino_model_state_dict` (train.py:384) and the extractor optimizer's state."""
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     opt = step.opt
     o = cfg["optimizer"]
@@ -151,6 +245,8 @@ def save_checkpoint(path, model, step, epoch, best_psnr, cfg, recipe="train"):
                                          "exp_avg_sq": None if opt.exp_avg_sq is None else opt.exp_avg_sq.cpu(), "lr": opt.lr},
                 # MultiStepLR is a pure function of the epoch (lr_at): its state is the epoch counter
                 "scheduler_state_dict": {"last_epoch": epoch + 1, "milestones": list(o["lr_milestones"]), "gamma": float(o["lr_gamma"])},
+                **({"dino_model_state_dict": {k: v.detach().cpu().clone() for k, v in extractor.extractor.state_dict().items()},
+                    "dino_optimizer_state_dict": extractor.opt.state_dict()} if extractor is not None else {}),
                 "config": cfg}, path)
 
 
@@ -186,6 +282,9 @@ def main(argv=None):
     ap.add_argument("--dino-maps", default=None, help="precomputed feature maps (V,Hp,Wp,C), torch.save'd, one per training view")
     ap.add_argument("--dino-weights", default=None, help="local transformers Dinov2Model checkpoint (dir or file) for the extractor of the config")
     ap.add_argument("--dino-random-init", action="store_true", help="build the extractor with random weights (pipeline runs, features meaningless)")
+    ap.add_argument("--train-extractor", action="store_true",
+                    help="backpropagate into the feature maps and train the extractor's LoRA matrices (train.py:105-110's trainable set), one "
+                         "extractor step per view; needs --dino-weights or --dino-random-init (module docstring)")
     ap.add_argument("--max-test-views", type=int, default=None)
     ap.add_argument("--max-batches", type=int, default=None, help="stop every epoch after this many ray batches (smoke runs)")
     ap.add_argument("--seed", type=int, default=0)
@@ -196,6 +295,9 @@ def main(argv=None):
                     help="--data-parallel on a box with ONE GPU: every rank on cuda:0, the gradient all-reduce over gloo through host memory "
                          "(RCCL refuses two ranks on one card); exercises the sharding and the collective, not multi-GPU speed")
     args = ap.parse_args(argv)
+    problem = extractor_args_error(args, load_config(args.config))
+    if problem:
+        raise SystemExit(problem)
     rank, world = 0, 1
     if args.data_parallel:
         import torch.distributed as dist
@@ -227,13 +329,16 @@ def main(argv=None):
         test_images, test_poses = test_images[: args.max_test_views], test_poses[: args.max_test_views]
 
     use_dino = bool(cfg.get("model", {}).get("use_dino", True))
-    dino_maps, dino_dim = None, 64
+    dino_maps, dino_dim, ext = None, 64, None
     if use_dino:
         if args.dino_maps:
             dino_maps = torch.load(args.dino_maps, map_location="cpu", weights_only=True).float().to(dev)
         elif args.dino_weights or args.dino_random_init:
             extractor = dino_model_from_config(cfg, weights=args.dino_weights).to(dev)           # train.py:57-75
             dino_maps = precompute_dino_features(extractor, torch.stack(images)[..., :3]).float()   # train.py:158-169: once, under no_grad
+            if args.train_extractor:
+                o = cfg["optimizer"]
+                ext = ExtractorTrainer(extractor, torch.stack(images)[..., :3], float(o["lr"]), float(o["weight_decay"]))
             del extractor
         else:
             raise SystemExit("this config conditions on DINO features: pass --dino-weights <local Dinov2Model checkpoint> (or --dino-random-init), "
@@ -245,6 +350,11 @@ def main(argv=None):
     ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=True) if args.checkpoint else None
     if ckpt is not None:
         load_checkpoint_into(model, ckpt)
+        if ext is not None and "dino_model_state_dict" in ckpt:
+            ext.extractor.load_state_dict(ckpt["dino_model_state_dict"])
+            if "dino_optimizer_state_dict" in ckpt:
+                ext.opt.load_state_dict(ckpt["dino_optimizer_state_dict"])
+    model.dino_grad = ext is not None
     model = model.to(dev).train()
     step = FusedStep(model, white_bkgd=rs["white_bkgd"], data_parallel=world > 1, **step_options(cfg, args.recipe),
                      **({"seed": args.seed} if args.recipe == "multiscale" else {}))
@@ -257,8 +367,11 @@ def main(argv=None):
     eval_dino = dict(features=dino_maps[0:1], pose=poses[0], focal=focal, H=H, W=W) if use_dino else None      # train.py:203-208
     for epoch in range(first_epoch, epochs):
         step.opt.lr = lr_at(cfg, epoch)
+        if ext is not None:
+            ext.set_lr(lr_at(cfg, epoch))
         t0 = time.perf_counter()
-        loss, samples = train_epoch(step, cfg, epoch, images, poses, H, W, focal, rs["near"], rs["far"], gen, dino_maps, args.max_batches, rank, world)
+        loss, samples = train_epoch(step, cfg, epoch, images, poses, H, W, focal, rs["near"], rs["far"], gen, dino_maps, args.max_batches, rank, world,
+                                    extractor=ext)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         rec = {"epoch": epoch + 1, "loss": loss, "lr": step.opt.lr, "seconds": round(dt, 3), "Msamples_per_s": round(world * samples / dt / 1e6, 2)}
@@ -266,15 +379,17 @@ def main(argv=None):
             log.append(rec)
             continue
         if (epoch + 1) % int(cfg["output"]["val_freq"]) == 0 or epoch + 1 == epochs:
+            if ext is not None:                                               # the extractor moved: view 0's map as it is now, under no_grad
+                eval_dino["features"] = precompute_dino_features(ext.extractor, ext.images[0:1]).float()
             m = evaluate_views(model, test_poses, H, W, focal, rs["near"], rs["far"], rs["n_samples"], targets=targets, white_bkgd=rs["white_bkgd"],
                                mma_mode=args.eval_mode, dino=eval_dino, out_dir=os.path.join(out_dir, f"val_{epoch + 1}"))
             model.train()
             rec.update(psnr=m["psnr"], ssim=m["ssim"])
             if m["psnr"] > best:
                 best = m["psnr"]
-                save_checkpoint(os.path.join(out_dir, f"best_{name}.pth"), model, step, epoch, best, cfg, args.recipe)
+                save_checkpoint(os.path.join(out_dir, f"best_{name}.pth"), model, step, epoch, best, cfg, args.recipe, ext)
         if (epoch + 1) % int(cfg["output"]["save_freq"]) == 0:
-            save_checkpoint(os.path.join(out_dir, f"epoch_{epoch + 1}.pth"), model, step, epoch, best, cfg, args.recipe)
+            save_checkpoint(os.path.join(out_dir, f"epoch_{epoch + 1}.pth"), model, step, epoch, best, cfg, args.recipe, ext)
         log.append(rec)
         print(json.dumps(rec), flush=True)
     if rank == 0:

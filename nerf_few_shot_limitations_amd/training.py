@@ -118,6 +118,74 @@ def _train_handle(module, dev, mma_mode=None):
     return h, mode
 
 
+def _dino_grad(module, mode, n, buf, nbytes, dev, out=None):
+    """dL/d (per-sample DINO features) (n, C) of a V3 module, from the context of a finished nrf_mlp_backward (one launch)."""
+    d_dino = out if out is not None else torch.empty((n, module.dino_dim), dtype=torch.float32, device=dev)
+    L.check(L.lib().nrf_mlp_backward_dino(module._handle, mode, n, C.c_void_p(buf.data_ptr()), nbytes, L.ptr(d_dino), L.stream_ptr()))
+    return d_dino
+
+
+_fetch_ws = {}
+
+
+def fetch_backward_workspace(Hp, Wp, Cc, n, device):
+    """The workspace of nrf_project_fetch_backward / nrf_sample_features_backward for these sizes, cached per (device, stream)
+    and grown on demand: the launches that use it are ordered on that stream.  Call with `device` current."""
+    nbytes = L.lib().nrf_fetch_backward_workspace_bytes(int(Hp), int(Wp), int(Cc), int(n))
+    if nbytes < 0:
+        raise L.NrfError(-1, L.lib().nrf_last_error().decode("utf-8", "replace"))
+    key = (str(device), L.stream_ptr())
+    ws = _fetch_ws.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        if len(_fetch_ws) > 16:
+            _fetch_ws.clear()
+        ws = _fetch_ws[key] = torch.empty((max(nbytes, 4) + 3) // 4, dtype=torch.float32, device=device)
+    return ws
+
+
+def project_fetch_backward(dino, points, d_feats, d_map, accumulate=True):
+    """d_map (1,Hp,Wp,C) [+]= the adjoint of nrf_project_fetch at `points` (n,3) applied to d_feats (n,C), for the source view
+    dino = dict(features= (only its shape is used), pose=, focal=, H=, W=): what a trainer that lets FusedStep write
+    `d_dino_out` calls per batch before map.backward(d_map).  Bit-reproducible (no atomics)."""
+    from .renderer import make_dino
+    dev = d_map.device
+    pts = L.dev_f32(points, dev).reshape(-1, 3)
+    g = L.dev_f32(d_feats, dev).reshape(pts.shape[0], -1)
+    dn, keep = make_dino(**{**dino, "features": d_map.detach()})
+    with torch.cuda.device(dev):
+        ws = fetch_backward_workspace(dn.Hp, dn.Wp, dn.C, pts.shape[0], dev)
+        L.check(L.lib().nrf_project_fetch_backward(C.byref(dn), L.ptr(pts), pts.shape[0], L.ptr(g), L.ptr(d_map), int(bool(accumulate)),
+                                                   L.ptr(ws), ws.numel() * 4, L.stream_ptr()))
+    del keep
+    return d_map
+
+
+class _ProjectFetchFn(torch.autograd.Function):
+    """train.py:203-217 with a live feature map: (1,Hp,Wp,C) map, (n,3) points -> (n,C) features; gradient for the map only."""
+
+    @staticmethod
+    def forward(ctx, fmap, pts, dino):
+        from .renderer import make_dino
+        dev = pts.device
+        fm = fmap.contiguous()
+        dn, keep = make_dino(**{**dino, "features": fm})
+        n = pts.shape[0]
+        feats = torch.empty((n, dn.C), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            L.check(L.lib().nrf_project_fetch(C.byref(dn), L.ptr(pts), n, L.ptr(feats), None, L.stream_ptr()))
+        del keep
+        ctx.dino, ctx.shape = dino, tuple(fm.shape)
+        ctx.save_for_backward(pts)
+        return feats
+
+    @staticmethod
+    def backward(ctx, g):
+        (pts,) = ctx.saved_tensors
+        d_map = torch.empty(ctx.shape, dtype=torch.float32, device=pts.device)
+        project_fetch_backward(ctx.dino, pts, g.to(torch.float32).contiguous(), d_map, accumulate=False)
+        return d_map, None, None
+
+
 class _MLPV1Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module, x_enc, *params):
@@ -195,25 +263,32 @@ class _MLPV2Fn(torch.autograd.Function):
         with torch.cuda.device(dev):
             L.check(L.lib().nrf_mlp_backward(module._handle, ctx.mode, L.ptr(rgb), L.ptr(dens), L.ptr(g_rgb), L.ptr(g_dens), ctx.n,
                                              C.c_void_p(ctx.buf.data_ptr()), ctx.nbytes, L.ptr(grad), L.stream_ptr()))
+            # dino_grad modules with features that require grad: one more launch over what the backward saved
+            d_dino = _dino_grad(module, ctx.mode, ctx.n, ctx.buf, ctx.nbytes, dev) if ctx.needs_input_grad[3] else None
         ctx.buf = None
         if direct is not None:
-            return (None, None, None, None) + (None,) * len(fp.offsets)
-        return (None, None, None, None, *fp.views(grad))
+            return (None, None, None, d_dino) + (None,) * len(fp.offsets)
+        return (None, None, None, d_dino, *fp.views(grad))
 
 
 def mlp_v2_train(module, positions, directions, dino_features=None):
     """(P,3) positions, (P,3) directions [, (P,C) DINO features for the use_dino=True form] -> rgb (P,3), density (P,1),
-    differentiable with respect to the parameters (not the inputs: a feature tensor that requires grad is refused)."""
+    differentiable with respect to the parameters and -- for a module built with dino_grad=True -- the DINO features (not the
+    other inputs; without the switch a feature tensor that requires grad is refused)."""
     pos = L.dev_f32(L.refuse_grad(positions, "NeRFMLP.forward(positions)")).reshape(-1, 3)
     dirs = L.dev_f32(L.refuse_grad(directions, "NeRFMLP.forward(directions)"), pos.device).reshape(-1, 3)
     dino = None
     if module.net == L.NRF_NET_V3:
         if dino_features is None:
             raise ValueError("use_dino=True needs dino_features")
-        if getattr(dino_features, "requires_grad", False):
-            raise NotImplementedError("no gradient with respect to the DINO features is produced (the feature extractor, LoRA "
-                                      "included, is outside the HIP path: SURVEY.md section 8 f4); detach them")
-        dino = L.dev_f32(dino_features, pos.device).reshape(-1, module.dino_dim)
+        if torch.is_grad_enabled() and getattr(dino_features, "requires_grad", False):
+            if not getattr(module, "dino_grad", False):
+                raise NotImplementedError("no gradient with respect to the DINO features is produced by default (the reference computes "
+                                          "its maps under no_grad: SURVEY.md section 8 f4); detach them, or build the module with "
+                                          "NeRFMLP(..., dino_grad=True)")
+            dino = dino_features.to(device=pos.device, dtype=torch.float32).reshape(-1, module.dino_dim).contiguous()      # stays in the graph
+        else:
+            dino = L.dev_f32(dino_features, pos.device).reshape(-1, module.dino_dim)
     return _MLPV2Fn.apply(module, pos, dirs, dino, *module.flat_params().params())
 
 
@@ -346,10 +421,12 @@ class _RenderFn(torch.autograd.Function):
                                                    L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w), L.ptr(d_rgb), 3, L.ptr(d_den), 1, st))
                 L.check(lib.nrf_mlp_backward(module._handle, ctx.mode, L.ptr(rgb), L.ptr(den), L.ptr(d_rgb), L.ptr(d_den), n, cb, ctx.nbytes,
                                              L.ptr(grad), st))
+            d_dino = _dino_grad(module, ctx.mode, n, ctx.buf, ctx.nbytes, dev) if ctx.needs_input_grad[3] else None      # a live feature map
         ctx.buf = None
+        ins = (None, None, None, d_dino) + (None,) * (n_in - 4)
         if direct is not None:
-            return (None,) * (n_in + len(fp.offsets))
-        return (None,) * n_in + tuple(fp.views(grad))
+            return ins + (None,) * len(fp.offsets)
+        return ins + tuple(fp.views(grad))
 
 
 _encoders = {}
@@ -359,7 +436,8 @@ def render_rays_train(module, rays_o, rays_d, near, far, n_samples, perturb=True
                       white_bkgd=False, dino=None, z_in=None, mma_mode=None, tail_mode=None):
     """renderer.render_rays when grad is enabled: the reference's own sequence (train.py:188-242) -- stratified samples,
     [project + fetch DINO features,] NeRFMLP, VolumeRenderer -- returning {'rgb','depth','weights','z_vals'} that carry a grad_fn.
-    Gradients reach the parameters only (rays, depths and features are data: a tensor that requires grad is refused).
+    Gradients reach the parameters and, for a module built with dino_grad=True, a dino['features'] map that requires grad (through
+    the adjoint of the bilinear fetch, nrf_project_fetch_backward); rays and depths are data: a tensor that requires grad is refused.
     The arithmetic mode is `mma_mode` (default: the module's own) mapped to a training mode (_lib.TRAIN_MODE: the split mode
     trains in exact fp32); early ray termination does not apply.  A `tail_mode` (renderer.render_rays) is refused: the training
     kernels have no split-f16 mode, and a silently different forward would be worse than a refusal."""
@@ -389,14 +467,22 @@ def render_rays_train(module, rays_o, rays_d, near, far, n_samples, perturb=True
         if module.net == L.NRF_NET_V3:
             if dino is None:
                 raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
-            if getattr(dino.get("features"), "requires_grad", False):
-                raise NotImplementedError("no gradient with respect to the DINO feature map is produced; detach it")
-            from .renderer import make_dino
-            dn, keep = make_dino(**dino)
-            feats = torch.empty((R * S, module.dino_dim), dtype=torch.float32, device=o.device)
-            with torch.cuda.device(o.device):
-                L.check(L.lib().nrf_project_fetch(C.byref(dn), L.ptr(pts), R * S, L.ptr(feats), None, L.stream_ptr()))   # train.py:203-217
-            del keep
+            fmap = dino.get("features")
+            if torch.is_grad_enabled() and getattr(fmap, "requires_grad", False):
+                if not getattr(module, "dino_grad", False):
+                    raise NotImplementedError("no gradient with respect to the DINO feature map is produced by default; detach it, or "
+                                              "build the module with NeRFMLP(..., dino_grad=True)")
+                if fmap.dim() != 4 or fmap.shape[0] != 1 or fmap.shape[3] != module.dino_dim:
+                    raise ValueError("features must be (1,Hp,Wp,dino_dim)")
+                live = fmap.to(device=o.device, dtype=torch.float32)
+                feats = _ProjectFetchFn.apply(live, pts.contiguous(), {k: v for k, v in dino.items() if k != "features"})
+            else:
+                from .renderer import make_dino
+                dn, keep = make_dino(**dino)
+                feats = torch.empty((R * S, module.dino_dim), dtype=torch.float32, device=o.device)
+                with torch.cuda.device(o.device):
+                    L.check(L.lib().nrf_project_fetch(C.byref(dn), L.ptr(pts), R * S, L.ptr(feats), None, L.stream_ptr()))   # train.py:203-217
+                del keep
     rgb, depth, w = _RenderFn.apply(module, x, dirs, feats, z, d, int(bool(white_bkgd)), mma_mode, *module.flat_params().params())
     return {"rgb": rgb, "depth": depth, "weights": w, "z_vals": z}
 
@@ -611,10 +697,18 @@ class FusedStep:
             self._key = key
 
     @torch.no_grad()
-    def __call__(self, points, z_vals, rays_d, target, dirs=None, dino=None, target_depth=None, noise=None):
+    def __call__(self, points, z_vals, rays_d, target, dirs=None, dino=None, target_depth=None, noise=None, d_dino_out=None):
         """target_depth (R): switches the depth term on (with depth_weight); noise (R,S): the standard normals of the density noise
-        (with noise_std) instead of the in-kernel RNG -- what torch.randn_like would have drawn, for parity runs."""
+        (with noise_std) instead of the in-kernel RNG -- what torch.randn_like would have drawn, for parity runs.
+        d_dino_out: a preallocated (R*S, dino_dim) fp32 tensor that receives dL/d dino of this step (V3 with model.dino_grad: one
+        more launch behind the weight gradients; project_fetch_backward turns it into the feature map's gradient)."""
         m = self.model
+        if d_dino_out is not None:
+            if m.net != L.NRF_NET_V3 or not getattr(m, "dino_grad", False):
+                raise ValueError("d_dino_out needs a use_dino model built with dino_grad=True")
+            if (not d_dino_out.is_cuda or d_dino_out.dtype != torch.float32 or not d_dino_out.is_contiguous()
+                    or d_dino_out.numel() != z_vals.numel() * m.dino_dim):
+                raise ValueError("d_dino_out must be a contiguous float32 (R*S, dino_dim) tensor on the GPU")
         pts = L.dev_f32(points)
         dev = pts.device
         z = L.dev_f32(z_vals, dev)
@@ -667,6 +761,8 @@ class FusedStep:
                                                        *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
             if v2:
                 L.check(lib.nrf_mlp_backward(h, mode, L.ptr(rgb), L.ptr(den), L.ptr(g_rgb), L.ptr(g_den), n, ctx, self.nbytes, L.ptr(self.grad), st))
+                if d_dino_out is not None:
+                    _dino_grad(m, mode, n, self.ctx, self.nbytes, dev, out=d_dino_out)
             else:
                 L.check(lib.nrf_mlp_backward_v1(h, mode, L.ptr(o4), L.ptr(d4), n, ctx, self.nbytes, L.ptr(self.grad), st))
             if self.data_parallel:
