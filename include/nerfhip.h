@@ -277,6 +277,15 @@ int nrf_debug_train_plan(const nrf_arch* arch, const nrf_linear* linears, int n_
 int nrf_debug_pack_dino_grad(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int mma_mode,
                              uint8_t* stream_out, int64_t stream_cap, int64_t* stream_bytes);
 
+/* Host-only: how render_kernel / render_hold_kernel deal a launch of n_rays rays x n_samples samples to the workgroups of a device
+ * with n_cu compute units, for a geometry of cols_per_wave sample columns per wave (64: NRF_MMA_BF16 / F16, 32: the fp32-class modes).
+ * head[4] = { 1: the even deal / 0: equal tiles round-robin, log2 of the uniform deal's samples per ray and pass, workgroups,
+ * MLP passes of the longest workgroup }.  items (may be NULL to query n_items) receives, per work item in the order the
+ * workgroups march them, 4 values: workgroup, first ray, rays (the launch's last item may reach past n_rays), log2 of its
+ * samples per ray and pass.  Honours NRF_SPW like the launchers. */
+int nrf_debug_ray_deal(int64_t n_rays, int n_samples, int cols_per_wave, int n_cu, int64_t* head,
+                       int64_t* items, int64_t cap, int64_t* n_items);
+
 /* ---- misc ------------------------------------------------------------------ */
 const char* nrf_last_error(void);
 int nrf_abi_version(void);

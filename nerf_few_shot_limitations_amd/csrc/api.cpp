@@ -15,6 +15,7 @@
 #include "../../include/nerfhip.h"
 #include "kernels.hpp"
 #include "packing.hpp"
+#include "ray_deal.hpp"
 
 namespace {
 
@@ -919,6 +920,38 @@ int nrf_debug_train_plan(const nrf_arch* arch, const nrf_linear* linears, int n_
         if (cap < (int64_t)v.size()) return fail(NRF_EINVAL, "out too small");
         std::memcpy(out, v.data(), v.size() * sizeof(int32_t));
     }
+    return NRF_OK;
+}
+
+int nrf_debug_ray_deal(int64_t n_rays, int n_samples, int cols_per_wave, int n_cu, int64_t* head, int64_t* items, int64_t cap, int64_t* n_items) {
+    if (n_rays <= 0 || n_samples <= 0 || n_cu <= 0 || (cols_per_wave != 32 && cols_per_wave != 64) || !head)
+        return fail(NRF_EINVAL, "nrf_debug_ray_deal: bad argument");
+    constexpr int waves = 4;                                  // both renderers run 4 waves
+    const int whole = waves * cols_per_wave;
+    const nrf::Deal d = nrf::pick_deal(n_rays, n_samples, waves, cols_per_wave, n_cu);
+    const int64_t grid = d.items < n_cu ? d.items : n_cu;
+    head[0] = d.even; head[1] = d.spw_log2; head[2] = grid; head[3] = d.passes;
+    int64_t n = 0;
+    auto put = [&](int64_t b, int64_t first, int64_t rays, int l) {
+        if (items && n < cap) { items[4 * n] = b; items[4 * n + 1] = first; items[4 * n + 2] = rays; items[4 * n + 3] = l; }
+        ++n;
+    };
+    for (int64_t b = 0; b < grid; ++b) {                     // the walk of render_march
+        if (d.even) {
+            nrf::DealRange r = nrf::deal_range(d.items, grid, b, waves);
+            while (r.rays > 0) {
+                const int l = nrf::deal_split(r.rays, whole);
+                put(b, r.first, whole >> l, l);
+                r.first += whole >> l;
+                r.rays -= whole >> l;
+            }
+        } else {
+            const int64_t tile = whole >> d.spw_log2;
+            for (int64_t t = b; t < d.items; t += grid) put(b, t * tile, tile, d.spw_log2);
+        }
+    }
+    if (n_items) *n_items = n;
+    if (items && cap < n) return fail(NRF_EINVAL, "items too small");
     return NRF_OK;
 }
 

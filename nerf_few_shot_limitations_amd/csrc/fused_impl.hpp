@@ -12,6 +12,7 @@
 
 #include "kernels.hpp"
 #include "nets.hpp"
+#include "ray_deal.hpp"
 
 namespace nrf {
 
@@ -34,7 +35,8 @@ struct NetArgs {
 struct RenderKArgs {
     NetArgs net;
     RenderArgs a;
-    int64_t n_tiles;
+    int64_t n_tiles;         // work items of the launch; with `even` set: units of WAVES rays (render_march)
+    int even = 0;            // render_kernel / render_hold_kernel: deal the rays evenly (pick_deal) instead of equal tiles round-robin
     float* carry = nullptr;  // tail mode: six rows of a.n_rays floats [T | r | g | b | depth | acc] between the prefix and the tail launch
 };
 
@@ -151,13 +153,8 @@ __device__ __forceinline__ void render_march(const RenderKArgs& P) {
     // on NT.  The state rows of a lane >= RPW mirror ray (lane mod RPW): column q's origin / direction are read from thread q's rows.
     // What SPW buys: frames whose ray count does not fill whole rounds of 256-ray tiles over the CUs (400x400; an 80 000-ray
     // shard) are cut into 2x / 4x as many, shorter, work items.
-    const int spw_log2 = PART == kTail ? 0 : a.spw_log2;         // the tail is one sample per ray: one pass of COLS rays per wave
-    const int rpw_log2 = (NT == 2 ? 6 : 5) - spw_log2;
-    const int SPW = 1 << spw_log2, RPW = COLS >> spw_log2;
-    const int64_t tile_rays = (int64_t)WAVES * RPW;
     const int SM = PART == kPrefix ? S - 1 : S;                   // samples [s_begin, SM) are marched
     const int s_begin = PART == kTail ? S - 1 : 0;
-    const int n_pass = PART == kTail ? 1 : (SM + SPW - 1) >> spw_log2;
 
     auto z_ray = [&](int64_t ray, int s) -> float {
         if (a.z_in) return a.z_in[ray * S + s];
@@ -177,10 +174,38 @@ __device__ __forceinline__ void render_march(const RenderKArgs& P) {
         return __fadd_rn(lower, __fmul_rn(__fsub_rn(upper, lower), u));
     };
 
-    for (int64_t tile = blockIdx.x; tile < P.n_tiles; tile += gridDim.x) {
+    // The work items of this workgroup: tiles of WAVES * RPW consecutive rays starting at `base`, each with its own split (ray_deal.hpp).
+    //   uniform deal: the launch's equal tiles (a.spw_log2) round-robin over the workgroups;
+    //   even deal: P.n_tiles counts units of WAVES rays; this workgroup's contiguous range of them is marched as whole tiles at one
+    //   sample per column, then as ever smaller tiles at the split that fills the wave's COLS columns.
+    const bool even = PART != kTail && P.even;
+    int64_t next = blockIdx.x, left = 0;
+    if (even) {
+        const DealRange r = deal_range(P.n_tiles, gridDim.x, blockIdx.x, WAVES);
+        next = r.first;
+        left = r.rays;
+    }
+    for (;;) {
+        int spw_log2 = 0;                                         // the tail is one sample per ray: one pass of COLS rays per wave
+        int64_t base;
+        if (even) {
+            if (left <= 0) break;
+            spw_log2 = deal_split(left, WAVES * COLS);
+            base = next;
+            next += (WAVES * COLS) >> spw_log2;
+            left -= (WAVES * COLS) >> spw_log2;
+        } else {
+            if (next >= P.n_tiles) break;
+            if (PART != kTail) spw_log2 = a.spw_log2;
+            base = next * (int64_t)(WAVES * (COLS >> spw_log2));
+            next += gridDim.x;
+        }
+        const int rpw_log2 = (NT == 2 ? 6 : 5) - spw_log2;
+        const int SPW = 1 << spw_log2, RPW = COLS >> spw_log2;
+        const int n_pass = PART == kTail ? 1 : (SM + SPW - 1) >> spw_log2;
         // column q's ray (clamped: the columns past the last ray of a ragged tile repeat it and store nothing)
         auto column_ray = [&](int q) -> int64_t {
-            const int64_t r = tile * tile_rays + wave * RPW + (q & (RPW - 1));
+            const int64_t r = base + wave * RPW + (q & (RPW - 1));
             return r < a.n_rays ? r : a.n_rays - 1;
         };
         {
@@ -281,7 +306,7 @@ __device__ __forceinline__ void render_march(const RenderKArgs& P) {
             lane = tid_now & 63; c = lane & 31; h = lane >> 5;
             st_me = st + tid_now;
             const int64_t rid = column_ray(lane);
-            const int64_t raw = tile * tile_rays + wave * RPW + (lane & (RPW - 1));
+            const int64_t raw = base + wave * RPW + (lane & (RPW - 1));
             const bool own_valid = lane < RPW && raw < a.n_rays;
             Composite comp;
             comp.T = ST(F_T); comp.r = ST(F_R); comp.g = ST(F_G); comp.b = ST(F_B); comp.depth = ST(F_DEPTH); comp.acc = ST(F_ACC);
@@ -344,7 +369,7 @@ __device__ __forceinline__ void render_march(const RenderKArgs& P) {
         }
 
         {
-            const int64_t raw = tile * tile_rays + wave * RPW + (lane & (RPW - 1));
+            const int64_t raw = base + wave * RPW + (lane & (RPW - 1));
             if (PART == kPrefix) {
                 if (lane < RPW && raw < a.n_rays) {                      // hold the state for the tail launch: six coalesced stores
                     float* cy = P.carry + raw;
@@ -769,39 +794,14 @@ int launch_persistent(const DeviceNet& net, const NetArgs& na, KArgs k, int64_t 
     return NRF_OK;
 }
 
-// Samples per ray and pass (log2; render_kernel): the work items of a launch are tiles of WAVES * COLS/SPW rays marched in
-// ceil(S/SPW) passes, dealt to the CUs in whole rounds -- pick the SPW = 1, 2, 4 ... COLS (a wave's columns: ONE ray per wave at the
-// far end) with the least rounds x passes.  What a wider split costs is the owner lane's serial composite of its SPW samples
-// per pass (~0.15 % of an MLP pass per sample: measured, profiles/r03_small_frames.txt); ties go to the smaller SPW.  Small frames live
-// off the far end: 100 x 100 x 32 (BASELINE config 1) is 157 tiles x 8 passes at SPW = 4 -- one round, 61 % of the CUs -- and
-// 1250 tiles x 1 pass = 5 rounds at SPW = 32; a 64 x 64 x 48 validation frame drops from 12 pass-times to 3.  Every choice is exact:
-// a ray's sequence of operations does not depend on it.  NRF_SPW=0..6 pins it (A/B runs).
-inline int pick_spw_log2(int64_t n_rays, int S, int waves, int cols_per_wave, int cu) {
-    const char* env = getenv("NRF_SPW");                 // read per launch: tests walk through every split inside one process
-    const int pinned = (env && *env) ? atoi(env) : -1;
-    int max_l = 0;
-    while ((2 << max_l) <= cols_per_wave) ++max_l;
-    if (pinned >= 0) return pinned < max_l ? pinned : max_l;
-    int best = 0;
-    double best_t = 0.0;
-    for (int l = 0; l <= max_l; ++l) {
-        const int64_t tile = (int64_t)waves * (cols_per_wave >> l);
-        const int64_t tiles = (n_rays + tile - 1) / tile;
-        const int64_t rounds = (tiles + cu - 1) / cu;
-        const double t = (double)rounds * (double)((S + (1 << l) - 1) >> l) * (1.0 + 0.0015 * (double)(1 << l));
-        if (l == 0 || t < best_t * (1.0 - 1e-9)) { best_t = t; best = l; }
-    }
-    return best;
-}
-
 template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
 int run_render_v(const DeviceNet& net, int mode, const RenderArgs& a, hipStream_t s, std::string& err) {
     RenderKArgs k;
     k.a = a;
-    k.a.spw_log2 = pick_spw_log2(a.n_rays, a.n_samples, WAVES, 32 * NT, net.cu_count);
-    const int64_t tile = (int64_t)WAVES * ((32 * NT) >> k.a.spw_log2);
-    return launch_persistent<render_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, (a.n_rays + tile - 1) / tile,
-                                                                                                 s, "render", err);
+    const Deal d = pick_deal(a.n_rays, a.n_samples, WAVES, 32 * NT, net.cu_count);
+    k.a.spw_log2 = d.spw_log2;
+    k.even = d.even;
+    return launch_persistent<render_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, d.items, s, "render", err);
 }
 
 // tail mode, first launch (16-bit geometry): samples 0 .. S-2 of every ray, compositor state -> carry.  The split is picked for the
@@ -811,9 +811,10 @@ int run_render_hold(const DeviceNet& net, int mode, const RenderArgs& a, float* 
     RenderKArgs k;
     k.a = a;
     k.carry = carry;
-    k.a.spw_log2 = pick_spw_log2(a.n_rays, a.n_samples - 1, WAVES, 32 * NT, net.cu_count);
-    const int64_t tile = (int64_t)WAVES * ((32 * NT) >> k.a.spw_log2);
-    return launch_persistent<render_hold_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, (a.n_rays + tile - 1) / tile,
+    const Deal d = pick_deal(a.n_rays, a.n_samples - 1, WAVES, 32 * NT, net.cu_count);
+    k.a.spw_log2 = d.spw_log2;
+    k.even = d.even;
+    return launch_persistent<render_hold_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, d.items,
                                                                                                       s, "render (tail mode, prefix)", err);
 }
 
