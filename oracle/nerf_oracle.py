@@ -509,21 +509,24 @@ def quantize(x: torch.Tensor, mode: str) -> torch.Tensor:
     return x.to(torch.float32)
 
 
-def mlp_v1_train_emulated(p: Dict[str, torch.Tensor], x_enc: torch.Tensor, g_out: torch.Tensor, mode: str = "f32"):
+def mlp_v1_train_emulated(p: Dict[str, torch.Tensor], x_enc: torch.Tensor, g_out: torch.Tensor, mode: str = "f32", acc=torch.float32):
     """Forward + backward of src/models/nerf_model.py:16-24 with every MFMA operand (weights, activations,
     masked gradients) rounded to `mode`'s operand type and fp32 accumulation -- the arithmetic of
     csrc/train_impl.hpp.  With mode='f32' this IS autograd's result up to summation order.
 
+    acc: the dtype the forward sums run in (they come back to fp32 before the rounding, like an accumulator).
+
     Returns (out4, grads {name: tensor}, acts [h_0..h_n], dzs [dz_1..dz_n, dz_head])."""
     q = lambda t: quantize(t, mode)
+    lin = lambda x, name: (x.to(acc) @ q(p[name + ".weight"]).to(acc).T + p[name + ".bias"].to(acc)).to(torch.float32)
     n = 0
     while f"layers.{n}.weight" in p:
         n += 1
     h = [q(x_enc.to(torch.float32))]
     for i in range(n):
-        h.append(q(F.relu(h[-1] @ q(p[f"layers.{i}.weight"]).T + p[f"layers.{i}.bias"])))
-    sigma = h[-1] @ q(p["sigma_out.weight"]).T + p["sigma_out.bias"]
-    rgb = torch.sigmoid(h[-1] @ q(p["rgb_out.weight"]).T + p["rgb_out.bias"])
+        h.append(q(F.relu(lin(h[-1], f"layers.{i}"))))
+    sigma = lin(h[-1], "sigma_out")
+    rgb = torch.sigmoid(lin(h[-1], "rgb_out"))
     out = torch.cat([rgb, sigma], -1)
     g_out = g_out.to(torch.float32)
     d_head = q(torch.cat([g_out[:, :3] * rgb * (1.0 - rgb), g_out[:, 3:4]], -1))        # [d rgb logits, d sigma]
@@ -585,3 +588,176 @@ def relu_margin(p: Dict[str, torch.Tensor], variant: str, x, directions=None, di
         m = torch.minimum(m, z.abs().amin(-1))
         c = F.relu(z)
     return m
+
+
+# --------------------------------------------------------------------------
+# f2  training path of V2 / V3, stage by stage, as the HIP kernels round it
+#     (csrc/train_v2_impl.hpp, train_v3_impl.hpp, train_impl.hpp:ChainTile; stage names: csrc/train_slots.hpp)
+# --------------------------------------------------------------------------
+
+def positional_encoding64(x, num_freqs: int) -> torch.Tensor:
+    """positional_encoding() of the fp32 inputs in float64 (x * 2^f is exact): what an encoder of any precision approximates."""
+    x = torch.as_tensor(x, dtype=torch.float32).double()
+    out = [x]
+    for f in range(num_freqs):
+        out += [torch.sin(x * 2.0 ** f), torch.cos(x * 2.0 ** f)]
+    return torch.cat(out, -1)
+
+
+def trunk_depth(p, prefix="density_mlp.density_layers.") -> int:
+    n = 0
+    while f"{prefix}{2 * n}.weight" in p:
+        n += 1
+    return n
+
+
+def train_stage_names(variant: str, n: int):
+    """(forward stages, backward stages) of a family in chain order; every name but 'gate' is a slot of SlotsV2 / SlotsV3."""
+    trunk = [f"trunk.{j}" for j in range(n)]
+    colour = ["colour.in", "colour.c0", "colour.c2"]
+    dz_colour = ["d_logits", "dz_density", "dz_c2", "dz_c0", "d_feature"]
+    dz_trunk = [f"dz_trunk.{j}" for j in range(n - 1, -1, -1)]
+    if variant == "v2":
+        return ["input"] + trunk + colour, dz_colour + dz_trunk
+    fwd = ["input.0", "fusion0.0", "fusion2.0", "attention0", "gate", "input.1", "fusion0.1", "fusion2.1", "proj"]
+    bwd = ["dz_proj", "dz_fusion2.1", "dz_fusion0.1", "d_gate", "dz_attention0", "dz_fusion2.0", "dz_fusion0.0"]
+    return fwd + trunk + colour, dz_colour + dz_trunk + bwd
+
+
+def train_stages(p: Dict[str, torch.Tensor], variant: str, pe, de, g_rgb, g_den, dino=None, mode: str = "f32",
+                 acc=torch.float32, given=None, tap=None):
+    """Forward + backward of mlp_v2 ('v2') / mlp_v3 ('v3') with every MFMA operand -- weights, saved activations, gated inputs,
+    masked gradients, head gradients -- rounded to `mode`'s operand type exactly where the chain kernels form it; biases, the
+    heads' outputs, the gate, sigmoid and softmax are not rounded.  Sums run in `acc` (torch.float32: the kernels' accumulators
+    up to summation order; torch.float64: the reference the 16-bit stage checks are held to) and come back to fp32 before the
+    rounding, like an accumulator.  mode='f32' is autograd through mlp_v2 / mlp_v3 up to summation order.
+
+    pe, de: the UNROUNDED encodings of positions / directions in the reference's feature order (positional_encoding or
+    positional_encoding64); dino: (P, C) for 'v3'.
+
+    given: a dict with the same keys as the result.  Every stage then reads its operands -- activations, ReLU masks, the gate, the
+    network's rgb / density outputs -- from `given` instead of from this function's own previous stages: the result is what a
+    correct implementation computes from THOSE inputs, stage by stage, and no flipped bit travels from one stage into the next.
+    tap(kind, name, tensor) -> tensor lets a caller falsify one ingredient (kind 'weight' / 'weight.T' / 'bias': the layer's operand in the forward / the backward chain, name =
+    its state_dict prefix; 'round': a stage's values in front of the rounding; 'encoding': 'pos' / 'dir'; 'gate': pass 0 / 1).
+
+    Returns (stages, grads).  stages: name -> (P, features) fp32 in the reference's feature order -- the names of
+    train_stage_names(), 'mask.<stage>' (bool, pre-activation > 0: the ReLU bit planes), 'gate' (P,2), 'd_gate.terms'
+    (|w0 dw0| + |w1 dw1|), 'density_raw', 'logits', 'rgb', 'density'.  grads: state_dict name -> gradient, the products and sums
+    of the stages it was given."""
+    q = lambda t: quantize(t, mode)
+    tap = tap or (lambda kind, name, t: t)
+    out = {}
+    get = (lambda k: out[k]) if given is None else (lambda k: given[k])
+    W = lambda name: tap("weight", name, q(p[name + ".weight"]))                   # the forward stream's operand
+    WT = lambda name: tap("weight.T", name, q(p[name + ".weight"])).T             # the transposed (backward) stream's
+    B = lambda name: tap("bias", name, p[name + ".bias"])
+    rnd = lambda stage, x: q(tap("round", stage, x.to(torch.float32)))
+    f32 = lambda t: t.to(torch.float32)
+
+    def mm(x, w, b=None):
+        y = x.to(acc) @ w.to(acc).T
+        return f32(y if b is None else y + b.to(acc))
+
+    def relu_stage(stage, layer, src):
+        z = mm(get(src), W(layer), B(layer))
+        out["mask." + stage] = z > 0
+        out[stage] = rnd(stage, F.relu(z))
+
+    def linear_stage(stage, layer, src):
+        out[stage] = rnd(stage, mm(get(src), W(layer), B(layer)))
+
+    n = trunk_depth(p)
+    trunk = lambda j: f"density_mlp.density_layers.{2 * j}"
+    pe = tap("encoding", "pos", torch.as_tensor(pe))
+    de = tap("encoding", "dir", torch.as_tensor(de))
+    n_pe = pe.shape[1]
+    # ---- forward ----
+    if variant == "v3":
+        dino = torch.as_tensor(dino)
+        fz = "dino_fusion."
+        for ps in (0, 1):
+            if ps == 0:
+                out["input.0"] = torch.cat([rnd("input.0", pe), rnd("input.0", dino)], -1)
+            else:
+                relu_stage("attention0", fz + "attention.0", "fusion2.0")
+                lg = mm(get("attention0"), W(fz + "attention.2"), B(fz + "attention.2")).double()
+                w0 = 1.0 / (1.0 + torch.exp(lg[:, 1] - lg[:, 0]))
+                out["gate"] = torch.stack([w0, 1.0 - w0], -1)
+                w = tap("gate", 1, get("gate").double())
+                out["input.1"] = torch.cat([rnd("input.1", pe.double() * w[:, 0:1]), rnd("input.1", dino.double() * w[:, 1:2])], -1)
+            relu_stage(f"fusion0.{ps}", fz + "fusion.0", f"input.{ps}")
+            relu_stage(f"fusion2.{ps}", fz + "fusion.2", f"fusion0.{ps}")
+        linear_stage("proj", fz + "output_proj", "fusion2.1")
+        below = "proj"
+    else:
+        out["input"] = rnd("input", pe)
+        below = "input"
+    for j in range(n):
+        relu_stage(f"trunk.{j}", trunk(j), below)
+        below = f"trunk.{j}"
+    top = below
+    out["density_raw"] = mm(get(top), W("density_mlp.density_head"), B("density_mlp.density_head"))
+    out["density"] = F.relu(out["density_raw"])
+    feat = rnd("colour.in", mm(get(top), W("density_mlp.feature_head"), B("density_mlp.feature_head")))
+    out["colour.in"] = torch.cat([feat, rnd("colour.in", de)], -1)
+    relu_stage("colour.c0", "color_mlp.color_layers.0", "colour.in")
+    relu_stage("colour.c2", "color_mlp.color_layers.2", "colour.c0")
+    out["logits"] = mm(get("colour.c2"), W("color_mlp.color_layers.4"), B("color_mlp.color_layers.4"))
+    out["rgb"] = f32(torch.sigmoid(out["logits"].double()))
+    # ---- backward: the dZ chain ----
+    g_rgb, g_den = f32(torch.as_tensor(g_rgb)), f32(torch.as_tensor(g_den))
+    rgb, den = get("rgb"), get("density")
+    out["d_logits"] = rnd("d_logits", g_rgb * rgb * (1.0 - rgb))
+    out["dz_density"] = rnd("dz_density", g_den * (den > 0))
+
+    def masked_stage(stage, layer, src, fwd):               # dZ(fwd) = (dZ(src) W(layer)) under ReLU'(fwd)
+        out[stage] = rnd(stage, mm(get(src), WT(layer)) * get("mask." + fwd))
+
+    masked_stage("dz_c2", "color_mlp.color_layers.4", "d_logits", "colour.c2")
+    masked_stage("dz_c0", "color_mlp.color_layers.2", "dz_c2", "colour.c0")
+    out["d_feature"] = rnd("d_feature", mm(get("dz_c0"), WT("color_mlp.color_layers.0"))[:, :feat.shape[1]])
+    wtop = torch.cat([WT("density_mlp.feature_head"), WT("density_mlp.density_head")], 1)     # one layer of K = 8 + 1 tiles
+    dh = mm(torch.cat([get("d_feature"), get("dz_density")], -1), wtop)
+    out[f"dz_trunk.{n - 1}"] = rnd(f"dz_trunk.{n - 1}", dh * get(f"mask.trunk.{n - 1}"))
+    for j in range(n - 1, 0, -1):
+        masked_stage(f"dz_trunk.{j - 1}", trunk(j), f"dz_trunk.{j}", f"trunk.{j - 1}")
+    if variant == "v3":
+        out["dz_proj"] = rnd("dz_proj", mm(get("dz_trunk.0"), WT(trunk(0))))
+        masked_stage("dz_fusion2.1", fz + "output_proj", "dz_proj", "fusion2.1")
+        masked_stage("dz_fusion0.1", fz + "fusion.2", "dz_fusion2.1", "fusion0.1")
+        # d [pe w0 | dino w1], and its dot products with the saved unscaled inputs: d w0, d w1 (lora_dino.py:187-190)
+        prod = mm(get("dz_fusion0.1"), WT(fz + "fusion.0")).to(acc) * get("input.0").to(acc)
+        dw = torch.stack([prod[:, :n_pe].sum(-1), prod[:, n_pe:].sum(-1)], -1).double()
+        w = get("gate").double()
+        s = (w * dw).sum(-1, keepdim=True)
+        out["d_gate.terms"] = f32((w * dw).abs().sum(-1, keepdim=True))
+        out["d_gate"] = rnd("d_gate", w * (dw - s))                       # softmax': d logit_i = w_i (d w_i - sum_j w_j d w_j)
+        masked_stage("dz_attention0", fz + "attention.2", "d_gate", "attention0")
+        masked_stage("dz_fusion2.0", fz + "attention.0", "dz_attention0", "fusion2.0")
+        masked_stage("dz_fusion0.0", fz + "fusion.2", "dz_fusion2.0", "fusion0.0")
+    # ---- parameter gradients: dW = dZ^T X, db = sum dZ ----
+    jobs = [("color_mlp.color_layers.4", "d_logits", "colour.c2"), ("color_mlp.color_layers.2", "dz_c2", "colour.c0"),
+            ("color_mlp.color_layers.0", "dz_c0", "colour.in"), ("density_mlp.feature_head", "d_feature", top),
+            ("density_mlp.density_head", "dz_density", top)]
+    jobs += [(trunk(j), f"dz_trunk.{j}", f"trunk.{j - 1}" if j else ("proj" if variant == "v3" else "input")) for j in range(n)]
+    if variant == "v3":
+        jobs += [(fz + "output_proj", "dz_proj", "fusion2.1"), (fz + "attention.2", "d_gate", "attention0"),
+                 (fz + "attention.0", "dz_attention0", "fusion2.0")]
+        jobs += [(fz + "fusion.2", f"dz_fusion2.{ps}", f"fusion0.{ps}") for ps in (0, 1)]
+        jobs += [(fz + "fusion.0", f"dz_fusion0.{ps}", f"input.{ps}") for ps in (0, 1)]
+    grads = {}
+    for layer, dz, x in jobs:                               # the fusion block's two passes add up
+        gw, gb = f32(get(dz).to(acc).T @ get(x).to(acc)), f32(get(dz).to(acc).sum(0))
+        grads[layer + ".weight"] = grads.get(layer + ".weight", 0) + gw
+        grads[layer + ".bias"] = grads.get(layer + ".bias", 0) + gb
+    return out, grads
+
+
+def dino_grad_from_stages(p, stages, mode: str, acc=torch.float32) -> torch.Tensor:
+    """dL/d dino = W0d^T d1 + w1 W0d^T d2 (csrc/train_dino_grad_impl.hpp) from the two dZ(fusion.0) stages and the gate."""
+    w = quantize(p["dino_fusion.fusion.0.weight"], mode)
+    wd = w[:, encoded_dim(12):].to(acc)                      # the columns that multiply the DINO channels
+    a1 = stages["dz_fusion0.0"].to(acc) @ wd
+    a2 = stages["dz_fusion0.1"].to(acc) @ wd
+    return (a1 + stages["gate"][:, 1:2].to(acc) * a2).to(torch.float32)

@@ -16,6 +16,8 @@ import pytest
 import torch
 
 from oracle import nerf_oracle as O
+from tests.test_training_host import train_plan
+from tests.train_ctx import SavedContext, kernel_feature_order
 
 pytestmark = pytest.mark.gpu
 
@@ -62,51 +64,10 @@ def cosine(a, b):
 # ---------------------------------------------------------------------------------------------
 # decode the saved tensors (csrc/train_core.hpp layout) for stage-wise checks
 # ---------------------------------------------------------------------------------------------
-def ctx_slot(buf, mode, n, n_layers, slot):
-    """Saved-tensor slot -> (features, padded samples) fp32 matrix."""
-    tiles32 = (n + 255) // 256 * 8
-    slot_tiles = [2] + [8] * (2 * n_layers) + [1]
-    tb = 4096 if mode == "f32" else 2048
-    off = sum(slot_tiles[:slot]) * tiles32 * tb
-    KT = slot_tiles[slot]
-    raw = buf[off:off + tiles32 * KT * tb].cpu().numpy()
-    if mode == "f32":
-        v = raw.view(np.float32).reshape(tiles32, KT, 4, 64, 4)            # st, t, vec, lane, e
-    else:
-        u = raw.view(np.uint16).reshape(tiles32, KT, 2, 64, 8)
-        if mode == "bf16":
-            v = (u.astype(np.uint32) << 16).view(np.float32)
-        else:
-            v = u.view(np.float16).astype(np.float32)
-    nv, ne = v.shape[2], v.shape[4]
-    out = np.zeros((32 * KT, 32 * tiles32), np.float32)
-    lanes = np.arange(64)
-    c, h = lanes & 31, lanes >> 5
-    for vec in range(nv):
-        for e in range(ne):
-            r = ne * vec + e
-            row = (r & 3) + 8 * (r >> 2) + 4 * h                           # accumulator row map
-            for t in range(KT):
-                # out[32t + row[lane], 32 st + c[lane]] = v[st, t, vec, lane, e]
-                out[(32 * t + row)[None, :], (32 * np.arange(tiles32)[:, None] + c[None, :])] = v[:, t, vec, :, e]
-    return out
-
-
-def kernel_feature_order(L=10):
-    """Row of saved slot 0 -> index into the reference's 63 encoded features (-1 = padding); feature_map.hpp."""
-    KT = (3 * L + 2 + 15) // 16
-    idx = np.full(32 * KT, -1)
-    for u in range(16 * KT):
-        for h in range(2):
-            t, r = u // 16, u % 16
-            k = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h
-            if u < 3 * L:
-                idx[k] = 3 + 6 * (u // 3) + 3 * h + (u % 3)
-            elif u == 3 * L:
-                idx[k] = 2 if h else 0
-            elif u == 3 * L + 1:
-                idx[k] = -1 if h else 1
-    return idx
+def v1_context(p, buf, mode, n, n_layers=8):
+    """The decoded context of a V1 pair (tests/train_ctx.py; slot sizes from the plan the library reports)."""
+    from nerf_few_shot_limitations_amd import _lib as L
+    return SavedContext(train_plan(L, "v1", p, n_layers, with_planes=True), "v1", n_layers, mode, n, buf)
 
 
 def close_but_for_mask_flips(a, e, bound, allowed=4):
@@ -164,22 +125,25 @@ def test_saved_tensors_match_oracle_fp32(N):
     o_out, _, acts, dzs = O.mlp_v1_train_emulated(p, x, g, mode)
     assert rel_to_max(out, o_out) < 1e-5
     order = kernel_feature_order()
-    a0 = ctx_slot(buf, mode, n, 8, 0)
+    ctx = v1_context(p, buf, mode, n)
+    S = ctx.slots                                                            # csrc/train_slots.hpp: SlotsV1 by name
+    a0 = ctx.slot("input")
     exp0 = np.zeros_like(a0[:, :n])
     for k, src in enumerate(order):
         if src >= 0:
             exp0[k] = acts[0][:, src].numpy()
     assert np.abs(a0[:, :n] - exp0).max() <= 1e-6
     for l in range(1, 9):
-        a = ctx_slot(buf, mode, n, 8, l)[:, :n]
+        a = ctx.slot(f"trunk.{l - 1}")[:, :n]
         e = acts[l].numpy().T
         assert close_but_for_mask_flips(a, e, tol * max(1.0, np.abs(e).max())), f"activation of layer {l}"
     for l in range(1, 9):
-        d = ctx_slot(buf, mode, n, 8, 8 + l)
+        d = ctx.slot(f"dz_trunk.{l - 1}")
         e = dzs[l - 1].numpy().T
         assert close_but_for_mask_flips(d[:, :n], e, tol * np.abs(e).max()), f"dZ of layer {l}"
         assert np.abs(d[:, n:]).max() == 0.0, "padding samples must carry no gradient"
-    dh = ctx_slot(buf, mode, n, 8, 17)
+    assert (S["input"], S["trunk.0"], S["dz_trunk.0"], S["dz_head"]) == (0, 1, 9, 17)
+    dh = ctx.slot("dz_head")
     assert np.abs(dh[:4, :n] - dzs[8].numpy().T).max() <= tol * np.abs(dzs[8].numpy()).max()
     assert np.abs(dh[4:]).max() == 0.0
 
@@ -196,9 +160,10 @@ def test_saved_tensors_stage_consistent_16bit(N, mode, n):
     x, g = inputs(n)
     out, grad, buf = run_raw(N, model, x, g)
     q = lambda t: O.quantize(t, mode)
-    acts = [torch.from_numpy(ctx_slot(buf, mode, n, 8, l)[:, :n].T.copy()) for l in range(9)]      # (n, features)
-    dzs = [torch.from_numpy(ctx_slot(buf, mode, n, 8, 8 + l)[:, :n].T.copy()) for l in range(1, 9)]
-    dhead = torch.from_numpy(ctx_slot(buf, mode, n, 8, 17)[:4, :n].T.copy())
+    ctx = v1_context(p, buf, mode, n)
+    acts = [torch.from_numpy(ctx.slot(nm)[:, :n].T.copy()) for nm in ["input"] + [f"trunk.{l}" for l in range(8)]]      # (n, features)
+    dzs = [torch.from_numpy(ctx.slot(f"dz_trunk.{l}")[:, :n].T.copy()) for l in range(8)]
+    dhead = torch.from_numpy(ctx.slot("dz_head")[:4, :n].T.copy())
 
     def stage_close(a, e, what):
         bound = ulp * e.abs() + 1e-6 * e.abs().max()

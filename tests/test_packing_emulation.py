@@ -102,9 +102,26 @@ def test_v1_stream_replay_matches_oracle(L, mode, tol):
     scale = max(1.0, float(np.abs(ref_raw).max()))
     assert np.abs(got - ref_raw).max() < tol * scale, (np.abs(got - ref_raw).max(), scale)
     assert np.array_equal(got, got_hi)
+    if mode in ("f16", "bf16"):
+        # ... and against the oracle's rounding model accumulated in float64: both sides round at the same points, so only
+        # float64 summation noise is left
+        xe = O.positional_encoding(torch.from_numpy(x), 10)
+        h = O.mlp_v1_train_emulated(p, xe, torch.zeros(32, 4), mode, acc=torch.float64)[2][-1].double()
+        q = lambda name: O.quantize(p[name + ".weight"], mode).double()
+        model = torch.cat([h @ q("rgb_out").T + p["rgb_out.bias"].double(), h @ q("sigma_out").T + p["sigma_out.bias"].double()], -1)
+        model = model.float().numpy()                                     # the replay hands its head back as an fp32 accumulator
+        assert np.abs(got - model).max() <= 1e-9 * np.abs(model).max(), np.abs(got - model).max()
 
 
-@pytest.mark.parametrize("mode,tol", [("f32", 2e-5), ("f16x3", 2e-5), ("bf16", 3e-2)])
+def _model_heads(p, variant, x, d, mode, dino=None):
+    """[rgb logits | raw density] of the oracle's rounding model accumulated in float64, on the encodings the replays round."""
+    st, _ = O.train_stages(p, variant, O.positional_encoding(torch.from_numpy(x), 12 if variant == "v3" else 10),
+                           O.positional_encoding(torch.from_numpy(d), 4), torch.zeros(32, 3), torch.zeros(32, 1),
+                           dino=None if dino is None else torch.from_numpy(dino), mode=mode, acc=torch.float64)
+    return torch.cat([st["logits"], st["density_raw"]], -1).numpy(), st
+
+
+@pytest.mark.parametrize("mode,tol", [("f32", 2e-5), ("f16x3", 2e-5), ("bf16", 3e-2), ("f16", 3e-3)])
 def test_v2_stream_replay_matches_oracle(L, mode, tol):
     p = O.make_weights("v2", 1)
     raw, bias = _pack(L, "v2", p, mode)
@@ -131,6 +148,10 @@ def test_v2_stream_replay_matches_oracle(L, mode, tol):
     assert np.abs(got_rgb - ref_rgb.numpy()).max() < tol
     assert np.abs(np.maximum(dens[0, :32, 0], 0) - ref_dens.numpy()[:, 0]).max() < tol * max(1.0, float(ref_dens.max()))
     assert np.array_equal(dens[0, :32, 0], dens[0, 32:, 0])               # both lane halves see the density
+    if mode in ("f16", "bf16"):                                           # the rounding model: float64 summation noise only
+        model, _ = _model_heads(p, "v2", x, d, mode)
+        got = np.concatenate([np.stack([rgb[0, :32, k] for k in range(3)], -1), dens[0, :32, :1]], -1)
+        assert np.abs(got - model).max() <= 1e-9 * np.abs(model).max(), np.abs(got - model).max()
 
 
 def test_v3_stream_replay_matches_oracle(L):
@@ -180,6 +201,56 @@ def test_v3_stream_replay_matches_oracle(L):
     got_rgb = 1 / (1 + np.exp(-np.stack([rgb[0, :32, k] for k in range(3)], -1)))
     assert np.abs(got_rgb - ref_rgb.numpy()).max() < 1e-4
     assert np.abs(np.maximum(dens[0, :32, 0], 0) - ref_dens.numpy()[:, 0]).max() < 1e-4 * max(1.0, float(ref_dens.max()))
+
+
+@pytest.mark.parametrize("mode,tol", [("f16x3", 1e-4), ("f16", 5e-3), ("bf16", 5e-2)])
+def test_v3_stream_replay_16bit_and_split_modes(L, mode, tol):
+    """The V3 walk in the 16-bit and split-f16 streams.  Against the fp32 oracle: the bars of the GPU forward tests (1e-4 split,
+    5e-3 f16, 5e-2 bf16).  The 16-bit replays also against the oracle's rounding model accumulated in float64 -- the gate in
+    float64 from the fp32 logits on both sides, the gated inputs rounded once -- which ties oracle.train_stages to the packer and
+    the lane maps: 1e-9 of the largest head value."""
+    p = O.make_weights("v3", 2)
+    raw, bias = _pack(L, "v3", p, mode)
+    st = E.Stream(raw, mode)
+    x = ((O.uniform01(6, 96).reshape(32, 3) * 2 - 1) * 3).astype(np.float32)
+    d = (O.uniform01(7, 96).reshape(32, 3) * 2 - 1).astype(np.float32)
+    dino = (O.uniform01(8, 32 * 64).reshape(32, 64) * 2 - 1).astype(np.float32)
+    dirt = E.quantize(_encode_tiles(d, 4), mode)
+    pe_m = E.matrix_from_tiles(_encode_tiles(x, 12)).astype(np.float64)
+
+    def inputs(w0, w1):
+        m = np.concatenate([pe_m * w0[None, :], dino.T.astype(np.float64) * w1[None, :]], 0).astype(np.float32)
+        return E.quantize(E.tiles_from_matrix(m), mode)
+
+    off = [0]
+
+    def layer(act, MT, relu=True, head=False):
+        acc = E.dense(st, bias[off[0]:off[0] + 32 * MT], act, MT, mode)
+        off[0] += 32 * MT
+        return acc if head else E.quantize(np.maximum(acc, 0) if relu else acc, mode)
+
+    cat = lambda a, b: np.concatenate([a, b], -3)                            # tile axis (the split mode's images carry a leading hi/lo axis)
+    one = np.ones(32)
+    a0 = layer(layer(layer(inputs(one, one), 8), 8), 2)
+    lg = layer(a0, 1, head=True)
+    w0 = 1 / (1 + np.exp(lg[0, :32, 1].astype(np.float64) - lg[0, :32, 0].astype(np.float64)))
+    hcur = layer(layer(layer(inputs(w0, 1 - w0), 8), 8), 8, relu=False)     # fusion twice, output_proj
+    for _ in range(8):
+        hcur = layer(hcur, 8)
+    dens = layer(hcur, 1, head=True)
+    c1 = layer(layer(cat(layer(hcur, 8, relu=False), dirt), 4), 2)
+    rgb = layer(c1, 1, head=True)
+    assert off[0] == bias.shape[0] and (st.pos + 15) // 16 == st.frags.shape[0] // 16
+    ref_rgb, ref_dens = O.mlp_v3(p, torch.from_numpy(x), torch.from_numpy(d), torch.from_numpy(dino))
+    logits = np.stack([rgb[0, :32, k] for k in range(3)], -1)
+    e_rgb = np.abs(1 / (1 + np.exp(-logits)) - ref_rgb.numpy()).max()
+    e_den = np.abs(np.maximum(dens[0, :32, 0], 0) - ref_dens.numpy()[:, 0]).max() / max(1.0, float(ref_dens.max()))
+    assert e_rgb < tol and e_den < tol, (e_rgb, e_den)
+    if mode in ("f16", "bf16"):
+        model, stages = _model_heads(p, "v3", x, d, mode, dino)
+        got = np.concatenate([logits, dens[0, :32, :1]], -1)
+        assert np.abs(w0 - stages["gate"][:, 0].numpy()).max() < 1e-12
+        assert np.abs(got - model).max() <= 1e-9 * np.abs(model).max(), np.abs(got - model).max()
 
 
 def test_model_create_validates_shapes(L):

@@ -19,15 +19,16 @@ def L():
     return _lib
 
 
-def _linears(L, variant, p, n_layers):
-    names = [n for n, _, _ in O.layer_shapes(variant, n_layers=n_layers)]
+def _linears(L, variant, p, n_layers, dino_dim=64):
+    names = [n for n, _, _ in O.layer_shapes(variant, n_layers=n_layers, dino_dim=dino_dim)]
     arr = (L.nrf_linear * len(names))()
     keep = []
     for i, n in enumerate(names):
         w = np.ascontiguousarray(p[n + ".weight"].numpy()); b = np.ascontiguousarray(p[n + ".bias"].numpy())
         keep += [w, b]
         arr[i] = L.nrf_linear(w.ctypes.data_as(L.c_float_p), b.ctypes.data_as(L.c_float_p), w.shape[0], w.shape[1])
-    arch = L.nrf_arch({"v1": 1, "v2": 2}[variant], 10, 4, 256, n_layers, 0)
+    v3 = variant == "v3"
+    arch = L.nrf_arch({"v1": 1, "v2": 2, "v3": 3}[variant], 12 if v3 else 10, 4, 256, n_layers, dino_dim if v3 else 0)
     return names, arr, arch, keep
 
 
@@ -40,8 +41,10 @@ def backward_stream(L, variant, p, n_layers, mode="f32"):
     return bytes(raw)
 
 
-def train_plan(L, variant, p, n_layers):
-    names, arr, arch, keep = _linears(L, variant, p, n_layers)
+def train_plan(L, variant, p, n_layers, dino_dim=64, with_planes=False):
+    """The saved-tensor / weight-gradient plan the library reports (nrf_debug_train_plan): (names, slot_tiles, jobs), and
+    with_planes: the number of ReLU bit planes as a fourth value."""
+    names, arr, arch, keep = _linears(L, variant, p, n_layers, dino_dim)
     n = C.c_int64()
     L.check(L.lib().nrf_debug_train_plan(C.byref(arch), arr, len(names), None, 0, C.byref(n)))
     buf = np.zeros(n.value, np.int32)
@@ -58,8 +61,8 @@ def train_plan(L, variant, p, n_layers):
         jobs.append(j)
     n_mask = next(it)
     assert next(it, None) is None
-    assert n_mask == (n_layers if variant == "v1" else n_layers + 2)
-    return names, slot_tiles, jobs
+    assert n_mask == n_layers + {"v1": 0, "v2": 2, "v3": 7}[variant]
+    return (names, slot_tiles, jobs, n_mask) if with_planes else (names, slot_tiles, jobs)
 
 
 def tiles(M):
