@@ -443,6 +443,46 @@ int nrf_adamw_step_loss(float* params, const float* grads, float* exp_avg, float
                         const float* ray_terms, int64_t n_rays, int n_samples,
                         float rgb_weight, float depth_weight, float reg_weight, float* losses, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Training from rays: what src/training/train.py:188-229 (`render_rays`: sample_points_along_rays, the directions expanded
+ * per sample, project_points_to_image + sample_features_at_points, the positional encodings) builds in front of the network
+ * happens inside the saving forward kernel instead.  A lane pair derives its sample's ray, depth and position with the same
+ * explicitly rounded functions the staged kernels use (nrf_get_rays, nrf_sample_along_rays), encodes it, and (NRF_NET_V3)
+ * gathers its feature-map channels with the renderer's taps in both fusion passes: no (n,3) positions, (n,3) directions,
+ * (n, dino_dim) features or (n,63) encodings in memory.  Additive to ABI 5: the struct carries its own size, nrf_abi_sizeof
+ * knows nothing of it.
+ * ------------------------------------------------------------------------ */
+typedef struct nrf_train_rays {
+    int32_t        struct_bytes;   /* sizeof(nrf_train_rays): checked by the library */
+    int32_t        reserved;       /* 0 */
+    const float*   rays_o;         /* device (R,3); NULL in pixel mode */
+    const float*   rays_d;         /* device (R,3); NULL in pixel mode */
+    const int64_t* pixels;         /* pixel mode: device (R) ray ids y*W+x of the camera below; else NULL */
+    int32_t        H;              /* pixel mode: the pinhole camera (ray_sampler.py:4-30) */
+    int32_t        W;
+    float          focal;
+    float          c2w[12];        /* first 3 rows of the camera-to-world matrix */
+    float*         z_vals;         /* out (R,S), required: the compositor and its backward read it */
+    float*         rays_d_out;     /* out (R,3), required in pixel mode (the compositor needs |d|); else may be NULL */
+    float*         points_out;     /* out (R*S,3), optional: what nrf_project_fetch_backward needs for dL/d map */
+} nrf_train_rays;
+
+/* The saving forward of all three families on n = n_rays * opts->n_samples samples, in sample order (ray-major), with the context
+ * of nrf_train_context_bytes(m, mode, n); its backward is nrf_mlp_backward_v1 / nrf_mlp_backward / nrf_mlp_backward_dino on the
+ * same context.
+ *   NRF_NET_V1      : out_a = the (n,4) tensor of nrf_mlp_forward_train_v1, out_b must be NULL;
+ *   NRF_NET_V2 / V3 : out_a = rgb (n,3), out_b = density (n,1), as nrf_mlp_forward_train.
+ * Of `opts` the call reads near, far, n_samples, lindisp, perturb, t_rand, z_ladder, z_in, rng_seed (the renderer's meaning),
+ * mma_mode (bf16, f16, f32; f16x3 trains in fp32) and dino (NRF_NET_V3: the source view's map, required).  The jitter of row r,
+ * sample s of the call is counter_uniform(rng_seed, r, s): nrf_sample_along_rays' key -- the row in the call, not the pixel id
+ * -- so that ray mode, pixel mode and the staged route produce the same depths.
+ * z_vals, points_out and rays_d_out receive what nrf_sample_along_rays / nrf_get_rays would have written, to the bit.
+ * NRF_EINVAL, before any launch: ert_eps > 0, a wrong struct_bytes, both or neither of rays and pixels, a missing required
+ * output, NRF_NET_V3 without dino or with dino->C != dino_dim, n_samples < 1, n_rays < 0, n > 2^31 - 1, a context that is too
+ * small.  n_rays == 0 succeeds and launches nothing. */
+int nrf_mlp_forward_train_rays(nrf_model* m, const nrf_train_rays* rays, int64_t n_rays, const nrf_render_opts* opts,
+                               float* out_a, float* out_b, void* ctx, int64_t ctx_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,19 @@ def loss_opts(rgb_weight=1.0, reg_weight=0.0, depth_weight=0.0, target_depth=Non
     return nrf_loss_opts(C.sizeof(nrf_loss_opts), rgb_weight, reg_weight, depth_weight, target_depth, noise_std, noise, int(rng_seed) & (2 ** 64 - 1))
 
 
+class nrf_train_rays(C.Structure):
+    """The ray source of nrf_mlp_forward_train_rays; struct_bytes is filled in by train_rays()."""
+    _fields_ = [("struct_bytes", C.c_int32), ("reserved", C.c_int32), ("rays_o", C.c_void_p), ("rays_d", C.c_void_p), ("pixels", C.c_void_p),
+                ("H", C.c_int32), ("W", C.c_int32), ("focal", C.c_float), ("c2w", C.c_float * 12),
+                ("z_vals", C.c_void_p), ("rays_d_out", C.c_void_p), ("points_out", C.c_void_p)]
+
+
+def train_rays(rays_o=None, rays_d=None, pixels=None, H=0, W=0, focal=0.0, c2w=None, z_vals=None, rays_d_out=None, points_out=None):
+    """nrf_train_rays with its size field set; the pointers are device addresses (ints) or None, c2w 12 floats (pixel mode)."""
+    return nrf_train_rays(C.sizeof(nrf_train_rays), 0, rays_o, rays_d, pixels, int(H), int(W), float(focal),
+                          (C.c_float * 12)(*([0.0] * 12 if c2w is None else [float(x) for x in c2w])), z_vals, rays_d_out, points_out)
+
+
 # name -> (restype, argtypes); tests/test_packing_emulation.py checks this table against include/nerfhip.h
 SIGNATURES = {
     "nrf_abi_version": (C.c_int, []),
@@ -143,6 +156,9 @@ SIGNATURES = {
     "nrf_adamw_step_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float,
                                       C.c_float, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
                                       C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    # training from rays: sampling, encoding and the feature fetch inside the saving forward
+    "nrf_mlp_forward_train_rays": (C.c_int, [C.c_void_p, C.POINTER(nrf_train_rays), C.c_int64, C.POINTER(nrf_render_opts), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 _lib = None

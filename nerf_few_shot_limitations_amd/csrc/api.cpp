@@ -660,6 +660,49 @@ int nrf_mlp_backward_dino(nrf_model* m, int mma_mode, int64_t n, void* ctx, int6
     });
 }
 
+int nrf_mlp_forward_train_rays(nrf_model* m, const nrf_train_rays* rays, int64_t n_rays, const nrf_render_opts* opts, float* out_a, float* out_b,
+                               void* ctx, int64_t ctx_bytes, void* stream) {
+    // what the arguments alone decide comes first, then what needs the model, then the device (context size)
+    if (!rays) return fail(NRF_EINVAL, "nrf_mlp_forward_train_rays: rays is NULL");
+    if (rays->struct_bytes != (int32_t)sizeof(nrf_train_rays)) return fail(NRF_EINVAL, "nrf_train_rays: struct_bytes is not sizeof(nrf_train_rays)");
+    if (n_rays < 0) return fail(NRF_EINVAL, "nrf_mlp_forward_train_rays: n_rays < 0");
+    const int rc = check_opts(opts);
+    if (rc != NRF_OK) return rc;
+    if (opts->ert_eps > 0.0f) return fail(NRF_EINVAL, "nrf_mlp_forward_train_rays takes ert_eps == 0: a training step evaluates every sample");
+    const bool by_rays = rays->rays_o || rays->rays_d, by_pixels = rays->pixels != nullptr;
+    if (by_rays == by_pixels) return fail(NRF_EINVAL, "nrf_train_rays: give either rays_o and rays_d or pixels, not both and not neither");
+    if (by_rays && (!rays->rays_o || !rays->rays_d)) return fail(NRF_EINVAL, "nrf_train_rays: rays_o and rays_d come together");
+    if (by_pixels && (rays->H < 1 || rays->W < 1 || !(rays->focal > 0.0f))) return fail(NRF_EINVAL, "nrf_train_rays: bad camera for the pixels");
+    if (!rays->z_vals) return fail(NRF_EINVAL, "nrf_train_rays: output z_vals is required");
+    if (by_pixels && !rays->rays_d_out) return fail(NRF_EINVAL, "nrf_train_rays: output rays_d_out is required in pixel mode");
+    if ((int64_t)opts->n_samples * n_rays > (int64_t)INT32_MAX) return fail(NRF_EINVAL, "ray-sample count too large (n_rays * n_samples < 2^31)");
+    if (!m) return fail(NRF_EINVAL, "model is NULL");
+    const int mode = opts->mma_mode == NRF_MMA_F16X3 ? NRF_MMA_F32 : opts->mma_mode;      // the split mode trains in exact fp32
+    const bool v1 = m->arch.net == NRF_NET_V1;
+    nrf::TrainRaysDev r{};
+    std::string derr;
+    if (m->arch.net == NRF_NET_V3 && !make_dino(opts->dino, m->arch.dino_dim, r.dino, derr)) return fail(NRF_EINVAL, "nrf_mlp_forward_train_rays: " + derr);
+    if (n_rays == 0) return NRF_OK;
+    const int64_t n = n_rays * opts->n_samples;
+    r.rays_o = rays->rays_o; r.rays_d = rays->rays_d; r.pixels = rays->pixels;
+    if (by_pixels) r.cam = make_camera(rays->H, rays->W, rays->focal, rays->c2w);
+    r.lad = nrf::make_ladder(opts->near, opts->far, opts->n_samples, opts->lindisp, opts->z_ladder);
+    r.perturb = opts->perturb; r.t_rand = opts->perturb ? opts->t_rand : nullptr; r.z_in = opts->z_in; r.seed = opts->rng_seed;
+    r.z_vals = rays->z_vals; r.rays_d_out = rays->rays_d_out; r.points_out = rays->points_out;
+    auto wrong = [&]() -> const char* {
+        if (v1 && out_b) return "nrf_mlp_forward_train_rays: a V1 model writes out_a (n,4) alone, out_b must be NULL";
+        return nullptr;
+    };
+    return train_entry(m, mode, n, !out_a || (!v1 && !out_b) || !ctx, ctx_bytes, false, wrong, [&](std::string& err) {
+        hipStream_t s = (hipStream_t)stream;
+        switch (m->arch.net) {
+            case NRF_NET_V1: return nrf::launch_train_forward_rays_v1(m->net, m->train, mode, r, n, out_a, ctx, s, err);
+            case NRF_NET_V3: return nrf::launch_train_forward_rays_v3(m->net, m->train, mode, r, n, out_a, out_b, ctx, s, err);
+            default:         return nrf::launch_train_forward_rays_v2(m->net, m->train, mode, r, n, out_a, out_b, ctx, s, err);
+        }
+    });
+}
+
 int nrf_composite_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals, const float* rays_d,
                            int64_t n_rays, int n_samples, int white_bkgd, const float* g_rgb, const float* g_depth, const float* g_weights,
                            float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, void* stream) {

@@ -114,6 +114,30 @@ int launch_train_forward_v3(const DeviceNet& net, const TrainDev& t, int mma_mod
                             float* rgb, float* density, void* ctx, hipStream_t s, std::string& err);
 int launch_train_backward_v3(const DeviceNet& net, const TrainDev& t, int mma_mode, const float* rgb, const float* density,
                              const float* g_rgb, const float* g_density, int64_t n, void* ctx, float* grad, hipStream_t s, std::string& err);
+// The ray-input source of the saving forward kernels (train_impl.hpp: RayInputs), by value in their arguments: a sample's ray,
+// depth, position, direction and (V3) feature-map taps are derived in the kernel (nerfhip.h: nrf_mlp_forward_train_rays)
+struct TrainRaysDev {
+    const float* rays_o;        // (R,3), or NULL: pixel mode
+    const float* rays_d;
+    const int64_t* pixels;      // pixel mode: (R) ray ids of `cam`
+    Camera cam;
+    DepthLadder lad;            // make_ladder on the host, as launch_sample hands it to sample_kernel
+    int perturb;
+    const float* t_rand;        // (R,S) or NULL: counter_uniform(seed, row, sample)
+    const float* z_in;          // (R,S) explicit depths or NULL
+    uint64_t seed;
+    float* z_vals;              // out (R,S)
+    float* rays_d_out;          // out (R,3) or NULL
+    float* points_out;          // out (R*S,3) or NULL
+    DinoDev dino;               // V3
+};
+// n = n_rays * r.lad.S samples; V1: out_a = out4 (n,4); V2 / V3: out_a = rgb (n,3), out_b = density (n,1)
+int launch_train_forward_rays_v1(const DeviceNet& net, const TrainDev& t, int mma_mode, const TrainRaysDev& r, int64_t n, float* out4, void* ctx,
+                                 hipStream_t s, std::string& err);
+int launch_train_forward_rays_v2(const DeviceNet& net, const TrainDev& t, int mma_mode, const TrainRaysDev& r, int64_t n, float* rgb,
+                                 float* density, void* ctx, hipStream_t s, std::string& err);
+int launch_train_forward_rays_v3(const DeviceNet& net, const TrainDev& t, int mma_mode, const TrainRaysDev& r, int64_t n, float* rgb,
+                                 float* density, void* ctx, hipStream_t s, std::string& err);
 // V3, after launch_train_backward_v3 on the same context: d_dino (n, dino_dim) = dL/d per-sample DINO features
 int launch_dino_grad(const DeviceNet& net, const TrainDev& t, int mma_mode, int64_t n, void* ctx, float* d_dino, hipStream_t s, std::string& err);
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd, int step,

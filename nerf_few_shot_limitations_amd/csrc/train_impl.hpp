@@ -47,6 +47,18 @@ struct TrainKArgs {
     int64_t partial_off;               // weight-gradient partial sums: one kPartialFloats block per workgroup
 };
 
+// the arguments of the ray-input forward kernels: the staged kernels' and, behind them, the ray source (no existing kernel sees it)
+struct TrainRayKArgs : TrainKArgs {
+    TrainRaysDev rays;
+};
+
+// The input source of the saving forward bodies (their last template argument; train_forward*_body, instantiated by the kernel
+// pairs *_kernel / *_rays_kernel).  StagedInputs: the caller's per-sample tensors
+// (x_enc | pos, dir, dino), as nrf_mlp_forward_train* documents them.  RayInputs: rays (or a camera and pixel ids) in P.rays;
+// RaySample below derives what the staged tensors would have held.
+struct StagedInputs { static constexpr bool kRays = false; typedef TrainKArgs KArgs; };
+struct RayInputs { static constexpr bool kRays = true; typedef TrainRayKArgs KArgs; };
+
 // ---- host-side helpers shared by the training translation units ---------------------------------------------
 constexpr int kWgSamples = 256;          // the context is laid out for whole 256-sample groups, whatever the geometry
 
@@ -146,6 +158,60 @@ inline bool check_train_common(const DeviceNet& net, const TrainDev& t, int mode
 
 // dW/db of every Linear from the saved tensors (defined in train_shared.hip; network independent)
 int launch_weight_grad(const DeviceNet& net, const TrainDev& t, int mode, const TrainKArgs& k, float* grad, hipStream_t s, std::string& err);
+
+// One sample of a RayInputs kernel: row `ray` of the call and sample `s` of it (n < 2^31: 32-bit division), with the operations of
+// get_rays_kernel / sample_kernel (staged_kernels.hip) in their order, so that depths, points and directions are theirs to the bit.
+// Only `ray` stays live across the network: the colour branch asks for the direction again (two L2 hits or ~20 VALU
+// instructions against three registers held through the trunk).
+struct RaySample {
+    uint32_t ray;
+    int s;
+    __device__ __forceinline__ RaySample(const TrainRaysDev& R, int64_t sid) {
+        ray = (uint32_t)sid / (uint32_t)R.lad.S;
+        s = (int)((uint32_t)sid - ray * (uint32_t)R.lad.S);
+    }
+    __device__ __forceinline__ void origin_dir(const TrainRaysDev& R, float (&o)[3], float (&d)[3]) const {
+        if (R.pixels) {
+            camera_ray(R.cam, R.pixels[ray], o, d);
+            // the origin is the camera's translation, a load from the kernel arguments: left as one, the compiler merges it with the
+            // other branch's load into ONE load through a selected pointer and parks the selection in scratch (12 bytes per lane)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) o[k] = uniform_f(o[k]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { o[k] = R.rays_o[(int64_t)ray * 3 + k]; d[k] = R.rays_d[(int64_t)ray * 3 + k]; }
+        }
+    }
+    __device__ __forceinline__ void dir(const TrainRaysDev& R, float (&d)[3]) const {
+        float o[3];
+        origin_dir(R, o, d);
+    }
+    __device__ __forceinline__ float depth(const TrainRaysDev& R, int64_t sid) const {
+        if (R.z_in) return R.z_in[sid];
+        if (!R.perturb) return ladder_z(R.lad, s);
+        const float u = R.t_rand ? R.t_rand[sid] : counter_uniform(R.seed, (uint64_t)ray, (uint32_t)s);
+        return ladder_z_jitter(R.lad, s, u);
+    }
+    // the sample's position; `writer` lanes (lane half 0 of a real sample) leave z_vals, points_out and, at s == 0, rays_d_out
+    __device__ __forceinline__ void position(const TrainRaysDev& R, int64_t sid, bool writer, float (&p)[3]) const {
+        float o[3], d[3];
+        origin_dir(R, o, d);
+        const float z = depth(R, sid);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k] = point_on_ray(o[k], d[k], z);
+        if (writer) {
+            R.z_vals[sid] = z;
+            if (R.points_out) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) R.points_out[sid * 3 + k] = p[k];
+            }
+            if (R.rays_d_out && s == 0) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) R.rays_d_out[(int64_t)ray * 3 + k] = d[k];
+            }
+        }
+    }
+};
 
 __device__ __forceinline__ i32x4* mask_ptr(const TrainKArgs& P, int mslot, int64_t st, int lane) {
     return (i32x4*)(P.ctx + P.mask_off[mslot] + st * (int64_t)kMaskBytes + lane * 16);
@@ -268,9 +334,11 @@ struct ChainTile {
     }
 
     // V2 / V3 colour branch on the trunk output X (nets.hpp:NetV2::tail with stores): density_head, feature_head, PE(dir),
-    // colour layers 0 / 2 / 4, with the bias of density_head at boff; write_rgb_density() stores the results.
-    template <int LD>
-    __device__ __forceinline__ void colour_forward(const ColourSlots& cs, const Tiles& X, int boff, float& dens_raw, float (&logit)[3]) {
+    // colour layers 0 / 2 / 4, with the bias of density_head at boff; write_rgb_density() stores the results.  Src: the kernel's
+    // input source -- the sample's direction is row sid of P.dir or that of its ray in *rays.
+    template <int LD, class Src = StagedInputs>
+    __device__ __forceinline__ void colour_forward(const ColourSlots& cs, const Tiles& X, int boff, float& dens_raw, float (&logit)[3],
+                                                   const TrainRaysDev* rays = nullptr) {
         {
             f32x16 dens[1];
             dense_head<Mode, 8, 1>(pipe, bias + boff, h, X, dens);
@@ -280,8 +348,12 @@ struct ChainTile {
         linear<8>(X, in9, cs.in(), boff + 32);
         {
             float dd[3];
+            if constexpr (Src::kRays) {
+                RaySample(*rays, sid).dir(*rays, dd);
+            } else {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) dd[k] = P.dir[sid * 3 + k];
+                for (int k = 0; k < 3; ++k) dd[k] = P.dir[sid * 3 + k];
+            }
             Act t1[pe_tiles(LD)];
             encode3<Mode, LD>(dd, h, t1);
             in9[8][0] = t1[0];
@@ -366,15 +438,18 @@ namespace {
 // The launch body of every family's chain launchers (train_v*.hip): F::check, then the chain kernel
 // F::forward<ChainGeo> / F::backward<ChainGeo> at the mode's geometry; the dZ chains stream the transposed weights and are
 // followed by the weight gradients.
-template <class F, bool FORWARD>
-int run_chain(const DeviceNet& net, const TrainDev& t, int mode, TrainKArgs k, float* grad, hipStream_t s, std::string& err) {
+template <class F, bool FORWARD, class Src = StagedInputs>
+int run_chain(const DeviceNet& net, const TrainDev& t, int mode, typename Src::KArgs k, float* grad, hipStream_t s, std::string& err) {
     if (!F::check(net, t, mode, err)) return NRF_EINVAL;
     const int64_t n = k.n;
     if (n <= 0) return NRF_OK;
     if (!fill_slots(t, mode, n, k, err)) return NRF_EINVAL;
     const int r = dispatch_chain(net, mode, n, [&](auto g) {
         typedef decltype(g) G;
-        if constexpr (FORWARD)
+        if constexpr (FORWARD && Src::kRays)
+            return launch_persistent<F::template forward_rays<G>, G::kWaves>(net, net_args(net, mode), k, tiles32(n) / G::kWaves, s,
+                                                                             "train forward (rays)", err);
+        else if constexpr (FORWARD)
             return launch_persistent<F::template forward<G>, G::kWaves>(net, net_args(net, mode), k, tiles32(n) / G::kWaves, s, "train forward", err);
         else
             return launch_persistent<F::template backward<G>, G::kWaves>(net, backward_net_args(net, t, mode), k, tiles32(n) / G::kWaves, s,
@@ -389,14 +464,25 @@ int run_chain(const DeviceNet& net, const TrainDev& t, int mode, TrainKArgs k, f
 // ---------------------------------------------------------------------------------------------
 // V1 forward
 // ---------------------------------------------------------------------------------------------
-template <class Mode, int WAVES, int LP>
-__global__ void __launch_bounds__(WAVES * 64) train_forward_kernel(const TrainKArgs P) {
+template <class Mode, int WAVES, int LP, class Src>
+__device__ __forceinline__ void train_forward_body(const typename Src::KArgs& P) {
     typedef typename Mode::Act Act;
     constexpr int KT0 = pe_tiles(LP), PE = pe_dim(LP);
     chain_kernel<Mode, WAVES, true>(P, [&](ChainTile<Mode, WAVES>& T) {
         const int h = T.h;
         Act A[8][1], B[8][1];
-        {
+        if constexpr (Src::kRays) {                              // the encoding of the fused renderer's V1 (nets.hpp:encode3) in place of a (n,63) tensor
+            float p[3];
+            RaySample(P.rays, T.sid).position(P.rays, T.sid, h == 0 && T.raw < P.n, p);
+            Act e1[KT0], enc[KT0][1];
+            encode3<Mode, LP>(p, h, e1);
+#pragma unroll
+            for (int t = 0; t < KT0; ++t) {
+                enc[t][0] = e1[t];
+                T.save(SlotsV1::input(), t, e1[t]);
+            }
+            T.relu_layer(enc, A, SlotsV1::trunk(0), SlotsV1::plane(0), 0);
+        } else {
             Act enc[KT0][1];
             const float* xin = P.x_enc + T.sid * PE;
             f32x16 e[KT0];
@@ -426,6 +512,16 @@ __global__ void __launch_bounds__(WAVES * 64) train_forward_kernel(const TrainKA
             *(float4*)(P.out4 + T.raw * 4) = make_float4(r, g, b, head[0][3]);      // nerf_model.py:22-24
         }
     });
+}
+
+template <class Mode, int WAVES, int LP>
+__global__ void __launch_bounds__(WAVES * 64) train_forward_kernel(const TrainKArgs P) {
+    train_forward_body<Mode, WAVES, LP, StagedInputs>(P);
+}
+
+template <class Mode, int WAVES, int LP>
+__global__ void __launch_bounds__(WAVES * 64) train_forward_rays_kernel(const TrainRayKArgs P) {
+    train_forward_body<Mode, WAVES, LP, RayInputs>(P);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ struct V1 {
         return true;
     }
     template <class G> static constexpr auto forward = train_forward_kernel<typename G::Mode, G::kWaves, 10>;
+    template <class G> static constexpr auto forward_rays = train_forward_rays_kernel<typename G::Mode, G::kWaves, 10>;
     template <class G> static constexpr auto backward = train_backward_kernel<typename G::Mode, G::kWaves, 10>;
 };
 
@@ -22,6 +23,13 @@ int launch_train_forward(const DeviceNet& net, const TrainDev& t, int mode, cons
     TrainKArgs k{};
     k.x_enc = x_enc; k.n = n; k.out4 = out4; k.ctx = (char*)ctx;
     return run_chain<V1, true>(net, t, mode, k, nullptr, s, err);
+}
+
+int launch_train_forward_rays_v1(const DeviceNet& net, const TrainDev& t, int mode, const TrainRaysDev& r, int64_t n, float* out4, void* ctx,
+                                 hipStream_t s, std::string& err) {
+    TrainRayKArgs k{};
+    k.rays = r; k.n = n; k.out4 = out4; k.ctx = (char*)ctx;
+    return run_chain<V1, true, RayInputs>(net, t, mode, k, nullptr, s, err);
 }
 
 int launch_train_backward(const DeviceNet& net, const TrainDev& t, int mode, const float* out4, const float* g_out4, int64_t n,

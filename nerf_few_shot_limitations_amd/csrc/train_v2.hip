@@ -12,6 +12,7 @@ struct V2 {
         return true;
     }
     template <class G> static constexpr auto forward = train_forward_v2_kernel<typename G::Mode, G::kWaves, 10, 4>;
+    template <class G> static constexpr auto forward_rays = train_forward_v2_rays_kernel<typename G::Mode, G::kWaves, 10, 4>;
     template <class G> static constexpr auto backward = train_backward_v2_kernel<typename G::Mode, G::kWaves, 10>;
 };
 
@@ -22,6 +23,13 @@ int launch_train_forward_v2(const DeviceNet& net, const TrainDev& t, int mode, c
     TrainKArgs k{};
     k.pos = pos; k.dir = dir; k.n = n; k.rgb = rgb; k.density = density; k.ctx = (char*)ctx;
     return run_chain<V2, true>(net, t, mode, k, nullptr, s, err);
+}
+
+int launch_train_forward_rays_v2(const DeviceNet& net, const TrainDev& t, int mode, const TrainRaysDev& r, int64_t n, float* rgb,
+                                 float* density, void* ctx, hipStream_t s, std::string& err) {
+    TrainRayKArgs k{};
+    k.rays = r; k.n = n; k.rgb = rgb; k.density = density; k.ctx = (char*)ctx;
+    return run_chain<V2, true, RayInputs>(net, t, mode, k, nullptr, s, err);
 }
 
 int launch_train_backward_v2(const DeviceNet& net, const TrainDev& t, int mode, const float* rgb, const float* density,

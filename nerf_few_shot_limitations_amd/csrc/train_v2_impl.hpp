@@ -8,17 +8,23 @@
 
 namespace nrf {
 
-template <class Mode, int WAVES, int LP, int LD>
-__global__ void __launch_bounds__(WAVES * 64) train_forward_v2_kernel(const TrainKArgs P) {
+template <class Mode, int WAVES, int LP, int LD, class Src>
+__device__ __forceinline__ void train_forward_v2_body(const typename Src::KArgs& P) {
     typedef typename Mode::Act Act;
     constexpr int KT0 = pe_tiles(LP);
+    const TrainRaysDev* rays = nullptr;
+    if constexpr (Src::kRays) rays = &P.rays;
     chain_kernel<Mode, WAVES, true>(P, [&](ChainTile<Mode, WAVES>& T) {
         const SlotsV2 S{P.net.n_layers};
         Act A[8][1], B[8][1];
         {
             float p[3];
+            if constexpr (Src::kRays) {
+                RaySample(P.rays, T.sid).position(P.rays, T.sid, T.h == 0 && T.raw < P.n, p);
+            } else {
 #pragma unroll
-            for (int k = 0; k < 3; ++k) p[k] = P.pos[T.sid * 3 + k];
+                for (int k = 0; k < 3; ++k) p[k] = P.pos[T.sid * 3 + k];
+            }
             Act e1[KT0], enc[KT0][1];
             encode3<Mode, LP>(p, T.h, e1);
 #pragma unroll
@@ -30,9 +36,19 @@ __global__ void __launch_bounds__(WAVES * 64) train_forward_v2_kernel(const Trai
         }
         float dens_raw = 0.0f, logit[3];
         int boff = 32 * 8;
-        T.trunk_forward(S, 1, S.n, A, B, boff, [&](const Act (&X)[8][1]) { T.template colour_forward<LD>(S.colour(), X, boff, dens_raw, logit); });
+        T.trunk_forward(S, 1, S.n, A, B, boff, [&](const Act (&X)[8][1]) { T.template colour_forward<LD, Src>(S.colour(), X, boff, dens_raw, logit, rays); });
         T.write_rgb_density(dens_raw, logit);
     });
+}
+
+template <class Mode, int WAVES, int LP, int LD>
+__global__ void __launch_bounds__(WAVES * 64) train_forward_v2_kernel(const TrainKArgs P) {
+    train_forward_v2_body<Mode, WAVES, LP, LD, StagedInputs>(P);
+}
+
+template <class Mode, int WAVES, int LP, int LD>
+__global__ void __launch_bounds__(WAVES * 64) train_forward_v2_rays_kernel(const TrainRayKArgs P) {
+    train_forward_v2_body<Mode, WAVES, LP, LD, RayInputs>(P);
 }
 
 template <class Mode, int WAVES, int LP>

@@ -18,6 +18,7 @@ struct V3 {
         return true;
     }
     template <class G> static constexpr auto forward = train_forward_v3_kernel<typename G::Mode, G::kWaves, 12, 4, DT>;
+    template <class G> static constexpr auto forward_rays = train_forward_v3_rays_kernel<typename G::Mode, G::kWaves, 12, 4, DT>;
     template <class G> static constexpr auto backward = train_backward_v3_kernel<typename G::Mode, G::kWaves, 12, DT>;
 };
 
@@ -28,6 +29,14 @@ int launch_train_forward_v3(const DeviceNet& net, const TrainDev& t, int mode, c
     TrainKArgs k{};
     k.pos = pos; k.dir = dir; k.dino = dino; k.n = n; k.rgb = rgb; k.density = density; k.ctx = (char*)ctx;
     return net.arch.dino_dim == 64 ? run_chain<V3<2>, true>(net, t, mode, k, nullptr, s, err) : run_chain<V3<4>, true>(net, t, mode, k, nullptr, s, err);
+}
+
+int launch_train_forward_rays_v3(const DeviceNet& net, const TrainDev& t, int mode, const TrainRaysDev& r, int64_t n, float* rgb,
+                                 float* density, void* ctx, hipStream_t s, std::string& err) {
+    TrainRayKArgs k{};
+    k.rays = r; k.n = n; k.rgb = rgb; k.density = density; k.ctx = (char*)ctx;
+    return net.arch.dino_dim == 64 ? run_chain<V3<2>, true, RayInputs>(net, t, mode, k, nullptr, s, err)
+                                   : run_chain<V3<4>, true, RayInputs>(net, t, mode, k, nullptr, s, err);
 }
 
 int launch_train_backward_v3(const DeviceNet& net, const TrainDev& t, int mode, const float* rgb, const float* density,

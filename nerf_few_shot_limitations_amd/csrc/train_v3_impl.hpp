@@ -55,33 +55,63 @@ struct ActF32<ModeF32> {
 
 __device__ __forceinline__ float2* gate_ptr(const TrainKArgs& P, int64_t sample) { return (float2*)(P.ctx + P.aux_off) + sample; }
 
-template <class Mode, int WAVES, int LP, int LD, int DT>
-__global__ void __launch_bounds__(WAVES * 64) train_forward_v3_kernel(const TrainKArgs P) {
+template <class Mode, int WAVES, int LP, int LD, int DT, class Src>
+__device__ __forceinline__ void train_forward_v3_body(const typename Src::KArgs& P) {
     typedef typename Mode::Act Act;
     constexpr int PT = pe_tiles(LP), KT0 = PT + DT;
+    const TrainRaysDev* rays = nullptr;
+    if constexpr (Src::kRays) rays = &P.rays;
     chain_kernel<Mode, WAVES, true>(P, [&](ChainTile<Mode, WAVES>& T) {
         const SlotsV3 S{P.net.n_layers};
         const int h = T.h;
         float p[3];
+        if constexpr (Src::kRays) {
+            RaySample(P.rays, T.sid).position(P.rays, T.sid, h == 0 && T.raw < P.n, p);
+        } else {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) p[k] = P.pos[T.sid * 3 + k];
+            for (int k = 0; k < 3; ++k) p[k] = P.pos[T.sid * 3 + k];
+        }
         // first-layer operand tiles [pe * w0 | dino * w1], saved into `slot` (lora_dino.py:181,187-191)
         auto inputs = [&](float w0, float w1, Act (&x)[KT0][1], int slot) {
-            Act e1[PT];
-            encode3<Mode, LP>(p, h, e1, w0);
+            if constexpr (Src::kRays) {
+                // The renderer's gather (nets.hpp: dino_taps, DinoRaw) from the source view's map, once per fusion pass and one operand
+                // tile at a time: a pass rounds round16(e * w1) from the fp32 blend as the staged route does (never a rescaled 16-bit
+                // tile: nets.hpp:DinoHeld), and neither the taps (8 registers) nor the channels (16 DT) are held across the layers
+                // between the passes -- the map is a few hundred KB and stays in L2.  The first tile's 16 loads fly during the
+                // positional encoding, every later tile's during the conversion of the one before.
+                const DinoTaps tp = dino_taps(P.rays.dino, p);
+                DinoRaw<1> raw;
+                raw.issue(P.rays.dino.features, tp, h);
+                Act e1[PT];
+                encode3<Mode, LP>(p, h, e1, w0);
 #pragma unroll
-            for (int t = 0; t < PT; ++t) x[t][0] = e1[t];
-            const float* f = P.dino + T.sid * (32 * DT);
+                for (int t = 0; t < PT; ++t) x[t][0] = e1[t];
 #pragma unroll
-            for (int t = 0; t < DT; ++t) {
-                f32x16 e;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 v = *(const f32x4*)(f + 32 * t + 8 * g + 4 * h);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) e[4 * g + q] = v[q] * w1;
+                for (int t = 0; t < DT; ++t) {
+                    float e[16];
+                    raw.finish(tp, e);
+                    if (t + 1 < DT) raw.issue(P.rays.dino.features + 32 * (t + 1), tp, h);
+                    Act d1[1];
+                    dino_scaled_tiles<Mode, 1>(e, w1, d1);
+                    x[PT + t][0] = d1[0];
                 }
-                x[PT + t][0] = Mode::template to_act<false>(e);
+            } else {
+                Act e1[PT];
+                encode3<Mode, LP>(p, h, e1, w0);
+#pragma unroll
+                for (int t = 0; t < PT; ++t) x[t][0] = e1[t];
+                const float* f = P.dino + T.sid * (32 * DT);
+#pragma unroll
+                for (int t = 0; t < DT; ++t) {
+                    f32x16 e;
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const f32x4 v = *(const f32x4*)(f + 32 * t + 8 * g + 4 * h);
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) e[4 * g + q] = v[q] * w1;
+                    }
+                    x[PT + t][0] = Mode::template to_act<false>(e);
+                }
             }
 #pragma unroll
             for (int t = 0; t < KT0; ++t) T.save(slot, t, x[t][0]);
@@ -116,9 +146,19 @@ __global__ void __launch_bounds__(WAVES * 64) train_forward_v3_kernel(const Trai
         boff += 32 * 8;
 
         float dens_raw = 0.0f, logit[3];
-        T.trunk_forward(S, 0, S.n, A, B, boff, [&](const Act (&X)[8][1]) { T.template colour_forward<LD>(S.colour(), X, boff, dens_raw, logit); });
+        T.trunk_forward(S, 0, S.n, A, B, boff, [&](const Act (&X)[8][1]) { T.template colour_forward<LD, Src>(S.colour(), X, boff, dens_raw, logit, rays); });
         T.write_rgb_density(dens_raw, logit);
     });
+}
+
+template <class Mode, int WAVES, int LP, int LD, int DT>
+__global__ void __launch_bounds__(WAVES * 64) train_forward_v3_kernel(const TrainKArgs P) {
+    train_forward_v3_body<Mode, WAVES, LP, LD, DT, StagedInputs>(P);
+}
+
+template <class Mode, int WAVES, int LP, int LD, int DT>
+__global__ void __launch_bounds__(WAVES * 64) train_forward_v3_rays_kernel(const TrainRayKArgs P) {
+    train_forward_v3_body<Mode, WAVES, LP, LD, DT, RayInputs>(P);
 }
 
 template <class Mode, int WAVES, int LP, int DT>

@@ -1,6 +1,6 @@
 """python -m nerf_few_shot_limitations_amd.train_cli --config experiments/baseline.yaml --data data/nerf_synthetic/lego \\
         [--recipe train|multiscale] [--epochs N] [--mode bf16|f16|f32] [--eval-mode f16] [--out DIR] [--checkpoint CKPT]
-        [--dino-weights DIR | --dino-maps maps.pt] [--train-extractor] [--seed 0]
+        [--dino-weights DIR | --dino-maps maps.pt] [--train-extractor] [--fused-inputs] [--seed 0]
 
 The training run of `NeRFDINOTrainer` (src/training/train.py:244-292 `train_step`, :344-372 `train`) as a command on the
 HIP path: the YAML loads unchanged; per epoch and training view the rays are cast at the progressive schedule's
@@ -42,6 +42,10 @@ with --dino-maps (nothing to train), with --data-parallel (the per-view d_map wo
 for `dino_model_type: multi_scale`: MultiScaleDINOFeatures runs its backbone under no_grad (multi_scale_dino.py:87, kept), so
 its LoRA matrices would still receive nothing -- refused rather than silently training nothing.
 
+--fused-inputs: every ray batch is one `FusedStep.step_view` -- the batch's pixel ids go to the saving forward kernel, which casts
+the rays, draws the stratified depths (same seed, same key), encodes and, for use_dino, gathers the features itself; no per-sample
+input tensor is built.  Same shuffle, seeds and sharding as the default route, which stays the default.
+
 --checkpoint resumes a run: weights, Adam moments and step count, epoch counter and best PSNR (the reference's train.py saves
 these keys, :374-389, but has no resume path); the LR schedule is a function of the epoch.  wandb and LPIPS are not part of
 this command.
@@ -60,6 +64,7 @@ import torch.nn.functional as F
 from . import _lib as L
 from . import (dino_model_from_config, evaluate_views, get_rays, load_blender_data, load_checkpoint_into, load_config, model_from_config,
                precompute_dino_features, render_settings, sample_points_along_rays)
+from .ray_sampler import _c2w12
 from .renderer import make_dino
 from .training import FusedStep, project_fetch_backward
 
@@ -81,17 +86,22 @@ def lr_at(cfg, epoch):
     return float(o["lr"]) * float(o["lr_gamma"]) ** sum(1 for m in o["lr_milestones"] if epoch >= m)
 
 
-def view_rays(image, pose, H, W, focal, Ht, Wt):
-    """Rays and target of one training view at the schedule's resolution (train.py:174-186,262-266)."""
+def view_target(image, H, W, focal, Ht, Wt):
+    """Target (Ht*Wt,3) of one training view at the schedule's resolution and the focal length of its rays (train.py:262-266)."""
     tgt = image
     if tgt.shape[-1] == 4:
         tgt = tgt[..., :3] * tgt[..., 3:4] + (1.0 - tgt[..., 3:4])
     if (Ht, Wt) == (H, W):
-        ro, rd = get_rays(H, W, focal, pose)
-    else:
-        ro, rd = get_rays(Ht, Wt, focal * (Ht / H), pose)
-        tgt = F.interpolate(tgt.permute(2, 0, 1).unsqueeze(0), size=(Ht, Wt), mode="bilinear", align_corners=False).squeeze(0).permute(1, 2, 0)
-    return ro.reshape(-1, 3), rd.reshape(-1, 3), tgt.reshape(-1, 3).contiguous()
+        return tgt.reshape(-1, 3).contiguous(), focal
+    tgt = F.interpolate(tgt.permute(2, 0, 1).unsqueeze(0), size=(Ht, Wt), mode="bilinear", align_corners=False).squeeze(0).permute(1, 2, 0)
+    return tgt.reshape(-1, 3).contiguous(), focal * (Ht / H)
+
+
+def view_rays(image, pose, H, W, focal, Ht, Wt):
+    """Rays and target of one training view at the schedule's resolution (train.py:174-186,262-266)."""
+    tgt, f = view_target(image, H, W, focal, Ht, Wt)
+    ro, rd = get_rays(Ht, Wt, f, pose)
+    return ro.reshape(-1, 3), rd.reshape(-1, 3), tgt
 
 
 def fetch_features(dino_struct, pts):
@@ -170,8 +180,10 @@ class ExtractorTrainer:
 
 
 def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, dino_maps=None, max_batches=None, rank=0, world=1,
-                extractor=None):
+                extractor=None, fused_inputs=False):
     """One pass of train.py:261-290 over the training views; returns (mean loss, ray-samples processed).
+    fused_inputs: every batch is one `step.step_view` on its pixel ids (--fused-inputs; module docstring) instead of torch gathers,
+    sample_points_along_rays, the expanded directions and fetch_features in front of `step(...)`.
     extractor: an ExtractorTrainer (--train-extractor; module docstring) -- the view's map comes from it, live, instead of
     dino_maps[v], and it takes one step per view.
     world > 1 (data parallel, `FusedStep(data_parallel=True)`): every rank draws the SAME shuffle (same generator seed) and
@@ -181,18 +193,43 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
     model = step.model
     use_dino = model.net == L.NRF_NET_V3
     total, n_batches, samples = None, 0, 0
+    pts_buf = None
     for v in range(len(images)):
-        ro, rd, tgt = view_rays(images[v], poses[v], H, W, focal, Ht, Wt)
+        if fused_inputs:
+            tgt, f_t = view_target(images[v], H, W, focal, Ht, Wt)
+            n_view, dev_v, c2w = Ht * Wt, tgt.device, _c2w12(poses[v])              # the camera of the view's batches, converted once
+        else:
+            ro, rd, tgt = view_rays(images[v], poses[v], H, W, focal, Ht, Wt)
+            n_view, dev_v = ro.shape[0], ro.device
         view_map = extractor.begin_view(v) if extractor is not None else (dino_maps[v:v + 1] if use_dino else None)
         dino = make_dino(view_map, poses[v], focal, H, W) if use_dino else None                 # train.py:204-206: full-resolution intrinsics
         cam = dict(features=view_map, pose=poses[v], focal=focal, H=H, W=W)
-        order = torch.randperm(ro.shape[0], device=ro.device, generator=gen)
+        order = torch.randperm(n_view, device=dev_v, generator=gen)
         for i in range(0, order.shape[0], batch):
             idx = order[i:i + batch]
             if world > 1:
                 idx = idx[: idx.shape[0] // world * world][rank::world]        # equal shards: the all-reduce averages per-rank means
                 if idx.shape[0] == 0:
                     continue
+            if fused_inputs:
+                n = idx.shape[0]
+                kw = dict(dino=dino, seed=epoch * 1_000_003 + v * 10_007 + i, target=tgt[idx])
+                if extractor is not None:
+                    d_feats = extractor.feats_grad_buffer(n * S, int(view_map.shape[-1]))
+                    if pts_buf is None or pts_buf.shape[0] < n * S:
+                        pts_buf = torch.empty((n * S, 3), dtype=torch.float32, device=tgt.device)
+                    kw.update(d_dino_out=d_feats, points_out=pts_buf[:n * S])
+                loss = step.step_view(None, c2w, Ht, Wt, f_t, idx, near, far, S, perturb=True, **kw)
+                if extractor is not None:
+                    extractor.add_batch(cam, pts_buf[:n * S], d_feats)
+                total = loss if total is None else total + loss
+                n_batches += 1
+                samples += n * S
+                if max_batches is not None and n_batches >= max_batches:
+                    if extractor is not None:
+                        extractor.end_view()
+                    return float(total) / n_batches, samples
+                continue
             o, d, t = ro[idx], rd[idx], tgt[idx]
             pts, z = sample_points_along_rays(o, d, near, far, S, perturb=True, seed=epoch * 1_000_003 + v * 10_007 + i)
             n = idx.shape[0]
@@ -285,6 +322,9 @@ def main(argv=None):
     ap.add_argument("--train-extractor", action="store_true",
                     help="backpropagate into the feature maps and train the extractor's LoRA matrices (train.py:105-110's trainable set), one "
                          "extractor step per view; needs --dino-weights or --dino-random-init (module docstring)")
+    ap.add_argument("--fused-inputs", action="store_true",
+                    help="cast rays, sample, encode and fetch the DINO features inside the training forward kernel (FusedStep.step_view) instead "
+                         "of building per-sample tensors in front of it; same shuffle, seeds and sharding")
     ap.add_argument("--max-test-views", type=int, default=None)
     ap.add_argument("--max-batches", type=int, default=None, help="stop every epoch after this many ray batches (smoke runs)")
     ap.add_argument("--seed", type=int, default=0)
@@ -371,7 +411,7 @@ def main(argv=None):
             ext.set_lr(lr_at(cfg, epoch))
         t0 = time.perf_counter()
         loss, samples = train_epoch(step, cfg, epoch, images, poses, H, W, focal, rs["near"], rs["far"], gen, dino_maps, args.max_batches, rank, world,
-                                    extractor=ext)
+                                    extractor=ext, fused_inputs=args.fused_inputs)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         rec = {"epoch": epoch + 1, "loss": loss, "lr": step.opt.lr, "seconds": round(dt, 3), "Msamples_per_s": round(world * samples / dt / 1e6, 2)}

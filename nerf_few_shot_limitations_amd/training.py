@@ -783,3 +783,151 @@ class FusedStep:
                 self._loss_vec, self.last_grad_norm = loss, None
         m._gen += 1
         return loss
+
+    # ---- the same step from rays: sampling, encoding and the feature fetch happen inside the saving forward ----------------
+    @torch.no_grad()
+    def step_rays(self, rays_o, rays_d, target, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False, z_in=None,
+                  dino=None, target_depth=None, noise=None, d_dino_out=None, points_out=None):
+        """One step on rays (R,3) and their target (R,3): what train.py:188-229 builds in front of the network -- stratified
+        samples, per-sample directions, projected DINO features, encodings -- is derived inside the forward kernel
+        (nrf_mlp_forward_train_rays), so no per-sample input tensor exists.  Depths, points and therefore (V2) every bit of the step
+        are those of `self(points, z_vals, rays_d, target, dirs=...)` on `sample_points_along_rays(rays_o, rays_d, near, far,
+        n_samples, perturb, lindisp, t_rand, seed)`.
+
+            step = FusedStep(model, lr=5e-4)
+            loss = step.step_rays(rays_o, rays_d, target, near=2.0, far=6.0, n_samples=64)                       # V1, V2
+            loss = step.step_rays(rays_o, rays_d, target, 2.0, 6.0, 64, dino=dict(features=fmap, pose=pose, focal=f, H=H, W=W))   # V3
+
+        t_rand (R,S): the jitter's uniforms instead of the counter RNG; z_in (R,S): explicit depths; dino: the renderer's dict of the
+        source view (V3); points_out: a preallocated (R*S,3) tensor that receives the sample positions (what
+        project_fetch_backward needs next to d_dino_out); target_depth, noise, d_dino_out, the returned loss, `last_losses` and
+        `last_grad_norm` as in __call__.  `last_z` holds the step's (R,S) depths: a buffer of this object that the next ray step
+        of the same shape overwrites -- clone it to keep it.  `dino` may also be the (struct, tensors) pair `renderer.make_dino`
+        returned, for a caller that steps many batches on one source view."""
+        o = L.dev_f32(rays_o).reshape(-1, 3)
+        d = L.dev_f32(rays_d, o.device).reshape(-1, 3)
+        if d.shape != o.shape:
+            raise ValueError("rays_o and rays_d must both be (R,3)")
+        return self._ray_step(o.shape[0], o.device, lambda z, d_out, p_out: L.train_rays(rays_o=L.ptr(o), rays_d=L.ptr(d), z_vals=z, points_out=p_out), d,
+                              target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise, d_dino_out, points_out)
+
+    @torch.no_grad()
+    def step_view(self, image, pose, H, W, focal, pixels, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False,
+                  z_in=None, dino=None, target_depth=None, noise=None, d_dino_out=None, points_out=None, target=None):
+        """step_rays on pixels of a pinhole view: `pixels` is an int64 device tensor of ray ids y*W+x of get_rays(H, W, focal, pose),
+        whose origins and directions the kernel computes itself.  The target is `target` (R,3) if given, otherwise
+        image.reshape(-1,3)[pixels] of the (H,W,3) image: one torch gather.  The jitter of a ray is keyed by its position in
+        `pixels`, not by the pixel id: the step equals step_rays on the gathered rays to the bit.  `pose` may also be the 12 floats
+        `ray_sampler._c2w12` made of it (as `dino` may be `make_dino`'s pair): nothing is converted per batch then."""
+        if not (isinstance(pixels, torch.Tensor) and pixels.is_cuda and pixels.dtype == torch.int64 and pixels.dim() == 1):
+            raise ValueError("pixels must be a 1-d int64 tensor of ray ids on the GPU")
+        pix = pixels.contiguous()
+        H, W = int(H), int(W)
+        if target is None:
+            img = L.dev_f32(image, pix.device)
+            if img.numel() != H * W * 3:
+                raise ValueError("image must be (H,W,3) (or pass target=)")
+            target = img.reshape(-1, 3)[pix]
+        from .ray_sampler import _c2w12
+        c2w = pose if isinstance(pose, C.Array) else _c2w12(pose)
+        return self._ray_step(pix.shape[0], pix.device,
+                              lambda z, d_out, p_out: L.train_rays(pixels=pix.data_ptr(), H=H, W=W, focal=focal, c2w=c2w, z_vals=z, rays_d_out=d_out,
+                                                                   points_out=p_out),
+                              None, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise, d_dino_out, points_out)
+
+    def _ray_step(self, R, dev, make_rays, d, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise,
+                  d_dino_out, points_out):
+        """__call__'s sequence with nrf_mlp_forward_train_rays in front; d is the caller's (R,3) directions or None (pixel mode:
+        the kernel writes them for the compositor)."""
+        from .renderer import _opts, make_dino
+        m = self.model
+        S = int(n_samples)
+        n = R * S
+        v3 = m.net == L.NRF_NET_V3
+        if R < 1:
+            raise ValueError("a step needs at least one ray")
+        if d_dino_out is not None:
+            if not v3 or not getattr(m, "dino_grad", False):
+                raise ValueError("d_dino_out needs a use_dino model built with dino_grad=True")
+            if (not d_dino_out.is_cuda or d_dino_out.dtype != torch.float32 or not d_dino_out.is_contiguous() or d_dino_out.numel() != n * m.dino_dim):
+                raise ValueError("d_dino_out must be a contiguous float32 (R*S, dino_dim) tensor on the GPU")
+        if points_out is not None and (not points_out.is_cuda or points_out.dtype != torch.float32 or not points_out.is_contiguous()
+                                       or points_out.numel() != n * 3):
+            raise ValueError("points_out must be a contiguous float32 (R*S, 3) tensor on the GPU")
+        tgt = L.dev_f32(target, dev).reshape(R, 3)
+        tr = L.dev_f32(t_rand, dev).reshape(R, S) if t_rand is not None else None
+        zin = L.dev_f32(z_in, dev).reshape(R, S) if z_in is not None else None
+        dn = keep = None
+        if v3:
+            if dino is None:
+                raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
+            dn, keep = make_dino(**dino) if isinstance(dino, dict) else dino
+        lib = L.lib()
+        h, mode = _train_handle(m, dev)
+        v2 = m.net != L.NRF_NET_V1
+        with torch.cuda.device(dev):
+            self._buffers(n, R, S, dev, h, mode)
+            if getattr(self, "_ray_key", None) != self._key:
+                self.last_z = torch.empty((R, S), dtype=torch.float32, device=dev)
+                self._rays_d = torch.empty((R, 3), dtype=torch.float32, device=dev)
+                self._ray_key = self._key
+            z = self.last_z
+            opts = _opts(near, far, S, perturb, tr, seed, lindisp, 0.0, self.white, L.TRAIN_MODE[m.mma_mode], dn, dev, zin)
+            rays = make_rays(L.ptr(z), L.ptr(self._rays_d), L.ptr(points_out))
+            if d is None:
+                d = self._rays_d
+            st = L.stream_ptr()
+            ctx = C.c_void_p(self.ctx.data_ptr())
+            o4, d4 = self.out4, self.d_out4
+            if v2:
+                rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
+                g_rgb, g_den = d4.view(-1)[:3 * n].view(n, 3), d4.view(-1)[3 * n:].view(n, 1)
+                L.check(lib.nrf_mlp_forward_train_rays(h, C.byref(rays), R, C.byref(opts), L.ptr(rgb), L.ptr(den), ctx, self.nbytes, st))
+                heads = (L.ptr(rgb), 3, L.ptr(den), 1)
+                d_heads = (L.ptr(g_rgb), 3, L.ptr(g_den), 1)
+            else:
+                L.check(lib.nrf_mlp_forward_train_rays(h, C.byref(rays), R, C.byref(opts), L.ptr(o4), None, ctx, self.nbytes, st))
+                heads = (L.ptr(o4), 4, C.c_void_p(o4.data_ptr() + 12), 4)
+                d_heads = (L.ptr(d4), 4, C.c_void_p(d4.data_ptr() + 12), 4)
+            del keep
+            opt = self.opt
+            multi = (self.reg_weight > 0.0 or self.depth_weight > 0.0 or self.noise_std > 0.0 or opt.extended or target_depth is not None
+                     or noise is not None)
+            if multi:
+                td = None if target_depth is None else L.dev_f32(target_depth, dev).reshape(R)
+                nz = None if noise is None or self.noise_std == 0.0 else L.dev_f32(noise, dev).reshape(R, S)
+                nseed = 0
+                if self.noise_std > 0.0 and nz is None:
+                    if self.seed is None:
+                        self.seed = L.fresh_seed()
+                    nseed = self.seed + opt.step_count
+                lo = L.loss_opts(self.rgb_weight, self.reg_weight, self.depth_weight, L.ptr(td), self.noise_std, L.ptr(nz), nseed)
+                loss = torch.empty((4,), dtype=torch.float32, device=dev)
+                L.check(lib.nrf_composite_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), L.ptr(self.pred),
+                                                        *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
+            else:
+                loss = torch.empty((), dtype=torch.float32, device=dev)
+                L.check(lib.nrf_composite_mse_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), self.rgb_weight, L.ptr(self.pred),
+                                                       *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
+            if v2:
+                L.check(lib.nrf_mlp_backward(h, mode, L.ptr(rgb), L.ptr(den), L.ptr(g_rgb), L.ptr(g_den), n, ctx, self.nbytes, L.ptr(self.grad), st))
+                if d_dino_out is not None:
+                    _dino_grad(m, mode, n, self.ctx, self.nbytes, dev, out=d_dino_out)
+            else:
+                L.check(lib.nrf_mlp_backward_v1(h, mode, L.ptr(o4), L.ptr(d4), n, ctx, self.nbytes, L.ptr(self.grad), st))
+            if self.data_parallel:
+                _all_reduce_mean(self.grad, self.group)
+            fp, flat = opt._buffers()
+            opt.step_count += 1
+            if multi:
+                opt._update(flat, self.grad, self.ray_loss, R, S, (self.rgb_weight, self.depth_weight if target_depth is not None else 0.0,
+                                                                   self.reg_weight), loss)
+                self._loss_vec, self.last_grad_norm = loss, opt.last_grad_norm
+                loss = loss[0]
+            else:
+                L.check(lib.nrf_adam_step_loss(L.ptr(flat), L.ptr(self.grad), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq), flat.numel(), opt.lr,
+                                               opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, opt.step_count, L.ptr(self.ray_loss), R,
+                                               self.rgb_weight, L.ptr(loss), st))
+                self._loss_vec, self.last_grad_norm = loss, None
+        m._gen += 1
+        return loss

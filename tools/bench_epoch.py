@@ -2,7 +2,10 @@
 128 x 128, batch 1024, stages [32,32,32] / [64,64,48] / [128,128,64]) through train_cli.train_epoch on a synthetic scene:
 everything the loop does per ray batch -- shuffle, gather, stratified sampling, FusedStep -- on one MI355X.
 
-    python tools/bench_epoch.py [--mode bf16] [--net v2|v3]
+    python tools/bench_epoch.py [--mode bf16] [--net v2|v3] [--inputs staged|rays]
+
+--inputs rays: train_epoch(fused_inputs=True) -- every batch is one FusedStep.step_view, the per-sample inputs are derived inside
+the forward kernel.
 """
 import argparse
 import json
@@ -23,7 +26,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="bf16")
     ap.add_argument("--net", default="v2", choices=["v2", "v3"])
+    ap.add_argument("--inputs", default="staged", choices=["staged", "rays"])
     args = ap.parse_args()
+    kw = {"fused_inputs": True} if args.inputs == "rays" else {}          # (a tree without the keyword still runs --inputs staged)
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     cfg = {"training": {"batch_size": 1024, "progressive_schedule": {"epochs_0_50": [32, 32, 32], "epochs_50_100": [64, 64, 48],
@@ -46,16 +51,16 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(0)
     for epoch in (0, 50, 100):
-        train_cli.train_epoch(step, cfg, epoch, images, poses, H, W, focal, 2.0, 6.0, gen, maps)      # warm-up (buffers, kernels)
+        train_cli.train_epoch(step, cfg, epoch, images, poses, H, W, focal, 2.0, 6.0, gen, maps, **kw)      # warm-up (buffers, kernels)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         reps = 3
         for _ in range(reps):
-            loss, samples = train_cli.train_epoch(step, cfg, epoch, images, poses, H, W, focal, 2.0, 6.0, gen, maps)
+            loss, samples = train_cli.train_epoch(step, cfg, epoch, images, poses, H, W, focal, 2.0, 6.0, gen, maps, **kw)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / reps
         Ht, Wt, S, batch = train_cli.schedule_for(cfg, epoch)
-        print(json.dumps({"net": args.net, "mode": args.mode, "epoch": epoch, "stage": [Ht, Wt, S], "batch_rays": batch, "ray_samples_per_epoch": samples,
+        print(json.dumps({"net": args.net, "mode": args.mode, "inputs": args.inputs, "epoch": epoch, "stage": [Ht, Wt, S], "batch_rays": batch, "ray_samples_per_epoch": samples,
                           "epoch_ms": round(dt * 1e3, 2), "Msamples_per_s": round(samples / dt / 1e6, 1)}), flush=True)
 
 

@@ -1,11 +1,13 @@
 """Timing of the training path on one MI355X.
 
-    python tools/bench_train.py [--mode bf16] [--samples 65536 1048576] [--steps 20]
+    python tools/bench_train.py [--mode bf16] [--samples 65536 1048576] [--steps 20] [--inputs staged|rays]
 
 Prints, per batch size, the time of the saving forward, of the backward (dZ chain + weight gradients) and of a
 whole optimisation step of the reference's loop shape (train_minimal.py:97-123: encode -> NeRFMLP -> composite ->
 mse -> backward -> Adam) through the drop-in surface.  FLOP accounting: forward = flops_per_sample, backward =
 2 x forward minus the first layer's dX (not needed), all as dense MAC counts of the Linear layers.
+--inputs rays: the saving forward is nrf_mlp_forward_train_rays on samples / rays-samples rays (near 2, far 6, jittered) and the
+fused step FusedStep.step_rays; the backward and the autograd step are the same as with --inputs staged.
 """
 import argparse
 import ctypes as C
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--samples", type=int, nargs="+", default=[65536, 1048576])
     ap.add_argument("--rays-samples", type=int, default=32, help="samples per ray of the whole-step timing")
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--inputs", default="staged", choices=["staged", "rays"])
     ap.add_argument("--cpu-samples", type=int, default=0, help="also time the CPU oracle's step on this many samples (0 = skip)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -75,8 +78,25 @@ def main():
         grad = torch.zeros(model.flat_params().flat.numel(), device=dev)
         ctx = C.c_void_p(buf.data_ptr())
 
+        S = args.rays_samples
+        R = n // S
+        rays = args.inputs == "rays"
+        if rays:
+            from nerf_few_shot_limitations_amd.renderer import _opts, make_dino
+            ro = torch.rand(R, 3, device=dev) * 0.2
+            rd = torch.nn.functional.normalize(torch.rand(R, 3, device=dev) - 0.5, dim=-1)
+            fmap = torch.rand(1, 9, 9, 64, device=dev) * 2 - 1 if v3 else None
+            cam = dict(features=fmap, pose=torch.eye(4), focal=100.0, H=64, W=64) if v3 else None
+            dstruct, keep = make_dino(**cam) if v3 else (None, None)
+            zr = torch.empty(R, S, device=dev)
+            tr = L.train_rays(rays_o=L.ptr(ro), rays_d=L.ptr(rd), z_vals=L.ptr(zr))
+            ropts = _opts(2.0, 6.0, S, True, None, 1234, False, 0.0, False, args.mode, dstruct, dev)
+
         def fwd():
-            if v2:
+            if rays:
+                L.check(L.lib().nrf_mlp_forward_train_rays(h, C.byref(tr), R, C.byref(ropts), L.ptr(rgb if v2 else out), L.ptr(den) if v2 else None,
+                                                           ctx, nbytes, L.stream_ptr()))
+            elif v2:
                 L.check(L.lib().nrf_mlp_forward_train(h, mode, L.ptr(x), L.ptr(dirs), L.ptr(dino), n, L.ptr(rgb), L.ptr(den), ctx, nbytes, L.stream_ptr()))
             else:
                 L.check(L.lib().nrf_mlp_forward_train_v1(h, mode, L.ptr(x), n, L.ptr(out), ctx, nbytes, L.stream_ptr()))
@@ -90,8 +110,6 @@ def main():
         t_f = timed(fwd, args.steps)
         t_b = timed(bwd, args.steps)
         # whole step through autograd + the flat Adam kernel
-        S = args.rays_samples
-        R = n // S
         z = torch.sort(torch.rand(R, S, device=dev) * 4 + 2, dim=-1).values
         d = torch.rand(R, 3, device=dev) - 0.5
         tgt = torch.rand(R, 3, device=dev)
@@ -118,14 +136,15 @@ def main():
         t_wall = (time.perf_counter() - t0) * 1e3 / args.steps
         fused = FusedStep(model, lr=5e-4)
         zs = z.contiguous()
-        t_fs = timed(lambda: fused(xs, zs, d, tgt, dirs=ds if v2 else None, dino=dn), args.steps)
+        one = (lambda: fused.step_rays(ro, rd, tgt, 2.0, 6.0, S, dino=cam)) if rays else (lambda: fused(xs, zs, d, tgt, dirs=ds if v2 else None, dino=dn))
+        t_fs = timed(one, args.steps)
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            fused(xs, zs, d, tgt, dirs=ds if v2 else None, dino=dn)
+            one()
         torch.cuda.synchronize()
         t_fs_wall = (time.perf_counter() - t0) * 1e3 / args.steps
         line = {
-            "net": args.net, "samples": n, "mode": args.mode, "ctx_MB": round(nbytes / 2 ** 20, 1),
+            "net": args.net, "samples": n, "mode": args.mode, "inputs": args.inputs, "ctx_MB": round(nbytes / 2 ** 20, 1),
             "forward_ms": round(t_f, 4), "forward_TFLOPs": round(n * fwd_flops / t_f / 1e9, 1),
             "backward_ms": round(t_b, 4), "backward_TFLOPs": round(n * bwd_flops / t_b / 1e9, 1),
             "autograd_step_ms": round(t_s, 4), "autograd_step_wall_ms": round(t_wall, 4),
