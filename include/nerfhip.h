@@ -198,6 +198,57 @@ int nrf_render_cameras_tiles_tail(const nrf_model* m, int H, int W, float focal,
                                   const nrf_render_opts* opts, const nrf_tail* tail,
                                   float* rgb, float* depth, float* weights, float* z_vals, void* stream);
 
+/* ---- empty-space skipping: an occupancy bit grid over the scene's box ----------------------
+ *
+ * The *_occ entry points render on the ray-queue kernel (the one behind ert_eps > 0) and let a
+ * column step over every sample whose cell of the grid is empty.  A skipped sample is composited
+ * as if the network had returned density 0: alpha = 0, weight 0, T unchanged, +0 on the colour,
+ * depth and acc sums -- so the result is, bit for bit, the plain render in which the density of
+ * every sample in an empty cell is replaced by 0, and with an all-ones grid the plain render.  A
+ * ray none of whose samples lies in an occupied cell costs no network pass.
+ *
+ * The cell of a sample at position p (the position the network is given), in fp32 with a rounding
+ * after every operation:  t_k = (p_k - lo_k) * scale_k;  inside iff 0 <= t_k < res_k for all k (a
+ * NaN is not inside);  i_k = (int)floor(t_k).  A sample that is not inside follows `outside`,
+ * except that a non-finite position is always evaluated.
+ *
+ * ert_eps >= 0 (0: skipping alone; > 0: skipping and early termination); everything else of opts
+ * keeps its meaning; weights / z_vals of a skipped sample are 0 and its depth.  Not combined with
+ * the *_tail family.  Refused with NRF_EINVAL before any launch: occ == NULL, a wrong
+ * struct_bytes, `outside` not 0 or 1, bits NULL or not 4-byte aligned, a res outside 1..512 or a
+ * res[0] that is no multiple of 32, a non-finite lo, a scale that is not finite and > 0, and
+ * 2^31 or more rays. */
+typedef struct nrf_occupancy {
+    int32_t  struct_bytes;   /* sizeof(nrf_occupancy), checked */
+    int32_t  outside;        /* sample outside the box: 0 = evaluate it (default), 1 = skip it */
+    const uint32_t* bits;    /* device, 4-byte aligned; bit index ((iz*res[1] + iy)*res[0] + ix), word = index >> 5, bit = index & 31; 1 = occupied */
+    int32_t  res[3];         /* cells along x, y, z: each 1..512, res[0] a multiple of 32 */
+    float    lo[3];          /* lower corner of the box */
+    float    scale[3];       /* cells per unit length, computed by the caller: res[k] / (hi[k] - lo[k]); finite, > 0 */
+    unsigned long long* stats; /* optional device [2], the call ADDS to it: [0] network-evaluated (ray, sample) pairs,
+                                  [1] MLP passes run by a wave that held at least one live ray: [0] / ([1] * columns per wave)
+                                  (64 in the 16-bit modes, 32 otherwise) is the column utilisation */
+} nrf_occupancy;
+
+/* nrf_render_rays / nrf_render_camera / nrf_render_cameras_tiles with a grid: same arguments, same outputs. */
+int nrf_render_rays_occ(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays,
+                        const nrf_render_opts* opts, const nrf_occupancy* occ,
+                        float* rgb, float* depth, float* weights, float* z_vals, void* stream);
+int nrf_render_camera_occ(const nrf_model* m, int H, int W, float focal, const float c2w[12],
+                          int64_t ray_begin, int64_t ray_end, const nrf_render_opts* opts, const nrf_occupancy* occ,
+                          float* rgb, float* depth, float* weights, float* z_vals, void* stream);
+int nrf_render_cameras_tiles_occ(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams,
+                                 int64_t tile_rays, int64_t first_tile, int64_t tile_step, int64_t n_tiles,
+                                 const nrf_render_opts* opts, const nrf_occupancy* occ,
+                                 float* rgb, float* depth, float* weights, float* z_vals, void* stream);
+
+/* Building a grid.  Cell c of n_cells (a multiple of 32) is occupied iff the maximum of its k consecutive
+ * densities density[c*k .. c*k + k-1] is > threshold; a NaN density makes the cell occupied.  bits: n_cells / 32 words. */
+int nrf_occupancy_pack(const float* density, int64_t n_cells, int k, float threshold, uint32_t* bits, void* stream);
+/* bits_out (res[0]*res[1]*res[2] / 32 words, not bits_in) = bits_in with every cell occupied whose 3x3x3 neighbourhood
+ * holds an occupied cell; cells beyond the box count as empty.  res as in nrf_occupancy. */
+int nrf_occupancy_dilate(const uint32_t* bits_in, const int32_t res[3], uint32_t* bits_out, void* stream);
+
 /* ---- staged entry points (one reference leaf each; used by the drop-in
  *      Python surface and by the stage-wise parity tests) ------------------- */
 

@@ -56,6 +56,18 @@ class nrf_tail(C.Structure):
     _fields_ = [("mode", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class nrf_occupancy(C.Structure):
+    """The occupancy bit grid of the *_occ render entry points; struct_bytes is filled in by occupancy()."""
+    _fields_ = [("struct_bytes", C.c_int32), ("outside", C.c_int32), ("bits", C.c_void_p), ("res", C.c_int32 * 3), ("lo", C.c_float * 3),
+                ("scale", C.c_float * 3), ("stats", C.c_void_p)]
+
+
+def occupancy(bits=None, res=(32, 32, 32), lo=(0.0, 0.0, 0.0), scale=(1.0, 1.0, 1.0), outside=0, stats=None):
+    """nrf_occupancy with its size field set; bits / stats are device addresses (ints) or None, res / lo / scale in x, y, z order."""
+    return nrf_occupancy(C.sizeof(nrf_occupancy), int(outside), bits, (C.c_int32 * 3)(*[int(r) for r in res]),
+                         (C.c_float * 3)(*[float(x) for x in lo]), (C.c_float * 3)(*[float(x) for x in scale]), stats)
+
+
 class nrf_loss_opts(C.Structure):
     """The multi-term loss of nrf_composite_loss_backward; struct_bytes is filled in by loss_opts()."""
     _fields_ = [("struct_bytes", C.c_int32), ("rgb_weight", C.c_float), ("reg_weight", C.c_float), ("depth_weight", C.c_float),
@@ -103,6 +115,16 @@ SIGNATURES = {
     "nrf_render_cameras_tiles_tail": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                                 C.c_int64, C.POINTER(nrf_render_opts), C.POINTER(nrf_tail), C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]),
+    # empty-space skipping: the render entry points with an occupancy bit grid, and the two kernels that build one
+    "nrf_render_rays_occ": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(nrf_render_opts), C.POINTER(nrf_occupancy),
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_render_camera_occ": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float * 12, C.c_int64, C.c_int64,
+                                        C.POINTER(nrf_render_opts), C.POINTER(nrf_occupancy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_render_cameras_tiles_occ": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                               C.c_int64, C.POINTER(nrf_render_opts), C.POINTER(nrf_occupancy), C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
+    "nrf_occupancy_pack": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "nrf_occupancy_dilate": (C.c_int, [C.c_void_p, C.c_int32 * 3, C.c_void_p, C.c_void_p]),
     "nrf_get_rays": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float * 12, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_sample_along_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),

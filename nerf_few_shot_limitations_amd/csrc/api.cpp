@@ -258,20 +258,46 @@ int check_tail(const nrf_render_opts* o, const nrf_tail* t, int64_t n_rays) {
     return NRF_OK;
 }
 
-// the launch of a render entry point: plain, or prefix + tail through the caller's workspace
-int launch_any(const nrf_model* m, const nrf_render_opts* opts, const nrf_tail* tail, const nrf::RenderArgs& a, void* stream, std::string& err) {
+// the grid of a *_occ entry point and the call's ray count (nerfhip.h: nrf_occupancy): everything the arguments alone decide,
+// looked at before the model
+int check_occ(const nrf_occupancy* g, int64_t n_rays) {
+    if (!g) return fail(NRF_EINVAL, "occ is NULL");
+    if (g->struct_bytes != (int32_t)sizeof(nrf_occupancy)) return fail(NRF_EINVAL, "nrf_occupancy: struct_bytes is not sizeof(nrf_occupancy)");
+    if (g->outside != 0 && g->outside != 1) return fail(NRF_EINVAL, "nrf_occupancy: outside must be 0 (evaluate) or 1 (skip)");
+    if (!g->bits || (reinterpret_cast<uintptr_t>(g->bits) & 3u) != 0) return fail(NRF_EINVAL, "nrf_occupancy: bits is NULL or not 4-byte aligned");
+    for (int k = 0; k < 3; ++k) {
+        if (g->res[k] < 1 || g->res[k] > 512) return fail(NRF_EINVAL, "nrf_occupancy: res must be in 1..512 on every axis");
+        if (!std::isfinite(g->lo[k])) return fail(NRF_EINVAL, "nrf_occupancy: lo must be finite");
+        if (!std::isfinite(g->scale[k]) || !(g->scale[k] > 0.0f)) return fail(NRF_EINVAL, "nrf_occupancy: scale must be finite and > 0");
+    }
+    if (g->res[0] % 32 != 0) return fail(NRF_EINVAL, "nrf_occupancy: res[0] must be a multiple of 32");
+    if (n_rays >= (int64_t)1 << 31) return fail(NRF_EINVAL, "a render with a grid runs on the ray queue: launch too large (>= 2^31 rays)");
+    return NRF_OK;
+}
+
+nrf::OccDev make_occ(const nrf_occupancy* g) {
+    nrf::OccDev d{};
+    d.bits = g->bits; d.outside = g->outside; d.stats = g->stats;
+    for (int k = 0; k < 3; ++k) { d.res[k] = g->res[k]; d.lo[k] = g->lo[k]; d.scale[k] = g->scale[k]; }
+    return d;
+}
+
+// the launch of a render entry point: plain, with a grid, or prefix + tail through the caller's workspace
+int launch_any(const nrf_model* m, const nrf_render_opts* opts, const nrf_tail* tail, const nrf_occupancy* occ, const nrf::RenderArgs& a, void* stream,
+               std::string& err) {
+    if (occ) return nrf::launch_render_occ(m->net, opts->mma_mode, a, make_occ(occ), (hipStream_t)stream, err);
     if (tail) return nrf::launch_render_tail(m->net, opts->mma_mode, a, static_cast<float*>(tail->workspace), (hipStream_t)stream, err);
     return nrf::launch_render(m->net, opts->mma_mode, a, (hipStream_t)stream, err);
 }
 
 int render_rays_any(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays, const nrf_render_opts* opts,
-                    const nrf_tail* tail, bool tailed, float* rgb, float* depth, float* weights, float* z_vals, void* stream);
+                    const nrf_tail* tail, bool tailed, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals, void* stream);
 int render_camera_any(const nrf_model* m, int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
-                      const nrf_render_opts* opts, const nrf_tail* tail, bool tailed, float* rgb, float* depth, float* weights, float* z_vals,
+                      const nrf_render_opts* opts, const nrf_tail* tail, bool tailed, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals,
                       void* stream);
 int render_cameras_tiles_any(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams, int64_t tile_rays,
                              int64_t first_tile, int64_t tile_step, int64_t n_tiles, const nrf_render_opts* opts, const nrf_tail* tail,
-                             bool tailed, float* rgb, float* depth, float* weights, float* z_vals, void* stream);
+                             bool tailed, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals, void* stream);
 
 }  // namespace
 
@@ -360,32 +386,72 @@ int64_t nrf_render_tail_bytes(int64_t n_rays) {
 
 int nrf_render_rays(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays, const nrf_render_opts* opts,
                     float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
-    return render_rays_any(m, rays_o, rays_d, n_rays, opts, nullptr, false, rgb, depth, weights, z_vals, stream);
+    return render_rays_any(m, rays_o, rays_d, n_rays, opts, nullptr, false, nullptr, rgb, depth, weights, z_vals, stream);
 }
 int nrf_render_rays_tail(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays, const nrf_render_opts* opts,
                          const nrf_tail* tail, float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
-    return render_rays_any(m, rays_o, rays_d, n_rays, opts, tail, true, rgb, depth, weights, z_vals, stream);
+    return render_rays_any(m, rays_o, rays_d, n_rays, opts, tail, true, nullptr, rgb, depth, weights, z_vals, stream);
 }
 int nrf_render_camera(const nrf_model* m, int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
                       const nrf_render_opts* opts, float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
-    return render_camera_any(m, H, W, focal, c2w, ray_begin, ray_end, opts, nullptr, false, rgb, depth, weights, z_vals, stream);
+    return render_camera_any(m, H, W, focal, c2w, ray_begin, ray_end, opts, nullptr, false, nullptr, rgb, depth, weights, z_vals, stream);
 }
 int nrf_render_camera_tail(const nrf_model* m, int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
                            const nrf_render_opts* opts, const nrf_tail* tail, float* rgb, float* depth, float* weights, float* z_vals,
                            void* stream) {
-    return render_camera_any(m, H, W, focal, c2w, ray_begin, ray_end, opts, tail, true, rgb, depth, weights, z_vals, stream);
+    return render_camera_any(m, H, W, focal, c2w, ray_begin, ray_end, opts, tail, true, nullptr, rgb, depth, weights, z_vals, stream);
 }
 int nrf_render_cameras_tiles(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams, int64_t tile_rays,
                              int64_t first_tile, int64_t tile_step, int64_t n_tiles, const nrf_render_opts* opts, float* rgb, float* depth,
                              float* weights, float* z_vals, void* stream) {
-    return render_cameras_tiles_any(m, H, W, focal, c2w, n_cams, tile_rays, first_tile, tile_step, n_tiles, opts, nullptr, false, rgb, depth,
+    return render_cameras_tiles_any(m, H, W, focal, c2w, n_cams, tile_rays, first_tile, tile_step, n_tiles, opts, nullptr, false, nullptr, rgb, depth,
                                     weights, z_vals, stream);
 }
 int nrf_render_cameras_tiles_tail(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams, int64_t tile_rays,
                                   int64_t first_tile, int64_t tile_step, int64_t n_tiles, const nrf_render_opts* opts, const nrf_tail* tail,
                                   float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
-    return render_cameras_tiles_any(m, H, W, focal, c2w, n_cams, tile_rays, first_tile, tile_step, n_tiles, opts, tail, true, rgb, depth,
+    return render_cameras_tiles_any(m, H, W, focal, c2w, n_cams, tile_rays, first_tile, tile_step, n_tiles, opts, tail, true, nullptr, rgb, depth,
                                     weights, z_vals, stream);
+}
+
+// with a grid: the grid and the ray count are checked first (they need no model), then the plain entry's own checks
+int nrf_render_rays_occ(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays, const nrf_render_opts* opts,
+                        const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
+    if (check_occ(occ, n_rays) != NRF_OK) return NRF_EINVAL;
+    return render_rays_any(m, rays_o, rays_d, n_rays, opts, nullptr, false, occ, rgb, depth, weights, z_vals, stream);
+}
+int nrf_render_camera_occ(const nrf_model* m, int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
+                          const nrf_render_opts* opts, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals,
+                          void* stream) {
+    if (check_occ(occ, ray_end - ray_begin) != NRF_OK) return NRF_EINVAL;
+    return render_camera_any(m, H, W, focal, c2w, ray_begin, ray_end, opts, nullptr, false, occ, rgb, depth, weights, z_vals, stream);
+}
+int nrf_render_cameras_tiles_occ(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams, int64_t tile_rays,
+                                 int64_t first_tile, int64_t tile_step, int64_t n_tiles, const nrf_render_opts* opts, const nrf_occupancy* occ,
+                                 float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
+    // (the product is formed in floating point: a tile description that overflows int64 is refused like any other launch too large)
+    const double rays = (double)(n_tiles > 0 ? n_tiles : 0) * (double)(tile_rays > 0 ? tile_rays : 0) * (double)(n_cams > 0 ? n_cams : 0);
+    if (check_occ(occ, rays >= 2147483648.0 ? (int64_t)1 << 31 : (int64_t)rays) != NRF_OK) return NRF_EINVAL;
+    return render_cameras_tiles_any(m, H, W, focal, c2w, n_cams, tile_rays, first_tile, tile_step, n_tiles, opts, nullptr, false, occ, rgb, depth,
+                                    weights, z_vals, stream);
+}
+
+int nrf_occupancy_pack(const float* density, int64_t n_cells, int k, float threshold, uint32_t* bits, void* stream) {
+    if (n_cells < 0 || n_cells % 32 != 0 || k < 1) return fail(NRF_EINVAL, "nrf_occupancy_pack: n_cells must be a non-negative multiple of 32 and k >= 1");
+    if (n_cells == 0) return NRF_OK;
+    if (!density || !bits) return fail(NRF_EINVAL, "nrf_occupancy_pack: null pointer");
+    const int r = nrf::launch_occupancy_pack(density, n_cells, k, threshold, bits, (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "occupancy_pack launch failed");
+}
+
+int nrf_occupancy_dilate(const uint32_t* bits_in, const int32_t res[3], uint32_t* bits_out, void* stream) {
+    if (!bits_in || !bits_out || !res || bits_in == bits_out) return fail(NRF_EINVAL, "nrf_occupancy_dilate: null pointer, or bits_out is bits_in");
+    for (int k = 0; k < 3; ++k)
+        if (res[k] < 1 || res[k] > 512) return fail(NRF_EINVAL, "nrf_occupancy_dilate: res must be in 1..512 on every axis");
+    if (res[0] % 32 != 0) return fail(NRF_EINVAL, "nrf_occupancy_dilate: res[0] must be a multiple of 32");
+    const int r3[3] = {res[0], res[1], res[2]};
+    const int r = nrf::launch_occupancy_dilate(bits_in, r3, bits_out, (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "occupancy_dilate launch failed");
 }
 
 extern "C++" {
@@ -394,7 +460,7 @@ namespace {
 // The three render entry points, plain (tailed == false) and with a tail (nerfhip.h: nrf_tail), which is checked once the call's
 // ray count is known.
 int render_rays_any(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays, const nrf_render_opts* opts,
-                    const nrf_tail* tail, bool tailed, float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
+                    const nrf_tail* tail, bool tailed, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
     if (rgbd_misaligned(opts, rgb)) return fail(NRF_EINVAL, kRgbdAlign);
     if (!m) return fail(NRF_EINVAL, "model is NULL");
     if (n_rays < 0) return fail(NRF_EINVAL, "n_rays < 0");
@@ -412,12 +478,12 @@ int render_rays_any(const nrf_model* m, const float* rays_o, const float* rays_d
     if (m->arch.net == NRF_NET_V3 && !make_dino(opts->dino, m->arch.dino_dim, a.dino, err)) return fail(NRF_EINVAL, err);
     DeviceGuard guard(m->device);
     if (!guard.ok) return fail(NRF_EHIP, "cannot select the model's device");
-    const int r = launch_any(m, opts, tail, a, stream, err);
+    const int r = launch_any(m, opts, tail, occ, a, stream, err);
     return r == NRF_OK ? NRF_OK : fail(r, err);
 }
 
 int render_camera_any(const nrf_model* m, int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
-                      const nrf_render_opts* opts, const nrf_tail* tail, bool tailed, float* rgb, float* depth, float* weights, float* z_vals,
+                      const nrf_render_opts* opts, const nrf_tail* tail, bool tailed, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals,
                       void* stream) {
     if (rgbd_misaligned(opts, rgb)) return fail(NRF_EINVAL, kRgbdAlign);
     if (!m) return fail(NRF_EINVAL, "model is NULL");
@@ -436,13 +502,13 @@ int render_camera_any(const nrf_model* m, int H, int W, float focal, const float
     if (m->arch.net == NRF_NET_V3 && !make_dino(opts->dino, m->arch.dino_dim, a.dino, err)) return fail(NRF_EINVAL, err);
     DeviceGuard guard(m->device);
     if (!guard.ok) return fail(NRF_EHIP, "cannot select the model's device");
-    const int r = launch_any(m, opts, tail, a, stream, err);
+    const int r = launch_any(m, opts, tail, occ, a, stream, err);
     return r == NRF_OK ? NRF_OK : fail(r, err);
 }
 
 int render_cameras_tiles_any(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams, int64_t tile_rays,
                              int64_t first_tile, int64_t tile_step, int64_t n_tiles, const nrf_render_opts* opts, const nrf_tail* tail,
-                             bool tailed, float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
+                             bool tailed, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
     if (rgbd_misaligned(opts, rgb)) return fail(NRF_EINVAL, kRgbdAlign);
     if (!m) return fail(NRF_EINVAL, "model is NULL");
     if (H < 1 || W < 1 || !(focal > 0.0f) || !c2w) return fail(NRF_EINVAL, "bad camera");
@@ -465,7 +531,7 @@ int render_cameras_tiles_any(const nrf_model* m, int H, int W, float focal, cons
     if (m->arch.net == NRF_NET_V3 && !make_dino(opts->dino, m->arch.dino_dim, a.dino, err)) return fail(NRF_EINVAL, err);
     DeviceGuard guard(m->device);
     if (!guard.ok) return fail(NRF_EHIP, "cannot select the model's device");
-    const int r = launch_any(m, opts, tail, a, stream, err);
+    const int r = launch_any(m, opts, tail, occ, a, stream, err);
     return r == NRF_OK ? NRF_OK : fail(r, err);
 }
 

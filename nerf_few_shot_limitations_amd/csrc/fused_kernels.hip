@@ -14,6 +14,17 @@ int launch_render(const DeviceNet& net, int mode, const RenderArgs& a, hipStream
     return NRF_EUNSUPPORTED;
 }
 
+int launch_render_occ(const DeviceNet& net, int mode, const RenderArgs& a, const OccDev& g, hipStream_t s, std::string& err) {
+    if (!check_net(net, mode, err)) return NRF_EINVAL;
+    if (a.n_rays <= 0) return NRF_OK;
+    if (net.arch.net == NRF_NET_V1 && net.arch.pos_freq == 10) return render_occ_v1(net, mode, a, g, s, err);
+    if (net.arch.net == NRF_NET_V2 && net.arch.pos_freq == 10) return render_occ_v2(net, mode, a, g, s, err);
+    if (net.arch.net == NRF_NET_V3 && net.arch.pos_freq == 12 && net.arch.dino_dim == 64) return render_occ_v3(net, mode, a, g, s, err);
+    if (net.arch.net == NRF_NET_V3 && net.arch.pos_freq == 12 && net.arch.dino_dim == 128) return render_occ_v3w(net, mode, a, g, s, err);
+    err = "no fused renderer built for this (net, pos_freq): see nrf_render_rays";
+    return NRF_EUNSUPPORTED;
+}
+
 int launch_render_tail(const DeviceNet& net, int base_mode, const RenderArgs& a, float* carry, hipStream_t s, std::string& err) {
     if (!check_net(net, base_mode, err) || !check_net(net, NRF_MMA_F16X3, err)) return NRF_EINVAL;
     if (a.n_rays <= 0) return NRF_OK;

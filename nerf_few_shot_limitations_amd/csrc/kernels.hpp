@@ -75,6 +75,16 @@ int launch_render(const DeviceNet& net, int mma_mode, const RenderArgs& a, hipSt
 constexpr int kCarryRows = 6;       // T, r, g, b, depth, acc: one row of n_rays floats each
 inline int64_t render_tail_floats(int64_t n_rays) { return kCarryRows * n_rays; }
 int launch_render_tail(const DeviceNet& net, int base_mode, const RenderArgs& a, float* carry, hipStream_t s, std::string& err);
+// Empty-space skipping (nerfhip.h: nrf_occupancy), by value in the arguments of the skipping ray-queue kernels alone
+struct OccDev {
+    const uint32_t* bits;       // bit ((iz * res[1] + iy) * res[0] + ix): 1 = occupied
+    int res[3];
+    float lo[3], scale[3];
+    int outside;                // 1: a (finite) sample outside the box is skipped
+    unsigned long long* stats;  // optional [2]: += evaluated (ray, sample) pairs | MLP passes of waves that held a live ray
+};
+// the ray-queue kernel with skipping (ert_eps >= 0: 0 = skipping alone)
+int launch_render_occ(const DeviceNet& net, int mma_mode, const RenderArgs& a, const OccDev& g, hipStream_t s, std::string& err);
 int launch_forward_v1(const DeviceNet& net, int mma_mode, const float* x_enc, int64_t n, float* out4, hipStream_t s, std::string& err);
 int launch_forward(const DeviceNet& net, int mma_mode, const float* pos, const float* dir, const float* dino, int64_t n,
                    float* rgb, float* density, hipStream_t s, std::string& err);
@@ -194,6 +204,10 @@ int launch_composite(const float* rgb, int rgb_stride, const float* sigma, int s
                      int64_t n_rays, int S, int white_bkgd, float* out_rgb, float* out_depth, float* out_w, hipStream_t s);
 int launch_sample_pdf(const float* z, const float* w, int64_t n_rays, int S, int Ni, const float* u, int64_t u_ray_stride, float* samples,
                       float* z_union, hipStream_t s);
+// occupancy bit grids: cell c is occupied iff max(density[c*k .. c*k+k-1]) > threshold (a NaN counts as occupied); n_cells a multiple of 32
+int launch_occupancy_pack(const float* density, int64_t n_cells, int k, float threshold, uint32_t* bits, hipStream_t s);
+// bits_out = the 3x3x3 dilation of bits_in (cells beyond the box are empty); res[0] a multiple of 32
+int launch_occupancy_dilate(const uint32_t* bits_in, const int res[3], uint32_t* bits_out, hipStream_t s);
 int launch_project_fetch(const DinoDev& d, const float* points, int64_t n, float* feats, float* xy, hipStream_t s);
 int launch_sample_features(const float* features, int Hp, int Wp, int C, const float* points_2d, int64_t n, float* feats, hipStream_t s);
 // adjoints of the two fetches with respect to the map (no atomics: per-slab private copies in `ws`, fetch_backward_ws_floats(...)

@@ -718,7 +718,60 @@ int fetch_backward_impl(const DinoDev& d, const float* points, int points2d, int
     return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
 }
 
+// ---- occupancy bit grids (nerfhip.h: nrf_occupancy) ----------------------------------------------
+// Cell c is occupied iff one of its k consecutive densities is > threshold or NaN; a wave packs 64 cells into two words with one
+// ballot, lanes 0 and 32 store them.  The loop bound is wave-uniform (whole waves step together), so the ballot sees every lane.
+__global__ void __launch_bounds__(kBlock) occupancy_pack_kernel(const float* __restrict__ density, int64_t n_cells, int k, float threshold,
+                                                                uint32_t* __restrict__ bits) {
+    const int lane = threadIdx.x & 63;
+    for (int64_t first = blockIdx.x * (int64_t)kBlock + (threadIdx.x - lane); first < n_cells; first += (int64_t)gridDim.x * kBlock) {
+        const int64_t c = first + lane;
+        bool occ = false;
+        if (c < n_cells) {
+            const float* d = density + c * k;
+            for (int j = 0; j < k; ++j) occ |= !(d[j] <= threshold);
+        }
+        const unsigned long long m = __ballot(occ);
+        if (lane == 0) bits[first >> 5] = (uint32_t)m;
+        if (lane == 32 && first + 32 < n_cells) bits[(first >> 5) + 1] = (uint32_t)(m >> 32);
+    }
+}
+
+// One thread per word (32 cells along x): the OR of the nine rows around it, each spread by one cell to either side
+__global__ void __launch_bounds__(kBlock) occupancy_dilate_kernel(const uint32_t* __restrict__ in, int wx, int ry, int rz, uint32_t* __restrict__ out) {
+    const int64_t n_words = (int64_t)wx * ry * rz;
+    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n_words; i += (int64_t)gridDim.x * kBlock) {
+        const int x = (int)(i % wx), y = (int)((i / wx) % ry), z = (int)(i / ((int64_t)wx * ry));
+        uint32_t acc = 0;
+        for (int dz = -1; dz <= 1; ++dz) {
+            for (int dy = -1; dy <= 1; ++dy) {
+                const int yy = y + dy, zz = z + dz;
+                if (yy < 0 || yy >= ry || zz < 0 || zz >= rz) continue;
+                const uint32_t* row = in + ((int64_t)zz * ry + yy) * wx;
+                const uint32_t w = row[x];
+                acc |= w | (w << 1) | (w >> 1);
+                if (x > 0) acc |= row[x - 1] >> 31;
+                if (x + 1 < wx) acc |= row[x + 1] << 31;
+            }
+        }
+        out[i] = acc;
+    }
+}
+
 }  // namespace
+
+int launch_occupancy_pack(const float* density, int64_t n_cells, int k, float threshold, uint32_t* bits, hipStream_t s) {
+    if (n_cells <= 0) return NRF_OK;
+    hipLaunchKernelGGL(occupancy_pack_kernel, dim3(grid_for(n_cells, kBlock, 8192)), dim3(kBlock), 0, s, density, n_cells, k, threshold, bits);
+    return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
+}
+
+int launch_occupancy_dilate(const uint32_t* bits_in, const int res[3], uint32_t* bits_out, hipStream_t s) {
+    const int wx = res[0] / 32;
+    hipLaunchKernelGGL(occupancy_dilate_kernel, dim3(grid_for((int64_t)wx * res[1] * res[2], kBlock, 8192)), dim3(kBlock), 0, s, bits_in, wx, res[1],
+                       res[2], bits_out);
+    return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
+}
 
 int launch_get_rays(const Camera& cam, int64_t ray_begin, int64_t n, float* rays_o, float* rays_d, hipStream_t s) {
     if (n <= 0) return NRF_OK;

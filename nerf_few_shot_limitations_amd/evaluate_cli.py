@@ -34,6 +34,13 @@ def main(argv=None):
                     help="with --mode f16 / bf16: evaluate every ray's last sample (composited with dist = 1e10) in split-f16")
     ap.add_argument("--max-views", type=int, default=None)
     ap.add_argument("--ert", type=float, default=0.0)
+    ap.add_argument("--occupancy-res", type=int, default=0,
+                    help="skip empty space with an occupancy grid of N^3 cells built from the checkpoint (0 = off; N a multiple of 32, <= 512)")
+    ap.add_argument("--occupancy-threshold", type=float, default=0.0, help="a cell is occupied when a probed density exceeds this")
+    ap.add_argument("--occupancy-samples", type=int, default=4, help="densities probed per cell")
+    ap.add_argument("--occupancy-dilate", type=int, default=1, help="cells the occupied set is grown by")
+    ap.add_argument("--occupancy-box", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="the grid's box on every axis (default: -far .. far)")
     ap.add_argument("--dino-map", default=None)
     ap.add_argument("--dino-weights", default=None, help="local transformers Dinov2Model checkpoint (dir or file) for the extractor of the config")
     ap.add_argument("--dino-random-init", action="store_true", help="build the extractor with random weights (pipeline runs, features meaningless)")
@@ -66,12 +73,25 @@ def main(argv=None):
         load_checkpoint_into(model, torch.load(args.checkpoint, map_location="cpu", weights_only=True))
     model = model.cuda().eval()
     targets = images.permute(0, 2, 3, 1).contiguous()
+    grid = None
+    if args.occupancy_res:
+        # built from the loaded weights; a use_dino model's grid belongs to its source view, and every evaluation render has the
+        # same one (training view 0), so one grid is built, on first use
+        from .occupancy import OccupancyGrid
+        lo, hi = args.occupancy_box if args.occupancy_box else (-rs["far"], rs["far"])
+        grid = OccupancyGrid.from_model(model, lo, hi, resolution=args.occupancy_res, threshold=args.occupancy_threshold,
+                                        samples_per_cell=args.occupancy_samples, dilate=args.occupancy_dilate, mma_mode=args.mode, dino=dino)
     res = evaluate_views(model, poses, H, W, focal, rs["near"], rs["far"], rs["n_samples"], targets=targets, out_dir=args.out,
-                         white_bkgd=rs["white_bkgd"], mma_mode=args.mode, ert_eps=args.ert, dino=dino, tail_mode=args.tail_mode)
+                         white_bkgd=rs["white_bkgd"], mma_mode=args.mode, ert_eps=args.ert, dino=dino, tail_mode=args.tail_mode, occupancy=grid,
+                         return_stats=grid is not None)
     metrics = {"psnr": res["psnr"], "ssim": res["ssim"], "views": len(res["per_view"]), "per_view": res["per_view"],
                "H": H, "W": W, "n_samples": rs["n_samples"], "mode": args.mode}
     if args.tail_mode:
         metrics["tail_mode"] = args.tail_mode
+    if grid is not None:
+        metrics["occupancy"] = {"res": args.occupancy_res, "threshold": args.occupancy_threshold, "samples": args.occupancy_samples,
+                                "dilate": args.occupancy_dilate, "occupied_fraction": grid.occupied_fraction,
+                                "evaluated_share": res["evaluated_share"]}
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         with open(os.path.join(args.out, "metrics.json"), "w") as f:

@@ -69,20 +69,29 @@ def save_png(path: str, img: torch.Tensor) -> None:
 
 @torch.no_grad()
 def evaluate_views(model, poses, H, W, focal, near, far, N_samples=64, targets=None, out_dir=None, white_bkgd=False,
-                   mma_mode=None, ert_eps=0.0, dino=None, max_png=5, tail_mode=None):
+                   mma_mode=None, ert_eps=0.0, dino=None, max_png=5, tail_mode=None, occupancy=None, return_stats=False):
     """Render every test pose (8 views per kernel launch) and, when `targets` (V,H,W,3|4) are given, score them.
     `tail_mode="f16x3"` with a 16-bit mma_mode: every ray's last sample in split-f16 (renderer.render_rays).
+    `occupancy=` (an OccupancyGrid; V3: of the source view `dino`): empty cells are skipped; return_stats=True adds 'stats'
+    [evaluated (ray, sample) pairs, live MLP passes] and 'evaluated_share' = stats[0] / (V*H*W*N_samples).
     Returns {'images' (V,H,W,3), 'depth' (V,H,W), 'psnr', 'ssim' (means), 'per_view': [...]} (train.py:294-342)."""
     model.eval()
     poses = torch.as_tensor(poses)
     V = poses.shape[0]
     tile_rays = 16 * int(W)
     local = tiles.render_tiles(model, H, W, focal, poses, near, far, N_samples, 0, 1, tile_rays, white_bkgd=white_bkgd,
-                               mma_mode=mma_mode, ert_eps=ert_eps, dino=dino, tail_mode=tail_mode)
+                               mma_mode=mma_mode, ert_eps=ert_eps, dino=dino, tail_mode=tail_mode, occupancy=occupancy,
+                               return_stats=return_stats)
+    stats = None
+    if isinstance(local, tuple):
+        local, stats = local
     frames = tiles.gather_frames(local, int(H) * int(W), tile_rays, world=1)      # rendered with rank 0 of 1: no collective
     images = frames[..., :3].reshape(V, H, W, 3)
     depth = frames[..., 3].reshape(V, H, W)
     out = {"images": images, "depth": depth, "per_view": []}
+    if stats is not None:
+        out["stats"] = [int(v) for v in stats.tolist()]
+        out["evaluated_share"] = out["stats"][0] / float(V * int(H) * int(W) * int(N_samples))
     if targets is not None:
         for v in range(V):
             t = torch.as_tensor(targets[v]).to(images.device).float()

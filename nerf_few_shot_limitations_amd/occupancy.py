@@ -1,0 +1,203 @@
+"""Occupancy bit grids for empty-space skipping (include/nerfhip.h: nrf_occupancy).
+
+An `OccupancyGrid` holds one bit per cell of an axis-aligned box: bit ((iz * ry + iy) * rx + ix) of the word array, 32 cells per
+word, 1 = occupied.  The render entry points that take `occupancy=` (renderer.py, tiles.py) step over every sample whose cell is
+empty; a skipped sample is composited as density 0.  `from_model` builds a grid by probing the network's density at a few points
+per cell (nrf_occupancy_pack) and growing the result by one cell (nrf_occupancy_dilate): it is NOT conservative between the
+probed points, which is why skipping is opt-in.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+
+def _triple(v, what):
+    t = tuple(float(x) for x in (v if hasattr(v, "__len__") else (v, v, v)))
+    if len(t) != 3:
+        raise ValueError(f"{what} must be a number or three numbers (x, y, z)")
+    return t
+
+
+def _counter_u01(seed, index):
+    """U[0,1) from (seed, int64 tensor of counters): a 32-bit integer hash (the murmur3 finaliser) evaluated in int64, identical on
+    every device; 24 random bits."""
+    m = 0xFFFFFFFF
+    h = (index + (int(seed) & 0x7FFFFFFF) * 0x9E3779B1) & m
+    h = ((h ^ (h >> 16)) * 0x85EBCA6B) & m
+    h = ((h ^ (h >> 13)) * 0xC2B2AE35) & m
+    h = h ^ (h >> 16)
+    return (h >> 8).to(torch.float32) * (1.0 / 16777216.0)
+
+
+class OccupancyGrid:
+    def __init__(self, bits, res, lo, hi, outside=0):
+        """bits: int32 tensor of rx*ry*rz/32 words; res = (rx, ry, rz); lo / hi: the box; outside: what happens to a sample
+        outside the box (0: it is evaluated, 1: it is skipped)."""
+        self.res = tuple(int(r) for r in res)
+        rx, ry, rz = self.res
+        if len(self.res) != 3 or not all(1 <= r <= 512 for r in self.res) or rx % 32:
+            raise ValueError("res = (rx, ry, rz): each in 1..512 and rx a multiple of 32")
+        self.lo, self.hi = _triple(lo, "lo"), _triple(hi, "hi")
+        if not all(np.isfinite(a) and np.isfinite(b) and b > a for a, b in zip(self.lo, self.hi)):
+            raise ValueError("need finite lo < hi on every axis")
+        if outside not in (0, 1):
+            raise ValueError("outside must be 0 (evaluate) or 1 (skip)")
+        self.outside = int(outside)
+        if bits.dtype != torch.int32 or bits.numel() != rx * ry * rz // 32:
+            raise ValueError("bits must be an int32 tensor of rx*ry*rz/32 words")
+        self.bits = bits.contiguous().reshape(-1)
+
+    # ---- geometry ---------------------------------------------------------------------------------
+    @property
+    def scale(self):
+        """Cells per unit length as the kernels get them: float32(res) / (float32(hi) - float32(lo))."""
+        lo, hi = np.asarray(self.lo, np.float32), np.asarray(self.hi, np.float32)
+        return tuple(float(v) for v in (np.asarray(self.res, np.float32) / (hi - lo)))
+
+    @property
+    def n_cells(self):
+        return self.res[0] * self.res[1] * self.res[2]
+
+    def to(self, device):
+        return OccupancyGrid(self.bits.to(device), self.res, self.lo, self.hi, self.outside)
+
+    # ---- masks ------------------------------------------------------------------------------------
+    @classmethod
+    def from_mask(cls, mask, lo, hi, outside=0):
+        """mask: bool tensor (rz, ry, rx), True = occupied."""
+        mask = torch.as_tensor(mask)
+        if mask.dim() != 3:
+            raise ValueError("mask must be (rz, ry, rx)")
+        rz, ry, rx = (int(v) for v in mask.shape)
+        if rx % 32:
+            raise ValueError("rx (the last axis of the mask) must be a multiple of 32")
+        sh = torch.arange(32, dtype=torch.int64, device=mask.device)
+        words = (mask.reshape(-1, 32).to(torch.int64) << sh).sum(dim=1)
+        words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)        # the bit pattern of the uint32 word
+        return cls(words, (rx, ry, rz), lo, hi, outside)
+
+    def to_mask(self):
+        rx, ry, rz = self.res
+        sh = torch.arange(32, dtype=torch.int64, device=self.bits.device)
+        return (((self.bits.to(torch.int64)[:, None] >> sh) & 1) != 0).reshape(rz, ry, rx)
+
+    @property
+    def occupied_fraction(self):
+        return float(self.to_mask().to(torch.float32).mean())
+
+    # ---- building ---------------------------------------------------------------------------------
+    def dilate(self, n=1):
+        """The grid grown by n cells in every direction (n passes of nrf_occupancy_dilate)."""
+        L.require_gpu()
+        if not self.bits.is_cuda:
+            raise ValueError("dilate runs on the GPU: move the grid there first (grid.to(device))")
+        cur = self.bits
+        res = (C.c_int32 * 3)(*self.res)
+        with torch.cuda.device(cur.device):
+            for _ in range(int(n)):
+                out = torch.empty_like(cur)
+                L.check(L.lib().nrf_occupancy_dilate(cur.data_ptr(), res, out.data_ptr(), L.stream_ptr()))
+                cur = out
+        return OccupancyGrid(cur, self.res, self.lo, self.hi, self.outside)
+
+    @staticmethod
+    def cell_points(res, lo, hi, first_cell, n_cells, samples_per_cell, seed=0, device="cpu"):
+        """(n_cells, samples_per_cell, 3) float32 points a build evaluates for cells first_cell .. first_cell + n_cells - 1 of a
+        (rx, ry, rz) grid over [lo, hi]: sample 0 is the cell centre, sample j > 0 sits at counter-RNG offsets (seed, cell, j, axis)
+        inside the cell.  Deterministic and the same on every device."""
+        rx, ry, rz = (int(r) for r in res)
+        lo, hi = _triple(lo, "lo"), _triple(hi, "hi")
+        k = int(samples_per_cell)
+        cell = torch.arange(int(first_cell), int(first_cell) + int(n_cells), dtype=torch.int64, device=device)
+        idx = torch.stack([cell % rx, (cell // rx) % ry, cell // (rx * ry)], dim=-1)                       # (n, 3): ix, iy, iz
+        j = torch.arange(k, dtype=torch.int64, device=device)
+        ax = torch.arange(3, dtype=torch.int64, device=device)
+        u = _counter_u01(seed, (cell[:, None, None] * k + j[None, :, None]) * 3 + ax[None, None, :])       # (n, k, 3)
+        u[:, 0, :] = 0.5
+        lo_t = torch.tensor(lo, dtype=torch.float32, device=device)
+        size = (torch.tensor(hi, dtype=torch.float32, device=device) - lo_t) / torch.tensor([rx, ry, rz], dtype=torch.float32, device=device)
+        return lo_t + (idx[:, None, :].to(torch.float32) + u) * size
+
+    @staticmethod
+    def _density(model, pts, dino):
+        """Densities (n,) of `model` at points (n,3) through NeRFMLP.forward: V1 encodes and takes the raw sigma, V2 / V3 run with a
+        fixed unit view direction (the density does not depend on it), V3 on the features of the source view `dino`."""
+        dev = pts.device
+        if model.net == L.NRF_NET_V1:
+            n, pe = pts.shape[0], 3 * (2 * model.pos_freq + 1)
+            enc = torch.empty((n, pe), dtype=torch.float32, device=dev)
+            L.check(L.lib().nrf_encode(L.ptr(pts), n, 3, model.pos_freq, 1, None, L.ptr(enc), L.stream_ptr()))
+            return model(enc)[:, 3]
+        dirs = torch.zeros_like(pts)
+        dirs[:, 2] = -1.0
+        feats = None
+        if model.net == L.NRF_NET_V3:
+            from .renderer import make_dino
+            d, keep = make_dino(**dino)
+            feats = torch.empty((pts.shape[0], model.dino_dim), dtype=torch.float32, device=dev)
+            L.check(L.lib().nrf_project_fetch(C.byref(d), L.ptr(pts), pts.shape[0], L.ptr(feats), None, L.stream_ptr()))
+            del keep
+        return model(pts, dirs, feats)[1].reshape(-1)
+
+    @classmethod
+    def from_model(cls, model, lo, hi, resolution=128, threshold=0.0, samples_per_cell=4, dilate=1, mma_mode=None, dino=None,
+                   chunk_cells=1 << 18, seed=0, device=None, outside=0):
+        """Probe `model`'s density at `samples_per_cell` points of every cell (cell_points), mark the cells whose maximum exceeds
+        `threshold`, grow the result by `dilate` cells.  resolution: cells per axis (a number or (rx, ry, rz)).  A V3 grid belongs
+        to ONE source view: dino=dict(features=, pose=, focal=, H=, W=) is required."""
+        L.require_gpu()
+        if model.net == L.NRF_NET_V3 and dino is None:
+            raise ValueError("a use_dino model's density depends on the source view: from_model needs dino=dict(features=, pose=, focal=, H=, W=)")
+        res = tuple(int(r) for r in (resolution if hasattr(resolution, "__len__") else (resolution,) * 3))
+        grid = cls(torch.zeros((res[0] * res[1] * res[2] // 32,), dtype=torch.int32), res, lo, hi, outside)        # validates res / box
+        if device is None:
+            p = next(model.parameters())
+            device = p.device if p.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        device = torch.device(device)
+        k = int(samples_per_cell)
+        if k < 1:
+            raise ValueError("samples_per_cell must be >= 1")
+        chunk = max(32, int(chunk_cells) // 32 * 32)
+        bits = torch.empty((grid.n_cells // 32,), dtype=torch.int32, device=device)
+        was_training, own_mode = model.training, model.mma_mode
+        model.eval()
+        if mma_mode is not None:
+            model.mma_mode = mma_mode
+        try:
+            with torch.no_grad(), torch.cuda.device(device):
+                for first in range(0, grid.n_cells, chunk):
+                    n = min(chunk, grid.n_cells - first)
+                    pts = cls.cell_points(res, lo, hi, first, n, k, seed, device).reshape(-1, 3).contiguous()
+                    dens = cls._density(model, pts, dino).contiguous()
+                    L.check(L.lib().nrf_occupancy_pack(L.ptr(dens), n, k, float(threshold), bits[first // 32:].data_ptr(), L.stream_ptr()))
+        finally:
+            model.mma_mode = own_mode
+            model.train(was_training)
+        grid = cls(bits, res, lo, hi, outside)
+        return grid.dilate(dilate) if dilate else grid
+
+    # ---- the C struct -----------------------------------------------------------------------------
+    def struct(self, device, stats=None):
+        """(nrf_occupancy for a launch on `device`, tensors to keep alive).  stats: an int64 device tensor [2] the call adds to."""
+        if not self.bits.is_cuda or self.bits.device != torch.device(device):
+            self.bits = self.bits.to(device)                          # moved once, then reused
+        return L.occupancy(self.bits.data_ptr(), self.res, self.lo, self.scale, self.outside,
+                           stats.data_ptr() if stats is not None else None), (self.bits, stats)
+
+
+def occupancy_arg(occupancy, return_stats, tail_mode, device):
+    """What a render call passes for `occupancy=` / `return_stats=`: (nrf_occupancy or None, stats tensor or None, keep-alive)."""
+    if occupancy is None:
+        if return_stats:
+            raise ValueError("return_stats needs occupancy=: the statistics are those of the skipping kernel")
+        return None, None, None
+    if tail_mode is not None:
+        raise ValueError("occupancy cannot be combined with tail_mode: the grid is not part of the tail family")
+    stats = torch.zeros((2,), dtype=torch.int64, device=device) if return_stats else None
+    st, keep = occupancy.struct(device, stats)
+    return st, stats, keep

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib as L
 from .nerf_model import NeRFMLP
+from .occupancy import occupancy_arg
 from .ray_sampler import _c2w12
 
 
@@ -57,7 +58,7 @@ def _handle(model, device, mma_mode, tail_mode):
 
 def render_rays(model: NeRFMLP, rays_o, rays_d, near, far, N_samples=64, perturb=False, t_rand=None, seed=None, lindisp=False,
                 ert_eps=0.0, white_bkgd=False, mma_mode: Optional[str] = None, dino=None, return_weights=True, return_z=False,
-                z_in=None, tail_mode: Optional[str] = None):
+                z_in=None, tail_mode: Optional[str] = None, occupancy=None, return_stats=False):
     """Render explicit rays (R,3)/(H,W,3) -> {'rgb' (R,3), 'depth' (R,), 'weights' (R,S)[, 'z_vals' (R,S)]}.
     Under torch.no_grad() or with the model in eval() mode (evaluate, train.py:294-296) this is ONE fused kernel launch.  With
     grad enabled and the model in train() mode (train_step, train.py:245,280-287) the same call returns tensors with a grad_fn:
@@ -65,9 +66,14 @@ def render_rays(model: NeRFMLP, rays_o, rays_d, near, far, N_samples=64, perturb
     work on the drop-in unchanged.  (`mma_mode` selects the arithmetic on both routes; the split mode trains in exact fp32.)
     `tail_mode="f16x3"` (with a 16-bit mma_mode): every ray's last sample -- the one composited with dist = 1e10, whose opacity
     is a step function of its density -- is evaluated in split-f16; two launches.  Refused under grad (ValueError): the training
-    kernels have no split mode."""
+    kernels have no split mode.
+    `occupancy=` (an occupancy.OccupancyGrid): samples in empty cells are stepped over and composited as density 0, on the ray-queue
+    kernel (ert_eps >= 0).  `return_stats=True` adds 'stats', an int64 device tensor [evaluated (ray, sample) pairs, MLP passes of
+    waves that held a live ray].  Refused with tail_mode and under grad (ValueError)."""
     L.require_gpu()
     if model.training and model._wants_grad():
+        if occupancy is not None:
+            raise ValueError("occupancy is for inference: the differentiable route (a model in train() mode under grad) evaluates every sample")
         from .training import render_rays_train
         out = render_rays_train(model, rays_o, rays_d, near, far, N_samples, perturb=perturb, t_rand=t_rand, seed=seed, lindisp=lindisp,
                                 white_bkgd=white_bkgd, dino=dino, z_in=z_in, mma_mode=mma_mode, tail_mode=tail_mode)
@@ -94,8 +100,12 @@ def render_rays(model: NeRFMLP, rays_o, rays_d, near, far, N_samples=64, perturb
         depth = torch.empty((R,), dtype=torch.float32, device=o.device)
         w = torch.empty((R, S), dtype=torch.float32, device=o.device) if return_weights else None
         z = torch.empty((R, S), dtype=torch.float32, device=o.device) if return_z else None
+        occ, stats, occ_keep = occupancy_arg(occupancy, return_stats, tail_mode, o.device)
         tail, ws = L.tail_arg(tail_mode, mma_mode or model.mma_mode, R, o.device)
-        if tail is None:
+        if occ is not None:
+            L.check(L.lib().nrf_render_rays_occ(h, L.ptr(o), L.ptr(d), R, C.byref(opts), C.byref(occ), L.ptr(rgb), L.ptr(depth), L.ptr(w), L.ptr(z),
+                                                L.stream_ptr()))
+        elif tail is None:
             L.check(L.lib().nrf_render_rays(h, L.ptr(o), L.ptr(d), R, C.byref(opts), L.ptr(rgb), L.ptr(depth), L.ptr(w), L.ptr(z), L.stream_ptr()))
         else:
             L.check(L.lib().nrf_render_rays_tail(h, L.ptr(o), L.ptr(d), R, C.byref(opts), C.byref(tail), L.ptr(rgb), L.ptr(depth), L.ptr(w),
@@ -106,14 +116,17 @@ def render_rays(model: NeRFMLP, rays_o, rays_d, near, far, N_samples=64, perturb
         out["weights"] = w
     if z is not None:
         out["z_vals"] = z
+    if stats is not None:
+        out["stats"] = stats
     return out
 
 
 def render_camera(model: NeRFMLP, H, W, focal, c2w, near, far, N_samples=64, ray_begin=0, ray_end=None, perturb=False, seed=None,
                   lindisp=False, ert_eps=0.0, white_bkgd=False, mma_mode: Optional[str] = None, dino=None, device=None,
-                  out_rgb=None, out_depth=None, tail_mode: Optional[str] = None):
+                  out_rgb=None, out_depth=None, tail_mode: Optional[str] = None, occupancy=None, return_stats=False):
     """Render rays [ray_begin, ray_end) of an HxW pinhole camera with in-kernel ray generation
-    (get_rays + render_rays of the reference, train.py:179,305-319) -> (rgb (n,3), depth (n,)).  `tail_mode`: see render_rays."""
+    (get_rays + render_rays of the reference, train.py:179,305-319) -> (rgb (n,3), depth (n,)).  `tail_mode`, `occupancy`: see render_rays; with
+    return_stats=True the result is (rgb, depth, stats)."""
     L.require_gpu()
     H, W = int(H), int(W)
     ray_end = H * W if ray_end is None else int(ray_end)
@@ -133,15 +146,19 @@ def render_camera(model: NeRFMLP, H, W, focal, c2w, near, far, N_samples=64, ray
     with torch.cuda.device(device):
         rgb = out_rgb if out_rgb is not None else torch.empty((n, 3), dtype=torch.float32, device=device)
         depth = out_depth if out_depth is not None else torch.empty((n,), dtype=torch.float32, device=device)
+        occ, stats, occ_keep = occupancy_arg(occupancy, return_stats, tail_mode, device)
         tail, ws = L.tail_arg(tail_mode, mma_mode or model.mma_mode, n, device)
-        if tail is None:
+        if occ is not None:
+            L.check(L.lib().nrf_render_camera_occ(h, H, W, float(focal), _c2w12(c2w), int(ray_begin), ray_end, C.byref(opts), C.byref(occ),
+                                                  L.ptr(rgb), L.ptr(depth), None, None, L.stream_ptr()))
+        elif tail is None:
             L.check(L.lib().nrf_render_camera(h, H, W, float(focal), _c2w12(c2w), int(ray_begin), ray_end, C.byref(opts),
                                               L.ptr(rgb), L.ptr(depth), None, None, L.stream_ptr()))
         else:
             L.check(L.lib().nrf_render_camera_tail(h, H, W, float(focal), _c2w12(c2w), int(ray_begin), ray_end, C.byref(opts), C.byref(tail),
                                                    L.ptr(rgb), L.ptr(depth), None, None, L.stream_ptr()))
     del keep
-    return rgb, depth
+    return (rgb, depth, stats) if stats is not None else (rgb, depth)
 
 
 def render_hierarchical(model: NeRFMLP, rays_o, rays_d, near, far, N_samples=128, N_importance=64, perturb=False, u=None, **kw):
@@ -150,7 +167,7 @@ def render_hierarchical(model: NeRFMLP, rays_o, rays_d, near, far, N_samples=128
     reference never calls and which raises on every input: parity of the resampling step is
     unpinned, the two render passes are the same kernel as `render_rays`.
     Returns the fine pass' dict plus 'coarse' (the coarse pass' dict) and 'z_vals' (R, S+Ni).  A `tail_mode` applies to both
-    passes (the fine pass marches its explicit depths, z_in, with the same split)."""
+    passes (the fine pass marches its explicit depths, z_in, with the same split), and so do `occupancy` / `return_stats`."""
     from .ray_sampler import sample_pdf
     coarse = render_rays(model, rays_o, rays_d, near, far, N_samples, perturb=perturb, return_weights=True, return_z=True, **kw)
     if u is None and perturb:
@@ -170,9 +187,10 @@ class NeRFRenderer:
     ignored: the fused kernel never materialises (rays x samples) intermediates."""
 
     def __init__(self, model: NeRFMLP, near, far, white_bkgd=False, mma_mode=None, ert_eps=0.0,
-                 dino_features=None, poses=None, focal=None, H=None, W=None, tail_mode=None):
+                 dino_features=None, poses=None, focal=None, H=None, W=None, tail_mode=None, occupancy=None):
         self.nerf_model, self.near, self.far = model, float(near), float(far)
         self.white_bkgd, self.mma_mode, self.ert_eps, self.tail_mode = white_bkgd, mma_mode, ert_eps, tail_mode
+        self.occupancy = occupancy           # an OccupancyGrid (V3: of the source view evaluation renders from, view 0); used outside training only
         self.dino_features_precomputed, self.poses, self.focal, self.H, self.W = dino_features, poses, focal, H, W
 
     def _dino(self, view_idx):
@@ -185,7 +203,8 @@ class NeRFRenderer:
         """train.py:188: differentiable under grad mode (train_step), the fused kernel under torch.no_grad() (evaluate)."""
         return render_rays(self.nerf_model, rays_o, rays_d, self.near, self.far, N_samples,
                            perturb=self.nerf_model.training, white_bkgd=self.white_bkgd, mma_mode=self.mma_mode,
-                           ert_eps=self.ert_eps, dino=self._dino(view_idx), tail_mode=self.tail_mode)
+                           ert_eps=self.ert_eps, dino=self._dino(view_idx), tail_mode=self.tail_mode,
+                           occupancy=None if (self.nerf_model.training and self.nerf_model._wants_grad()) else self.occupancy)
 
     @torch.no_grad()
     def render_full_image(self, rays_o, rays_d, closest_view_idx=0, chunk_size=1024, N_samples=64):

@@ -70,7 +70,9 @@ class TileJob:
     `launch()` enqueues exactly the render kernel(s), which write rgb+depth rows straight into the gather buffer `buf`."""
 
     def __init__(self, model, H, W, focal, c2w, near, far, N_samples, rank, world, tile_rays, perturb=False, seed=0, lindisp=False,
-                 ert_eps=0.0, white_bkgd=False, mma_mode: Optional[str] = None, dino=None, device=None, tail_mode: Optional[str] = None):
+                 ert_eps=0.0, white_bkgd=False, mma_mode: Optional[str] = None, dino=None, device=None, tail_mode: Optional[str] = None,
+                 occupancy=None, return_stats=False):
+        from .occupancy import occupancy_arg
         from .renderer import _opts, make_dino
         L.require_gpu()
         self.H, self.W, self.focal = int(H), int(W), float(focal)
@@ -94,6 +96,9 @@ class TileJob:
         self.opts.out_rgbd = 1                                               # the kernel writes [r,g,b,depth] rows: no packing pass
         with torch.cuda.device(self.device):
             self.buf = torch.zeros((self.V, self.per_rank * self.tile_rays, 4), dtype=torch.float32, device=self.device)
+            # empty-space skipping (renderer.render_rays: occupancy=): the grid's struct once; `stats` (return_stats=True) is this rank's
+            # [evaluated samples, live MLP passes], which every launch() adds to
+            self._occ, self.stats, self._occ_keep = occupancy_arg(occupancy, return_stats, tail_mode, self.device)
 
     @property
     def views_per_launch(self):
@@ -135,7 +140,11 @@ class TileJob:
                     # launch's first view so that the pattern is a function of the GLOBAL view index, however the views are batched
                     self.opts.rng_seed = (seed0 + v0 * 0x51ED27) & 0xFFFFFFFFFFFFFFFF
                     tail, ws = L.tail_arg(self.tail_mode, self.mma_mode, nv * n, self.device)
-                    if tail is None:
+                    if self._occ is not None:
+                        L.check(L.lib().nrf_render_cameras_tiles_occ(h, self.H, self.W, self.focal, C.cast(sub, C.c_void_p), nv, self.tile_rays,
+                                                                     self.rank, self.world, self.n_real, C.byref(self.opts), C.byref(self._occ),
+                                                                     L.ptr(out), None, None, None, L.stream_ptr()))
+                    elif tail is None:
                         L.check(L.lib().nrf_render_cameras_tiles(h, self.H, self.W, self.focal, C.cast(sub, C.c_void_p), nv, self.tile_rays,
                                                                  self.rank, self.world, self.n_real, C.byref(self.opts),
                                                                  L.ptr(out), None, None, None, L.stream_ptr()))
@@ -196,10 +205,10 @@ class OverlappedGather:
 
 def render_tiles(model, H, W, focal, c2w, near, far, N_samples, rank, world, tile_rays, **kw):
     """This rank's tiles of a batch of V views (c2w (V,4,4), or one (4,4) pose) -> (V, per_rank*tile_rays, 4) = [r,g,b,depth].
-    Up to 8 views go into one kernel launch."""
+    Up to 8 views go into one kernel launch.  With occupancy= and return_stats=True: (that buffer, this rank's stats)."""
     job = TileJob(model, H, W, focal, c2w, near, far, N_samples, rank, world, tile_rays, **kw)
     job.launch()
-    return job.pack()
+    return (job.pack(), job.stats) if job.stats is not None else job.pack()
 
 
 def gather_frames(local: torch.Tensor, n_rays: int, tile_rays: int, group=None, world=None) -> torch.Tensor:
@@ -219,14 +228,17 @@ def gather_frames(local: torch.Tensor, n_rays: int, tile_rays: int, group=None, 
 
 def render_frame_sharded(model, H, W, focal, c2w, near, far, N_samples=64, tile_rows=16, group=None, **kw):
     """Full frame(s) on every rank: (rgb (H,W,3), depth (H,W)) -- with a leading view axis if c2w is a batch.
-    One launch (per 8 views) + one all_gather per rank."""
+    One launch (per 8 views) + one all_gather per rank.  With occupancy= and return_stats=True this rank's stats come third."""
     import torch.distributed as dist
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     tile_rays = int(tile_rows) * int(W)
     local = render_tiles(model, H, W, focal, c2w, near, far, N_samples, rank, world, tile_rays, **kw)
+    stats = None
+    if isinstance(local, tuple):
+        local, stats = local
     frames = gather_frames(local, int(H) * int(W), tile_rays, group)
     rgb, depth = frames[..., :3].reshape(-1, H, W, 3), frames[..., 3].reshape(-1, H, W)
     if torch.as_tensor(c2w).dim() == 2:
-        return rgb[0], depth[0]
-    return rgb, depth
+        rgb, depth = rgb[0], depth[0]
+    return (rgb, depth, stats) if stats is not None else (rgb, depth)
