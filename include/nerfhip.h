@@ -249,6 +249,32 @@ int nrf_occupancy_pack(const float* density, int64_t n_cells, int k, float thres
  * holds an occupied cell; cells beyond the box count as empty.  res as in nrf_occupancy. */
 int nrf_occupancy_dilate(const uint32_t* bits_in, const int32_t res[3], uint32_t* bits_out, void* stream);
 
+/* Marking a grid from what the renderer itself produced: weights (R,S) and z_vals (R,S) of a batch of rays, as the render entry
+ * points write them, and the rays -- explicit (R,3) origins and directions, or rays [ray_begin, ray_end) of a pinhole camera,
+ * generated exactly as nrf_render_camera generates them.  hit_bits / seen_bits are two bit arrays in the layout of
+ * nrf_occupancy.bits (res[0]*res[1]*res[2] / 32 words, device, 4-byte aligned); the call ORs into them, the caller zeroes them
+ * first; either may be NULL, not both.  Per sample i of a ray (origin o, direction d):
+ *   position  p = o + d * z_i (one rounded product, one rounded sum per axis: the renderer's own points);
+ *   cell      t = (p - lo) * scale per axis, each one rounded fp32 operation; the sample is inside iff 0 <= t < res on every axis,
+ *             its cell index is (floor(t_z)*res[1] + floor(t_y))*res[0] + floor(t_x): the rule the *_occ entry points skip by;
+ *             a sample outside the box or at a non-finite position marks nothing;
+ *   hit       bit set iff !(w_i <= weight_threshold): a NaN weight marks, as a NaN density does in nrf_occupancy_pack;
+ *   seen      bit set iff 1 - sum_{j<i} w_j > seen_eps, the sum in fp32 over the ray's earlier samples (the order of the additions is
+ *             not specified); a NaN in that sum makes every later sample of the ray unseen.
+ * OR is order-independent: the arrays are the same bits from run to run and for every cut of the rays into calls.
+ * res, lo, scale as in nrf_occupancy; n_samples >= 1; fewer than 2^31 rays; weight_threshold finite and >= 0; seen_eps in [0,1).
+ * n_rays == 0 is NRF_OK.  Runs on the current device. */
+int nrf_occupancy_mark_rays(const float* rays_o, const float* rays_d, int64_t n_rays, int n_samples,
+                            const float* z_vals, const float* weights,
+                            const int32_t res[3], const float lo[3], const float scale[3],
+                            float weight_threshold, float seen_eps,
+                            uint32_t* hit_bits, uint32_t* seen_bits, void* stream);
+int nrf_occupancy_mark_camera(int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
+                              int n_samples, const float* z_vals, const float* weights,
+                              const int32_t res[3], const float lo[3], const float scale[3],
+                              float weight_threshold, float seen_eps,
+                              uint32_t* hit_bits, uint32_t* seen_bits, void* stream);
+
 /* ---- staged entry points (one reference leaf each; used by the drop-in
  *      Python surface and by the stage-wise parity tests) ------------------- */
 

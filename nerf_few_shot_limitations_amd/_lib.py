@@ -125,6 +125,11 @@ SIGNATURES = {
                                                C.c_void_p, C.c_void_p]),
     "nrf_occupancy_pack": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "nrf_occupancy_dilate": (C.c_int, [C.c_void_p, C.c_int32 * 3, C.c_void_p, C.c_void_p]),
+    # marks from rendered weights: rays given explicitly, or as a ray range of a pinhole camera
+    "nrf_occupancy_mark_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int32 * 3, C.c_float * 3,
+                                          C.c_float * 3, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_occupancy_mark_camera": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float * 12, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_int32 * 3, C.c_float * 3, C.c_float * 3, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_get_rays": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float * 12, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_sample_along_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),

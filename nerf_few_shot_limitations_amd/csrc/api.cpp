@@ -258,6 +258,17 @@ int check_tail(const nrf_render_opts* o, const nrf_tail* t, int64_t n_rays) {
     return NRF_OK;
 }
 
+// the box of a grid (nerfhip.h: nrf_occupancy): res, lo and scale as the render entry points and the marking entry points take them
+int check_occ_box(const int32_t res[3], const float lo[3], const float scale[3]) {
+    for (int k = 0; k < 3; ++k) {
+        if (res[k] < 1 || res[k] > 512) return fail(NRF_EINVAL, "nrf_occupancy: res must be in 1..512 on every axis");
+        if (!std::isfinite(lo[k])) return fail(NRF_EINVAL, "nrf_occupancy: lo must be finite");
+        if (!std::isfinite(scale[k]) || !(scale[k] > 0.0f)) return fail(NRF_EINVAL, "nrf_occupancy: scale must be finite and > 0");
+    }
+    if (res[0] % 32 != 0) return fail(NRF_EINVAL, "nrf_occupancy: res[0] must be a multiple of 32");
+    return NRF_OK;
+}
+
 // the grid of a *_occ entry point and the call's ray count (nerfhip.h: nrf_occupancy): everything the arguments alone decide,
 // looked at before the model
 int check_occ(const nrf_occupancy* g, int64_t n_rays) {
@@ -265,12 +276,7 @@ int check_occ(const nrf_occupancy* g, int64_t n_rays) {
     if (g->struct_bytes != (int32_t)sizeof(nrf_occupancy)) return fail(NRF_EINVAL, "nrf_occupancy: struct_bytes is not sizeof(nrf_occupancy)");
     if (g->outside != 0 && g->outside != 1) return fail(NRF_EINVAL, "nrf_occupancy: outside must be 0 (evaluate) or 1 (skip)");
     if (!g->bits || (reinterpret_cast<uintptr_t>(g->bits) & 3u) != 0) return fail(NRF_EINVAL, "nrf_occupancy: bits is NULL or not 4-byte aligned");
-    for (int k = 0; k < 3; ++k) {
-        if (g->res[k] < 1 || g->res[k] > 512) return fail(NRF_EINVAL, "nrf_occupancy: res must be in 1..512 on every axis");
-        if (!std::isfinite(g->lo[k])) return fail(NRF_EINVAL, "nrf_occupancy: lo must be finite");
-        if (!std::isfinite(g->scale[k]) || !(g->scale[k] > 0.0f)) return fail(NRF_EINVAL, "nrf_occupancy: scale must be finite and > 0");
-    }
-    if (g->res[0] % 32 != 0) return fail(NRF_EINVAL, "nrf_occupancy: res[0] must be a multiple of 32");
+    if (check_occ_box(g->res, g->lo, g->scale) != NRF_OK) return NRF_EINVAL;
     if (n_rays >= (int64_t)1 << 31) return fail(NRF_EINVAL, "a render with a grid runs on the ray queue: launch too large (>= 2^31 rays)");
     return NRF_OK;
 }
@@ -452,6 +458,51 @@ int nrf_occupancy_dilate(const uint32_t* bits_in, const int32_t res[3], uint32_t
     const int r3[3] = {res[0], res[1], res[2]};
     const int r = nrf::launch_occupancy_dilate(bits_in, r3, bits_out, (hipStream_t)stream);
     return r == NRF_OK ? NRF_OK : fail(r, "occupancy_dilate launch failed");
+}
+
+extern "C++" {
+namespace {
+// what the two marking entry points share: everything but the rays (nerfhip.h: nrf_occupancy_mark_rays)
+int mark_any(const char* who, const float* rays_o, const float* rays_d, const nrf::Camera* cam, int64_t ray_begin, int64_t n_rays, int n_samples,
+             const float* z_vals, const float* weights, const int32_t res[3], const float lo[3], const float scale[3], float weight_threshold,
+             float seen_eps, uint32_t* hit_bits, uint32_t* seen_bits, void* stream) {
+    const std::string w(who);
+    if (n_rays < 0) return fail(NRF_EINVAL, w + ": n_rays < 0");
+    if (n_rays >= (int64_t)1 << 31) return fail(NRF_EINVAL, w + ": launch too large (>= 2^31 rays)");
+    if (n_samples < 1) return fail(NRF_EINVAL, w + ": n_samples must be >= 1");
+    if (!res || !lo || !scale) return fail(NRF_EINVAL, w + ": res, lo or scale is NULL");
+    if (check_occ_box(res, lo, scale) != NRF_OK) return NRF_EINVAL;
+    if (!std::isfinite(weight_threshold) || weight_threshold < 0.0f) return fail(NRF_EINVAL, w + ": weight_threshold must be finite and >= 0");
+    if (!(seen_eps >= 0.0f) || seen_eps >= 1.0f) return fail(NRF_EINVAL, w + ": seen_eps must be in [0,1)");
+    if (!hit_bits && !seen_bits) return fail(NRF_EINVAL, w + ": hit_bits and seen_bits are both NULL");
+    if (((reinterpret_cast<uintptr_t>(hit_bits) | reinterpret_cast<uintptr_t>(seen_bits)) & 3u) != 0)
+        return fail(NRF_EINVAL, w + ": hit_bits / seen_bits must be 4-byte aligned");
+    if (!z_vals || !weights) return fail(NRF_EINVAL, w + ": z_vals or weights is NULL");
+    if (!cam && (!rays_o || !rays_d)) return fail(NRF_EINVAL, w + ": null ray pointer");
+    if (n_rays == 0) return NRF_OK;
+    const int r3[3] = {res[0], res[1], res[2]};
+    const int r = nrf::launch_occupancy_mark(rays_o, rays_d, cam, ray_begin, n_rays, n_samples, z_vals, weights, r3, lo, scale, weight_threshold,
+                                             seen_eps, hit_bits, seen_bits, (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "occupancy_mark launch failed");
+}
+}  // namespace
+}  // extern "C++"
+
+int nrf_occupancy_mark_rays(const float* rays_o, const float* rays_d, int64_t n_rays, int n_samples, const float* z_vals, const float* weights,
+                            const int32_t res[3], const float lo[3], const float scale[3], float weight_threshold, float seen_eps,
+                            uint32_t* hit_bits, uint32_t* seen_bits, void* stream) {
+    return mark_any("nrf_occupancy_mark_rays", rays_o, rays_d, nullptr, 0, n_rays, n_samples, z_vals, weights, res, lo, scale, weight_threshold, seen_eps,
+                    hit_bits, seen_bits, stream);
+}
+
+int nrf_occupancy_mark_camera(int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end, int n_samples, const float* z_vals,
+                              const float* weights, const int32_t res[3], const float lo[3], const float scale[3], float weight_threshold,
+                              float seen_eps, uint32_t* hit_bits, uint32_t* seen_bits, void* stream) {
+    if (H < 1 || W < 1 || !(focal > 0.0f) || !c2w) return fail(NRF_EINVAL, "bad camera");
+    if (ray_begin < 0 || ray_end < ray_begin || ray_end > (int64_t)H * W) return fail(NRF_EINVAL, "ray range outside the image");
+    const nrf::Camera cam = make_camera(H, W, focal, c2w);
+    return mark_any("nrf_occupancy_mark_camera", nullptr, nullptr, &cam, ray_begin, ray_end - ray_begin, n_samples, z_vals, weights, res, lo, scale,
+                    weight_threshold, seen_eps, hit_bits, seen_bits, stream);
 }
 
 extern "C++" {

@@ -208,6 +208,10 @@ int launch_sample_pdf(const float* z, const float* w, int64_t n_rays, int S, int
 int launch_occupancy_pack(const float* density, int64_t n_cells, int k, float threshold, uint32_t* bits, hipStream_t s);
 // bits_out = the 3x3x3 dilation of bits_in (cells beyond the box are empty); res[0] a multiple of 32
 int launch_occupancy_dilate(const uint32_t* bits_in, const int res[3], uint32_t* bits_out, hipStream_t s);
+// marks from rendered weights (nerfhip.h: nrf_occupancy_mark_rays): cam == NULL takes rays_o / rays_d, otherwise rays ray_begin .. of the camera
+int launch_occupancy_mark(const float* rays_o, const float* rays_d, const Camera* cam, int64_t ray_begin, int64_t n_rays, int S, const float* z_vals,
+                          const float* weights, const int res[3], const float lo[3], const float scale[3], float weight_threshold, float seen_eps,
+                          uint32_t* hit_bits, uint32_t* seen_bits, hipStream_t s);
 int launch_project_fetch(const DinoDev& d, const float* points, int64_t n, float* feats, float* xy, hipStream_t s);
 int launch_sample_features(const float* features, int Hp, int Wp, int C, const float* points_2d, int64_t n, float* feats, hipStream_t s);
 // adjoints of the two fetches with respect to the map (no atomics: per-slab private copies in `ws`, fetch_backward_ws_floats(...)

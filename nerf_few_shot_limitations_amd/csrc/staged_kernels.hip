@@ -758,7 +758,85 @@ __global__ void __launch_bounds__(kBlock) occupancy_dilate_kernel(const uint32_t
     }
 }
 
+// Marking a grid from rendered weights (nerfhip.h: nrf_occupancy_mark_rays).  One WAVE per ray, LANE <-> sample, 64-sample segments
+// front to back like composite_ray: the rows of weights and z_vals are read as contiguous segments (8 B per sample), the
+// transmittance in front of a sample is 1 - (the wave's exclusive prefix sum of the weights + the carry of the earlier segments).
+// The cell rule is that of fused_impl.hpp:occ_skips, restated here in the same single fp32 operations (sharing it would put this
+// translation unit's needs into the ray-queue kernels' register allocation).  Marks are word-wide atomic ORs, issued only where a
+// plain load of the word shows the bit clear and the lane in front does not set the same bit: OR is order-independent, so the arrays
+// are the same bits from run to run and for any cut of the rays into calls.
+struct MarkGrid { int res[3]; float lo[3], scale[3]; float weight_threshold, seen_eps; };
+
+__device__ __forceinline__ void mark_bit(uint32_t* bits, int idx, bool mark, int lane) {
+    // the lane in front often sits in the same cell (adjacent samples of one ray): one of the two is enough
+    const int idx_up = __shfl_up(mark ? idx : -1, 1, 64);
+    if (mark && !(lane > 0 && idx_up == idx)) {
+        uint32_t* word = bits + (idx >> 5);
+        const uint32_t bit = 1u << (idx & 31);
+        if ((__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) == 0u) atomicOr(word, bit);       // (read where the atomics land)
+    }
+}
+
+template <bool CAMERA>
+__global__ void __launch_bounds__(kBlock) occupancy_mark_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d, const Camera cam,
+                                                                int64_t ray_begin, int64_t n_rays, int S, const float* __restrict__ z_vals,
+                                                                const float* __restrict__ weights, const MarkGrid g, uint32_t* hit_bits,
+                                                                uint32_t* seen_bits) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave0 = (blockIdx.x * (int64_t)kBlock + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * kBlock) >> 6;
+    for (int64_t r = wave0; r < n_rays; r += n_waves) {
+        float o[3], d[3];
+        if constexpr (CAMERA) {
+            camera_ray(cam, ray_begin + r, o, d);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { o[k] = rays_o[r * 3 + k]; d[k] = rays_d[r * 3 + k]; }
+        }
+        float carry = 0.0f;                                  // sum of the weights of the earlier segments
+        for (int s0 = 0; s0 < S; s0 += 64) {
+            const int s = s0 + lane;
+            const bool valid = s < S;
+            const int64_t i = r * S + (valid ? s : S - 1);
+            const float w = valid ? weights[i] : 0.0f;
+            const float z = z_vals[i];
+            const float incl = wave_incl_sum(w, lane);
+            float excl = __shfl_up(incl, 1, 64);
+            if (lane == 0) excl = 0.0f;
+            const float T = __fsub_rn(1.0f, __fadd_rn(carry, excl));           // a NaN in the prefix: no later sample is seen
+            carry = __fadd_rn(carry, __shfl(incl, 63, 64));
+            float t[3];
+            bool inside = valid;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                t[k] = __fmul_rn(__fsub_rn(point_on_ray(o[k], d[k], z), g.lo[k]), g.scale[k]);
+                inside = inside && t[k] >= 0.0f && t[k] < (float)g.res[k];      // (a NaN or an infinity fails one of the comparisons)
+            }
+            const int idx = inside ? ((int)floorf(t[2]) * g.res[1] + (int)floorf(t[1])) * g.res[0] + (int)floorf(t[0]) : 0;   // < 512^3 = 2^27
+            if (hit_bits) mark_bit(hit_bits, idx, inside && !(w <= g.weight_threshold), lane);
+            if (seen_bits) mark_bit(seen_bits, idx, inside && T > g.seen_eps, lane);
+        }
+    }
+}
+
 }  // namespace
+
+int launch_occupancy_mark(const float* rays_o, const float* rays_d, const Camera* cam, int64_t ray_begin, int64_t n_rays, int S, const float* z_vals,
+                          const float* weights, const int res[3], const float lo[3], const float scale[3], float weight_threshold, float seen_eps,
+                          uint32_t* hit_bits, uint32_t* seen_bits, hipStream_t s) {
+    if (n_rays <= 0) return NRF_OK;
+    MarkGrid g;
+    for (int k = 0; k < 3; ++k) { g.res[k] = res[k]; g.lo[k] = lo[k]; g.scale[k] = scale[k]; }
+    g.weight_threshold = weight_threshold; g.seen_eps = seen_eps;
+    const dim3 grid(grid_for(n_rays * 64, kBlock, 16384)), block(kBlock);
+    if (cam)
+        hipLaunchKernelGGL(occupancy_mark_kernel<true>, grid, block, 0, s, nullptr, nullptr, *cam, ray_begin, n_rays, S, z_vals, weights, g, hit_bits,
+                           seen_bits);
+    else
+        hipLaunchKernelGGL(occupancy_mark_kernel<false>, grid, block, 0, s, rays_o, rays_d, Camera{}, (int64_t)0, n_rays, S, z_vals, weights, g, hit_bits,
+                           seen_bits);
+    return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
+}
 
 int launch_occupancy_pack(const float* density, int64_t n_cells, int k, float threshold, uint32_t* bits, hipStream_t s) {
     if (n_cells <= 0) return NRF_OK;

@@ -41,10 +41,33 @@ def main(argv=None):
     ap.add_argument("--occupancy-dilate", type=int, default=1, help="cells the occupied set is grown by")
     ap.add_argument("--occupancy-box", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="the grid's box on every axis (default: -far .. far)")
+    ap.add_argument("--occupancy-prune-views", type=int, default=0, metavar="N",
+                    help="prune the grid by the weights the first N views of the train split render (0 = off; needs --occupancy-res)")
+    ap.add_argument("--occupancy-weight-threshold", type=float, default=None,
+                    help="pruning: a cell stays when a sample of weight above this fell into it (default 0: the marking views render unchanged)")
+    ap.add_argument("--occupancy-seen-eps", type=float, default=None,
+                    help="pruning: a cell counts as seen when a ray reached it with transmittance above this (default 1e-2)")
+    ap.add_argument("--occupancy-unseen", default=None, choices=["keep", "drop"],
+                    help="pruning: cells no marking ray reached keep what the probed grid says (keep, the default) or are emptied (drop)")
     ap.add_argument("--dino-map", default=None)
     ap.add_argument("--dino-weights", default=None, help="local transformers Dinov2Model checkpoint (dir or file) for the extractor of the config")
     ap.add_argument("--dino-random-init", action="store_true", help="build the extractor with random weights (pipeline runs, features meaningless)")
     args = ap.parse_args(argv)
+    pruning = (args.occupancy_prune_views != 0 or args.occupancy_weight_threshold is not None or args.occupancy_seen_eps is not None
+               or args.occupancy_unseen is not None)
+    if pruning and not args.occupancy_res:
+        raise SystemExit("--occupancy-prune-views / --occupancy-weight-threshold / --occupancy-seen-eps / --occupancy-unseen prune the grid "
+                         "of --occupancy-res: pass --occupancy-res N as well")
+    if args.occupancy_prune_views < 0:
+        raise SystemExit("--occupancy-prune-views must be >= 0")
+    if pruning and not args.occupancy_prune_views:
+        raise SystemExit("--occupancy-weight-threshold / --occupancy-seen-eps / --occupancy-unseen set how --occupancy-prune-views N prunes: "
+                         "pass --occupancy-prune-views N (N >= 1) as well")
+    tau, eps = args.occupancy_weight_threshold, args.occupancy_seen_eps
+    if tau is not None and not (0.0 <= tau < float("inf")):
+        raise SystemExit("--occupancy-weight-threshold must be finite and >= 0")
+    if eps is not None and not (0.0 <= eps < 1.0):
+        raise SystemExit("--occupancy-seen-eps must be in [0, 1)")
 
     cfg = load_config(args.config)
     rs = render_settings(cfg)
@@ -52,6 +75,9 @@ def main(argv=None):
     if args.max_views:
         images, poses = images[: args.max_views], poses[: args.max_views]
     use_dino = bool(cfg.get("model", {}).get("use_dino", True))
+    prune_poses = None
+    if args.occupancy_prune_views:
+        prune_poses = load_blender_data(args.data, "train", img_size=cfg["data"].get("resolution"))[1][: args.occupancy_prune_views]
     dino = None
     dino_dim = 128 if cfg.get("model", {}).get("dino_model_type") == "multi_scale" else 64
     if use_dino:
@@ -81,6 +107,15 @@ def main(argv=None):
         lo, hi = args.occupancy_box if args.occupancy_box else (-rs["far"], rs["far"])
         grid = OccupancyGrid.from_model(model, lo, hi, resolution=args.occupancy_res, threshold=args.occupancy_threshold,
                                         samples_per_cell=args.occupancy_samples, dilate=args.occupancy_dilate, mma_mode=args.mode, dino=dino)
+        if prune_poses is not None:
+            # the probed grid is the base: the train views empty the cells they show to be empty, nothing is added
+            prune = {"prune_views": int(prune_poses.shape[0]),
+                     "weight_threshold": 0.0 if args.occupancy_weight_threshold is None else args.occupancy_weight_threshold,
+                     "seen_eps": 1e-2 if args.occupancy_seen_eps is None else args.occupancy_seen_eps,
+                     "unseen": args.occupancy_unseen or "keep", "occupied_fraction_before": grid.occupied_fraction}
+            grid = grid.prune(model, prune_poses, H, W, focal, rs["near"], rs["far"], rs["n_samples"], weight_threshold=prune["weight_threshold"],
+                              seen_eps=prune["seen_eps"], unseen=prune["unseen"], dilate=args.occupancy_dilate, mma_mode=args.mode, dino=dino)
+            prune["occupied_fraction_after"] = grid.occupied_fraction
     res = evaluate_views(model, poses, H, W, focal, rs["near"], rs["far"], rs["n_samples"], targets=targets, out_dir=args.out,
                          white_bkgd=rs["white_bkgd"], mma_mode=args.mode, ert_eps=args.ert, dino=dino, tail_mode=args.tail_mode, occupancy=grid,
                          return_stats=grid is not None)
@@ -92,6 +127,8 @@ def main(argv=None):
         metrics["occupancy"] = {"res": args.occupancy_res, "threshold": args.occupancy_threshold, "samples": args.occupancy_samples,
                                 "dilate": args.occupancy_dilate, "occupied_fraction": grid.occupied_fraction,
                                 "evaluated_share": res["evaluated_share"]}
+        if prune_poses is not None:
+            metrics["occupancy"].update(prune)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         with open(os.path.join(args.out, "metrics.json"), "w") as f:

@@ -4,7 +4,10 @@ An `OccupancyGrid` holds one bit per cell of an axis-aligned box: bit ((iz * ry 
 word, 1 = occupied.  The render entry points that take `occupancy=` (renderer.py, tiles.py) step over every sample whose cell is
 empty; a skipped sample is composited as density 0.  `from_model` builds a grid by probing the network's density at a few points
 per cell (nrf_occupancy_pack) and growing the result by one cell (nrf_occupancy_dilate): it is NOT conservative between the
-probed points, which is why skipping is opt-in.
+probed points, which is why skipping is opt-in.  `from_views` / `prune` build a grid from what the training views render instead
+(nrf_occupancy_mark_camera): a cell stays when a sample of weight > weight_threshold fell into it (hit), or -- by default -- when no
+marking ray reached it with transmittance > seen_eps (not seen: behind a surface or outside every frustum, where a held-out view
+may look).  Grids over the same box combine with `&`, `|` and `~`.
 """
 from __future__ import annotations
 
@@ -65,6 +68,26 @@ class OccupancyGrid:
 
     def to(self, device):
         return OccupancyGrid(self.bits.to(device), self.res, self.lo, self.hi, self.outside)
+
+    # ---- algebra: bitwise operations on the words, on whatever device they live -------------------------
+    def _like(self, bits):
+        return OccupancyGrid(bits, self.res, self.lo, self.hi, self.outside)
+
+    def _same_cells(self, other):
+        if not isinstance(other, OccupancyGrid):
+            raise TypeError("an OccupancyGrid combines with an OccupancyGrid")
+        if (self.res, self.lo, self.hi, self.outside) != (other.res, other.lo, other.hi, other.outside):
+            raise ValueError("grids combine only over the same res, box (lo, hi) and outside")
+        return other.bits.to(self.bits.device)
+
+    def __and__(self, other):
+        return self._like(torch.bitwise_and(self.bits, self._same_cells(other)))
+
+    def __or__(self, other):
+        return self._like(torch.bitwise_or(self.bits, self._same_cells(other)))
+
+    def __invert__(self):
+        return self._like(torch.bitwise_not(self.bits))
 
     # ---- masks ------------------------------------------------------------------------------------
     @classmethod
@@ -180,6 +203,157 @@ class OccupancyGrid:
             model.train(was_training)
         grid = cls(bits, res, lo, hi, outside)
         return grid.dilate(dilate) if dilate else grid
+
+    # ---- building from rendered weights -----------------------------------------------------------
+    def _box_args(self):
+        return (C.c_int32 * 3)(*self.res), (C.c_float * 3)(*self.lo), (C.c_float * 3)(*self.scale)
+
+    @staticmethod
+    def _mark_settings(weight_threshold, seen_eps):
+        tau = float(weight_threshold)
+        if not (np.isfinite(tau) and tau >= 0.0):
+            raise ValueError("weight_threshold must be finite and >= 0")
+        if seen_eps is not None and not (0.0 <= float(seen_eps) < 1.0):
+            raise ValueError("seen_eps must be in [0, 1)")
+        return tau, None if seen_eps is None else float(seen_eps)
+
+    def _mark_words(self, words, what):
+        """The word array a mark call ORs into: the caller's (checked) or a zeroed one on the grid's device."""
+        if words is None:
+            return torch.zeros_like(self.bits)
+        if not (isinstance(words, torch.Tensor) and words.dtype == torch.int32 and words.is_contiguous() and words.device == self.bits.device
+                and words.numel() == self.bits.numel()):
+            raise ValueError(f"{what} must be a contiguous int32 tensor of rx*ry*rz/32 words on the grid's device")
+        return words
+
+    def mark(self, rays_o, rays_d, z_vals, weights, weight_threshold=0.0, seen_eps=None, hit=None, seen=None):
+        """Mark this grid's cells from a render's per-sample outputs (nrf_occupancy_mark_rays): rays_o / rays_d (R,3), z_vals and
+        weights (R,S) as render_rays(return_z=True) returns them.  Returns (hit, seen), int32 word tensors in the layout of `bits`:
+        hit -- a sample with !(weight <= weight_threshold) fell into the cell; seen -- a sample fell into it while its ray still had
+        transmittance 1 - sum(earlier weights) > seen_eps (seen_eps=None: not computed, `seen` is returned as it came).  hit= / seen=
+        are accumulated into (OR); the grid's own bits play no part."""
+        L.require_gpu()
+        if not self.bits.is_cuda:
+            raise ValueError("mark runs on the GPU: move the grid there first (grid.to(device))")
+        tau, eps = self._mark_settings(weight_threshold, seen_eps)
+        dev = self.bits.device
+        w = L.dev_f32(weights, dev)
+        z = L.dev_f32(z_vals, dev)
+        if w.dim() != 2 or z.shape != w.shape or w.shape[1] < 1:
+            raise ValueError("weights and z_vals must both be (R, S) with S >= 1")
+        o, d = L.dev_f32(rays_o, dev).reshape(-1, 3), L.dev_f32(rays_d, dev).reshape(-1, 3)
+        if o.shape[0] != w.shape[0] or d.shape[0] != w.shape[0]:
+            raise ValueError("rays_o and rays_d must be (R, 3) for weights (R, S)")
+        hit = self._mark_words(hit, "hit")
+        if eps is not None:
+            seen = self._mark_words(seen, "seen")
+        res, lo, scale = self._box_args()
+        with torch.cuda.device(dev):
+            L.check(L.lib().nrf_occupancy_mark_rays(L.ptr(o), L.ptr(d), w.shape[0], w.shape[1], L.ptr(z), L.ptr(w), res, lo, scale, tau,
+                                                    eps if eps is not None else 0.0, hit.data_ptr(), seen.data_ptr() if eps is not None else None,
+                                                    L.stream_ptr()))
+        return hit, seen
+
+    def _view_marks(self, model, poses, H, W, focal, near, far, n_samples, weight_threshold=0.0, seen_eps=1e-2, base=None, mma_mode=None,
+                   dino=None, lindisp=False, chunk_rays=1 << 16):
+        """(hit, seen) word tensors of this grid's cells over the views `poses` ((n,4,4) or one (4,4) camera-to-world): every view is
+        rendered through the camera route in ray ranges of `chunk_rays` -- unjittered, ert_eps = 0, in `mma_mode`, under
+        occupancy=base when a base grid is given -- with weights and z_vals requested, and each range is marked by
+        nrf_occupancy_mark_camera.  seen_eps=None: seen is not computed (None)."""
+        from .ray_sampler import _c2w12
+        from .renderer import _handle, _opts, make_dino
+        L.require_gpu()
+        if not self.bits.is_cuda:
+            raise ValueError("marking runs on the GPU: move the grid there first (grid.to(device))")
+        tau, eps = self._mark_settings(weight_threshold, seen_eps)
+        if model.net == L.NRF_NET_V3 and dino is None:
+            raise ValueError("a use_dino model's weights depend on the source view: marking needs dino=dict(features=, pose=, focal=, H=, W=)")
+        poses = torch.as_tensor(poses).detach().to("cpu", torch.float32)
+        poses = poses.reshape(1, *poses.shape) if poses.dim() == 2 else poses
+        H, W, S = int(H), int(W), int(n_samples)
+        chunk = max(1, min(int(chunk_rays), H * W))
+        dev = self.bits.device
+        mode = mma_mode or model.mma_mode
+        hit = torch.zeros_like(self.bits)
+        seen = torch.zeros_like(self.bits) if eps is not None else None
+        res, lo, scale = self._box_args()
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad(), torch.cuda.device(dev):
+                dn, keep = make_dino(**dino) if model.net == L.NRF_NET_V3 else (None, None)
+                opts = _opts(near, far, S, False, None, None, lindisp, 0.0, False, mode, dn, dev)
+                h = _handle(model, dev, mode, None)
+                occ, occ_keep = base.struct(dev) if base is not None else (None, None)
+                rgb = torch.empty((chunk, 3), dtype=torch.float32, device=dev)
+                depth = torch.empty((chunk,), dtype=torch.float32, device=dev)
+                w = torch.empty((chunk, S), dtype=torch.float32, device=dev)
+                z = torch.empty((chunk, S), dtype=torch.float32, device=dev)
+                for pose in poses:
+                    c2w = _c2w12(pose)
+                    for a in range(0, H * W, chunk):
+                        b = min(a + chunk, H * W)
+                        if occ is not None:
+                            L.check(L.lib().nrf_render_camera_occ(h, H, W, float(focal), c2w, a, b, C.byref(opts), C.byref(occ), L.ptr(rgb),
+                                                                  L.ptr(depth), L.ptr(w), L.ptr(z), L.stream_ptr()))
+                        else:
+                            L.check(L.lib().nrf_render_camera(h, H, W, float(focal), c2w, a, b, C.byref(opts), L.ptr(rgb), L.ptr(depth), L.ptr(w),
+                                                              L.ptr(z), L.stream_ptr()))
+                        L.check(L.lib().nrf_occupancy_mark_camera(H, W, float(focal), c2w, a, b, S, L.ptr(z), L.ptr(w), res, lo, scale, tau,
+                                                                  eps if eps is not None else 0.0, hit.data_ptr(),
+                                                                  seen.data_ptr() if seen is not None else None, L.stream_ptr()))
+                del keep, occ_keep
+        finally:
+            model.train(was_training)
+        return hit, seen
+
+    @classmethod
+    def from_views(cls, model, poses, H, W, focal, near, far, n_samples, lo, hi, resolution=128, weight_threshold=0.0, seen_eps=1e-2,
+                   unseen="keep", base=None, dilate=1, mma_mode=None, dino=None, lindisp=False, chunk_rays=1 << 16, outside=0):
+        """A grid pruned by the weights the views `poses` render (_view_marks):
+
+            (dilate^n(hit) | (~seen if unseen == "keep" else 0)) & (base or all-ones)
+
+        hit: a sample of weight > weight_threshold fell into the cell; seen: a sample fell into it while its ray still had
+        transmittance > seen_eps.  unseen="keep" (the default) leaves the cells no marking ray reached -- behind an opaque surface,
+        outside every frustum -- to the base grid, "drop" empties them.  With weight_threshold = 0 and dilate = 0 a render of the
+        marking views' own rays at the same n_samples is the plain render bit for bit; a larger weight_threshold trades image for
+        time: a dropped sample contributed at most weight_threshold of a colour to its pixel.  base: a grid over the same cells (for
+        instance from_model's), applied while the views are rendered and to the result.  A V3 grid belongs to ONE source view:
+        dino=dict(features=, pose=, focal=, H=, W=) is required."""
+        if unseen not in ("keep", "drop"):
+            raise ValueError('unseen must be "keep" or "drop"')
+        cls._mark_settings(weight_threshold, seen_eps)
+        if seen_eps is None and unseen == "keep":
+            raise ValueError('unseen="keep" needs a seen_eps')
+        res = tuple(int(r) for r in (resolution if hasattr(resolution, "__len__") else (resolution,) * 3))
+        probe = cls(torch.zeros((res[0] * res[1] * res[2] // 32,), dtype=torch.int32), res, lo, hi, outside)        # validates res / box
+        if base is not None:
+            probe._same_cells(base)
+        if model.net == L.NRF_NET_V3 and dino is None:
+            raise ValueError("a use_dino model's weights depend on the source view: from_views needs dino=dict(features=, pose=, focal=, H=, W=)")
+        L.require_gpu()
+        if base is not None and base.bits.is_cuda:
+            device = base.bits.device
+        else:
+            p = next(model.parameters())
+            device = p.device if p.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        probe = probe.to(device)
+        hit, seen = probe._view_marks(model, poses, H, W, focal, near, far, n_samples, weight_threshold=weight_threshold,
+                                     seen_eps=seen_eps if unseen == "keep" else None, base=base, mma_mode=mma_mode, dino=dino, lindisp=lindisp,
+                                     chunk_rays=chunk_rays)
+        grid = probe._like(hit)
+        if dilate:
+            grid = grid.dilate(dilate)
+        if unseen == "keep":
+            grid = grid | ~probe._like(seen)
+        return grid & base if base is not None else grid
+
+    def prune(self, model, poses, H, W, focal, near, far, n_samples, **kw):
+        """from_views(..., base=self) on this grid's own box, resolution and `outside`: the grid with the cells emptied that the
+        views `poses` show to be empty."""
+        return OccupancyGrid.from_views(model, poses, H, W, focal, near, far, n_samples, self.lo, self.hi, resolution=self.res, base=self,
+                                        outside=self.outside, **kw)
 
     # ---- the C struct -----------------------------------------------------------------------------
     def struct(self, device, stats=None):

@@ -3,6 +3,7 @@ numbers quoted in DESIGN.md sections 3.1 / 7 and kept under profiles/.  Needs th
 
     python tools/bench_occupancy.py --cost    > profiles/occupancy_frame_time.txt
     python tools/bench_occupancy.py --fields  > profiles/occupancy_trained_fields.txt
+    python tools/bench_occupancy.py --pruned  > profiles/occupancy_pruned_fields.txt
 
 --cost  : 800 x 800 x 64, f16.  The arms of a row alternate frame by frame in one process after a warm-up, HIP events around a frame.
           a) nothing skipped: V1 / V2 / V3 "solid" with an all-ones grid against the plain render_kernel and the plain ray-queue
@@ -13,6 +14,11 @@ numbers quoted in DESIGN.md sections 3.1 / 7 and kept under profiles/.  Needs th
           800 x 800 x 64 with and without a from_model grid, evaluated share stats[0] / (R S), column utilisation
           stats[0] / (stats[1] x columns per wave), and what the grid costs in image quality on the scene's test views at the
           training resolution -- max |rgb - rgb(no grid)| and the PSNR difference against the ground truth -- at dilate 1 and 0.
+--pruned: the same two fields with the from_model grid (dilate 1) pruned by the weights their own training views render
+          (OccupancyGrid.prune: weight_threshold x unseen, seen_eps 1e-2, dilate 1): occupied cells, evaluated share and column
+          utilisation at 800 x 800 x 64, frame time against the plain ray-queue kernel, the from_model grid and render_kernel (four
+          arms alternating), and PSNR difference / max |rgb - rgb(no grid)| at the training resolution, on the training views and on
+          the held-out test views separately; the build time per view; the marker kernel's own time on one 800 x 800 x 64 frame.
 """
 import argparse
 import os
@@ -154,10 +160,116 @@ def fields_report(frames, warmup, epochs, mode="f16"):
                           f"{share:.4f}, utilisation {util:.4f}", flush=True)
 
 
+def marker_time(model, H, S, focal, pose, mode, grid, frames, warmup):
+    """ms of nrf_occupancy_mark_camera alone on one H x H x S frame of `model`: into zeroed arrays (every first mark is an atomic) and
+    into arrays that already hold the frame's marks (no atomic left)."""
+    import ctypes as C
+    from nerf_few_shot_limitations_amd import _lib as L
+    from nerf_few_shot_limitations_amd.ray_sampler import _c2w12
+    ro, rd = N.get_rays(H, H, focal, pose)
+    r = N.render_rays(model, ro.reshape(-1, 3), rd.reshape(-1, 3), 2.0, 6.0, S, mma_mode=mode, return_z=True)
+    w, z = r["weights"], r["z_vals"]
+    del ro, rd
+    res, lo, scale = (C.c_int32 * 3)(*grid.res), (C.c_float * 3)(*grid.lo), (C.c_float * 3)(*grid.scale)
+    c2w = _c2w12(pose)
+    hit, seen = torch.zeros_like(grid.bits), torch.zeros_like(grid.bits)
+
+    def mark():
+        L.check(L.lib().nrf_occupancy_mark_camera(H, H, float(focal), c2w, 0, H * H, S, L.ptr(z), L.ptr(w), res, lo, scale, 0.0, 1e-2,
+                                                  hit.data_ptr(), seen.data_ptr(), L.stream_ptr()))
+
+    def fresh():
+        hit.zero_(); seen.zero_()
+        torch.cuda.synchronize()
+
+    cold, warm = [], []
+    for i in range(warmup + frames):
+        for times, prepare in ((cold, fresh), (warm, lambda: None)):
+            prepare()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            mark()
+            e1.record()
+            e1.synchronize()
+            if i >= warmup:
+                times.append(e0.elapsed_time(e1))
+    return np.array(cold), np.array(warm), H * H * S * 8
+
+
+def pruned_report(frames, warmup, epochs, mode="f16"):
+    import synthetic_scene
+    import trained_scene
+    size, views, S, big = 128, 8, 64, 800
+    print(f"fields fitted by tools/trained_scene.py ({epochs} epochs, {views} views of {size} px, trained in bf16), rendered in {mode}.  base grid: from_model, "
+          f"128^3 over [-4, 4]^3, threshold 0, 4 probes per cell, dilate 1.  pruned grid: base.prune over the {views} training views at {size} px x {S} samples, "
+          "seen_eps 1e-2, dilate 1.")
+    print(f"frame time: {big}x{big}x{S}, test pose 0; the four arms of a row (render_kernel, plain ray queue at ert_eps 1e-30, base grid, pruned grid) alternate "
+          f"frame by frame in one process, {frames} frames each after {warmup} warm-up frames, HIP events around a frame on the launch stream; ms = median [min .. max].")
+    print(f"image: all {views} training views / all held-out test views at {size} px against the render without a grid; d psnr = PSNR(grid) - PSNR(no grid) "
+          "against the ground truth; the 0.01 dB bar of BASELINE.json is |d psnr| <= 0.01.")
+    with tempfile.TemporaryDirectory() as tmp:
+        scene = os.path.join(tmp, "scene")
+        synthetic_scene.write_scene(scene, size=size, n_train=views, n_test=4)
+        split = {}
+        for name in ("train", "test"):
+            images, poses, (H, W, focal) = N.load_blender_data(scene, name, img_size=size)
+            split[name] = (images.permute(0, 2, 3, 1).contiguous().cuda(), poses)
+        tr_poses, te_poses = split["train"][1], split["test"][1]
+        fb = focal * big / W
+        rgb = torch.empty((big * big, 3), device="cuda"); depth = torch.empty((big * big,), device="cuda")
+        for net in ("v1", "v2"):
+            model, info, _ = trained_scene.train_field(net, trained_scene.config(size, views, epochs), scene, "bf16", 0, epoch_scale=epochs / 200.0, sigma_bias=0.5)
+            print(f"{net}: loss {info['loss_first_epoch']} -> {info['loss_last_epoch']}")
+            with torch.no_grad():
+                ref = {}
+                for name, (gt, poses) in split.items():
+                    im = N.evaluate_views(model, poses, H, W, focal, 2.0, 6.0, S, mma_mode=mode)["images"]
+                    ref[name] = (im, N.psnr(im, gt))
+                base = N.OccupancyGrid.from_model(model, -4.0, 4.0, resolution=128, dilate=1, mma_mode=mode)
+
+                def frame(**kw):
+                    return lambda: N.render_camera(model, big, big, fb, te_poses[0], 2.0, 6.0, S, mma_mode=mode, out_rgb=rgb, out_depth=depth, **kw)
+
+                def image(grid):
+                    out = []
+                    for name, (gt, poses) in split.items():
+                        r = N.evaluate_views(model, poses, H, W, focal, 2.0, 6.0, S, mma_mode=mode, occupancy=grid)
+                        d = N.psnr(r["images"], gt) - ref[name][1]
+                        out.append(f"{name} views: d psnr {d:+.5f} dB ({'met' if abs(d) <= 0.01 else 'NOT met'}), max |d rgb| "
+                                   f"{float((r['images'] - ref[name][0]).abs().max()):.3e}")
+                    return "; ".join(out)
+
+                share, util = stats_of(model, big, big, fb, te_poses[0], S, mode, base)
+                print(f"  {net} base grid: occupied cells {base.occupied_fraction:.4f}, evaluated share {share:.4f}, utilisation {util:.4f}; {image(base)}")
+                for tau in (0.0, 1e-4, 1e-3, 1e-2):
+                    for unseen in ("keep", "drop"):
+                        cfg = dict(weight_threshold=tau, seen_eps=1e-2, unseen=unseen, dilate=1, mma_mode=mode)
+                        for _ in range(2):                                     # wall clock around a synchronised build, second of two
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            grid = base.prune(model, tr_poses, H, W, focal, 2.0, 6.0, S, **cfg)
+                            torch.cuda.synchronize()
+                            build_ms = (time.perf_counter() - t0) * 1e3
+                        t = alternate({"plain": frame(), "queue": frame(ert_eps=1e-30), "base": frame(occupancy=base), "pruned": frame(occupancy=grid)},
+                                      frames, warmup)
+                        share, util = stats_of(model, big, big, fb, te_poses[0], S, mode, grid)
+                        med = {k: np.median(v) for k, v in t.items()}
+                        print(f"  {net} tau {tau:g} unseen {unseen}: occupied cells {grid.occupied_fraction:.4f}, evaluated share {share:.4f}, utilisation {util:.4f}; "
+                              f"pruned {fmt(t['pruned'])} ms, base grid {fmt(t['base'])} ms, plain queue {fmt(t['queue'])} ms, render_kernel {fmt(t['plain'])} ms; "
+                              f"pruned / queue {med['pruned'] / med['queue']:.4f}, pruned / base {med['pruned'] / med['base']:.4f}, pruned / render_kernel "
+                              f"{med['pruned'] / med['plain']:.4f}; {image(grid)}; build {build_ms:.1f} ms = {build_ms / views:.2f} ms per view", flush=True)
+                cold, warm, nbytes = marker_time(model, big, S, fb, te_poses[0], mode, base, frames, warmup)
+                print(f"  {net} marker kernel alone, one {big}x{big}x{S} frame, camera rays, hit and seen, {nbytes / 1e6:.1f} MB read (8 B per sample, no ray bytes): "
+                      f"into zeroed arrays {fmt(cold)} ms = {nbytes / np.median(cold) / 1e9:.3f} TB/s; into arrays that hold the marks {fmt(warm)} ms = "
+                      f"{nbytes / np.median(warm) / 1e9:.3f} TB/s (composite_kernel, the comparable wave-per-ray row kernel: 2.9 TB/s, "
+                      "profiles/r01_staged_kernels_bandwidth.txt)", flush=True)
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--cost", action="store_true")
     ap.add_argument("--fields", action="store_true")
+    ap.add_argument("--pruned", action="store_true")
     ap.add_argument("--frames", type=int, default=12)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--epochs", type=int, default=200)
@@ -168,3 +280,5 @@ if __name__ == "__main__":
         cost_report(a.frames, a.warmup)
     if a.fields:
         fields_report(a.frames, a.warmup, a.epochs)
+    if a.pruned:
+        pruned_report(a.frames, a.warmup, a.epochs)
