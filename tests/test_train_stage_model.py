@@ -71,14 +71,7 @@ def test_the_reference_alone_keeps_half_of_the_caps(variant, dino_dim, depth, n,
 # ---------------------------------------------------------------------------------------------
 # deliberately wrong models
 # ---------------------------------------------------------------------------------------------
-def truncate(t, mode):
-    """Round toward zero to the operand type (a normal-range value: clear the dropped mantissa bits)."""
-    drop = 16 if mode == "bf16" else 13
-    return (t.contiguous().view(torch.int32) & ~((1 << drop) - 1)).view(torch.float32)
-
-
-def fault(kind, name, fn):
-    return lambda k, nm, t: fn(t) if (k, nm) == (kind, name) else t
+truncate, fault = T.truncate, T.fault          # the planted-fault helpers, shared with tests/test_render_link_host.py
 
 
 def swap_k(w):

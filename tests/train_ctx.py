@@ -246,6 +246,19 @@ def failed(findings):
 
 
 # ---------------------------------------------------------------------------------------------
+# planted faults: taps for oracle.train_stages (tests/test_train_stage_model.py, tests/test_render_link_host.py)
+# ---------------------------------------------------------------------------------------------
+def truncate(t, mode):
+    """Round toward zero to the operand type (a normal-range value: clear the dropped mantissa bits)."""
+    drop = 16 if mode == "bf16" else 13
+    return (t.contiguous().view(torch.int32) & ~((1 << drop) - 1)).view(torch.float32)
+
+
+def fault(kind, name, fn):
+    return lambda k, nm, t: fn(t) if (k, nm) == (kind, name) else t
+
+
+# ---------------------------------------------------------------------------------------------
 # the committed cases of the stage tests: weights and inputs, from counter-based hashes (no torch RNG)
 # ---------------------------------------------------------------------------------------------
 FAMILIES = [("v2", 0), ("v3", 64), ("v3", 128)]                 # (family, dino_dim)
