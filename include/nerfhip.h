@@ -353,6 +353,13 @@ int nrf_debug_train_plan(const nrf_arch* arch, const nrf_linear* linears, int n_
  * dino_fusion.fusion.0 (lora_dino.py:156) transposed: dino_dim/32 output tiles x 8 K tiles, fragment order (m, t, s). */
 int nrf_debug_pack_dino_grad(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int mma_mode,
                              uint8_t* stream_out, int64_t stream_cap, int64_t* stream_bytes);
+/* NRF_NET_V1 / V2, host-only: the fragment stream of nrf_mlp_backward_inputs' A operands, every layer from a 16-fragment boundary.
+ * Layer 0: W0^T of the first Linear restricted to the positional-encoding tiles, pe_tiles(pos_freq) output tiles x 8 K tiles in
+ * (m, t, s) order; accumulator register r of lane half h in output tile m belongs to feature (slot 16m + r, half h) of the kernel
+ * order (slot u < 3L: sin | cos of (f = u/3, c = u%3); u = 3L: x | z; u = 3L+1: y | unused).  Layer 1 (V2): color_layers.0^T
+ * restricted to the direction-encoding tile, 1 output tile x 4 K tiles. */
+int nrf_debug_pack_input_grad(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int mma_mode,
+                              uint8_t* stream_out, int64_t stream_cap, int64_t* stream_bytes);
 
 /* Host-only: how render_kernel / render_hold_kernel deal a launch of n_rays rays x n_samples samples to the workgroups of a device
  * with n_cu compute units, for a geometry of cols_per_wave sample columns per wave (64: NRF_MMA_BF16 / F16, 32: the fp32-class modes).
@@ -417,8 +424,8 @@ int nrf_mlp_backward_v1(nrf_model* m, int mma_mode, const float* out4, const flo
 
 /* The same pair for NRF_NET_V2 (train.py:229 `rgb, density = self.nerf_model(positions, directions, None)` with grad
  * enabled; nerf_mlp.py:134-158 without the DINO branch).  rgb (n,3) / density (n,1) are written by the forward and
- * read again by the backward (sigmoid', relu'); g_rgb / g_density are dL/d of them.  No gradient with respect to
- * positions, directions or the DINO features.  NRF_NET_V3 (nerf_mlp.py:134-158 with lora_dino.py:171-193: the fusion
+ * read again by the backward (sigmoid', relu'); g_rgb / g_density are dL/d of them.  These calls produce no gradient with respect to
+ * positions, directions or the DINO features (one more launch does: nrf_mlp_backward_inputs, nrf_mlp_backward_dino).  NRF_NET_V3 (nerf_mlp.py:134-158 with lora_dino.py:171-193: the fusion
  * block runs twice on the same weights, gated by a 2-way softmax) takes the per-sample features as `dino`; up to 8 trunk
  * layers. */
 int nrf_mlp_forward_train(nrf_model* m, int mma_mode, const float* positions, const float* directions,
@@ -434,6 +441,22 @@ int nrf_mlp_backward(nrf_model* m, int mma_mode, const float* rgb, const float* 
  * (16-byte aligned).  NRF_EINVAL for another network family, a context that is too small or stale backward weights. */
 int nrf_mlp_backward_dino(nrf_model* m, int mma_mode, int64_t n, void* ctx, int64_t ctx_bytes, float* d_dino, void* stream);
 
+/* NRF_NET_V1 / V2, after nrf_mlp_backward_v1 / nrf_mlp_backward on the same ctx (same n and mode): the gradient with respect to
+ * the inputs of the field, from the dZ tiles of the first Linear (and, V2, of color_layers.0) that the backward saved.  One more
+ * launch; nrf_train_context_bytes does not change.  Any output may be NULL (not computed), not all of them:
+ *   d_x_enc      (n, pe_dim)  V1 only: dL/d x_enc in the reference's column order (positional_encoding.py:27-33);
+ *   d_positions  (n,3)        dL/d positions through the adjoint of the encoding; reads `positions` (n,3), the points the forward
+ *                             encoded (V1: the points x_enc was computed from);
+ *   d_directions (n,3)        V2 only: the same for the view directions; reads `directions` (n,3).
+ * Rows >= n are not written; the outputs are overwritten.  A sample's result does not depend on the batch around it and two runs
+ * give the same bits.  NRF_EINVAL before any launch for NRF_NET_V3 (it also needs the adjoint of the projection and bilinear
+ * fetch with respect to the points), d_x_enc on another family than V1, d_directions on V1, a missing positions / directions
+ * where its derivative is asked for, no output at all, a pointer that is not 4-byte aligned, a context that is too small, or
+ * stale backward weights (nrf_model_update_device).  n == 0 is NRF_OK and launches nothing. */
+int nrf_mlp_backward_inputs(nrf_model* m, int mma_mode, int64_t n, void* ctx, int64_t ctx_bytes,
+                            const float* positions, const float* directions,
+                            float* d_x_enc, float* d_positions, float* d_directions, void* stream);
+
 /* Backward of nrf_composite (autograd through nerf_mlp.py:181-212): given
  * dL/d rgb_map (n_rays,3), optionally dL/d depth (n_rays) and dL/d weights
  * (n_rays,S), writes dL/d rgb (strided like the inputs) and dL/d sigma. */
@@ -441,6 +464,22 @@ int nrf_composite_backward(const float* rgb, int rgb_stride, const float* sigma,
                            const float* z_vals, const float* rays_d, int64_t n_rays, int n_samples, int white_bkgd,
                            const float* g_rgb, const float* g_depth, const float* g_weights,
                            float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, void* stream);
+/* The same, and the geometric terms of that autograd: d_z (n_rays,S) = dL/d z_vals (through the interval lengths and the depth
+ * map) and d_rays_d (n_rays,3) = dL/d rays_d through |rays_d| (nerf_mlp.py:185).  Both required.  d_rgb / d_sigma are
+ * nrf_composite_backward's bits. */
+int nrf_composite_backward_geom(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride,
+                                const float* z_vals, const float* rays_d, int64_t n_rays, int n_samples, int white_bkgd,
+                                const float* g_rgb, const float* g_depth, const float* g_weights,
+                                float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride,
+                                float* d_z, float* d_rays_d, void* stream);
+/* Adjoint of pts = rays_o + rays_d * z (nrf_sample_along_rays) and of the expansion of rays_d over a ray's samples:
+ *   d_rays_o (R,3) = sum_s d_points;   d_rays_d (R,3) = sum_s (z_s d_points + d_dirs) + d_rays_d_in;
+ *   d_z_out (R,S)  = rays_d . d_points + d_z_in.
+ * d_points (R*S,3), z_vals (R,S), rays_d (R,3) are required; d_dirs (R*S,3), d_z_in (R,S), d_rays_d_in (R,3) may be NULL (zero);
+ * any output may be NULL, not all.  Sums in a fixed order, no atomics: two runs give the same bits.  n_rays == 0 is NRF_OK. */
+int nrf_ray_grad(const float* d_points, const float* d_dirs, const float* z_vals, const float* rays_d,
+                 const float* d_z_in, const float* d_rays_d_in, int64_t n_rays, int n_samples,
+                 float* d_rays_o, float* d_rays_d, float* d_z_out, void* stream);
 
 /* `rgb_weight * nn.MSELoss()(pred, target)` (train.py:36-44) and its gradient in one launch: loss[0] = weight * mean((pred -
  * target)^2) over n values, g_pred = d loss / d pred.  n <= 2^22 (ray batches). */

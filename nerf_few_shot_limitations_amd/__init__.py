@@ -8,7 +8,7 @@ contain '-'.)
 """
 from .ray_sampler import get_rays, sample_points_along_rays, hierarchical_sampling, sample_pdf, get_ray_batch
 from .positional_encoding import PositionalEncoding
-from .nerf_model import NeRFMLP, load_checkpoint_into
+from .nerf_model import NeRFMLP, density_normals, load_checkpoint_into
 from .volume_renderer import VolumeRenderer, volume_render_radiance
 from .renderer import render_rays, render_camera, render_hierarchical, NeRFRenderer, make_dino
 from .occupancy import OccupancyGrid
@@ -21,7 +21,7 @@ from .dino_feature_model import LoRALinear, SpatialDINOFeatures, MultiScaleDINOF
 from .dino_backbone import Dinov2Backbone, build_backbone, load_backbone_weights
 
 __all__ = ["get_rays", "sample_points_along_rays", "hierarchical_sampling", "sample_pdf", "get_ray_batch",
-           "PositionalEncoding", "NeRFMLP", "load_checkpoint_into", "VolumeRenderer", "volume_render_radiance",
+           "PositionalEncoding", "NeRFMLP", "density_normals", "load_checkpoint_into", "VolumeRenderer", "volume_render_radiance",
            "render_rays", "render_camera", "render_hierarchical", "NeRFRenderer", "make_dino", "OccupancyGrid",
            "load_config", "resolve_near_far", "model_from_config", "render_settings",
            "load_blender_data", "psnr", "ssim", "save_png", "evaluate_views", "evaluate_config",

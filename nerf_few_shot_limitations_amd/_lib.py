@@ -154,6 +154,15 @@ SIGNATURES = {
     "nrf_sample_features_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                C.c_int64, C.c_void_p]),
     "nrf_mlp_backward_dino": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    # input gradient (train_input_grad_impl.hpp, staged_kernels.hip: GEOM compositor backward, ray_grad_kernel)
+    "nrf_mlp_backward_inputs": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "nrf_composite_backward_geom": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    "nrf_ray_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p]),
+    "nrf_debug_pack_input_grad": (C.c_int, [C.POINTER(nrf_arch), C.POINTER(nrf_linear), C.c_int, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     # training path
     "nrf_param_count": (C.c_int64, [C.c_void_p]),
     "nrf_model_update_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
@@ -241,8 +250,8 @@ def dev_f32(t, device=None):
 
 
 def refuse_grad(t, what):
-    """The staged leaf kernels produce no gradient with respect to their inputs (the reference never needs one: positions,
-    directions, rays and depths are data).  Under grad mode a tensor that requires grad is refused -- as NeRFMLP.forward refuses
+    """By default the staged leaf kernels produce no gradient with respect to their inputs (the reference never needs one: positions,
+    directions, rays and depths are data; the opt-in switches are NeRFMLP(input_grad=True), ray_grad=, geom_grad=, pose_grad=).  Under grad mode a tensor that requires grad is refused -- as NeRFMLP.forward refuses
     DINO features that require grad -- instead of being detached silently."""
     if torch.is_grad_enabled() and isinstance(t, torch.Tensor) and t.requires_grad:
         raise NotImplementedError(f"{what}: no gradient with respect to this input is produced; pass it detached or call under torch.no_grad()")

@@ -104,6 +104,7 @@ struct nrf_model {
     nrf::ParamLayout layout;
     nrf::NetPlan bplan;                     // the dZ chain's layers, and behind them (V3) the feature-gradient kernel's W0d^T layer:
     int g_frags16 = 0;                      // one device stream, one gather table, one re-pack, one freshness flag; 16-bit fragments of that layer
+    int i_frags16[2] = {0, 0};              // V1 / V2: the same for input_grad_kernel's W0^T and (V2) color_layers.0^T layers
     nrf::TrainPlan tplan;
     nrf::TrainDev train{};
     void* d_bstream[3] = {nullptr, nullptr, nullptr};
@@ -179,6 +180,14 @@ int ensure_train(nrf_model* m) {
         if (!nrf::make_dino_grad_plan(m->arch, m->lin, gplan, err)) return fail(NRF_EUNSUPPORTED, err);
         m->g_frags16 = gplan.layers[0].MT * gplan.layers[0].KT * 2;
         m->bplan.layers.push_back(gplan.layers[0]);
+    } else {
+        // W0^T and color_layers.0^T restricted to the encodings (train_input_grad_impl.hpp) ride there in the same way
+        nrf::NetPlan iplan;
+        if (!nrf::make_input_grad_plan(m->arch, m->lin, iplan, err)) return fail(NRF_EUNSUPPORTED, err);
+        for (size_t i = 0; i < iplan.layers.size() && i < 2; ++i) {
+            m->i_frags16[i] = iplan.layers[i].MT * iplan.layers[i].KT * 2;
+            m->bplan.layers.push_back(iplan.layers[i]);
+        }
     }
     for (int mode = 0; mode < 3; ++mode) {
         const nrf::PackedStream ps = nrf::pack_stream(m->bplan, m->lin, mode);
@@ -186,9 +195,12 @@ int ensure_train(nrf_model* m) {
         NRF_HIP(hipMemcpy(m->d_bstream[mode], ps.bytes.data(), ps.bytes.size(), hipMemcpyHostToDevice));
         // the layer is whole chunks: 16 fragments per chunk, DT * 16 (16-bit) or DT * 32 (fp32) fragments
         const uint32_t g_chunks = (uint32_t)(m->g_frags16 * (mode == NRF_MMA_F32 ? 2 : 1) / 16);
+        uint32_t i_chunks = 0;                  // every layer starts on a chunk boundary (packing.cpp:stream_sources)
+        for (int i = 0; i < 2; ++i) i_chunks += (uint32_t)((m->i_frags16[i] * (mode == NRF_MMA_F32 ? 2 : 1) + 15) / 16);
         m->train.bstream[mode] = m->d_bstream[mode];
-        m->train.n_bchunks[mode] = ps.n_chunks - g_chunks;
+        m->train.n_bchunks[mode] = ps.n_chunks - g_chunks - i_chunks;
         m->train.gstream[mode] = g_chunks ? static_cast<const char*>(m->d_bstream[mode]) + (size_t)m->train.n_bchunks[mode] * 16 * 1024 : nullptr;
+        m->train.istream[mode] = i_chunks ? static_cast<const char*>(m->d_bstream[mode]) + (size_t)m->train.n_bchunks[mode] * 16 * 1024 : nullptr;
         m->bfresh[mode] = !m->lin_stale;
     }
     for (int f32 = 0; f32 < 2; ++f32) {
@@ -777,6 +789,28 @@ int nrf_mlp_backward_dino(nrf_model* m, int mma_mode, int64_t n, void* ctx, int6
     });
 }
 
+int nrf_mlp_backward_inputs(nrf_model* m, int mma_mode, int64_t n, void* ctx, int64_t ctx_bytes, const float* positions, const float* directions,
+                            float* d_x_enc, float* d_positions, float* d_directions, void* stream) {
+    auto wrong = [&]() -> const char* {
+        if (m->arch.net == NRF_NET_V3)
+            return "nrf_mlp_backward_inputs: the V3 network also needs the adjoint of the projection and the bilinear fetch with respect to the points";
+        if (m->arch.net != NRF_NET_V1 && m->arch.net != NRF_NET_V2) return "nrf_mlp_backward_inputs: unknown network family";
+        if (!d_x_enc && !d_positions && !d_directions) return "nrf_mlp_backward_inputs: no output asked for";
+        if (d_x_enc && m->arch.net != NRF_NET_V1) return "nrf_mlp_backward_inputs: d_x_enc belongs to the V1 network (encoded inputs)";
+        if (d_directions && m->arch.net == NRF_NET_V1) return "nrf_mlp_backward_inputs: the V1 network has no direction input";
+        if (d_positions && !positions) return "nrf_mlp_backward_inputs: d_positions needs the positions";
+        if (d_directions && !directions) return "nrf_mlp_backward_inputs: d_directions needs the directions";
+        if (((reinterpret_cast<uintptr_t>(d_x_enc) | reinterpret_cast<uintptr_t>(d_positions) | reinterpret_cast<uintptr_t>(d_directions) |
+              reinterpret_cast<uintptr_t>(positions) | reinterpret_cast<uintptr_t>(directions)) & 3u) != 0)
+            return "nrf_mlp_backward_inputs: float tensors must be 4-byte aligned";
+        return nullptr;
+    };
+    return train_entry(m, mma_mode, n, !ctx, ctx_bytes, true, wrong, [&](std::string& err) {
+        return nrf::launch_input_grad(m->net, m->train, mma_mode, n, ctx, positions, directions, d_x_enc, d_positions, d_directions,
+                                      (hipStream_t)stream, err);
+    });
+}
+
 int nrf_mlp_forward_train_rays(nrf_model* m, const nrf_train_rays* rays, int64_t n_rays, const nrf_render_opts* opts, float* out_a, float* out_b,
                                void* ctx, int64_t ctx_bytes, void* stream) {
     // what the arguments alone decide comes first, then what needs the model, then the device (context size)
@@ -831,6 +865,31 @@ int nrf_composite_backward(const float* rgb, int rgb_stride, const float* sigma,
     const int r = nrf::launch_composite_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, g_rgb,
                                                  g_depth, g_weights, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, (hipStream_t)stream);
     return r == NRF_OK ? NRF_OK : fail(r, "composite backward launch failed");
+}
+
+int nrf_composite_backward_geom(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals, const float* rays_d,
+                                int64_t n_rays, int n_samples, int white_bkgd, const float* g_rgb, const float* g_depth, const float* g_weights,
+                                float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* d_z, float* d_rays_d, void* stream) {
+    if (n_rays < 0 || n_samples < 1 || n_samples > 4096) return fail(NRF_EINVAL, "bad sizes");
+    if (rgb_stride < 3 || sigma_stride < 1 || d_rgb_stride < 3 || d_sigma_stride < 1) return fail(NRF_EINVAL, "bad strides");
+    if (n_rays == 0) return NRF_OK;
+    if (!rgb || !sigma || !z_vals || !rays_d || !d_rgb || !d_sigma || !d_z || !d_rays_d) return fail(NRF_EINVAL, "null pointer");
+    if (!g_rgb && !g_depth && !g_weights) return fail(NRF_EINVAL, "no incoming gradient");
+    const int r = nrf::launch_composite_backward_geom(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, g_rgb,
+                                                      g_depth, g_weights, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, d_z, d_rays_d,
+                                                      (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "composite backward (geometry) launch failed");
+}
+
+int nrf_ray_grad(const float* d_points, const float* d_dirs, const float* z_vals, const float* rays_d, const float* d_z_in,
+                 const float* d_rays_d_in, int64_t n_rays, int n_samples, float* d_rays_o, float* d_rays_d, float* d_z_out, void* stream) {
+    if (n_rays < 0 || n_samples < 1 || n_samples > 4096) return fail(NRF_EINVAL, "bad sizes");
+    if (n_rays == 0) return NRF_OK;
+    if (!d_points || !z_vals || !rays_d) return fail(NRF_EINVAL, "null pointer");
+    if (!d_rays_o && !d_rays_d && !d_z_out) return fail(NRF_EINVAL, "nrf_ray_grad: no output asked for");
+    const int r = nrf::launch_ray_grad(d_points, d_dirs, z_vals, rays_d, d_z_in, d_rays_d_in, n_rays, n_samples, d_rays_o, d_rays_d, d_z_out,
+                                       (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "ray_grad launch failed");
 }
 
 int nrf_mse_grad(const float* pred, const float* target, int64_t n, float weight, float* g_pred, float* loss, void* stream) {
@@ -1029,6 +1088,23 @@ int nrf_debug_pack_dino_grad(const nrf_arch* arch, const nrf_linear* linears, in
     std::vector<nrf::HostLinear> lin;
     nrf::NetPlan plan;
     if (!copy_linears(linears, n_linear, lin, err) || !nrf::make_dino_grad_plan(*arch, lin, plan, err)) return fail(NRF_EINVAL, err);
+    const nrf::PackedStream ps = nrf::pack_stream(plan, lin, mma_mode);
+    if (stream_bytes) *stream_bytes = (int64_t)ps.bytes.size();
+    if (stream_out) {
+        if (stream_cap < (int64_t)ps.bytes.size()) return fail(NRF_EINVAL, "stream_out too small");
+        std::memcpy(stream_out, ps.bytes.data(), ps.bytes.size());
+    }
+    return NRF_OK;
+}
+
+int nrf_debug_pack_input_grad(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int mma_mode, uint8_t* stream_out, int64_t stream_cap,
+                              int64_t* stream_bytes) {
+    if (!arch || !linears || n_linear <= 0) return fail(NRF_EINVAL, "nrf_debug_pack_input_grad: null argument");
+    if (mma_mode < 0 || mma_mode > 2) return fail(NRF_EINVAL, "unknown mma_mode");
+    std::string err;
+    std::vector<nrf::HostLinear> lin;
+    nrf::NetPlan plan;
+    if (!copy_linears(linears, n_linear, lin, err) || !nrf::make_input_grad_plan(*arch, lin, plan, err)) return fail(NRF_EINVAL, err);
     const nrf::PackedStream ps = nrf::pack_stream(plan, lin, mma_mode);
     if (stream_bytes) *stream_bytes = (int64_t)ps.bytes.size();
     if (stream_out) {

@@ -108,6 +108,7 @@ struct TrainDev {
     int job_x_slot[kMaxJobs], job_dz_slot[kMaxJobs], job_KT[kMaxJobs], job_MT[kMaxJobs], job_x_first[kMaxJobs];
     int64_t n_params;
     const void* gstream[3];     // V3: the W0d^T fragments of dino_grad_kernel (train_dino_grad_impl.hpp), behind the chain's layers in bstream
+    const void* istream[3];     // V1, V2: the W0^T (and color_layers.0^T) fragments of input_grad_kernel (train_input_grad_impl.hpp), likewise
 };
 
 int64_t train_ctx_bytes(const TrainDev& t, int mma_mode, int64_t n);
@@ -150,6 +151,10 @@ int launch_train_forward_rays_v3(const DeviceNet& net, const TrainDev& t, int mm
                                  float* density, void* ctx, hipStream_t s, std::string& err);
 // V3, after launch_train_backward_v3 on the same context: d_dino (n, dino_dim) = dL/d per-sample DINO features
 int launch_dino_grad(const DeviceNet& net, const TrainDev& t, int mma_mode, int64_t n, void* ctx, float* d_dino, hipStream_t s, std::string& err);
+// V1 / V2, after the family's launch_train_backward* on the same context: dL/d encoded inputs (V1), positions, directions (V2); a NULL
+// output is not computed
+int launch_input_grad(const DeviceNet& net, const TrainDev& t, int mma_mode, int64_t n, void* ctx, const float* positions, const float* directions,
+                      float* d_x_enc, float* d_positions, float* d_directions, hipStream_t s, std::string& err);
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd, int step,
                 const float* ray_loss, int64_t n_rays, float loss_weight, float* loss, hipStream_t s);
 int launch_mse_grad(const float* pred, const float* target, int64_t n, float weight, float* g_pred, float* loss, hipStream_t s);
@@ -194,6 +199,13 @@ int launch_repack3(const float* flat, const int32_t* const src[3], const int64_t
 int launch_composite_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
                               int64_t n_rays, int S, int white_bkgd, const float* g_rgb, const float* g_depth, const float* g_w,
                               float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, hipStream_t s);
+// launch_composite_backward with the geometric terms: d_z (R,S) = dL/d z_vals, d_rays_d (R,3) = dL/d rays_d through the ray norm
+int launch_composite_backward_geom(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
+                                   int64_t n_rays, int S, int white_bkgd, const float* g_rgb, const float* g_depth, const float* g_w,
+                                   float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* d_z, float* d_rays_d, hipStream_t s);
+// adjoint of point_on_ray and of the expansion of the directions over a ray's samples (nerfhip.h: nrf_ray_grad)
+int launch_ray_grad(const float* d_points, const float* d_dirs, const float* z, const float* rays_d, const float* d_z_in, const float* d_rays_d_in,
+                    int64_t n_rays, int S, float* d_rays_o, float* d_rays_d, float* d_z_out, hipStream_t s);
 
 // staged kernels (staged_kernels.hip)
 int launch_get_rays(const Camera& cam, int64_t ray_begin, int64_t n, float* rays_o, float* rays_d, hipStream_t s);

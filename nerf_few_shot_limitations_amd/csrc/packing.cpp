@@ -410,6 +410,36 @@ bool make_dino_grad_plan(const nrf_arch& a, const std::vector<HostLinear>& lin, 
     return true;
 }
 
+// The A operands of input_grad_kernel (train_input_grad_impl.hpp), both in the manner of make_dino_grad_plan.  Layer 0: W0^T of
+// the first Linear restricted to its positional-encoding tiles -- K = its 256 rows, rcol = the forward plan's col, so accumulator
+// register r of lane half h in output tile m is the derivative of feature (slot 16m + r, half h) of feature_map.hpp.  Layer 1
+// (V2): color_layers.0^T restricted to its direction-encoding tile -- K = its 128 rows.
+bool make_input_grad_plan(const nrf_arch& a, const std::vector<HostLinear>& lin, NetPlan& plan, std::string& err) {
+    plan = NetPlan();
+    if (a.net != NRF_NET_V1 && a.net != NRF_NET_V2) { err = "the input gradient is built for the V1 and V2 networks"; return false; }
+    NetPlan fwd;
+    if (!make_plan(a, lin, fwd, err)) return false;
+    const int H = a.hidden, HT = H / 32, n = a.n_layers;
+    const LayerPlan& F0 = fwd.layers[0];
+    LayerPlan L; L.transposed = true; L.KT = HT; L.MT = F0.KT; L.krow.assign(32 * HT, {-1, 0});
+    for (int k = 0; k < H; ++k) L.krow[k] = {0, k};
+    L.rcol = F0.col;
+    L.bias_off = 0;
+    int off = 32 * L.MT;
+    plan.layers.push_back(std::move(L));
+    if (a.net == NRF_NET_V2) {
+        const LayerPlan& C0 = fwd.layers[n + 2];                                   // [feature_vec | PE(dir)] -> 128
+        LayerPlan D; D.transposed = true; D.KT = H / 64; D.MT = 1; D.krow.assign(32 * D.KT, {-1, 0});
+        for (int k = 0; k < H / 2; ++k) D.krow[k] = {n + 2, k};
+        D.rcol.assign(C0.col.begin() + H, C0.col.begin() + H + 32);
+        D.bias_off = off;
+        off += 32;
+        plan.layers.push_back(std::move(D));
+    }
+    plan.n_bias = off;
+    return true;
+}
+
 bool make_train_plan(const nrf_arch& a, const NetPlan& fwd, const ParamLayout& lay, TrainPlan& tp, std::string& err) {
     tp = TrainPlan();
     if (a.net != NRF_NET_V1 && a.net != NRF_NET_V2 && a.net != NRF_NET_V3) { err = "unknown network family"; return false; }

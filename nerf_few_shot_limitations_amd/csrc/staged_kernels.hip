@@ -196,14 +196,20 @@ constexpr int kMaxSegments = 64;     // S <= 4096
 
 // One ray on one wave; gr, gg, gb, gd = dL/d rgb_map, dL/d depth of the ray (wave-uniform), g_w = dL/d weights or NULL;
 // seg_T = the wave's LDS row of kMaxSegments floats.  EXT: the density noise `ns`, and the regulariser's dL/d weights formed in
-// registers, g_w[i] = gw_scale * w_i (no (R,S) tensor)
-template <bool EXT = false>
+// registers, g_w[i] = gw_scale * w_i (no (R,S) tensor).  GEOM: the geometric terms of the same autograd as well --
+//   dL/d dist_i = dL/dalpha_i * relu(sigma_i) * e_i                      (dist_i = (z_{i+1} - z_i) |d|, the last one 1e10 |d|)
+//   dL/d z_i    = g_depth * w_i + |d| (dL/d dist_{i-1} - [i < S-1] dL/d dist_i)              -> d_z (R,S)
+//   dL/d |d|    = sum_{i<S-1} dL/d dist_i (z_{i+1} - z_i) + dL/d dist_{S-1} * 1e10,   d_rays_d (R,3) = dL/d |d| * d / |d|
+// The neighbour term of a segment's first sample waits for the segment in front of it (walked later), as the suffix sum's carry
+// travels the other way.  The instantiations without GEOM are the code the kernels had before it existed.
+template <bool EXT = false, bool GEOM = false>
 __device__ __forceinline__ void composite_backward_ray(const float* __restrict__ rgb, int rgb_stride, const float* __restrict__ sigma,
                                                        int sigma_stride, const float* __restrict__ z, const float* __restrict__ rays_d,
                                                        int64_t r, int S, int lane, int white_bkgd, float gr, float gg, float gb, float gd,
                                                        const float* __restrict__ g_w, float* __restrict__ d_rgb, int d_rgb_stride,
                                                        float* __restrict__ d_sigma, int d_sigma_stride, float* seg_T,
-                                                       const NoiseSrc ns = NoiseSrc{}, float gw_scale = 0.0f) {
+                                                       const NoiseSrc ns = NoiseSrc{}, float gw_scale = 0.0f, float* __restrict__ d_z = nullptr,
+                                                       float* __restrict__ d_rays_d = nullptr) {
     const int n_seg = (S + 63) / 64;
     const float d[3] = {rays_d[r * 3], rays_d[r * 3 + 1], rays_d[r * 3 + 2]};
     const float norm = ray_norm(d);
@@ -233,6 +239,7 @@ __device__ __forceinline__ void composite_backward_ray(const float* __restrict__
     }
     // pass 2, back to front
     float carry = 0.0f;                                  // sum of w_j v_j over all later segments
+    float pend_z = 0.0f, s_norm = 0.0f;                  // GEOM: dL/d z of the later segment's first sample without its neighbour term; dL/d |d|
     for (int k = n_seg - 1; k >= 0; --k) {
         float alpha, e, dist, f, zc, sg; bool valid; int64_t i;
         sample(64 * k, alpha, e, dist, f, zc, valid, i, sg);
@@ -261,6 +268,32 @@ __device__ __forceinline__ void composite_backward_ray(const float* __restrict__
             d_rgb[i * d_rgb_stride + 1] = __fmul_rn(w, gg);
             d_rgb[i * d_rgb_stride + 2] = __fmul_rn(w, gb);
         }
+        if constexpr (GEOM) {
+            float dd = 0.0f;                             // dL/d dist_i
+            if (valid) {
+                const float d_alpha = __fsub_rn(__fmul_rn(T, v), suffix / f);
+                dd = __fmul_rn(__fmul_rn(d_alpha, fmaxf(sg, 0.0f)), e);
+            }
+            const bool last = (64 * k + lane + 1 == S);
+            // (z_{i+1} - z_i) again, as `sample` formed it: dist / |d| would divide by zero on a zero direction
+            float zn = __shfl_down(zc, 1, 64);
+            if (lane == 63 && 64 * k + lane + 1 < S) zn = z[i + 1];
+            s_norm = __fadd_rn(s_norm, __fmul_rn(dd, last ? 1e10f : __fsub_rn(zn, zc)));
+            float up = __shfl_up(dd, 1, 64);
+            if (lane == 0) up = 0.0f;
+            const float own = last ? 0.0f : dd;
+            const float dz = __fadd_rn(__fmul_rn(gd, w), __fmul_rn(norm, __fsub_rn(up, own)));
+            if (valid && (lane > 0 || k == 0)) d_z[i] = dz;
+            const float dd_end = __shfl(dd, 63, 64);
+            if (k + 1 < n_seg && lane == 0)              // the first sample of segment k + 1: its neighbour is this segment's lane 63
+                d_z[r * S + 64 * (k + 1)] = __fadd_rn(pend_z, __fmul_rn(norm, dd_end));
+            pend_z = __shfl(dz, 0, 64);
+        }
+    }
+    if constexpr (GEOM) {
+        const float dn = wave_sum(s_norm);
+        const float dk = lane == 0 ? d[0] : (lane == 1 ? d[1] : d[2]);
+        if (lane < 3) d_rays_d[r * 3 + lane] = norm > 0.0f ? __fmul_rn(dn, dk / norm) : 0.0f;
     }
 }
 
@@ -878,6 +911,91 @@ int launch_composite(const float* rgb, int rgb_stride, const float* sigma, int s
     if (n_rays <= 0) return NRF_OK;
     hipLaunchKernelGGL(composite_kernel, dim3(grid_for(n_rays * 64, kBlock, 16384)), dim3(kBlock), 0, s, rgb, rgb_stride, sigma, sigma_stride, z,
                        rays_d, n_rays, S, white_bkgd, out_rgb, out_depth, out_w);
+    return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
+}
+
+// composite_backward_kernel with the geometric terms (composite_backward_ray<false, true>): a kernel of its own, so that the one
+// above stays what it is
+__global__ void __launch_bounds__(kBlock) composite_backward_geom_kernel(const float* __restrict__ rgb, int rgb_stride, const float* __restrict__ sigma,
+                                                                         int sigma_stride, const float* __restrict__ z,
+                                                                         const float* __restrict__ rays_d, int64_t n_rays, int S, int white_bkgd,
+                                                                         const float* __restrict__ g_rgb, const float* __restrict__ g_depth,
+                                                                         const float* __restrict__ g_w, float* __restrict__ d_rgb,
+                                                                         int d_rgb_stride, float* __restrict__ d_sigma, int d_sigma_stride,
+                                                                         float* __restrict__ d_z, float* __restrict__ d_rays_d) {
+    __shared__ float seg_T[kBlock / 64][kMaxSegments];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t wave0 = (blockIdx.x * (int64_t)kBlock + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * kBlock) >> 6;
+    for (int64_t r = wave0; r < n_rays; r += n_waves) {
+        const float gr = g_rgb ? g_rgb[r * 3] : 0.0f, gg = g_rgb ? g_rgb[r * 3 + 1] : 0.0f, gb = g_rgb ? g_rgb[r * 3 + 2] : 0.0f;
+        const float gd = g_depth ? g_depth[r] : 0.0f;
+        composite_backward_ray<false, true>(rgb, rgb_stride, sigma, sigma_stride, z, rays_d, r, S, lane, white_bkgd, gr, gg, gb, gd, g_w, d_rgb,
+                                            d_rgb_stride, d_sigma, d_sigma_stride, seg_T[wv], NoiseSrc{}, 0.0f, d_z, d_rays_d);
+    }
+}
+
+// Adjoint of point_on_ray (p = o + d z) and of the expansion of a ray's direction over its samples.  One WAVE per ray, LANE <->
+// sample, 64-sample segments, wave_sum in a fixed order, no atomics:
+//   d_rays_o = sum_s d_p,   d_rays_d = sum_s (z_s d_p + d_dirs) + d_rays_d_in,   d_z_out[s] = d . d_p_s + d_z_in[s]
+// HBM-bound: 16 (+ 12 + 4) B read and 4 B written per ray-sample.
+__global__ void __launch_bounds__(kBlock) ray_grad_kernel(const float* __restrict__ d_points, const float* __restrict__ d_dirs,
+                                                          const float* __restrict__ z, const float* __restrict__ rays_d,
+                                                          const float* __restrict__ d_z_in, const float* __restrict__ d_rays_d_in,
+                                                          int64_t n_rays, int S, float* __restrict__ d_rays_o, float* __restrict__ d_rays_d,
+                                                          float* __restrict__ d_z_out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave0 = (blockIdx.x * (int64_t)kBlock + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * kBlock) >> 6;
+    for (int64_t r = wave0; r < n_rays; r += n_waves) {
+        const float d[3] = {rays_d[r * 3], rays_d[r * 3 + 1], rays_d[r * 3 + 2]};
+        float so[3] = {0.0f, 0.0f, 0.0f}, sd[3] = {0.0f, 0.0f, 0.0f};
+        for (int s0 = 0; s0 < S; s0 += 64) {
+            const int s = s0 + lane;
+            if (s < S) {
+                const int64_t i = r * S + s;
+                const float zc = z[i];
+                float dot = 0.0f;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float dp = d_points[i * 3 + k];
+                    so[k] = __fadd_rn(so[k], dp);
+                    float t = __fmul_rn(zc, dp);
+                    if (d_dirs) t = __fadd_rn(t, d_dirs[i * 3 + k]);
+                    sd[k] = __fadd_rn(sd[k], t);
+                    dot = __fadd_rn(dot, __fmul_rn(d[k], dp));
+                }
+                if (d_z_out) d_z_out[i] = d_z_in ? __fadd_rn(dot, d_z_in[i]) : dot;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { so[k] = wave_sum(so[k]); sd[k] = wave_sum(sd[k]); }
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                if (d_rays_o) d_rays_o[r * 3 + k] = so[k];
+                if (d_rays_d) d_rays_d[r * 3 + k] = d_rays_d_in ? __fadd_rn(sd[k], d_rays_d_in[r * 3 + k]) : sd[k];
+            }
+        }
+    }
+}
+
+int launch_composite_backward_geom(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
+                                   int64_t n_rays, int S, int white_bkgd, const float* g_rgb, const float* g_depth, const float* g_w,
+                                   float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* d_z, float* d_rays_d, hipStream_t s) {
+    if (n_rays <= 0) return NRF_OK;
+    if (S > 64 * kMaxSegments) return NRF_EINVAL;
+    hipLaunchKernelGGL(composite_backward_geom_kernel, dim3(grid_for(n_rays * 64, kBlock, 16384)), dim3(kBlock), 0, s, rgb, rgb_stride, sigma,
+                       sigma_stride, z, rays_d, n_rays, S, white_bkgd, g_rgb, g_depth, g_w, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, d_z,
+                       d_rays_d);
+    return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
+}
+
+int launch_ray_grad(const float* d_points, const float* d_dirs, const float* z, const float* rays_d, const float* d_z_in, const float* d_rays_d_in,
+                    int64_t n_rays, int S, float* d_rays_o, float* d_rays_d, float* d_z_out, hipStream_t s) {
+    if (n_rays <= 0) return NRF_OK;
+    hipLaunchKernelGGL(ray_grad_kernel, dim3(grid_for(n_rays * 64, kBlock, 16384)), dim3(kBlock), 0, s, d_points, d_dirs, z, rays_d, d_z_in,
+                       d_rays_d_in, n_rays, S, d_rays_o, d_rays_d, d_z_out);
     return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
 }
 

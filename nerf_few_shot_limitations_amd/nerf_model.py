@@ -13,6 +13,9 @@ transposed-stream backward, MFMA weight gradients); gradients reach the paramete
 `dino_grad=True` (use_dino form), the per-sample DINO features, so that a feature extractor in front
 of the module -- the LoRA matrices of lora.yaml -- trains; by default a dino_features tensor that
 requires grad is refused instead of silently detached (the reference computes its maps under no_grad).
+`input_grad=True` (legacy and trainer form without DINO) backpropagates to the inputs of the field as well:
+x_encoded (legacy form), positions and directions (trainer form) that require grad receive gradients, which is
+what pose refinement, surface normals (`density_normals`) and depth-distribution losses need.
 """
 from __future__ import annotations
 
@@ -70,9 +73,13 @@ class _FreqBuffer(nn.Module):          # nerf_mlp.py:14-15 registers freq_bands 
 
 class NeRFMLP(nn.Module):
     def __init__(self, pos_dim=63, hidden_dim=256, n_layers=8, *, pos_freq=None, dir_freq=4, num_density_layers=None,
-                 use_dino=False, dino_dim=0, mma_mode="f32", dino_grad=False):
+                 use_dino=False, dino_dim=0, mma_mode="f32", dino_grad=False, input_grad=False):
         super().__init__()
+        if input_grad and use_dino and pos_freq is not None:
+            raise ValueError("input_grad=True is built for the forms without DINO features: a use_dino model (V3) also needs the adjoint of "
+                             "the projection and the bilinear fetch with respect to the points, which does not exist yet")
         self.mma_mode = mma_mode
+        self.input_grad = bool(input_grad)   # opt-in: backpropagate into x_encoded / positions / directions / rays that require grad
         self.dino_grad = bool(dino_grad)     # opt-in: backpropagate into dino_features / feature maps that require grad
         self.hidden_dim = int(hidden_dim)
         if pos_freq is None:
@@ -240,11 +247,19 @@ class NeRFMLP(nn.Module):
     def _wants_grad(self):
         return torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
-    def forward(self, positions, directions=None, dino_features=None):
-        if self._wants_grad():
+    def _wants_input_grad(self, *inputs):
+        """An input_grad module under grad mode with an input that requires grad: the training kernels run even when every
+        parameter is frozen."""
+        return (self.__dict__.get("input_grad", False) and torch.is_grad_enabled()
+                and any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs))
+
+    def forward(self, positions, directions=None, dino_features=None, points=None):
+        """`points` (legacy form of an input_grad module): the (P,3) positions that `positions` (= x_encoded) encodes; when they
+        require grad they receive dL/d points through the adjoint of the encoding."""
+        if self._wants_grad() or self._wants_input_grad(positions, directions, points):
             from .training import mlp_v1_train, mlp_v2_train
             if self.net == L.NRF_NET_V1:
-                return mlp_v1_train(self, positions)
+                return mlp_v1_train(self, positions, points)
             return mlp_v2_train(self, positions, directions, dino_features)
         mode = L.MMA_MODES[self.mma_mode]
         x = L.dev_f32(positions)            # reached only when no parameter wants a gradient (inference): inputs carry none either
@@ -268,6 +283,15 @@ class NeRFMLP(nn.Module):
             dens = torch.empty((n, 1), dtype=torch.float32, device=x.device)
             L.check(L.lib().nrf_mlp_forward(h, mode, L.ptr(pos), L.ptr(dirs), L.ptr(dino), n, L.ptr(rgb), L.ptr(dens), L.stream_ptr()))
             return rgb, dens
+
+
+def density_normals(model: NeRFMLP, points):
+    """(density (P,1), normals (P,3)) of an input_grad model at `points` (P,3): normals = -grad(sigma) / |grad(sigma)| (zero where the
+    gradient vanishes), from ONE saving forward and one input-gradient backward.  Parameter gradients are not touched."""
+    if not getattr(model, "input_grad", False):
+        raise ValueError("density_normals needs a model built with NeRFMLP(..., input_grad=True)")
+    from .training import field_input_grad
+    return field_input_grad(model, points)
 
 
 def load_checkpoint_into(model: NeRFMLP, ckpt: dict):

@@ -20,10 +20,44 @@ def _c2w12(c2w) -> "C.Array":
     return (C.c_float * 12)(*m[:3, :4].reshape(-1).tolist())
 
 
-def get_rays(H, W, focal, c2w):
-    """rays_o, rays_d of shape (H,W,3); ray id y*W+x.  ray_sampler.py:4-30 == ray_utils.py:4-37."""
+class _GetRaysFn(torch.autograd.Function):
+    """get_rays with a pose that requires grad: the staged kernel forward, and in torch the adjoint of rays_d = R dirs_cam,
+    rays_o = t with the camera-frame directions of ray_sampler.py:4-30."""
+
+    @staticmethod
+    def forward(ctx, c2w, H, W, focal):
+        rays_o, rays_d = get_rays(H, W, focal, c2w.detach())
+        ctx.H, ctx.W, ctx.focal, ctx.shape = H, W, float(focal), tuple(c2w.shape)
+        ctx.set_materialize_grads(False)
+        return rays_o, rays_d
+
+    @staticmethod
+    def backward(ctx, g_o, g_d):
+        H, W = ctx.H, ctx.W
+        g = g_o if g_o is not None else g_d
+        if g is None:
+            return None, None, None, None
+        d_c2w = torch.zeros(ctx.shape, dtype=torch.float32, device=g.device)
+        if g_o is not None:
+            d_c2w[:3, 3] = g_o.to(torch.float32).reshape(-1, 3).sum(0)
+        if g_d is not None:
+            x = torch.arange(W, dtype=torch.float32, device=g.device)[None, :].expand(H, W)
+            y = torch.arange(H, dtype=torch.float32, device=g.device)[:, None].expand(H, W)
+            cam = torch.stack([(x - W * 0.5) / ctx.focal, -(y - H * 0.5) / ctx.focal, -torch.ones_like(x)], -1).reshape(-1, 3)
+            d_c2w[:3, :3] = g_d.to(torch.float32).reshape(-1, 3).t() @ cam
+        return d_c2w, None, None, None
+
+
+def get_rays(H, W, focal, c2w, pose_grad=False):
+    """rays_o, rays_d of shape (H,W,3); ray id y*W+x.  ray_sampler.py:4-30 == ray_utils.py:4-37.
+    pose_grad=True: a (4,4) / (3,4) c2w tensor that requires grad receives dL/d c2w (camera-pose refinement); the rays are the
+    same bits."""
     L.require_gpu()
     H, W = int(H), int(W)
+    if pose_grad and torch.is_grad_enabled() and isinstance(c2w, torch.Tensor) and c2w.requires_grad:
+        if c2w.shape not in ((4, 4), (3, 4)):
+            raise ValueError(f"c2w must be (4,4) or (3,4), got {tuple(c2w.shape)}")
+        return _GetRaysFn.apply(c2w, H, W, focal)
     dev = c2w.device if isinstance(c2w, torch.Tensor) and c2w.is_cuda else torch.device("cuda", torch.cuda.current_device())
     with torch.cuda.device(dev):
         rays_o = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
@@ -32,7 +66,38 @@ def get_rays(H, W, focal, c2w):
     return rays_o, rays_d
 
 
-def sample_points_along_rays(rays_o, rays_d, near, far, N_samples, perturb=True, lindisp=False, t_rand=None, seed=None):
+class _SampleFn(torch.autograd.Function):
+    """sample_points_along_rays with rays that require grad: the staged kernel forward; backward nrf_ray_grad, the adjoint of
+    pts = o + d z (the depths are the ladder's: constants) and of the expansion of rays_d over the samples (`dirs`, the per-sample
+    view directions of train.py:225)."""
+
+    @staticmethod
+    def forward(ctx, o, d, args):
+        pts, z = sample_points_along_rays(o.detach(), d.detach(), *args)
+        S = z.shape[-1]
+        dirs = d.detach().reshape(-1, 1, 3).expand(-1, S, 3).reshape(*z.shape, 3).contiguous()
+        ctx.save_for_backward(z.reshape(-1, S), d.detach().reshape(-1, 3).contiguous())
+        ctx.shape = tuple(o.shape)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(z)
+        return pts, z, dirs
+
+    @staticmethod
+    def backward(ctx, g_pts, g_z, g_dirs):
+        if g_pts is None and g_dirs is None:
+            return None, None, None
+        z, d = ctx.saved_tensors
+        R, S = z.shape
+        g = L.dev_f32(g_pts, z.device).reshape(R * S, 3) if g_pts is not None else torch.zeros((R * S, 3), dtype=torch.float32, device=z.device)
+        gd = L.dev_f32(g_dirs, z.device).reshape(R * S, 3) if g_dirs is not None else None
+        with torch.cuda.device(z.device):
+            d_o, d_d = torch.empty_like(d), torch.empty_like(d)
+            L.check(L.lib().nrf_ray_grad(L.ptr(g), L.ptr(gd), L.ptr(z), L.ptr(d), None, None, R, S, L.ptr(d_o), L.ptr(d_d), None, L.stream_ptr()))
+        return d_o.reshape(ctx.shape), d_d.reshape(ctx.shape), None
+
+
+def sample_points_along_rays(rays_o, rays_d, near, far, N_samples, perturb=True, lindisp=False, t_rand=None, seed=None, ray_grad=False,
+                             return_dirs=False):
     """pts (...,S,3), z_vals (...,S) for rays of shape (N,3) or (H,W,3).
 
     ray_utils.py:39-84 (flat) == ray_sampler.py:32-61 (image).  `perturb=True`
@@ -41,8 +106,21 @@ def sample_points_along_rays(rays_o, rays_d, near, far, N_samples, perturb=True,
     call taken from torch's CPU generator, so that, as with the reference's
     torch.rand (ray_utils.py:78), consecutive calls jitter differently and a run
     repeats under torch.manual_seed; an int pins the pattern.
+    ray_grad=True: rays that require grad receive gradients through pts (same
+    bits as without the flag).  return_dirs=True adds the per-sample view
+    directions (...,S,3), rays_d repeated over the samples (train.py:225); with
+    ray_grad their gradient flows back into rays_d in the same launch.
     """
     L.require_gpu()
+    if ray_grad and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (rays_o, rays_d)):
+        # rays that require grad receive gradients through pts; the forward is this function on the detached rays: the same bits
+        if seed is None:
+            seed = L.fresh_seed() if (perturb and t_rand is None) else 0
+        dev = rays_o.device if isinstance(rays_o, torch.Tensor) and rays_o.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        o = torch.as_tensor(rays_o).to(device=dev, dtype=torch.float32)
+        d = torch.as_tensor(rays_d).to(device=dev, dtype=torch.float32)
+        pts, z, dirs = _SampleFn.apply(o, d, (near, far, N_samples, perturb, lindisp, t_rand, seed))
+        return (pts, z, dirs) if return_dirs else (pts, z)
     o = L.dev_f32(L.refuse_grad(rays_o, "sample_points_along_rays(rays_o)"))
     d = L.dev_f32(L.refuse_grad(rays_d, "sample_points_along_rays(rays_d)"), o.device)
     if seed is None:
@@ -62,6 +140,8 @@ def sample_points_along_rays(rays_o, rays_d, near, far, N_samples, perturb=True,
         L.check(L.lib().nrf_sample_along_rays(L.ptr(o2), L.ptr(d2), R, float(near), float(far), S, int(bool(lindisp)),
                                               int(bool(perturb) or tr is not None), L.ptr(tr), L.ptr(lad), int(seed), L.ptr(pts), L.ptr(z),
                                               L.stream_ptr()))
+    if return_dirs:
+        return pts.reshape(*lead, S, 3), z.reshape(*lead, S), d2[:, None, :].expand(R, S, 3).reshape(*lead, S, 3).contiguous()
     return pts.reshape(*lead, S, 3), z.reshape(*lead, S)
 
 

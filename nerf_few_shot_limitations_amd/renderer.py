@@ -71,7 +71,7 @@ def render_rays(model: NeRFMLP, rays_o, rays_d, near, far, N_samples=64, perturb
     kernel (ert_eps >= 0).  `return_stats=True` adds 'stats', an int64 device tensor [evaluated (ray, sample) pairs, MLP passes of
     waves that held a live ray].  Refused with tail_mode and under grad (ValueError)."""
     L.require_gpu()
-    if model.training and model._wants_grad():
+    if (model.training and model._wants_grad()) or model._wants_input_grad(rays_o, rays_d, z_in):
         if occupancy is not None:
             raise ValueError("occupancy is for inference: the differentiable route (a model in train() mode under grad) evaluates every sample")
         from .training import render_rays_train
@@ -204,7 +204,8 @@ class NeRFRenderer:
         return render_rays(self.nerf_model, rays_o, rays_d, self.near, self.far, N_samples,
                            perturb=self.nerf_model.training, white_bkgd=self.white_bkgd, mma_mode=self.mma_mode,
                            ert_eps=self.ert_eps, dino=self._dino(view_idx), tail_mode=self.tail_mode,
-                           occupancy=None if (self.nerf_model.training and self.nerf_model._wants_grad()) else self.occupancy)
+                           occupancy=None if ((self.nerf_model.training and self.nerf_model._wants_grad())
+                                              or self.nerf_model._wants_input_grad(rays_o, rays_d)) else self.occupancy)
 
     @torch.no_grad()
     def render_full_image(self, rays_o, rays_d, closest_view_idx=0, chunk_size=1024, N_samples=64):

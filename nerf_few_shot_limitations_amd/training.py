@@ -125,6 +125,30 @@ def _dino_grad(module, mode, n, buf, nbytes, dev, out=None):
     return d_dino
 
 
+def _live_input(module, t, what, device=None):
+    """An input of the field as the kernels read it.  A tensor that requires grad stays in the graph on a module built with
+    input_grad=True and is refused otherwise (_lib.refuse_grad)."""
+    if torch.is_grad_enabled() and isinstance(t, torch.Tensor) and t.requires_grad and getattr(module, "input_grad", False):
+        if device is None:
+            device = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        return t.to(device=device, dtype=torch.float32).contiguous()
+    return L.dev_f32(L.refuse_grad(t, what), device)
+
+
+def _input_grad(module, mode, n, buf, nbytes, dev, positions=None, directions=None, want_x=False, want_p=False, want_d=False):
+    """(d_x_enc, d_positions, d_directions) -- None where not asked for -- of a V1 / V2 module, from the context of a finished
+    nrf_mlp_backward_v1 / nrf_mlp_backward (one launch)."""
+    if not (want_x or want_p or want_d):
+        return None, None, None
+    pe = 3 * (2 * module.pos_freq + 1)
+    d_x = torch.empty((n, pe), dtype=torch.float32, device=dev) if want_x else None
+    d_p = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_p else None
+    d_d = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_d else None
+    L.check(L.lib().nrf_mlp_backward_inputs(module._handle, mode, n, C.c_void_p(buf.data_ptr()), nbytes, L.ptr(positions) if want_p else None,
+                                            L.ptr(directions) if want_d else None, L.ptr(d_x), L.ptr(d_p), L.ptr(d_d), L.stream_ptr()))
+    return d_x, d_p, d_d
+
+
 _fetch_ws = {}
 
 
@@ -188,7 +212,7 @@ class _ProjectFetchFn(torch.autograd.Function):
 
 class _MLPV1Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, module, x_enc, *params):
+    def forward(ctx, module, x_enc, points, *params):
         dev = x_enc.device
         h, mode = _train_handle(module, dev)
         n = x_enc.shape[0]
@@ -201,7 +225,7 @@ class _MLPV1Fn(torch.autograd.Function):
             L.check(L.lib().nrf_mlp_forward_train_v1(h, mode, L.ptr(x_enc), n, L.ptr(out), C.c_void_p(buf.data_ptr()), nbytes, L.stream_ptr()))
         ctx.module, ctx.buf, ctx.nbytes, ctx.n, ctx.mode = module, buf, nbytes, n, mode
         ctx.versions = module._versions()
-        ctx.save_for_backward(out)
+        ctx.save_for_backward(out, points)
         return out
 
     @staticmethod
@@ -210,19 +234,26 @@ class _MLPV1Fn(torch.autograd.Function):
         if module._versions() != ctx.versions:
             raise RuntimeError("NeRFMLP parameters were modified between forward and backward: the saved activations "
                                "no longer match the packed weights")
-        (out,) = ctx.saved_tensors
+        out, points = ctx.saved_tensors
         dev = out.device
         g = g_out.to(torch.float32).contiguous()
         fp = module.flat_params()
-        direct = _grad_target(module)
-        grad = direct if direct is not None else torch.zeros_like(fp.flat)
+        wanted = any(ctx.needs_input_grad[3:])
+        if not wanted:                                   # frozen parameters: an input-gradient backward
+            grad, direct = torch.zeros_like(fp.flat), fp.flat
+        else:
+            direct = _grad_target(module)
+            grad = direct if direct is not None else torch.zeros_like(fp.flat)
         with torch.cuda.device(dev):
             L.check(L.lib().nrf_mlp_backward_v1(module._handle, ctx.mode, L.ptr(out), L.ptr(g), ctx.n, C.c_void_p(ctx.buf.data_ptr()), ctx.nbytes,
                                                 L.ptr(grad), L.stream_ptr()))
+            # input_grad modules with inputs that require grad: one more launch over what the backward saved
+            d_x, d_p, _ = _input_grad(module, ctx.mode, ctx.n, ctx.buf, ctx.nbytes, dev, positions=points,
+                                      want_x=ctx.needs_input_grad[1], want_p=ctx.needs_input_grad[2])
         ctx.buf = None
         if direct is not None:
-            return (None, None) + (None,) * len(fp.offsets)       # already accumulated into the parameters' .grad
-        return (None, None, *fp.views(grad))
+            return (None, d_x, d_p) + (None,) * len(fp.offsets)   # already accumulated into the parameters' .grad
+        return (None, d_x, d_p, *fp.views(grad))
 
 
 class _MLPV2Fn(torch.autograd.Function):
@@ -244,7 +275,7 @@ class _MLPV2Fn(torch.autograd.Function):
                                                   C.c_void_p(buf.data_ptr()), nbytes, L.stream_ptr()))
         ctx.module, ctx.buf, ctx.nbytes, ctx.n, ctx.mode = module, buf, nbytes, n, mode
         ctx.versions = module._versions()
-        ctx.save_for_backward(rgb, dens)
+        ctx.save_for_backward(rgb, dens, pos, dirs)
         return rgb, dens
 
     @staticmethod
@@ -253,30 +284,36 @@ class _MLPV2Fn(torch.autograd.Function):
         if module._versions() != ctx.versions:
             raise RuntimeError("NeRFMLP parameters were modified between forward and backward: the saved activations "
                                "no longer match the packed weights")
-        rgb, dens = ctx.saved_tensors
+        rgb, dens, pos, dirs = ctx.saved_tensors
         dev = rgb.device
         g_rgb = g_rgb.to(torch.float32).contiguous()
         g_dens = g_dens.to(torch.float32).contiguous()
         fp = module.flat_params()
-        direct = _grad_target(module)
-        grad = direct if direct is not None else torch.zeros_like(fp.flat)
+        if not any(ctx.needs_input_grad[4:]):            # frozen parameters: an input-gradient backward
+            grad, direct = torch.zeros_like(fp.flat), fp.flat
+        else:
+            direct = _grad_target(module)
+            grad = direct if direct is not None else torch.zeros_like(fp.flat)
         with torch.cuda.device(dev):
             L.check(L.lib().nrf_mlp_backward(module._handle, ctx.mode, L.ptr(rgb), L.ptr(dens), L.ptr(g_rgb), L.ptr(g_dens), ctx.n,
                                              C.c_void_p(ctx.buf.data_ptr()), ctx.nbytes, L.ptr(grad), L.stream_ptr()))
             # dino_grad modules with features that require grad: one more launch over what the backward saved
             d_dino = _dino_grad(module, ctx.mode, ctx.n, ctx.buf, ctx.nbytes, dev) if ctx.needs_input_grad[3] else None
+            # input_grad modules with positions / directions that require grad: likewise
+            _, d_p, d_d = _input_grad(module, ctx.mode, ctx.n, ctx.buf, ctx.nbytes, dev, positions=pos, directions=dirs,
+                                      want_p=ctx.needs_input_grad[1], want_d=ctx.needs_input_grad[2])
         ctx.buf = None
         if direct is not None:
-            return (None, None, None, d_dino) + (None,) * len(fp.offsets)
-        return (None, None, None, d_dino, *fp.views(grad))
+            return (None, d_p, d_d, d_dino) + (None,) * len(fp.offsets)
+        return (None, d_p, d_d, d_dino, *fp.views(grad))
 
 
 def mlp_v2_train(module, positions, directions, dino_features=None):
     """(P,3) positions, (P,3) directions [, (P,C) DINO features for the use_dino=True form] -> rgb (P,3), density (P,1),
-    differentiable with respect to the parameters and -- for a module built with dino_grad=True -- the DINO features (not the
-    other inputs; without the switch a feature tensor that requires grad is refused)."""
-    pos = L.dev_f32(L.refuse_grad(positions, "NeRFMLP.forward(positions)")).reshape(-1, 3)
-    dirs = L.dev_f32(L.refuse_grad(directions, "NeRFMLP.forward(directions)"), pos.device).reshape(-1, 3)
+    differentiable with respect to the parameters, -- for a module built with dino_grad=True -- the DINO features and -- for a
+    module built with input_grad=True -- the positions and directions (without the switch a tensor that requires grad is refused)."""
+    pos = _live_input(module, positions, "NeRFMLP.forward(positions)").reshape(-1, 3)
+    dirs = _live_input(module, directions, "NeRFMLP.forward(directions)", pos.device).reshape(-1, 3)
     dino = None
     if module.net == L.NRF_NET_V3:
         if dino_features is None:
@@ -292,13 +329,53 @@ def mlp_v2_train(module, positions, directions, dino_features=None):
     return _MLPV2Fn.apply(module, pos, dirs, dino, *module.flat_params().params())
 
 
-def mlp_v1_train(module, x_enc):
-    """(P, 63) encoded points -> (P, 4) = [sigmoid rgb, raw sigma], differentiable with respect to the parameters."""
-    x = L.dev_f32(L.refuse_grad(x_enc, "NeRFMLP.forward(x_encoded)"))
+def mlp_v1_train(module, x_enc, points=None):
+    """(P, 63) encoded points -> (P, 4) = [sigmoid rgb, raw sigma], differentiable with respect to the parameters and -- for a
+    module built with input_grad=True -- x_enc and `points`, the (P,3) positions x_enc encodes."""
+    x = _live_input(module, x_enc, "NeRFMLP.forward(x_encoded)")
     pe = 3 * (2 * module.pos_freq + 1)
     flat_in = x.reshape(-1, pe)
-    out = _MLPV1Fn.apply(module, flat_in, *module.flat_params().params())
+    pts = None
+    if points is not None:
+        pts = _live_input(module, points, "NeRFMLP.forward(points)", x.device).reshape(-1, 3)
+        if pts.shape[0] != flat_in.shape[0]:
+            raise ValueError("points must hold one (x,y,z) row per row of x_encoded")
+    out = _MLPV1Fn.apply(module, flat_in, pts, *module.flat_params().params())
     return out.reshape(*x.shape[:-1], 4)
+
+
+def field_input_grad(module, points):
+    """nerf_model.density_normals: one saving forward, the dZ chain with dL/d sigma = 1 (its parameter gradients go to a scratch
+    vector) and the input-gradient kernel."""
+    pts = L.dev_f32(points).reshape(-1, 3)
+    dev, n = pts.device, pts.shape[0]
+    h, mode = _train_handle(module, dev)
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        nbytes = lib.nrf_train_context_bytes(h, mode, n)
+        if nbytes < 0:
+            raise L.NrfError(-2, lib.nrf_last_error().decode("utf-8", "replace"))
+        buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        scratch = torch.zeros_like(module.flat_params().flat)
+        st, cb = L.stream_ptr(), C.c_void_p(buf.data_ptr())
+        if module.net == L.NRF_NET_V1:
+            out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            g = torch.zeros_like(out)
+            g[:, 3] = 1.0
+            L.check(lib.nrf_mlp_forward_train_v1(h, mode, L.ptr(_encoder(module.pos_freq)(pts)), n, L.ptr(out), cb, nbytes, st))
+            L.check(lib.nrf_mlp_backward_v1(h, mode, L.ptr(out), L.ptr(g), n, cb, nbytes, L.ptr(scratch), st))
+            sigma = out[:, 3:4].contiguous()
+        else:
+            dirs = torch.zeros_like(pts)                 # the density does not depend on the view direction
+            rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            sigma = torch.empty((n, 1), dtype=torch.float32, device=dev)
+            L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(pts), L.ptr(dirs), None, n, L.ptr(rgb), L.ptr(sigma), cb, nbytes, st))
+            g_rgb, g_den = torch.zeros_like(rgb), torch.ones_like(sigma)          # (named: they must outlive the launch's pointers)
+            L.check(lib.nrf_mlp_backward(h, mode, L.ptr(rgb), L.ptr(sigma), L.ptr(g_rgb), L.ptr(g_den), n, cb, nbytes, L.ptr(scratch), st))
+        _, g, _ = _input_grad(module, mode, n, buf, nbytes, dev, positions=pts, want_p=True)
+    norm = g.norm(dim=-1, keepdim=True)
+    normals = torch.where(norm > 0, -g / norm.clamp_min(1e-30), torch.zeros_like(g))
+    return sigma, normals
 
 
 # ---------------------------------------------------------------------------------------------
@@ -306,10 +383,11 @@ def mlp_v1_train(module, x_enc):
 # ---------------------------------------------------------------------------------------------
 class _CompositeFn(torch.autograd.Function):
     """rgb (R,S,Cs>=3 strided), sigma (R,S strided) -> rgb_map, depth, weights; gradients for rgb and sigma only
-    (the reference never differentiates the sample depths or ray directions)."""
+    (the reference never differentiates the sample depths or ray directions) unless `geom`: then also for z and d
+    (nrf_composite_backward_geom)."""
 
     @staticmethod
-    def forward(ctx, packed, z, d, white_bkgd):
+    def forward(ctx, packed, z, d, white_bkgd, geom=False):
         R, S = z.shape
         dev = z.device
         out_rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
@@ -319,7 +397,7 @@ class _CompositeFn(torch.autograd.Function):
             L.check(L.lib().nrf_composite(L.ptr(packed), 4, C.c_void_p(packed.data_ptr() + 12), 4, L.ptr(z), L.ptr(d), R, S,
                                           int(bool(white_bkgd)), L.ptr(out_rgb), L.ptr(out_depth), L.ptr(out_w), L.stream_ptr()))
         ctx.save_for_backward(packed, z, d)
-        ctx.white = int(bool(white_bkgd))
+        ctx.white, ctx.geom = int(bool(white_bkgd)), bool(geom)
         ctx.set_materialize_grads(False)      # unused outputs arrive as None, not as zero tensors
         return out_rgb, out_depth, out_w
 
@@ -333,16 +411,27 @@ class _CompositeFn(torch.autograd.Function):
             return None if g is None else g.to(torch.float32).contiguous()
         g_rgb, g_depth, g_w = prep(g_rgb), prep(g_depth), prep(g_w)
         d_packed = torch.empty_like(packed)
+        if g_rgb is None and g_depth is None and g_w is None:
+            return None, None, None, None, None
         with torch.cuda.device(dev):
+            if ctx.geom:
+                d_z, d_d = torch.empty_like(z), torch.empty_like(d)
+                L.check(L.lib().nrf_composite_backward_geom(L.ptr(packed), 4, C.c_void_p(packed.data_ptr() + 12), 4, L.ptr(z), L.ptr(d), R, S,
+                                                            ctx.white, L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w), L.ptr(d_packed), 4,
+                                                            C.c_void_p(d_packed.data_ptr() + 12), 4, L.ptr(d_z), L.ptr(d_d), L.stream_ptr()))
+                return d_packed, d_z, d_d, None, None
             L.check(L.lib().nrf_composite_backward(L.ptr(packed), 4, C.c_void_p(packed.data_ptr() + 12), 4, L.ptr(z), L.ptr(d), R, S, ctx.white,
                                                    L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w), L.ptr(d_packed), 4,
                                                    C.c_void_p(d_packed.data_ptr() + 12), 4, L.stream_ptr()))
-        return d_packed, None, None, None
+        return d_packed, None, None, None, None
 
 
-def composite(rgb_sigma, z, d, white_bkgd=False):
-    """Differentiable alpha compositing of (R,S,4) [r,g,b,sigma] rows."""
-    return _CompositeFn.apply(rgb_sigma.contiguous(), z, d, white_bkgd)
+def composite(rgb_sigma, z, d, white_bkgd=False, geom_grad=False):
+    """Differentiable alpha compositing of (R,S,4) [r,g,b,sigma] rows.  geom_grad=True: z (R,S) and d (R,3) that require grad
+    receive dL/d z_vals and dL/d rays_d (through |rays_d|) as well."""
+    if geom_grad:
+        return _CompositeFn.apply(rgb_sigma.contiguous(), z.to(torch.float32).contiguous(), d.to(torch.float32).contiguous(), white_bkgd, True)
+    return _CompositeFn.apply(rgb_sigma.contiguous(), z, d, white_bkgd, False)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -432,12 +521,113 @@ class _RenderFn(torch.autograd.Function):
 _encoders = {}
 
 
+def _encoder(pos_freq):
+    from .positional_encoding import PositionalEncoding
+    enc = _encoders.get(pos_freq)
+    if enc is None:
+        enc = _encoders[pos_freq] = PositionalEncoding(pos_freq)
+    return enc
+
+
+class _RenderGeomFn(torch.autograd.Function):
+    """_RenderFn of a V1 / V2 module built with input_grad=True whose rays or depths require grad: the same forward launches, and a
+    backward that also runs the geometric compositor backward, the input-gradient kernel and the adjoint of the points:
+    gradients for rays_o, rays_d and explicit depths as well as the parameters."""
+
+    @staticmethod
+    def forward(ctx, module, o, d, z, z_live, pts, white, mma_mode, *params):
+        dev = z.device
+        R, S = z.shape
+        n = R * S
+        h, mode = _train_handle(module, dev, mma_mode)
+        v1 = module.net == L.NRF_NET_V1
+        lib = L.lib()
+        dirs = None if v1 else d[:, None, :].expand(R, S, 3).reshape(-1, 3).contiguous()
+        with torch.cuda.device(dev):
+            nbytes = lib.nrf_train_context_bytes(h, mode, n)
+            if nbytes < 0:
+                raise L.NrfError(-2, lib.nrf_last_error().decode("utf-8", "replace"))
+            buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+            o4 = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            out_rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+            out_depth = torch.empty((R,), dtype=torch.float32, device=dev)
+            out_w = torch.empty((R, S), dtype=torch.float32, device=dev)
+            st, cb = L.stream_ptr(), C.c_void_p(buf.data_ptr())
+            if v1:
+                L.check(lib.nrf_mlp_forward_train_v1(h, mode, L.ptr(_encoder(module.pos_freq)(pts)), n, L.ptr(o4), cb, nbytes, st))
+                L.check(lib.nrf_composite(L.ptr(o4), 4, C.c_void_p(o4.data_ptr() + 12), 4, L.ptr(z), L.ptr(d), R, S, white,
+                                          L.ptr(out_rgb), L.ptr(out_depth), L.ptr(out_w), st))
+            else:
+                rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
+                L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(pts), L.ptr(dirs), None, n, L.ptr(rgb), L.ptr(den), cb, nbytes, st))
+                L.check(lib.nrf_composite(L.ptr(rgb), 3, L.ptr(den), 1, L.ptr(z), L.ptr(d), R, S, white, L.ptr(out_rgb), L.ptr(out_depth), L.ptr(out_w), st))
+        ctx.module, ctx.buf, ctx.nbytes, ctx.mode, ctx.white, ctx.v1, ctx.z_live = module, buf, nbytes, mode, white, v1, bool(z_live)
+        ctx.versions = module._packed
+        ctx.save_for_backward(o4, z, d, pts, dirs)
+        ctx.set_materialize_grads(False)
+        return out_rgb, out_depth, out_w
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_w):
+        module = ctx.module
+        if module._versions() != ctx.versions:
+            raise RuntimeError("NeRFMLP parameters were modified between render_rays and backward: the saved activations "
+                               "no longer match the packed weights")
+        o4, z, d, pts, dirs = ctx.saved_tensors
+        R, S = z.shape
+        n = R * S
+        dev = z.device
+        lib = L.lib()
+
+        def prep(g):
+            return None if g is None else g.to(torch.float32).contiguous()
+        g_rgb, g_depth, g_w = prep(g_rgb), prep(g_depth), prep(g_w)
+        n_in = 8
+        fp = module.flat_params()
+        if g_rgb is None and g_depth is None and g_w is None:
+            return (None,) * (n_in + len(fp.offsets))
+        direct = None
+        if any(ctx.needs_input_grad[n_in:]):
+            direct = _grad_target(module)
+        grad = direct if direct is not None else torch.zeros_like(fp.flat)      # (frozen parameters: a scratch vector)
+        with torch.cuda.device(dev):
+            d4 = torch.empty_like(o4)
+            d_zc, d_dc = torch.empty_like(z), torch.empty_like(d)
+            st, cb = L.stream_ptr(), C.c_void_p(ctx.buf.data_ptr())
+            if ctx.v1:
+                L.check(lib.nrf_composite_backward_geom(L.ptr(o4), 4, C.c_void_p(o4.data_ptr() + 12), 4, L.ptr(z), L.ptr(d), R, S, ctx.white,
+                                                        L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w), L.ptr(d4), 4, C.c_void_p(d4.data_ptr() + 12), 4,
+                                                        L.ptr(d_zc), L.ptr(d_dc), st))
+                L.check(lib.nrf_mlp_backward_v1(module._handle, ctx.mode, L.ptr(o4), L.ptr(d4), n, cb, ctx.nbytes, L.ptr(grad), st))
+            else:
+                rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
+                d_rgb, d_den = d4.view(-1)[:3 * n].view(n, 3), d4.view(-1)[3 * n:].view(n, 1)
+                L.check(lib.nrf_composite_backward_geom(L.ptr(rgb), 3, L.ptr(den), 1, L.ptr(z), L.ptr(d), R, S, ctx.white,
+                                                        L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w), L.ptr(d_rgb), 3, L.ptr(d_den), 1,
+                                                        L.ptr(d_zc), L.ptr(d_dc), st))
+                L.check(lib.nrf_mlp_backward(module._handle, ctx.mode, L.ptr(rgb), L.ptr(den), L.ptr(d_rgb), L.ptr(d_den), n, cb, ctx.nbytes,
+                                             L.ptr(grad), st))
+            _, d_p, d_dirs = _input_grad(module, ctx.mode, n, ctx.buf, ctx.nbytes, dev, positions=pts, directions=dirs, want_p=True,
+                                         want_d=not ctx.v1)
+            d_o, d_d = torch.empty_like(d), torch.empty_like(d)
+            d_z = torch.empty_like(z) if ctx.z_live else None
+            L.check(lib.nrf_ray_grad(L.ptr(d_p), L.ptr(d_dirs), L.ptr(z), L.ptr(d), L.ptr(d_zc), L.ptr(d_dc), R, S, L.ptr(d_o), L.ptr(d_d),
+                                     L.ptr(d_z), st))
+        ctx.buf = None
+        ins = (None, d_o, d_d, d_z) + (None,) * (n_in - 4)
+        if direct is not None or not any(ctx.needs_input_grad[n_in:]):
+            return ins + (None,) * len(fp.offsets)
+        return ins + tuple(fp.views(grad))
+
+
 def render_rays_train(module, rays_o, rays_d, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False,
                       white_bkgd=False, dino=None, z_in=None, mma_mode=None, tail_mode=None):
     """renderer.render_rays when grad is enabled: the reference's own sequence (train.py:188-242) -- stratified samples,
     [project + fetch DINO features,] NeRFMLP, VolumeRenderer -- returning {'rgb','depth','weights','z_vals'} that carry a grad_fn.
     Gradients reach the parameters and, for a module built with dino_grad=True, a dino['features'] map that requires grad (through
-    the adjoint of the bilinear fetch, nrf_project_fetch_backward); rays and depths are data: a tensor that requires grad is refused.
+    the adjoint of the bilinear fetch, nrf_project_fetch_backward); rays and depths are data: a tensor that requires grad is refused,
+    unless the module was built with input_grad=True: then rays_o, rays_d and z_in that require grad receive gradients (the ladder's
+    own depths are constants).
     The arithmetic mode is `mma_mode` (default: the module's own) mapped to a training mode (_lib.TRAIN_MODE: the split mode
     trains in exact fp32); early ray termination does not apply.  A `tail_mode` (renderer.render_rays) is refused: the training
     kernels have no split-f16 mode, and a silently different forward would be worse than a refusal."""
@@ -445,6 +635,22 @@ def render_rays_train(module, rays_o, rays_d, near, far, n_samples, perturb=True
         raise ValueError("tail_mode is an inference option: the training kernels have no split-f16 mode (render under "
                          "torch.no_grad() or model.eval())")
     from .ray_sampler import sample_points_along_rays
+    if module._wants_input_grad(rays_o, rays_d, z_in):
+        o_live = _live_input(module, rays_o, "render_rays(rays_o)").reshape(-1, 3)
+        d_live = _live_input(module, rays_d, "render_rays(rays_d)", o_live.device).reshape(-1, 3)
+        o, d = o_live.detach(), d_live.detach()
+        R, S = o.shape[0], int(n_samples)
+        z_live = None
+        if z_in is not None:
+            z_live = _live_input(module, z_in, "render_rays(z_in)", o.device).reshape(R, S)
+            z = z_live.detach()
+            pts = o[:, None, :] + d[:, None, :] * z[:, :, None]
+        else:
+            pts, z = sample_points_along_rays(o, d, near, far, S, perturb=perturb, lindisp=lindisp, t_rand=t_rand, seed=seed)
+        live = z_live is not None and z_live.requires_grad
+        rgb, depth, w = _RenderGeomFn.apply(module, o_live, d_live, z_live if live else z, live, pts.reshape(-1, 3).contiguous(),
+                                            int(bool(white_bkgd)), mma_mode, *module.flat_params().params())
+        return {"rgb": rgb, "depth": depth, "weights": w, "z_vals": z_live if live else z}
     o = L.dev_f32(L.refuse_grad(rays_o, "render_rays(rays_o)")).reshape(-1, 3)
     d = L.dev_f32(L.refuse_grad(rays_d, "render_rays(rays_d)"), o.device).reshape(-1, 3)
     R, S = o.shape[0], int(n_samples)
