@@ -331,6 +331,23 @@ int nrf_project_fetch_backward(const nrf_dino* dino, const float* points, int64_
 int nrf_sample_features_backward(int Hp, int Wp, int C, const float* points_2d, int64_t n, const float* d_feats,
                                  float* d_map, int accumulate, void* ws, int64_t ws_bytes, void* stream);
 
+/* The adjoints of the two fetches with respect to the points -- what autograd through ray_utils.py:176-210 and F.grid_sample hands
+ * to points (or rays, or a pose) that require grad: with m_ab the texel row at (x0+a, y0+b), or 0 where that tap is off the map
+ * (selected out, not multiplied by 0: a NaN / Inf texel reaches only the samples that have it among their on-map taps), and
+ * (tx, ty) the fractional texel coordinates,
+ *   G_x = sum_c g_c [(1-ty)(m_10 - m_00) + ty (m_11 - m_01)],   G_y = sum_c g_c [(1-tx)(m_01 - m_00) + tx (m_11 - m_10)],
+ *   d_xy = (G_x Wp/2, G_y Hp/2)                                                   (nrf_sample_features_backward_points, (n,2))
+ *   d_points = inv_pose[:3,:3]^T (d_x 2f/(W Zi), d_y 2f/(H Zi), -(d_x 2f X/W + d_y 2f Y/H)/Zi^2),  Zi = Z + 1e-8  ((n,3))
+ * the same gx, gy, floor and on-map test as the forward.  The fetch is piecewise bilinear: on a texel edge the derivative is the
+ * one of the cell floor() selects.  A sample with no tap on the map gets +0.  accumulate != 0 adds onto d_points (the V3 input
+ * gradient: onto nrf_mlp_backward_inputs_v3's d_positions); otherwise the output is overwritten.  No atomics: a sample's result
+ * is bit-identical from run to run and does not depend on the batch around it.  No gradient with respect to the source view's
+ * pose or intrinsics. */
+int nrf_project_fetch_backward_points(const nrf_dino* dino, const float* points, int64_t n, const float* d_feats,
+                                      float* d_points, int accumulate, void* stream);
+int nrf_sample_features_backward_points(const float* features, int Hp, int Wp, int C, const float* points_2d, int64_t n,
+                                        const float* d_feats, float* d_xy, void* stream);
+
 /* ---- host-only introspection (no GPU needed; used by the CPU test-suite to replay the
  *      kernel's MFMA walk over the packed stream) -------------------------------- */
 /* Packs `linears` exactly as nrf_model_create would for `mma_mode`.  stream_out / bias_out may be
@@ -360,6 +377,13 @@ int nrf_debug_pack_dino_grad(const nrf_arch* arch, const nrf_linear* linears, in
  * restricted to the direction-encoding tile, 1 output tile x 4 K tiles. */
 int nrf_debug_pack_input_grad(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int mma_mode,
                               uint8_t* stream_out, int64_t stream_cap, int64_t* stream_bytes);
+
+/* NRF_NET_V3, host-only: the fragment stream of nrf_mlp_backward_inputs_v3's A operands, every layer from a 16-fragment boundary.
+ * Layer 0: W0p^T, the positional-encoding columns of dino_fusion.fusion.0 transposed, pe_tiles(pos_freq) output tiles x 8 K tiles
+ * in (m, t, s) order and the slot order of nrf_debug_pack_input_grad.  Layer 1: color_layers.0^T restricted to the
+ * direction-encoding tile, 1 output tile x 4 K tiles. */
+int nrf_debug_pack_input_grad_v3(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int mma_mode,
+                                 uint8_t* stream_out, int64_t stream_cap, int64_t* stream_bytes);
 
 /* Host-only: how render_kernel / render_hold_kernel deal a launch of n_rays rays x n_samples samples to the workgroups of a device
  * with n_cu compute units, for a geometry of cols_per_wave sample columns per wave (64: NRF_MMA_BF16 / F16, 32: the fp32-class modes).
@@ -450,12 +474,27 @@ int nrf_mlp_backward_dino(nrf_model* m, int mma_mode, int64_t n, void* ctx, int6
  *   d_directions (n,3)        V2 only: the same for the view directions; reads `directions` (n,3).
  * Rows >= n are not written; the outputs are overwritten.  A sample's result does not depend on the batch around it and two runs
  * give the same bits.  NRF_EINVAL before any launch for NRF_NET_V3 (it also needs the adjoint of the projection and bilinear
- * fetch with respect to the points), d_x_enc on another family than V1, d_directions on V1, a missing positions / directions
+ * fetch with respect to the points: nrf_mlp_backward_inputs_v3 and nrf_project_fetch_backward_points), d_x_enc on another family than V1, d_directions on V1, a missing positions / directions
  * where its derivative is asked for, no output at all, a pointer that is not 4-byte aligned, a context that is too small, or
  * stale backward weights (nrf_model_update_device).  n == 0 is NRF_OK and launches nothing. */
 int nrf_mlp_backward_inputs(nrf_model* m, int mma_mode, int64_t n, void* ctx, int64_t ctx_bytes,
                             const float* positions, const float* directions,
                             float* d_x_enc, float* d_positions, float* d_directions, void* stream);
+
+/* NRF_NET_V3, after nrf_mlp_backward on the same ctx (same n and mode): the gradient with respect to positions and directions
+ * through the positional encodings, from the two dZ tiles of dino_fusion.fusion.0, the gate and the dZ tiles of color_layers.0 that
+ * the backward saved: dL/d PE(pos) = W0p^T d1 + w0 (W0p^T d2) (joined in fp32), dL/d PE(dir) as for V2, then the adjoint of the
+ * encodings.  One more launch; nrf_train_context_bytes does not change.  This is NOT all of dL/d positions: the features the
+ * forward read were fetched at the projections of the same points.  That share is nrf_mlp_backward_dino's d_dino handed to
+ * nrf_project_fetch_backward_points with accumulate = 1 on this call's d_positions.  (On fields of the reference's initialisation
+ * it is 100 to 3000 times smaller than the share through the encoding: test it on its own.)
+ * Either output may be NULL (not computed), not both; rows >= n are not written; the outputs are overwritten.  A sample's result
+ * does not depend on the batch around it and two runs give the same bits.  NRF_EINVAL before any launch for another network
+ * family, a missing positions / directions where its derivative is asked for, a pointer that is not 4-byte aligned, a context
+ * that is too small, or stale backward weights.  n == 0 is NRF_OK and launches nothing. */
+int nrf_mlp_backward_inputs_v3(nrf_model* m, int mma_mode, int64_t n, void* ctx, int64_t ctx_bytes,
+                               const float* positions, const float* directions,
+                               float* d_positions, float* d_directions, void* stream);
 
 /* Backward of nrf_composite (autograd through nerf_mlp.py:181-212): given
  * dL/d rgb_map (n_rays,3), optionally dL/d depth (n_rays) and dL/d weights

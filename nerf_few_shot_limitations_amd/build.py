@@ -31,7 +31,7 @@ TAIL = [("fused_tail.hip", "fused_tail", HALF32)]
 # empty-space skipping (fused_impl.hpp: render_queue_occ_kernel): units of their own, both halves with the flags of their fused_v* siblings
 OCC = [(f"fused_occ_{fam}.hip", f"fused_occ_{fam}_{half}", flags) for fam in ("v1", "v2", "v3", "v3w") for half, flags in (("16", HALF16), ("32", HALF32))]
 SOURCES = FUSED + OCC + TAIL + [(f, os.path.splitext(f)[0], []) for f in
-                   ("fused_kernels.hip", "train_shared.hip", "train_v1.hip", "train_v2.hip", "train_v3.hip", "train_dino_grad.hip", "train_input_grad.hip", "staged_kernels.hip", "api.cpp",
+                   ("fused_kernels.hip", "train_shared.hip", "train_v1.hip", "train_v2.hip", "train_v3.hip", "train_dino_grad.hip", "train_input_grad.hip", "train_input_grad_v3.hip", "staged_kernels.hip", "api.cpp",
                     "packing.cpp")]
 # -Rpass-analysis=kernel-resource-usage: the backend reports every kernel's registers / spills / scratch; kept beside the object
 # (<name>.o.remarks, see kernel_resources()) so that a toolchain or flag change that breaks the AGPR parking or introduces

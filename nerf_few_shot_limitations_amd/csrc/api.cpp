@@ -104,7 +104,7 @@ struct nrf_model {
     nrf::ParamLayout layout;
     nrf::NetPlan bplan;                     // the dZ chain's layers, and behind them (V3) the feature-gradient kernel's W0d^T layer:
     int g_frags16 = 0;                      // one device stream, one gather table, one re-pack, one freshness flag; 16-bit fragments of that layer
-    int i_frags16[2] = {0, 0};              // V1 / V2: the same for input_grad_kernel's W0^T and (V2) color_layers.0^T layers
+    int i_frags16[2] = {0, 0};              // the same for input_grad_kernel's W0^T and (V2) color_layers.0^T layers; V3: input_grad_v3_kernel's, behind W0d^T
     nrf::TrainPlan tplan;
     nrf::TrainDev train{};
     void* d_bstream[3] = {nullptr, nullptr, nullptr};
@@ -180,6 +180,13 @@ int ensure_train(nrf_model* m) {
         if (!nrf::make_dino_grad_plan(m->arch, m->lin, gplan, err)) return fail(NRF_EUNSUPPORTED, err);
         m->g_frags16 = gplan.layers[0].MT * gplan.layers[0].KT * 2;
         m->bplan.layers.push_back(gplan.layers[0]);
+        // and behind it W0p^T and color_layers.0^T's direction tile (train_input_grad_v3_impl.hpp)
+        nrf::NetPlan iplan;
+        if (!nrf::make_input_grad_v3_plan(m->arch, m->lin, iplan, err)) return fail(NRF_EUNSUPPORTED, err);
+        for (size_t i = 0; i < iplan.layers.size() && i < 2; ++i) {
+            m->i_frags16[i] = iplan.layers[i].MT * iplan.layers[i].KT * 2;
+            m->bplan.layers.push_back(iplan.layers[i]);
+        }
     } else {
         // W0^T and color_layers.0^T restricted to the encodings (train_input_grad_impl.hpp) ride there in the same way
         nrf::NetPlan iplan;
@@ -200,7 +207,7 @@ int ensure_train(nrf_model* m) {
         m->train.bstream[mode] = m->d_bstream[mode];
         m->train.n_bchunks[mode] = ps.n_chunks - g_chunks - i_chunks;
         m->train.gstream[mode] = g_chunks ? static_cast<const char*>(m->d_bstream[mode]) + (size_t)m->train.n_bchunks[mode] * 16 * 1024 : nullptr;
-        m->train.istream[mode] = i_chunks ? static_cast<const char*>(m->d_bstream[mode]) + (size_t)m->train.n_bchunks[mode] * 16 * 1024 : nullptr;
+        m->train.istream[mode] = i_chunks ? static_cast<const char*>(m->d_bstream[mode]) + ((size_t)m->train.n_bchunks[mode] + g_chunks) * 16 * 1024 : nullptr;
         m->bfresh[mode] = !m->lin_stale;
     }
     for (int f32 = 0; f32 < 2; ++f32) {
@@ -793,7 +800,8 @@ int nrf_mlp_backward_inputs(nrf_model* m, int mma_mode, int64_t n, void* ctx, in
                             float* d_x_enc, float* d_positions, float* d_directions, void* stream) {
     auto wrong = [&]() -> const char* {
         if (m->arch.net == NRF_NET_V3)
-            return "nrf_mlp_backward_inputs: the V3 network also needs the adjoint of the projection and the bilinear fetch with respect to the points";
+            return "nrf_mlp_backward_inputs: the V3 network also needs the adjoint of the projection and the bilinear fetch with respect to the points "
+                   "(nrf_mlp_backward_inputs_v3, then nrf_project_fetch_backward_points)";
         if (m->arch.net != NRF_NET_V1 && m->arch.net != NRF_NET_V2) return "nrf_mlp_backward_inputs: unknown network family";
         if (!d_x_enc && !d_positions && !d_directions) return "nrf_mlp_backward_inputs: no output asked for";
         if (d_x_enc && m->arch.net != NRF_NET_V1) return "nrf_mlp_backward_inputs: d_x_enc belongs to the V1 network (encoded inputs)";
@@ -808,6 +816,23 @@ int nrf_mlp_backward_inputs(nrf_model* m, int mma_mode, int64_t n, void* ctx, in
     return train_entry(m, mma_mode, n, !ctx, ctx_bytes, true, wrong, [&](std::string& err) {
         return nrf::launch_input_grad(m->net, m->train, mma_mode, n, ctx, positions, directions, d_x_enc, d_positions, d_directions,
                                       (hipStream_t)stream, err);
+    });
+}
+
+int nrf_mlp_backward_inputs_v3(nrf_model* m, int mma_mode, int64_t n, void* ctx, int64_t ctx_bytes, const float* positions, const float* directions,
+                               float* d_positions, float* d_directions, void* stream) {
+    auto wrong = [&]() -> const char* {
+        if (m->arch.net != NRF_NET_V3) return "nrf_mlp_backward_inputs_v3: only the V3 network (V1 / V2: nrf_mlp_backward_inputs)";
+        if (!d_positions && !d_directions) return "nrf_mlp_backward_inputs_v3: no output asked for";
+        if (d_positions && !positions) return "nrf_mlp_backward_inputs_v3: d_positions needs the positions";
+        if (d_directions && !directions) return "nrf_mlp_backward_inputs_v3: d_directions needs the directions";
+        if (((reinterpret_cast<uintptr_t>(d_positions) | reinterpret_cast<uintptr_t>(d_directions) | reinterpret_cast<uintptr_t>(positions) |
+              reinterpret_cast<uintptr_t>(directions)) & 3u) != 0)
+            return "nrf_mlp_backward_inputs_v3: float tensors must be 4-byte aligned";
+        return nullptr;
+    };
+    return train_entry(m, mma_mode, n, !ctx, ctx_bytes, true, wrong, [&](std::string& err) {
+        return nrf::launch_input_grad_v3(m->net, m->train, mma_mode, n, ctx, positions, directions, d_positions, d_directions, (hipStream_t)stream, err);
     });
 }
 
@@ -1080,6 +1105,33 @@ int nrf_sample_features_backward(int Hp, int Wp, int C, const float* points_2d, 
     return r == NRF_OK ? NRF_OK : fail(r, "sample_features backward launch failed");
 }
 
+int nrf_project_fetch_backward_points(const nrf_dino* dino, const float* points, int64_t n, const float* d_feats, float* d_points, int accumulate,
+                                      void* stream) {
+    if (n < 0) return fail(NRF_EINVAL, "n < 0");
+    if (n == 0) return NRF_OK;
+    if (!points || !d_feats || !d_points) return fail(NRF_EINVAL, "null pointer");
+    if (((reinterpret_cast<uintptr_t>(points) | reinterpret_cast<uintptr_t>(d_feats) | reinterpret_cast<uintptr_t>(d_points)) & 3u) != 0)
+        return fail(NRF_EINVAL, "nrf_project_fetch_backward_points: float tensors must be 4-byte aligned");
+    nrf::DinoDev d{};
+    std::string err;
+    if (!make_dino(dino, 0, d, err)) return fail(NRF_EINVAL, err);
+    if ((reinterpret_cast<uintptr_t>(d.features) & 3u) != 0) return fail(NRF_EINVAL, "nrf_project_fetch_backward_points: float tensors must be 4-byte aligned");
+    const int r = nrf::launch_project_fetch_backward_points(d, points, n, d_feats, d_points, accumulate, (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "project_fetch backward (points) launch failed");
+}
+
+int nrf_sample_features_backward_points(const float* features, int Hp, int Wp, int C, const float* points_2d, int64_t n, const float* d_feats,
+                                        float* d_xy, void* stream) {
+    if (n < 0 || Hp < 1 || Wp < 1 || C < 1) return fail(NRF_EINVAL, "bad sizes");
+    if (n == 0) return NRF_OK;
+    if (!features || !points_2d || !d_feats || !d_xy) return fail(NRF_EINVAL, "null pointer");
+    if (((reinterpret_cast<uintptr_t>(features) | reinterpret_cast<uintptr_t>(points_2d) | reinterpret_cast<uintptr_t>(d_feats) |
+          reinterpret_cast<uintptr_t>(d_xy)) & 3u) != 0)
+        return fail(NRF_EINVAL, "nrf_sample_features_backward_points: float tensors must be 4-byte aligned");
+    const int r = nrf::launch_sample_features_backward_points(features, Hp, Wp, C, points_2d, n, d_feats, d_xy, (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "sample_features backward (points) launch failed");
+}
+
 int nrf_debug_pack_dino_grad(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int mma_mode, uint8_t* stream_out, int64_t stream_cap,
                              int64_t* stream_bytes) {
     if (!arch || !linears || n_linear <= 0) return fail(NRF_EINVAL, "nrf_debug_pack_dino_grad: null argument");
@@ -1105,6 +1157,23 @@ int nrf_debug_pack_input_grad(const nrf_arch* arch, const nrf_linear* linears, i
     std::vector<nrf::HostLinear> lin;
     nrf::NetPlan plan;
     if (!copy_linears(linears, n_linear, lin, err) || !nrf::make_input_grad_plan(*arch, lin, plan, err)) return fail(NRF_EINVAL, err);
+    const nrf::PackedStream ps = nrf::pack_stream(plan, lin, mma_mode);
+    if (stream_bytes) *stream_bytes = (int64_t)ps.bytes.size();
+    if (stream_out) {
+        if (stream_cap < (int64_t)ps.bytes.size()) return fail(NRF_EINVAL, "stream_out too small");
+        std::memcpy(stream_out, ps.bytes.data(), ps.bytes.size());
+    }
+    return NRF_OK;
+}
+
+int nrf_debug_pack_input_grad_v3(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int mma_mode, uint8_t* stream_out, int64_t stream_cap,
+                                 int64_t* stream_bytes) {
+    if (!arch || !linears || n_linear <= 0) return fail(NRF_EINVAL, "nrf_debug_pack_input_grad_v3: null argument");
+    if (mma_mode < 0 || mma_mode > 2) return fail(NRF_EINVAL, "unknown mma_mode");
+    std::string err;
+    std::vector<nrf::HostLinear> lin;
+    nrf::NetPlan plan;
+    if (!copy_linears(linears, n_linear, lin, err) || !nrf::make_input_grad_v3_plan(*arch, lin, plan, err)) return fail(NRF_EINVAL, err);
     const nrf::PackedStream ps = nrf::pack_stream(plan, lin, mma_mode);
     if (stream_bytes) *stream_bytes = (int64_t)ps.bytes.size();
     if (stream_out) {

@@ -108,7 +108,8 @@ struct TrainDev {
     int job_x_slot[kMaxJobs], job_dz_slot[kMaxJobs], job_KT[kMaxJobs], job_MT[kMaxJobs], job_x_first[kMaxJobs];
     int64_t n_params;
     const void* gstream[3];     // V3: the W0d^T fragments of dino_grad_kernel (train_dino_grad_impl.hpp), behind the chain's layers in bstream
-    const void* istream[3];     // V1, V2: the W0^T (and color_layers.0^T) fragments of input_grad_kernel (train_input_grad_impl.hpp), likewise
+    const void* istream[3];     // V1, V2: the W0^T (and color_layers.0^T) fragments of input_grad_kernel (train_input_grad_impl.hpp), likewise;
+                                // V3: the W0p^T and color_layers.0^T fragments of input_grad_v3_kernel (train_input_grad_v3_impl.hpp), behind gstream's
 };
 
 int64_t train_ctx_bytes(const TrainDev& t, int mma_mode, int64_t n);
@@ -155,6 +156,10 @@ int launch_dino_grad(const DeviceNet& net, const TrainDev& t, int mma_mode, int6
 // output is not computed
 int launch_input_grad(const DeviceNet& net, const TrainDev& t, int mma_mode, int64_t n, void* ctx, const float* positions, const float* directions,
                       float* d_x_enc, float* d_positions, float* d_directions, hipStream_t s, std::string& err);
+// V3, after launch_train_backward_v3 on the same context: dL/d positions and directions through the positional encodings alone (the
+// share through the fetched features: launch_dino_grad, then launch_project_fetch_backward_points); a NULL output is not computed
+int launch_input_grad_v3(const DeviceNet& net, const TrainDev& t, int mma_mode, int64_t n, void* ctx, const float* positions, const float* directions,
+                         float* d_positions, float* d_directions, hipStream_t s, std::string& err);
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd, int step,
                 const float* ray_loss, int64_t n_rays, float loss_weight, float* loss, hipStream_t s);
 int launch_mse_grad(const float* pred, const float* target, int64_t n, float weight, float* g_pred, float* loss, hipStream_t s);
@@ -233,5 +238,10 @@ int launch_project_fetch_backward(const DinoDev& d, const float* points, int64_t
                                   hipStream_t s);
 int launch_sample_features_backward(int Hp, int Wp, int C, const float* points_2d, int64_t n, const float* d_feats, float* d_map, int accumulate,
                                     float* ws, hipStream_t s);
+// adjoints of the two fetches with respect to the points: d_points (n,3) = [d_points +] (projection o fetch)^T d_feats (n,C), or d_xy (n,2)
+int launch_project_fetch_backward_points(const DinoDev& d, const float* points, int64_t n, const float* d_feats, float* d_points, int accumulate,
+                                         hipStream_t s);
+int launch_sample_features_backward_points(const float* features, int Hp, int Wp, int C, const float* points_2d, int64_t n, const float* d_feats,
+                                           float* d_xy, hipStream_t s);
 
 }  // namespace nrf

@@ -440,6 +440,33 @@ bool make_input_grad_plan(const nrf_arch& a, const std::vector<HostLinear>& lin,
     return true;
 }
 
+// The A operands of input_grad_v3_kernel (train_input_grad_v3_impl.hpp), the V3 sibling of the plan above.  Layer 0: W0p^T, the
+// F0T layer of make_backward_plan restricted to the PT positional tiles of fusion.0's input (make_dino_grad_plan takes the DT
+// tiles behind them) -- K = fusion.0's 256 rows, rcol = the forward plan's col of those tiles.  Layer 1: color_layers.0^T
+// restricted to its direction-encoding tile, as for V2.
+bool make_input_grad_v3_plan(const nrf_arch& a, const std::vector<HostLinear>& lin, NetPlan& plan, std::string& err) {
+    plan = NetPlan();
+    if (a.net != NRF_NET_V3) { err = "this input-gradient plan belongs to the V3 network"; return false; }
+    NetPlan fwd;
+    if (!make_plan(a, lin, fwd, err)) return false;
+    const int H = a.hidden, HT = H / 32, n = a.n_layers, DT = a.dino_dim / 32;
+    const LayerPlan& F0 = fwd.layers[0];
+    const int PT = F0.KT - DT;
+    LayerPlan L; L.transposed = true; L.KT = HT; L.MT = PT; L.krow.assign(32 * HT, {-1, 0});
+    for (int k = 0; k < H; ++k) L.krow[k] = {0, k};
+    L.rcol.assign(F0.col.begin(), F0.col.begin() + 32 * PT);
+    L.bias_off = 0;
+    plan.layers.push_back(std::move(L));
+    const LayerPlan& C0 = fwd.layers[7 + n + 2];                                   // [feature_vec | PE(dir)] -> 128 (make_train_plan: colour branch at 7 + n)
+    LayerPlan D; D.transposed = true; D.KT = H / 64; D.MT = 1; D.krow.assign(32 * D.KT, {-1, 0});
+    for (int k = 0; k < H / 2; ++k) D.krow[k] = {5 + n + 2, k};
+    D.rcol.assign(C0.col.begin() + H, C0.col.begin() + H + 32);
+    D.bias_off = 32 * PT;
+    plan.layers.push_back(std::move(D));
+    plan.n_bias = 32 * PT + 32;
+    return true;
+}
+
 bool make_train_plan(const nrf_arch& a, const NetPlan& fwd, const ParamLayout& lay, TrainPlan& tp, std::string& err) {
     tp = TrainPlan();
     if (a.net != NRF_NET_V1 && a.net != NRF_NET_V2 && a.net != NRF_NET_V3) { err = "unknown network family"; return false; }

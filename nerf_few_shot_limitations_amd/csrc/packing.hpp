@@ -55,6 +55,8 @@ bool make_backward_plan(const nrf_arch& arch, const std::vector<HostLinear>& lin
 bool make_dino_grad_plan(const nrf_arch& arch, const std::vector<HostLinear>& lin, NetPlan& plan, std::string& err);
 // W0^T (positional-encoding tiles) and, V2, color_layers.0^T (direction-encoding tile) of input_grad_kernel
 bool make_input_grad_plan(const nrf_arch& arch, const std::vector<HostLinear>& lin, NetPlan& plan, std::string& err);
+// V3: W0p^T (the positional-encoding tiles of dino_fusion.fusion.0) and color_layers.0^T (direction-encoding tile) of input_grad_v3_kernel
+bool make_input_grad_v3_plan(const nrf_arch& arch, const std::vector<HostLinear>& lin, NetPlan& plan, std::string& err);
 
 // Where every element of a packed stream comes from: flat-parameter offset, -1 = zero.  Elements in stream
 // order (fragment, lane, element); 512 per fragment in the 16-bit modes, 256 in the fp32 mode.  The host packer

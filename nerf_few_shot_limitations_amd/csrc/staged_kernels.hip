@@ -751,6 +751,126 @@ int fetch_backward_impl(const DinoDev& d, const float* points, int points2d, int
     return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
 }
 
+// Adjoint of project_fetch_kernel with respect to the point: the bilinear fetch's derivative along x and y (the same gx, gy,
+// floorf and on-map test as the forward; piecewise constant in the sample, with a kink at every texel edge), the normalisation,
+// the pinhole projection with Zi = Z + 1e-8, and inv_pose's rotation.  With m_ab the texel row at (x0 + a, y0 + b), or 0 where
+// that tap is off the map, and (tx, ty) = (gx - x0, gy - y0):
+//     G_x = sum_c g_c [(1 - ty)(m_10 - m_00) + ty (m_11 - m_01)]        G_y = sum_c g_c [(1 - tx)(m_01 - m_00) + tx (m_11 - m_10)]
+//     d_xn = G_x Wp / 2,  d_yn = G_y Hp / 2                              (points2d: these two are the result)
+//     d_pc = (d_xn 2f / (W Zi),  d_yn 2f / (H Zi),  -(d_xn 2f X / W + d_yn 2f Y / H) / Zi^2),      d_p_j = sum_i inv_pose[i][j] d_pc_i
+// An off-map tap is selected out, not multiplied by 0: a NaN / Inf texel reaches only the samples that have it among their
+// on-map taps, and a sample with no tap on the map gets +0.  kFetchPtLanes lanes per sample: each takes every kFetchPtLanes-th
+// group of 4 channels of the d_feats row and of the four tap rows (16-byte loads; the map is L2-resident) in ascending
+// order, then a fixed xor-shuffle tree adds the lanes' sums -- no atomics, so a sample's result is bit-reproducible and does
+// not depend on the batch around it -- and lane 0 writes.  Per sample 4 C bytes of d_feats read, 12 (8) B written, + 12 B read
+// when accumulating.
+constexpr int kFetchPtLanes = 16;
+
+struct FetchVec { float v[4]; };
+
+// channels c0 .. c0 + 3 of a row: one 16-byte load, or (VEC == false: C no multiple of 4, or a misaligned base) the ones below C
+template <bool VEC>
+__device__ __forceinline__ FetchVec fetch_vec_load(const float* row, int c0, int C) {
+    FetchVec r;
+    if constexpr (VEC) {
+        const float4 q = *(const float4*)(row + c0);
+        r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r.v[k] = c0 + k < C ? row[c0 + k] : 0.0f;
+    }
+    return r;
+}
+
+template <bool VEC>
+__global__ void __launch_bounds__(kBlock) fetch_points_backward_kernel(DinoDev d, const float* __restrict__ points, int64_t n,
+                                                                       const float* __restrict__ d_feats, float* __restrict__ out, int points2d,
+                                                                       int accumulate) {
+    constexpr int kGroups = kBlock / kFetchPtLanes;
+    const int sub = threadIdx.x % kFetchPtLanes, grp = threadIdx.x / kFetchPtLanes;
+    for (int64_t base = blockIdx.x * (int64_t)kGroups; base < n; base += (int64_t)gridDim.x * kGroups) {
+        const bool live = base + grp < n;
+        const int64_t pi = live ? base + grp : n - 1;            // groups past the end keep their lanes in the shuffles and write nothing
+        float xn, yn, pc[3] = {0.0f, 0.0f, 0.0f};
+        if (points2d) {
+            xn = points[pi * 2]; yn = points[pi * 2 + 1];
+        } else {
+            const float p[3] = {points[pi * 3], points[pi * 3 + 1], points[pi * 3 + 2]};
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+                pc[i] = d.inv_pose[4 * i + 0] * p[0] + d.inv_pose[4 * i + 1] * p[1] + d.inv_pose[4 * i + 2] * p[2] + d.inv_pose[4 * i + 3];
+            project_point(d, p, xn, yn);
+        }
+        const float gx = ((xn + 1.0f) * (float)d.Wp - 1.0f) * 0.5f;
+        const float gy = ((yn + 1.0f) * (float)d.Hp - 1.0f) * 0.5f;
+        const float x0 = floorf(gx), y0 = floorf(gy);
+        const float tx = gx - x0, ty = gy - y0;
+        bool on[4];
+        const float* row[4];
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const float xi = x0 + dx, yi = y0 + dy;
+                const bool ok = xi >= 0.0f && xi <= (float)(d.Wp - 1) && yi >= 0.0f && yi <= (float)(d.Hp - 1);
+                on[2 * dy + dx] = ok;
+                row[2 * dy + dx] = d.features + (ok ? ((int64_t)yi * d.Wp + (int64_t)xi) * d.C : 0);
+            }
+        const bool any = on[0] || on[1] || on[2] || on[3];
+        float Gx = 0.0f, Gy = 0.0f;
+        if (any) {
+            const float* g_row = d_feats + pi * d.C;
+            for (int c0 = sub * 4; c0 < d.C; c0 += kFetchPtLanes * 4) {
+                const FetchVec g = fetch_vec_load<VEC>(g_row, c0, d.C);
+                FetchVec m[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    if (on[k]) m[k] = fetch_vec_load<VEC>(row[k], c0, d.C);
+                    else m[k] = FetchVec{{0.0f, 0.0f, 0.0f, 0.0f}};
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (!VEC && c0 + q >= d.C) continue;
+                    const float m00 = m[0].v[q], m10 = m[1].v[q], m01 = m[2].v[q], m11 = m[3].v[q];
+                    Gx += g.v[q] * ((1.0f - ty) * (m10 - m00) + ty * (m11 - m01));
+                    Gy += g.v[q] * ((1.0f - tx) * (m01 - m00) + tx * (m11 - m10));
+                }
+            }
+        }
+#pragma unroll
+        for (int m = kFetchPtLanes / 2; m >= 1; m >>= 1) {
+            Gx += __shfl_xor(Gx, m, kFetchPtLanes);
+            Gy += __shfl_xor(Gy, m, kFetchPtLanes);
+        }
+        if (!live || sub != 0) continue;
+        const float dxn = Gx * ((float)d.Wp * 0.5f), dyn = Gy * ((float)d.Hp * 0.5f);
+        if (points2d) {
+            out[pi * 2] = any ? dxn : 0.0f;
+            out[pi * 2 + 1] = any ? dyn : 0.0f;
+            continue;
+        }
+        const float zi = pc[2] + 1e-8f;
+        const float ax = dxn * (2.0f * d.focal / (float)d.W), ay = dyn * (2.0f * d.focal / (float)d.H);
+        const float dpc[3] = {ax / zi, ay / zi, -(ax * pc[0] + ay * pc[1]) / (zi * zi)};
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const float v = d.inv_pose[j] * dpc[0] + d.inv_pose[4 + j] * dpc[1] + d.inv_pose[8 + j] * dpc[2];
+            const float r = any ? v : 0.0f;
+            out[pi * 3 + j] = accumulate ? out[pi * 3 + j] + r : r;
+        }
+    }
+}
+
+int fetch_points_backward_impl(const DinoDev& d, const float* points, int points2d, int64_t n, const float* d_feats, float* out, int accumulate,
+                               hipStream_t s) {
+    if (n <= 0) return NRF_OK;
+    const unsigned grid = grid_for(n * kFetchPtLanes, kBlock, 8192);
+    const bool vec = d.C % 4 == 0 && ((reinterpret_cast<uintptr_t>(d.features) | reinterpret_cast<uintptr_t>(d_feats)) & 15u) == 0;
+    if (vec) hipLaunchKernelGGL(fetch_points_backward_kernel<true>, dim3(grid), dim3(kBlock), 0, s, d, points, n, d_feats, out, points2d, accumulate);
+    else hipLaunchKernelGGL(fetch_points_backward_kernel<false>, dim3(grid), dim3(kBlock), 0, s, d, points, n, d_feats, out, points2d, accumulate);
+    return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
+}
+
 // ---- occupancy bit grids (nerfhip.h: nrf_occupancy) ----------------------------------------------
 // Cell c is occupied iff one of its k consecutive densities is > threshold or NaN; a wave packs 64 cells into two words with one
 // ballot, lanes 0 and 32 store them.  The loop bound is wave-uniform (whole waves step together), so the ballot sees every lane.
@@ -1106,6 +1226,18 @@ int launch_sample_features_backward(int Hp, int Wp, int C, const float* points_2
     DinoDev d{};
     d.Hp = Hp; d.Wp = Wp; d.C = C;
     return fetch_backward_impl(d, points_2d, 1, n, d_feats, d_map, accumulate, ws, s);
+}
+
+int launch_project_fetch_backward_points(const DinoDev& d, const float* points, int64_t n, const float* d_feats, float* d_points, int accumulate,
+                                         hipStream_t s) {
+    return fetch_points_backward_impl(d, points, 0, n, d_feats, d_points, accumulate, s);
+}
+
+int launch_sample_features_backward_points(const float* features, int Hp, int Wp, int C, const float* points_2d, int64_t n, const float* d_feats,
+                                           float* d_xy, hipStream_t s) {
+    DinoDev d{};
+    d.features = features; d.Hp = Hp; d.Wp = Wp; d.C = C;
+    return fetch_points_backward_impl(d, points_2d, 1, n, d_feats, d_xy, 0, s);
 }
 
 }  // namespace nrf

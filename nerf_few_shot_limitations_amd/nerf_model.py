@@ -16,6 +16,10 @@ requires grad is refused instead of silently detached (the reference computes it
 `input_grad=True` (legacy and trainer form without DINO) backpropagates to the inputs of the field as well:
 x_encoded (legacy form), positions and directions (trainer form) that require grad receive gradients, which is
 what pose refinement, surface normals (`density_normals`) and depth-distribution losses need.
+`point_grad=True` is that switch for the use_dino form: positions, directions and dino_features that require grad receive
+gradients.  dL/d positions of NeRFMLP.forward is the share through the positional encoding; the share through the features
+belongs to whoever fetched them (`dino_features.project_points_to_image` / `sample_features_at_points` with point_grad=True, or
+`render_rays`, which does both in one autograd node).
 """
 from __future__ import annotations
 
@@ -73,13 +77,16 @@ class _FreqBuffer(nn.Module):          # nerf_mlp.py:14-15 registers freq_bands 
 
 class NeRFMLP(nn.Module):
     def __init__(self, pos_dim=63, hidden_dim=256, n_layers=8, *, pos_freq=None, dir_freq=4, num_density_layers=None,
-                 use_dino=False, dino_dim=0, mma_mode="f32", dino_grad=False, input_grad=False):
+                 use_dino=False, dino_dim=0, mma_mode="f32", dino_grad=False, input_grad=False, point_grad=False):
         super().__init__()
         if input_grad and use_dino and pos_freq is not None:
             raise ValueError("input_grad=True is built for the forms without DINO features: a use_dino model (V3) also needs the adjoint of "
-                             "the projection and the bilinear fetch with respect to the points, which does not exist yet")
+                             "the projection and the bilinear fetch with respect to the points; build it with point_grad=True instead")
+        if point_grad and not (use_dino and pos_freq is not None):
+            raise ValueError("point_grad=True belongs to the use_dino form (V3): the forms without DINO features take input_grad=True")
         self.mma_mode = mma_mode
         self.input_grad = bool(input_grad)   # opt-in: backpropagate into x_encoded / positions / directions / rays that require grad
+        self.point_grad = bool(point_grad)   # the same for the use_dino form: positions, directions, DINO features, rays, depths
         self.dino_grad = bool(dino_grad)     # opt-in: backpropagate into dino_features / feature maps that require grad
         self.hidden_dim = int(hidden_dim)
         if pos_freq is None:
@@ -250,13 +257,13 @@ class NeRFMLP(nn.Module):
     def _wants_input_grad(self, *inputs):
         """An input_grad module under grad mode with an input that requires grad: the training kernels run even when every
         parameter is frozen."""
-        return (self.__dict__.get("input_grad", False) and torch.is_grad_enabled()
+        return ((self.__dict__.get("input_grad", False) or self.__dict__.get("point_grad", False)) and torch.is_grad_enabled()
                 and any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs))
 
     def forward(self, positions, directions=None, dino_features=None, points=None):
         """`points` (legacy form of an input_grad module): the (P,3) positions that `positions` (= x_encoded) encodes; when they
         require grad they receive dL/d points through the adjoint of the encoding."""
-        if self._wants_grad() or self._wants_input_grad(positions, directions, points):
+        if self._wants_grad() or self._wants_input_grad(positions, directions, points, dino_features):
             from .training import mlp_v1_train, mlp_v2_train
             if self.net == L.NRF_NET_V1:
                 return mlp_v1_train(self, positions, points)
@@ -285,11 +292,18 @@ class NeRFMLP(nn.Module):
             return rgb, dens
 
 
-def density_normals(model: NeRFMLP, points):
+def density_normals(model: NeRFMLP, points, dino=None):
     """(density (P,1), normals (P,3)) of an input_grad model at `points` (P,3): normals = -grad(sigma) / |grad(sigma)| (zero where the
-    gradient vanishes), from ONE saving forward and one input-gradient backward.  Parameter gradients are not touched."""
+    gradient vanishes), from ONE saving forward and one input-gradient backward.  Parameter gradients are not touched.
+    A point_grad model (use_dino form) also takes the source view dino=dict(features=, pose=, focal=, H=, W=): its density depends
+    on the point through the features fetched at the point's projection as well."""
+    if getattr(model, "point_grad", False):
+        if dino is None:
+            raise ValueError("density_normals of a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
+        from .training import field_input_grad_v3
+        return field_input_grad_v3(model, points, dino)
     if not getattr(model, "input_grad", False):
-        raise ValueError("density_normals needs a model built with NeRFMLP(..., input_grad=True)")
+        raise ValueError("density_normals needs a model built with NeRFMLP(..., input_grad=True) (use_dino form: point_grad=True)")
     from .training import field_input_grad
     return field_input_grad(model, points)
 

@@ -127,8 +127,9 @@ def _dino_grad(module, mode, n, buf, nbytes, dev, out=None):
 
 def _live_input(module, t, what, device=None):
     """An input of the field as the kernels read it.  A tensor that requires grad stays in the graph on a module built with
-    input_grad=True and is refused otherwise (_lib.refuse_grad)."""
-    if torch.is_grad_enabled() and isinstance(t, torch.Tensor) and t.requires_grad and getattr(module, "input_grad", False):
+    input_grad=True (use_dino form: point_grad=True) and is refused otherwise (_lib.refuse_grad)."""
+    if (torch.is_grad_enabled() and isinstance(t, torch.Tensor) and t.requires_grad
+            and (getattr(module, "input_grad", False) or getattr(module, "point_grad", False))):
         if device is None:
             device = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
         return t.to(device=device, dtype=torch.float32).contiguous()
@@ -147,6 +148,39 @@ def _input_grad(module, mode, n, buf, nbytes, dev, positions=None, directions=No
     L.check(L.lib().nrf_mlp_backward_inputs(module._handle, mode, n, C.c_void_p(buf.data_ptr()), nbytes, L.ptr(positions) if want_p else None,
                                             L.ptr(directions) if want_d else None, L.ptr(d_x), L.ptr(d_p), L.ptr(d_d), L.stream_ptr()))
     return d_x, d_p, d_d
+
+
+def _input_grad_v3(module, mode, n, buf, nbytes, dev, positions=None, directions=None, want_p=False, want_d=False):
+    """(d_positions, d_directions) -- None where not asked for -- of a V3 module through the positional encodings, from the context
+    of a finished nrf_mlp_backward (one launch).  The share of d_positions through the fetched features is not in it
+    (points_fetch_backward)."""
+    if not (want_p or want_d):
+        return None, None
+    d_p = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_p else None
+    d_d = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_d else None
+    L.check(L.lib().nrf_mlp_backward_inputs_v3(module._handle, mode, n, C.c_void_p(buf.data_ptr()), nbytes, L.ptr(positions) if want_p else None,
+                                               L.ptr(directions) if want_d else None, L.ptr(d_p), L.ptr(d_d), L.stream_ptr()))
+    return d_p, d_d
+
+
+def points_fetch_backward(dino, points, d_feats, d_points=None):
+    """d_points (n,3) [+]= the adjoint of nrf_project_fetch with respect to `points` (n,3) applied to d_feats (n,C), for the source
+    view dino = dict(features= (1,Hp,Wp,C), pose=, focal=, H=, W=).  With d_points given the result is added onto it (the V3 input
+    gradient: onto the share through the positional encoding); otherwise a new tensor is returned.  Bit-reproducible."""
+    from .renderer import make_dino
+    dn, keep = make_dino(**dino)
+    dev = keep.device
+    pts = L.dev_f32(points, dev).reshape(-1, 3)
+    g = L.dev_f32(d_feats, dev).reshape(pts.shape[0], -1)
+    if g.shape[1] != dn.C:
+        raise ValueError("d_feats must hold one row of C channels per point")
+    acc = d_points is not None
+    if not acc:
+        d_points = torch.empty((pts.shape[0], 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().nrf_project_fetch_backward_points(C.byref(dn), L.ptr(pts), pts.shape[0], L.ptr(g), L.ptr(d_points), int(acc), L.stream_ptr()))
+    del keep
+    return d_points
 
 
 _fetch_ws = {}
@@ -300,8 +334,12 @@ class _MLPV2Fn(torch.autograd.Function):
             # dino_grad modules with features that require grad: one more launch over what the backward saved
             d_dino = _dino_grad(module, ctx.mode, ctx.n, ctx.buf, ctx.nbytes, dev) if ctx.needs_input_grad[3] else None
             # input_grad modules with positions / directions that require grad: likewise
-            _, d_p, d_d = _input_grad(module, ctx.mode, ctx.n, ctx.buf, ctx.nbytes, dev, positions=pos, directions=dirs,
-                                      want_p=ctx.needs_input_grad[1], want_d=ctx.needs_input_grad[2])
+            if module.net == L.NRF_NET_V3:               # point_grad modules: the share through the positional encodings
+                d_p, d_d = _input_grad_v3(module, ctx.mode, ctx.n, ctx.buf, ctx.nbytes, dev, positions=pos, directions=dirs,
+                                          want_p=ctx.needs_input_grad[1], want_d=ctx.needs_input_grad[2])
+            else:
+                _, d_p, d_d = _input_grad(module, ctx.mode, ctx.n, ctx.buf, ctx.nbytes, dev, positions=pos, directions=dirs,
+                                          want_p=ctx.needs_input_grad[1], want_d=ctx.needs_input_grad[2])
         ctx.buf = None
         if direct is not None:
             return (None, d_p, d_d, d_dino) + (None,) * len(fp.offsets)
@@ -319,7 +357,7 @@ def mlp_v2_train(module, positions, directions, dino_features=None):
         if dino_features is None:
             raise ValueError("use_dino=True needs dino_features")
         if torch.is_grad_enabled() and getattr(dino_features, "requires_grad", False):
-            if not getattr(module, "dino_grad", False):
+            if not (getattr(module, "dino_grad", False) or getattr(module, "point_grad", False)):
                 raise NotImplementedError("no gradient with respect to the DINO features is produced by default (the reference computes "
                                           "its maps under no_grad: SURVEY.md section 8 f4); detach them, or build the module with "
                                           "NeRFMLP(..., dino_grad=True)")
@@ -342,6 +380,41 @@ def mlp_v1_train(module, x_enc, points=None):
             raise ValueError("points must hold one (x,y,z) row per row of x_encoded")
     out = _MLPV1Fn.apply(module, flat_in, pts, *module.flat_params().params())
     return out.reshape(*x.shape[:-1], 4)
+
+
+def field_input_grad_v3(module, points, dino):
+    """nerf_model.density_normals of a point_grad (V3) module: the fetch, one saving forward, the dZ chain with dL/d sigma = 1 (its
+    parameter gradients go to a scratch vector), dL/d features, the input-gradient kernel and the adjoint of the fetch added onto it."""
+    from .renderer import make_dino
+    pts = L.dev_f32(points).reshape(-1, 3)
+    dev, n = pts.device, pts.shape[0]
+    h, mode = _train_handle(module, dev)
+    lib = L.lib()
+    dn, keep = make_dino(**{**dino, "features": L.dev_f32(dino["features"], dev)})
+    if dn.C != module.dino_dim:
+        raise ValueError("features must be (1,Hp,Wp,dino_dim)")
+    with torch.cuda.device(dev):
+        nbytes = lib.nrf_train_context_bytes(h, mode, n)
+        if nbytes < 0:
+            raise L.NrfError(-2, lib.nrf_last_error().decode("utf-8", "replace"))
+        buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        scratch = torch.zeros_like(module.flat_params().flat)
+        st, cb = L.stream_ptr(), C.c_void_p(buf.data_ptr())
+        feats = torch.empty((n, dn.C), dtype=torch.float32, device=dev)
+        L.check(lib.nrf_project_fetch(C.byref(dn), L.ptr(pts), n, L.ptr(feats), None, st))
+        dirs = torch.zeros_like(pts)                     # the density does not depend on the view direction
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        sigma = torch.empty((n, 1), dtype=torch.float32, device=dev)
+        L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(pts), L.ptr(dirs), L.ptr(feats), n, L.ptr(rgb), L.ptr(sigma), cb, nbytes, st))
+        g_rgb, g_den = torch.zeros_like(rgb), torch.ones_like(sigma)
+        L.check(lib.nrf_mlp_backward(h, mode, L.ptr(rgb), L.ptr(sigma), L.ptr(g_rgb), L.ptr(g_den), n, cb, nbytes, L.ptr(scratch), st))
+        d_feats = _dino_grad(module, mode, n, buf, nbytes, dev)
+        g, _ = _input_grad_v3(module, mode, n, buf, nbytes, dev, positions=pts, want_p=True)
+        L.check(lib.nrf_project_fetch_backward_points(C.byref(dn), L.ptr(pts), n, L.ptr(d_feats), L.ptr(g), 1, st))
+    del keep
+    norm = g.norm(dim=-1, keepdim=True)
+    normals = torch.where(norm > 0, -g / norm.clamp_min(1e-30), torch.zeros_like(g))
+    return sigma, normals
 
 
 def field_input_grad(module, points):
@@ -620,14 +693,110 @@ class _RenderGeomFn(torch.autograd.Function):
         return ins + tuple(fp.views(grad))
 
 
+class _RenderPointFn(torch.autograd.Function):
+    """_RenderGeomFn of a V3 module built with point_grad=True whose rays or depths require grad.  Forward: project + fetch, the
+    saving forward, the compositor.  Backward, one node: the geometric compositor backward, the V3 dZ chain, dino_grad_kernel into a
+    scratch d_feats, input_grad_v3_kernel, fetch_points_backward_kernel adding onto its d_positions, the adjoint of the points; a
+    live feature map (a dino_grad module) receives d_map from the same d_feats."""
+
+    @staticmethod
+    def forward(ctx, module, o, d, z, z_live, pts, fmap, dino, white, mma_mode, *params):
+        from .renderer import make_dino
+        dev = z.device
+        R, S = z.shape
+        n = R * S
+        h, mode = _train_handle(module, dev, mma_mode)
+        lib = L.lib()
+        dirs = d[:, None, :].expand(R, S, 3).reshape(-1, 3).contiguous()
+        fm = fmap.detach().contiguous()
+        dn, keep = make_dino(**{**dino, "features": fm})
+        with torch.cuda.device(dev):
+            nbytes = lib.nrf_train_context_bytes(h, mode, n)
+            if nbytes < 0:
+                raise L.NrfError(-2, lib.nrf_last_error().decode("utf-8", "replace"))
+            buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+            o4 = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            out_rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+            out_depth = torch.empty((R,), dtype=torch.float32, device=dev)
+            out_w = torch.empty((R, S), dtype=torch.float32, device=dev)
+            feats = torch.empty((n, dn.C), dtype=torch.float32, device=dev)
+            st, cb = L.stream_ptr(), C.c_void_p(buf.data_ptr())
+            L.check(lib.nrf_project_fetch(C.byref(dn), L.ptr(pts), n, L.ptr(feats), None, st))
+            rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
+            L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(pts), L.ptr(dirs), L.ptr(feats), n, L.ptr(rgb), L.ptr(den), cb, nbytes, st))
+            L.check(lib.nrf_composite(L.ptr(rgb), 3, L.ptr(den), 1, L.ptr(z), L.ptr(d), R, S, white, L.ptr(out_rgb), L.ptr(out_depth), L.ptr(out_w), st))
+        del keep
+        ctx.module, ctx.buf, ctx.nbytes, ctx.mode, ctx.white, ctx.z_live, ctx.dino = module, buf, nbytes, mode, white, bool(z_live), dino
+        ctx.versions = module._packed
+        ctx.save_for_backward(o4, z, d, pts, dirs, fm)
+        ctx.set_materialize_grads(False)
+        return out_rgb, out_depth, out_w
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_w):
+        from .renderer import make_dino
+        module = ctx.module
+        if module._versions() != ctx.versions:
+            raise RuntimeError("NeRFMLP parameters were modified between render_rays and backward: the saved activations "
+                               "no longer match the packed weights")
+        o4, z, d, pts, dirs, fm = ctx.saved_tensors
+        R, S = z.shape
+        n = R * S
+        dev = z.device
+        lib = L.lib()
+
+        def prep(g):
+            return None if g is None else g.to(torch.float32).contiguous()
+        g_rgb, g_depth, g_w = prep(g_rgb), prep(g_depth), prep(g_w)
+        n_in = 10
+        fp = module.flat_params()
+        if g_rgb is None and g_depth is None and g_w is None:
+            return (None,) * (n_in + len(fp.offsets))
+        direct = None
+        if any(ctx.needs_input_grad[n_in:]):
+            direct = _grad_target(module)
+        grad = direct if direct is not None else torch.zeros_like(fp.flat)      # (frozen parameters: a scratch vector)
+        dn, keep = make_dino(**{**ctx.dino, "features": fm})
+        d_map = None
+        with torch.cuda.device(dev):
+            d4 = torch.empty_like(o4)
+            d_zc, d_dc = torch.empty_like(z), torch.empty_like(d)
+            st, cb = L.stream_ptr(), C.c_void_p(ctx.buf.data_ptr())
+            rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
+            d_rgb, d_den = d4.view(-1)[:3 * n].view(n, 3), d4.view(-1)[3 * n:].view(n, 1)
+            L.check(lib.nrf_composite_backward_geom(L.ptr(rgb), 3, L.ptr(den), 1, L.ptr(z), L.ptr(d), R, S, ctx.white,
+                                                    L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w), L.ptr(d_rgb), 3, L.ptr(d_den), 1,
+                                                    L.ptr(d_zc), L.ptr(d_dc), st))
+            L.check(lib.nrf_mlp_backward(module._handle, ctx.mode, L.ptr(rgb), L.ptr(den), L.ptr(d_rgb), L.ptr(d_den), n, cb, ctx.nbytes,
+                                         L.ptr(grad), st))
+            d_feats = _dino_grad(module, ctx.mode, n, ctx.buf, ctx.nbytes, dev)
+            d_p, d_dirs = _input_grad_v3(module, ctx.mode, n, ctx.buf, ctx.nbytes, dev, positions=pts, directions=dirs, want_p=True, want_d=True)
+            L.check(lib.nrf_project_fetch_backward_points(C.byref(dn), L.ptr(pts), n, L.ptr(d_feats), L.ptr(d_p), 1, st))
+            if ctx.needs_input_grad[6]:                  # a live feature map
+                d_map = torch.empty_like(fm)
+                ws = fetch_backward_workspace(dn.Hp, dn.Wp, dn.C, n, dev)
+                L.check(lib.nrf_project_fetch_backward(C.byref(dn), L.ptr(pts), n, L.ptr(d_feats), L.ptr(d_map), 0, L.ptr(ws), ws.numel() * 4, st))
+            d_o, d_d = torch.empty_like(d), torch.empty_like(d)
+            d_z = torch.empty_like(z) if ctx.z_live else None
+            L.check(lib.nrf_ray_grad(L.ptr(d_p), L.ptr(d_dirs), L.ptr(z), L.ptr(d), L.ptr(d_zc), L.ptr(d_dc), R, S, L.ptr(d_o), L.ptr(d_d),
+                                     L.ptr(d_z), st))
+        del keep
+        ctx.buf = None
+        ins = (None, d_o, d_d, d_z, None, None, d_map) + (None,) * (n_in - 7)
+        if direct is not None or not any(ctx.needs_input_grad[n_in:]):
+            return ins + (None,) * len(fp.offsets)
+        return ins + tuple(fp.views(grad))
+
+
 def render_rays_train(module, rays_o, rays_d, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False,
                       white_bkgd=False, dino=None, z_in=None, mma_mode=None, tail_mode=None):
     """renderer.render_rays when grad is enabled: the reference's own sequence (train.py:188-242) -- stratified samples,
     [project + fetch DINO features,] NeRFMLP, VolumeRenderer -- returning {'rgb','depth','weights','z_vals'} that carry a grad_fn.
     Gradients reach the parameters and, for a module built with dino_grad=True, a dino['features'] map that requires grad (through
     the adjoint of the bilinear fetch, nrf_project_fetch_backward); rays and depths are data: a tensor that requires grad is refused,
-    unless the module was built with input_grad=True: then rays_o, rays_d and z_in that require grad receive gradients (the ladder's
-    own depths are constants).
+    unless the module was built with input_grad=True (use_dino form: point_grad=True): then rays_o, rays_d and z_in that require grad
+    receive gradients (the ladder's own depths are constants) -- for the use_dino form through the positional encodings and through
+    the features fetched at the points' projections into the source view (whose own pose and intrinsics are data).
     The arithmetic mode is `mma_mode` (default: the module's own) mapped to a training mode (_lib.TRAIN_MODE: the split mode
     trains in exact fp32); early ray termination does not apply.  A `tail_mode` (renderer.render_rays) is refused: the training
     kernels have no split-f16 mode, and a silently different forward would be worse than a refusal."""
@@ -648,6 +817,20 @@ def render_rays_train(module, rays_o, rays_d, near, far, n_samples, perturb=True
         else:
             pts, z = sample_points_along_rays(o, d, near, far, S, perturb=perturb, lindisp=lindisp, t_rand=t_rand, seed=seed)
         live = z_live is not None and z_live.requires_grad
+        if module.net == L.NRF_NET_V3:
+            if dino is None:
+                raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
+            fmap = dino.get("features")
+            if torch.is_grad_enabled() and getattr(fmap, "requires_grad", False) and not getattr(module, "dino_grad", False):
+                raise NotImplementedError("no gradient with respect to the DINO feature map is produced by default; detach it, or "
+                                          "build the module with NeRFMLP(..., dino_grad=True)")
+            fmap = torch.as_tensor(fmap)
+            if fmap.dim() != 4 or fmap.shape[0] != 1 or fmap.shape[3] != module.dino_dim:
+                raise ValueError("features must be (1,Hp,Wp,dino_dim)")
+            rgb, depth, w = _RenderPointFn.apply(module, o_live, d_live, z_live if live else z, live, pts.reshape(-1, 3).contiguous(),
+                                                 fmap.to(device=o.device, dtype=torch.float32), {k: v for k, v in dino.items() if k != "features"},
+                                                 int(bool(white_bkgd)), mma_mode, *module.flat_params().params())
+            return {"rgb": rgb, "depth": depth, "weights": w, "z_vals": z_live if live else z}
         rgb, depth, w = _RenderGeomFn.apply(module, o_live, d_live, z_live if live else z, live, pts.reshape(-1, 3).contiguous(),
                                             int(bool(white_bkgd)), mma_mode, *module.flat_params().params())
         return {"rgb": rgb, "depth": depth, "weights": w, "z_vals": z_live if live else z}
