@@ -638,6 +638,67 @@ typedef struct nrf_train_rays {
 int nrf_mlp_forward_train_rays(nrf_model* m, const nrf_train_rays* rays, int64_t n_rays, const nrf_render_opts* opts,
                                float* out_a, float* out_b, void* ctx, int64_t ctx_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Training under an occupancy grid.  A step under a grid G is the plain step with every sample in an empty cell of G replaced by
+ * a constant: it composites as colour (0,0,0) and EFFECTIVE density -inf -- effective means behind the density noise, so that
+ * noise_std > 0 cannot bring it back.  In the compositor that gives relu(-inf) = 0, exp(-0) = 1, alpha = 0, weight 0 and the
+ * factor 1 + 1e-10 on the transmittance; in its backward the mask [sigma > 0] is false, so d_sigma = 0, and d_rgb = w g = 0.
+ * Without noise these are the bits of density 0, which is how the *_occ renderers skip.  The network -- forward, dZ chain, weight
+ * gradients -- runs on the M occupied samples alone, as dense rows: the staged entry points (nrf_encode, nrf_project_fetch,
+ * nrf_mlp_forward_train[_v1], nrf_mlp_backward[_v1]) take any n and treat every sample independently of its neighbours.  A skipped
+ * sample passes no gradient to the parameters; the regulariser and the depth term see its weight 0.  z_vals is always the full
+ * (R,S) ladder: the interval of an evaluated sample still runs to the next ladder sample, as in the renderers.
+ * Additive to ABI 5: the struct carries its own size, nrf_abi_sizeof knows nothing of it.
+ * ------------------------------------------------------------------------ */
+typedef struct nrf_compact {
+    int32_t  struct_bytes;   /* sizeof(nrf_compact): checked by the library */
+    int32_t  reserved;       /* 0 */
+    int64_t  capacity;       /* rows the compacted outputs hold; R*S always suffices (and is required: M is not known before the call) */
+    int32_t* index;          /* out (capacity): flat sample id r*S+s of compacted row j < M, strictly ascending */
+    int32_t* slot;           /* out (R*S): compacted row of sample i, or -1 */
+    float*   positions;      /* out (capacity,3): the renderer's points, o + d*z, bit for bit */
+    float*   directions;     /* out (capacity,3): the ray's direction per row; may be NULL (V1) */
+    int64_t* count;          /* out, device [1], 8-byte aligned: M */
+    void*    workspace;      /* device, 4-byte aligned, written and read by the call */
+    int64_t  workspace_bytes; /* >= nrf_occupancy_compact_workspace_bytes(n_rays) */
+} nrf_compact;
+
+/* Bytes of workspace a compaction of n_rays rays needs (4 per ray, rounded up to 16; 16 for no ray); -1 if n_rays < 0. */
+int64_t nrf_occupancy_compact_workspace_bytes(int64_t n_rays);
+
+/* Chooses the samples of a ray batch that the grid `occ` keeps and leaves them as dense rows in ascending order of the flat id:
+ * row j of index / positions / directions belongs to sample index[j] = r*S+s, slot is the inverse map with -1 for a skipped sample.
+ * The cell of a sample is decided by the rule of nrf_occupancy above, in the same single fp32 operations on p = o + d*z, the
+ * point the network would be given (a sample outside the box follows occ->outside; a non-finite position is always kept).
+ * `rays` is the ray source of nrf_mlp_forward_train_rays -- explicit rays, or pixel ids and a camera; of `opts` the call reads the
+ * fields that entry point reads (near, far, n_samples, lindisp, perturb, t_rand, z_ladder, z_in, rng_seed), the jitter of row r,
+ * sample s of the call is counter_uniform(rng_seed, r, s).  rays->z_vals (required) and rays->rays_d_out (required in pixel mode)
+ * receive what nrf_sample_along_rays / nrf_get_rays would have written, to the bit; rays->points_out is not used.  occ->stats is
+ * not touched.  Rows >= M of the outputs are not written.
+ * Three launches on `stream` (per-ray counts, an exclusive scan of them by one workgroup, the write pass): no workgroup waits for
+ * another, no atomics; the outputs are the same bits from run to run.  Nothing synchronises: the caller reads `count` back when it
+ * needs M on the host.
+ * NRF_EINVAL, before any launch: rays, opts, occ or out NULL, a wrong struct_bytes in any of them, both or neither of rays and
+ * pixels, a missing required output (z_vals, rays_d_out in pixel mode, index, slot, positions, count), capacity < R*S,
+ * R*S > 2^31 - 1, index / slot / positions / directions / z_vals / workspace not 4-byte aligned or count not 8-byte aligned, a
+ * workspace that is NULL or too small, ert_eps > 0, and every condition nrf_occupancy refuses.  n_rays == 0 is NRF_OK and launches
+ * nothing (count is not written). */
+int nrf_occupancy_compact_rays(const nrf_train_rays* rays, int64_t n_rays, const nrf_render_opts* opts,
+                               const nrf_occupancy* occ, const nrf_compact* out, void* stream);
+
+/* nrf_composite_loss_backward on compacted rows: `slot` (n_rays, n_samples) is nrf_compact.slot, and rgb / sigma / d_rgb / d_sigma
+ * address compacted rows (row slot[i] of sample i, with their strides).  A sample with slot[i] < 0 is composited as colour (0,0,0)
+ * and effective density -inf and stores nothing; z_vals, loss->noise and loss->target_depth keep their (n_rays, n_samples) /
+ * (n_rays) layouts, the counter RNG its key (ray index in the call, sample).  With every slot[i] == i the results are
+ * nrf_composite_loss_backward's bits -- and so, with noise_std == 0, reg_weight == 0 and no target_depth, those of
+ * nrf_composite_mse_backward: the one entry serves both steps.  slot must be 4-byte aligned; everything else as
+ * nrf_composite_loss_backward. */
+int nrf_composite_loss_backward_indexed(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride,
+                                        const float* z_vals, const float* rays_d, int64_t n_rays, int n_samples, int white_bkgd,
+                                        const float* target, const nrf_loss_opts* loss, const int32_t* slot, float* pred,
+                                        float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride,
+                                        float* ray_terms, float* zero_buf, int64_t zero_n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

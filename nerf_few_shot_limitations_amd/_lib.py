@@ -92,6 +92,18 @@ def train_rays(rays_o=None, rays_d=None, pixels=None, H=0, W=0, focal=0.0, c2w=N
                           (C.c_float * 12)(*([0.0] * 12 if c2w is None else [float(x) for x in c2w])), z_vals, rays_d_out, points_out)
 
 
+class nrf_compact(C.Structure):
+    """The outputs of nrf_occupancy_compact_rays; struct_bytes is filled in by compact()."""
+    _fields_ = [("struct_bytes", C.c_int32), ("reserved", C.c_int32), ("capacity", C.c_int64), ("index", C.c_void_p), ("slot", C.c_void_p),
+                ("positions", C.c_void_p), ("directions", C.c_void_p), ("count", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64)]
+
+
+def compact(capacity=0, index=None, slot=None, positions=None, directions=None, count=None, workspace=None, workspace_bytes=0):
+    """nrf_compact with its size field set; the pointers are device addresses (ints) or None."""
+    return nrf_compact(C.sizeof(nrf_compact), 0, int(capacity), index, slot, positions, directions, count, workspace, int(workspace_bytes))
+
+
 # name -> (restype, argtypes); tests/test_packing_emulation.py checks this table against include/nerfhip.h
 SIGNATURES = {
     "nrf_abi_version": (C.c_int, []),
@@ -203,6 +215,13 @@ SIGNATURES = {
     # training from rays: sampling, encoding and the feature fetch inside the saving forward
     "nrf_mlp_forward_train_rays": (C.c_int, [C.c_void_p, C.POINTER(nrf_train_rays), C.c_int64, C.POINTER(nrf_render_opts), C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_int64, C.c_void_p]),
+    # training under an occupancy grid: compaction of the occupied samples, and the compositor / loss / backward on compacted rows
+    "nrf_occupancy_compact_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "nrf_occupancy_compact_rays": (C.c_int, [C.POINTER(nrf_train_rays), C.c_int64, C.POINTER(nrf_render_opts), C.POINTER(nrf_occupancy),
+                                             C.POINTER(nrf_compact), C.c_void_p]),
+    "nrf_composite_loss_backward_indexed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                                      C.c_void_p, C.POINTER(nrf_loss_opts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                      C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 _lib = None

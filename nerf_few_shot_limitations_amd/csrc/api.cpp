@@ -961,9 +961,12 @@ int nrf_adam_step_loss(float* params, const float* grads, float* exp_avg, float*
     return r == NRF_OK ? NRF_OK : fail(r, "adam launch failed");
 }
 
-int nrf_composite_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals, const float* rays_d,
-                                int64_t n_rays, int n_samples, int white_bkgd, const float* target, const nrf_loss_opts* loss, float* pred,
-                                float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf,
+extern "C++" {
+namespace {
+// nrf_composite_loss_backward and its indexed form (slot != NULL: rgb / sigma / d_rgb / d_sigma hold compacted rows)
+int composite_loss_backward_any(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals, const float* rays_d,
+                                int64_t n_rays, int n_samples, int white_bkgd, const float* target, const nrf_loss_opts* loss, const int32_t* slot,
+                                float* pred, float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf,
                                 int64_t zero_n, void* stream) {
     if (!loss) return fail(NRF_EINVAL, "nrf_composite_loss_backward: loss is NULL");
     if (loss->struct_bytes != (int32_t)sizeof(nrf_loss_opts)) return fail(NRF_EINVAL, "nrf_loss_opts.struct_bytes is not sizeof(nrf_loss_opts)");
@@ -980,8 +983,76 @@ int nrf_composite_loss_backward(const float* rgb, int rgb_stride, const float* s
     lt.target_depth = loss->target_depth; lt.noise_std = loss->noise_std; lt.noise = loss->noise; lt.rng_seed = loss->rng_seed;
     const int r = nrf::launch_composite_loss_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, lt,
                                                       pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n,
-                                                      (hipStream_t)stream);
+                                                      (hipStream_t)stream, slot);
     return r == NRF_OK ? NRF_OK : fail(r, "composite + loss + backward launch failed");
+}
+}  // namespace
+}  // extern "C++"
+
+int nrf_composite_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals, const float* rays_d,
+                                int64_t n_rays, int n_samples, int white_bkgd, const float* target, const nrf_loss_opts* loss, float* pred,
+                                float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf,
+                                int64_t zero_n, void* stream) {
+    return composite_loss_backward_any(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, loss, nullptr,
+                                       pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream);
+}
+
+int nrf_composite_loss_backward_indexed(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals,
+                                        const float* rays_d, int64_t n_rays, int n_samples, int white_bkgd, const float* target,
+                                        const nrf_loss_opts* loss, const int32_t* slot, float* pred, float* d_rgb, int d_rgb_stride,
+                                        float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n, void* stream) {
+    if (!slot) return fail(NRF_EINVAL, "nrf_composite_loss_backward_indexed: slot is NULL");
+    if ((reinterpret_cast<uintptr_t>(slot) & 3u) != 0) return fail(NRF_EINVAL, "nrf_composite_loss_backward_indexed: slot must be 4-byte aligned");
+    return composite_loss_backward_any(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, loss, slot, pred,
+                                       d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream);
+}
+
+int64_t nrf_occupancy_compact_workspace_bytes(int64_t n_rays) {
+    if (n_rays < 0) { (void)fail(NRF_EINVAL, "nrf_occupancy_compact_workspace_bytes: n_rays < 0"); return -1; }
+    return nrf::occupancy_compact_ws_bytes(n_rays);
+}
+
+int nrf_occupancy_compact_rays(const nrf_train_rays* rays, int64_t n_rays, const nrf_render_opts* opts, const nrf_occupancy* occ,
+                               const nrf_compact* out, void* stream) {
+    // the order of nrf_mlp_forward_train_rays: the ray source and the options, then the grid, then the outputs
+    if (!rays) return fail(NRF_EINVAL, "nrf_occupancy_compact_rays: rays is NULL");
+    if (rays->struct_bytes != (int32_t)sizeof(nrf_train_rays)) return fail(NRF_EINVAL, "nrf_train_rays: struct_bytes is not sizeof(nrf_train_rays)");
+    if (n_rays < 0) return fail(NRF_EINVAL, "nrf_occupancy_compact_rays: n_rays < 0");
+    const int rc = check_opts(opts);
+    if (rc != NRF_OK) return rc;
+    if (opts->ert_eps > 0.0f) return fail(NRF_EINVAL, "nrf_occupancy_compact_rays takes ert_eps == 0: a training step composites every sample of the ladder");
+    const bool by_rays = rays->rays_o || rays->rays_d, by_pixels = rays->pixels != nullptr;
+    if (by_rays == by_pixels) return fail(NRF_EINVAL, "nrf_train_rays: give either rays_o and rays_d or pixels, not both and not neither");
+    if (by_rays && (!rays->rays_o || !rays->rays_d)) return fail(NRF_EINVAL, "nrf_train_rays: rays_o and rays_d come together");
+    if (by_pixels && (rays->H < 1 || rays->W < 1 || !(rays->focal > 0.0f))) return fail(NRF_EINVAL, "nrf_train_rays: bad camera for the pixels");
+    if (!rays->z_vals) return fail(NRF_EINVAL, "nrf_train_rays: output z_vals is required");
+    if (by_pixels && !rays->rays_d_out) return fail(NRF_EINVAL, "nrf_train_rays: output rays_d_out is required in pixel mode");
+    const int64_t n = (int64_t)opts->n_samples * n_rays;
+    if (n > (int64_t)INT32_MAX) return fail(NRF_EINVAL, "ray-sample count too large (n_rays * n_samples < 2^31)");
+    if (check_occ(occ, n_rays) != NRF_OK) return NRF_EINVAL;
+    if (!out) return fail(NRF_EINVAL, "nrf_occupancy_compact_rays: out is NULL");
+    if (out->struct_bytes != (int32_t)sizeof(nrf_compact)) return fail(NRF_EINVAL, "nrf_compact: struct_bytes is not sizeof(nrf_compact)");
+    if (!out->index || !out->slot || !out->positions || !out->count)
+        return fail(NRF_EINVAL, "nrf_compact: outputs index, slot, positions and count are required");
+    if (out->capacity < n) return fail(NRF_EINVAL, "nrf_compact: capacity is below n_rays * n_samples (M is not known before the call)");
+    if (((reinterpret_cast<uintptr_t>(out->index) | reinterpret_cast<uintptr_t>(out->slot) | reinterpret_cast<uintptr_t>(out->positions) |
+          reinterpret_cast<uintptr_t>(out->directions) | reinterpret_cast<uintptr_t>(rays->z_vals) | reinterpret_cast<uintptr_t>(rays->rays_d_out) |
+          reinterpret_cast<uintptr_t>(out->workspace)) & 3u) != 0)
+        return fail(NRF_EINVAL, "nrf_compact: index, slot, positions, directions, z_vals, rays_d_out and workspace must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(out->count) & 7u) != 0) return fail(NRF_EINVAL, "nrf_compact: count must be 8-byte aligned");
+    if (!out->workspace) return fail(NRF_EINVAL, "nrf_compact: workspace is NULL");
+    if (out->workspace_bytes < nrf::occupancy_compact_ws_bytes(n_rays))
+        return fail(NRF_EINVAL, "nrf_compact: workspace smaller than nrf_occupancy_compact_workspace_bytes");
+    if (n_rays == 0) return NRF_OK;
+    nrf::TrainRaysDev r{};
+    r.rays_o = rays->rays_o; r.rays_d = rays->rays_d; r.pixels = rays->pixels;
+    if (by_pixels) r.cam = make_camera(rays->H, rays->W, rays->focal, rays->c2w);
+    r.lad = nrf::make_ladder(opts->near, opts->far, opts->n_samples, opts->lindisp, opts->z_ladder);
+    r.perturb = opts->perturb; r.t_rand = opts->perturb ? opts->t_rand : nullptr; r.z_in = opts->z_in; r.seed = opts->rng_seed;
+    r.z_vals = rays->z_vals; r.rays_d_out = rays->rays_d_out;
+    const int rl = nrf::launch_occupancy_compact(r, n_rays, make_occ(occ), out->capacity, out->index, out->slot, out->positions, out->directions,
+                                                 out->count, out->workspace, (hipStream_t)stream);
+    return rl == NRF_OK ? NRF_OK : fail(rl, "occupancy_compact launch failed");
 }
 
 int64_t nrf_grad_sqnorm_workspace_bytes(int64_t n) {

@@ -180,7 +180,7 @@ struct LossTerms {
 int launch_composite_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
                                    int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, float* pred, float* d_rgb,
                                    int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n,
-                                   hipStream_t s);
+                                   hipStream_t s, const int32_t* slot = nullptr);      // slot (R,S): the indexed form, rgb / sigma / d_* hold compacted rows
 // partial sums of squares of a flat vector (one float per workgroup, fixed order); the optimiser launch adds them up
 constexpr int kMaxSqnormPartials = 1024;
 inline int sqnorm_partials(int64_t n) {
@@ -229,6 +229,11 @@ int launch_occupancy_dilate(const uint32_t* bits_in, const int res[3], uint32_t*
 int launch_occupancy_mark(const float* rays_o, const float* rays_d, const Camera* cam, int64_t ray_begin, int64_t n_rays, int S, const float* z_vals,
                           const float* weights, const int res[3], const float lo[3], const float scale[3], float weight_threshold, float seen_eps,
                           uint32_t* hit_bits, uint32_t* seen_bits, hipStream_t s);
+// compaction in front of a training step under a grid (nerfhip.h: nrf_occupancy_compact_rays): of `r` the ray source, the sampling fields,
+// z_vals and rays_d_out are used; workspace: occupancy_compact_ws_bytes(n_rays) bytes
+int64_t occupancy_compact_ws_bytes(int64_t n_rays);
+int launch_occupancy_compact(const TrainRaysDev& r, int64_t n_rays, const OccDev& g, int64_t capacity, int32_t* index, int32_t* slot,
+                             float* positions, float* directions, int64_t* count, void* workspace, hipStream_t s);
 int launch_project_fetch(const DinoDev& d, const float* points, int64_t n, float* feats, float* xy, hipStream_t s);
 int launch_sample_features(const float* features, int Hp, int Wp, int C, const float* points_2d, int64_t n, float* feats, hipStream_t s);
 // adjoints of the two fetches with respect to the map (no atomics: per-slab private copies in `ws`, fetch_backward_ws_floats(...)

@@ -113,11 +113,16 @@ __device__ __forceinline__ float sigma_eff(float sigma, const NoiseSrc& ns, int6
 
 // One ray on one wave (LANE <-> sample, 64-sample segments front to back): every lane returns the ray's sums
 // (w2 = sum of squared weights, the regulariser of nerf_mlp.py:245: EXT only)
+// IDX (training under an occupancy grid, nerfhip.h: nrf_composite_loss_backward_indexed): rgb / sigma hold the rows of the evaluated
+// samples alone, sample i of the (R,S) ladder reads row slot[i]; slot[i] < 0 is a skipped sample, composited as colour (0,0,0) and
+// effective density -inf -- behind the noise, so that no draw brings it back.  The instantiations without IDX are the code the
+// kernels had before it existed.
 struct RaySums { float r, g, b, depth, acc, w2; };
-template <bool EXT = false>
+template <bool EXT = false, bool IDX = false>
 __device__ __forceinline__ RaySums composite_ray(const float* __restrict__ rgb, int rgb_stride, const float* __restrict__ sigma, int sigma_stride,
                                                  const float* __restrict__ z, const float* __restrict__ rays_d, int64_t r, int S, int lane,
-                                                 float* __restrict__ out_w, const NoiseSrc ns = NoiseSrc{}) {
+                                                 float* __restrict__ out_w, const NoiseSrc ns = NoiseSrc{},
+                                                 const int32_t* __restrict__ slot = nullptr) {
     const float d[3] = {rays_d[r * 3], rays_d[r * 3 + 1], rays_d[r * 3 + 2]};
     const float norm = ray_norm(d);
     float T_in = 1.0f;                                   // transmittance entering this 64-sample segment
@@ -132,7 +137,16 @@ __device__ __forceinline__ RaySums composite_ray(const float* __restrict__ rgb, 
         const bool last = (s + 1 == S);
         const float dist = last ? __fmul_rn(1e10f, norm) : __fmul_rn(__fsub_rn(zn, zc), norm);
         float alpha = 0.0f;
-        if (valid) alpha = __fsub_rn(1.0f, expf(__fmul_rn(-fmaxf(sigma_eff<EXT>(sigma[i * sigma_stride], ns, i, r, s), 0.0f), dist)));
+        int64_t row = i;                                 // the sample's row of rgb / sigma
+        if constexpr (IDX) row = slot[i];
+        if constexpr (IDX) {
+            if (valid) {
+                const float sg = row < 0 ? -__builtin_huge_valf() : sigma_eff<EXT>(sigma[row * sigma_stride], ns, i, r, s);
+                alpha = __fsub_rn(1.0f, expf(__fmul_rn(-fmaxf(sg, 0.0f), dist)));
+            }
+        } else {
+            if (valid) alpha = __fsub_rn(1.0f, expf(__fmul_rn(-fmaxf(sigma_eff<EXT>(sigma[i * sigma_stride], ns, i, r, s), 0.0f), dist)));
+        }
         const float f = valid ? __fadd_rn(__fsub_rn(1.0f, alpha), 1e-10f) : 1.0f;
         const float incl = wave_incl_prod(f, lane);
         float excl = __shfl_up(incl, 1, 64);
@@ -140,9 +154,16 @@ __device__ __forceinline__ RaySums composite_ray(const float* __restrict__ rgb, 
         const float w = __fmul_rn(alpha, __fmul_rn(T_in, excl));
         if (valid) {
             if (out_w) out_w[i] = w;
-            sr = __fadd_rn(sr, __fmul_rn(w, rgb[i * rgb_stride]));
-            sg = __fadd_rn(sg, __fmul_rn(w, rgb[i * rgb_stride + 1]));
-            sb = __fadd_rn(sb, __fmul_rn(w, rgb[i * rgb_stride + 2]));
+            if constexpr (IDX) {
+                const bool ev = row >= 0;
+                sr = __fadd_rn(sr, __fmul_rn(w, ev ? rgb[row * rgb_stride] : 0.0f));
+                sg = __fadd_rn(sg, __fmul_rn(w, ev ? rgb[row * rgb_stride + 1] : 0.0f));
+                sb = __fadd_rn(sb, __fmul_rn(w, ev ? rgb[row * rgb_stride + 2] : 0.0f));
+            } else {
+                sr = __fadd_rn(sr, __fmul_rn(w, rgb[i * rgb_stride]));
+                sg = __fadd_rn(sg, __fmul_rn(w, rgb[i * rgb_stride + 1]));
+                sb = __fadd_rn(sb, __fmul_rn(w, rgb[i * rgb_stride + 2]));
+            }
             sd = __fadd_rn(sd, __fmul_rn(w, zc));
             sa = __fadd_rn(sa, w);
             if constexpr (EXT) sw2 = __fadd_rn(sw2, __fmul_rn(w, w));
@@ -202,18 +223,21 @@ constexpr int kMaxSegments = 64;     // S <= 4096
 //   dL/d |d|    = sum_{i<S-1} dL/d dist_i (z_{i+1} - z_i) + dL/d dist_{S-1} * 1e10,   d_rays_d (R,3) = dL/d |d| * d / |d|
 // The neighbour term of a segment's first sample waits for the segment in front of it (walked later), as the suffix sum's carry
 // travels the other way.  The instantiations without GEOM are the code the kernels had before it existed.
-template <bool EXT = false, bool GEOM = false>
+// IDX: as in composite_ray; d_rgb / d_sigma address the evaluated rows too, a skipped sample stores nothing (its d_sigma is masked
+// to 0 by [-inf > 0] and its d_rgb is w g = 0: there is no row to leave them in).
+template <bool EXT = false, bool GEOM = false, bool IDX = false>
 __device__ __forceinline__ void composite_backward_ray(const float* __restrict__ rgb, int rgb_stride, const float* __restrict__ sigma,
                                                        int sigma_stride, const float* __restrict__ z, const float* __restrict__ rays_d,
                                                        int64_t r, int S, int lane, int white_bkgd, float gr, float gg, float gb, float gd,
                                                        const float* __restrict__ g_w, float* __restrict__ d_rgb, int d_rgb_stride,
                                                        float* __restrict__ d_sigma, int d_sigma_stride, float* seg_T,
                                                        const NoiseSrc ns = NoiseSrc{}, float gw_scale = 0.0f, float* __restrict__ d_z = nullptr,
-                                                       float* __restrict__ d_rays_d = nullptr) {
+                                                       float* __restrict__ d_rays_d = nullptr, const int32_t* __restrict__ slot = nullptr) {
     const int n_seg = (S + 63) / 64;
     const float d[3] = {rays_d[r * 3], rays_d[r * 3 + 1], rays_d[r * 3 + 2]};
     const float norm = ray_norm(d);
     const float bg = white_bkgd ? __fadd_rn(__fadd_rn(gr, gg), gb) : 0.0f;
+    int64_t row = 0;                                     // IDX: the row of rgb / sigma / d_rgb / d_sigma of the lane's sample, < 0 = skipped
     auto sample = [&](int s0, float& alpha, float& e, float& dist, float& f, float& zc, bool& valid, int64_t& i, float& sg) {
         const int s = s0 + lane;
         valid = s < S;
@@ -223,7 +247,12 @@ __device__ __forceinline__ void composite_backward_ray(const float* __restrict__
         if (lane == 63 && s + 1 < S) zn = z[i + 1];
         const bool last = (s + 1 == S);
         dist = last ? __fmul_rn(1e10f, norm) : __fmul_rn(__fsub_rn(zn, zc), norm);
-        sg = sigma_eff<EXT>(sigma[i * sigma_stride], ns, i, r, s);
+        if constexpr (IDX) {
+            row = slot[i];
+            sg = row < 0 ? -__builtin_huge_valf() : sigma_eff<EXT>(sigma[row * sigma_stride], ns, i, r, s);
+        } else {
+            sg = sigma_eff<EXT>(sigma[i * sigma_stride], ns, i, r, s);
+        }
         e = valid ? expf(__fmul_rn(-fmaxf(sg, 0.0f), dist)) : 1.0f;
         alpha = valid ? __fsub_rn(1.0f, e) : 0.0f;
         f = valid ? __fadd_rn(__fsub_rn(1.0f, alpha), 1e-10f) : 1.0f;
@@ -250,7 +279,11 @@ __device__ __forceinline__ void composite_backward_ray(const float* __restrict__
         const float w = __fmul_rn(alpha, T);
         float v = 0.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
         if (valid) {
-            cr = rgb[i * rgb_stride]; cg = rgb[i * rgb_stride + 1]; cb = rgb[i * rgb_stride + 2];
+            if constexpr (IDX) {
+                if (row >= 0) { cr = rgb[row * rgb_stride]; cg = rgb[row * rgb_stride + 1]; cb = rgb[row * rgb_stride + 2]; }
+            } else {
+                cr = rgb[i * rgb_stride]; cg = rgb[i * rgb_stride + 1]; cb = rgb[i * rgb_stride + 2];
+            }
             v = __fadd_rn(__fadd_rn(__fmul_rn(gr, cr), __fmul_rn(gg, cg)), __fmul_rn(gb, cb));
             v = __fadd_rn(v, __fmul_rn(gd, zc));
             if (g_w) v = __fadd_rn(v, g_w[i]);
@@ -261,12 +294,13 @@ __device__ __forceinline__ void composite_backward_ray(const float* __restrict__
         const float incl_rev = wave_incl_sum_rev(wv_, lane);
         const float suffix = __fadd_rn(__fsub_rn(incl_rev, wv_), carry);     // strictly later samples
         carry = __fadd_rn(carry, __shfl(incl_rev, 0, 64));
-        if (valid) {
+        if (IDX ? (valid && row >= 0) : valid) {
+            const int64_t o = IDX ? row : i;
             const float d_alpha = __fsub_rn(__fmul_rn(T, v), suffix / f);
-            d_sigma[i * d_sigma_stride] = sg > 0.0f ? __fmul_rn(__fmul_rn(d_alpha, dist), e) : 0.0f;
-            d_rgb[i * d_rgb_stride] = __fmul_rn(w, gr);
-            d_rgb[i * d_rgb_stride + 1] = __fmul_rn(w, gg);
-            d_rgb[i * d_rgb_stride + 2] = __fmul_rn(w, gb);
+            d_sigma[o * d_sigma_stride] = sg > 0.0f ? __fmul_rn(__fmul_rn(d_alpha, dist), e) : 0.0f;
+            d_rgb[o * d_rgb_stride] = __fmul_rn(w, gr);
+            d_rgb[o * d_rgb_stride + 1] = __fmul_rn(w, gg);
+            d_rgb[o * d_rgb_stride + 2] = __fmul_rn(w, gb);
         }
         if constexpr (GEOM) {
             float dd = 0.0f;                             // dL/d dist_i
@@ -368,6 +402,46 @@ __global__ void __launch_bounds__(kBlock) composite_loss_backward_kernel(const f
         }
         composite_backward_ray<EXT>(rgb, rgb_stride, sigma, sigma_stride, z, rays_d, r, S, lane, white_bkgd, scale * dr, scale * dg, scale * db, gd,
                                     nullptr, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, seg_T[wv], ext.noise, ext.gw_scale);
+    }
+}
+
+// The step under an occupancy grid (nrf_composite_loss_backward_indexed): the EXT = true kernel above on compacted rows -- rgb / sigma /
+// d_rgb / d_sigma hold the evaluated samples alone, `slot` (R,S) names each ladder sample's row or -1 (composite_ray: IDX).  A kernel of
+// its own, so that the two above stay the code they were.  It holds one more pointer than the scalar register file has room for next
+// to the others: the four that are touched once per ray (and live across both passes over its samples) travel in vector registers
+// instead of being spilled.
+__global__ void __launch_bounds__(kBlock) indexed_loss_backward_kernel(const float* __restrict__ rgb, int rgb_stride, const float* __restrict__ sigma,
+                                                                       int sigma_stride, const float* __restrict__ z, const float* __restrict__ rays_d,
+                                                                       int64_t n_rays, int S, int white_bkgd, const float* __restrict__ target,
+                                                                       float weight, float* __restrict__ pred, float* __restrict__ d_rgb,
+                                                                       int d_rgb_stride, float* __restrict__ d_sigma, int d_sigma_stride,
+                                                                       float* __restrict__ ray_loss, float* __restrict__ zero_buf, int64_t zero_n,
+                                                                       const LossExt ext, const int32_t* __restrict__ slot) {
+    __shared__ float seg_T[kBlock / 64][kMaxSegments];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int64_t gtid = blockIdx.x * (int64_t)kBlock + threadIdx.x, n_threads = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = gtid; i < zero_n; i += n_threads) zero_buf[i] = 0.0f;
+    const float* tdepth = ext.target_depth;
+    asm volatile("" : "+v"(target), "+v"(pred), "+v"(ray_loss), "+v"(tdepth));
+    const float count = 3.0f * (float)n_rays;
+    const float scale = 2.0f * weight / count;
+    for (int64_t r = gtid >> 6; r < n_rays; r += n_threads >> 6) {
+        RaySums o = composite_ray<true, true>(rgb, rgb_stride, sigma, sigma_stride, z, rays_d, r, S, lane, nullptr, ext.noise, slot);
+        if (white_bkgd) {
+            const float bg = __fsub_rn(1.0f, o.acc);
+            o.r = __fadd_rn(o.r, bg); o.g = __fadd_rn(o.g, bg); o.b = __fadd_rn(o.b, bg);
+        }
+        const float dr = o.r - target[r * 3], dg = o.g - target[r * 3 + 1], db = o.b - target[r * 3 + 2];
+        const float dd = tdepth ? __fsub_rn(o.depth, tdepth[r]) : 0.0f;
+        const float gd = dd > 0.0f ? ext.gd_scale : (dd < 0.0f ? -ext.gd_scale : 0.0f);          // l1_loss: sign(0) = 0
+        if (lane == 0) {
+            ray_loss[n_rays + r] = o.w2; ray_loss[2 * n_rays + r] = fabsf(dd);
+            if (pred) { pred[r * 3] = o.r; pred[r * 3 + 1] = o.g; pred[r * 3 + 2] = o.b; }
+            ray_loss[r] = dr * dr + dg * dg + db * db;
+        }
+        composite_backward_ray<true, false, true>(rgb, rgb_stride, sigma, sigma_stride, z, rays_d, r, S, lane, white_bkgd, scale * dr, scale * dg,
+                                                  scale * db, gd, nullptr, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, seg_T[wv], ext.noise,
+                                                  ext.gw_scale, nullptr, nullptr, slot);
     }
 }
 
@@ -972,7 +1046,188 @@ __global__ void __launch_bounds__(kBlock) occupancy_mark_kernel(const float* __r
     }
 }
 
+// ---- compaction in front of a training step under a grid (nerfhip.h: nrf_occupancy_compact_rays) ----------------------------------
+// Chooses the samples of a ray batch that lie in occupied cells and leaves their points, directions and flat ids as dense rows, in
+// ascending order of the flat id r * S + s.  One WAVE per ray, LANE <-> sample, 64-sample segments front to back like the marker;
+// three launches, none of which waits for another workgroup:
+//   count : a ray's kept samples (ballot + popcount per segment) -> counts[r]; z_vals and (pixel mode) rays_d_out on the way
+//   scan  : ONE workgroup turns counts[] into exclusive offsets in place, 1024 rays per round with a running carry, and leaves M
+//   write : lane ranks (mbcnt of the segment's ballot) below the ray's offset -> index / slot / positions / directions
+// Depths, rays and points are formed with sample_kernel's / get_rays_kernel's operations in their order (RaySample of train_impl.hpp
+// does the same): z_vals, rays_d_out and positions are theirs to the bit.  The cell rule is that of fused_impl.hpp:occ_skips,
+// restated here as the marker restates it.  Both passes evaluate the same pure function of (ray, depth, grid): the write pass reads
+// the depths the count pass stored.  A row index is still checked against the capacity in front of every store.
+struct CompactDev {
+    const float* rays_o;        // (R,3), or NULL: pixel mode
+    const float* rays_d;
+    const int64_t* pixels;      // pixel mode: (R) ray ids of `cam`
+    Camera cam;
+    DepthLadder lad;
+    int perturb;
+    const float* t_rand;        // (R,S) or NULL: counter_uniform(seed, row, sample)
+    const float* z_in;          // (R,S) explicit depths or NULL
+    uint64_t seed;
+    float* z_vals;              // out (R,S)
+    float* rays_d_out;          // out (R,3) or NULL
+    const uint32_t* bits;
+    int res[3];
+    float lo[3], scale[3];
+    int outside;
+};
+
+__device__ __forceinline__ void compact_ray(const CompactDev& P, int64_t r, float (&o)[3], float (&d)[3]) {
+    if (P.pixels) {
+        camera_ray(P.cam, P.pixels[r], o, d);
+        // (the origin is a load from the kernel arguments: left as one, the compiler merges it with the other branch's load into ONE
+        // load through a selected pointer and parks the selection in scratch -- train_impl.hpp:RaySample::origin_dir)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[k] = uniform_f(o[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { o[k] = P.rays_o[r * 3 + k]; d[k] = P.rays_d[r * 3 + k]; }
+    }
+}
+
+// true: the sample at p is evaluated (occ_skips negated: an empty cell skips; outside the box `outside` decides, except that a
+// non-finite position is always evaluated)
+__device__ __forceinline__ bool compact_keeps(const CompactDev& P, const float (&p)[3]) {
+    float t[3];
+    bool inside = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        t[k] = __fmul_rn(__fsub_rn(p[k], P.lo[k]), P.scale[k]);
+        inside = inside && t[k] >= 0.0f && t[k] < (float)P.res[k];              // (a NaN fails both comparisons)
+    }
+    if (!inside) {
+        const float big = __builtin_huge_valf();
+        return !(P.outside && fabsf(p[0]) < big && fabsf(p[1]) < big && fabsf(p[2]) < big);
+    }
+    const int idx = ((int)floorf(t[2]) * P.res[1] + (int)floorf(t[1])) * P.res[0] + (int)floorf(t[0]);       // < 512^3 = 2^27
+    return ((P.bits[idx >> 5] >> (idx & 31)) & 1u) != 0u;
+}
+
+__global__ void __launch_bounds__(kBlock) occupancy_compact_count_kernel(const CompactDev P, int64_t n_rays, int32_t* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const int S = P.lad.S;
+    const int64_t wave0 = (blockIdx.x * (int64_t)kBlock + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * kBlock) >> 6;
+    for (int64_t r = wave0; r < n_rays; r += n_waves) {
+        float o[3], d[3];
+        compact_ray(P, r, o, d);
+        if (P.rays_d_out && lane < 3) P.rays_d_out[r * 3 + lane] = lane == 0 ? d[0] : (lane == 1 ? d[1] : d[2]);
+        int count = 0;
+        for (int s0 = 0; s0 < S; s0 += 64) {
+            const int s = s0 + lane;
+            const bool valid = s < S;
+            bool keep = false;
+            if (valid) {
+                const int64_t i = r * S + s;
+                float z;
+                if (P.z_in) {
+                    z = P.z_in[i];
+                } else if (!P.perturb) {
+                    z = ladder_z(P.lad, s);
+                } else {
+                    const float u = P.t_rand ? P.t_rand[i] : counter_uniform(P.seed, (uint64_t)r, (uint32_t)s);
+                    z = ladder_z_jitter(P.lad, s, u);
+                }
+                P.z_vals[i] = z;
+                const float p[3] = {point_on_ray(o[0], d[0], z), point_on_ray(o[1], d[1], z), point_on_ray(o[2], d[2], z)};
+                keep = compact_keeps(P, p);
+            }
+            count += __popcll(__ballot(keep));
+        }
+        if (lane == 0) counts[r] = count;
+    }
+}
+
+// counts[0..n) -> exclusive prefix sums in place, total[0] = their sum.  One workgroup of 1024 threads; n_rays * S < 2^31 bounds every sum.
+__global__ void __launch_bounds__(1024) occupancy_compact_scan_kernel(int32_t* __restrict__ counts, int64_t n, int64_t* __restrict__ total) {
+    __shared__ int wave_sums[16];
+    __shared__ int round_sum;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int carry = 0;
+    for (int64_t base = 0; base < n; base += 1024) {
+        const int64_t i = base + threadIdx.x;
+        const int c = i < n ? counts[i] : 0;
+        int incl = c;
+#pragma unroll
+        for (int k = 1; k < 64; k <<= 1) {
+            const int u = __shfl_up(incl, k, 64);
+            if (lane >= k) incl += u;
+        }
+        if (lane == 63) wave_sums[wv] = incl;
+        __syncthreads();
+        int before = 0;
+        for (int w = 0; w < wv; ++w) before += wave_sums[w];
+        if (i < n) counts[i] = carry + before + incl - c;
+        if (threadIdx.x == 1023) round_sum = before + incl;
+        __syncthreads();
+        carry += round_sum;
+    }
+    if (threadIdx.x == 0) total[0] = carry;
+}
+
+__global__ void __launch_bounds__(kBlock) occupancy_compact_write_kernel(const CompactDev P, int64_t n_rays, const int32_t* __restrict__ offsets,
+                                                                         int64_t capacity, int32_t* __restrict__ index, int32_t* __restrict__ slot,
+                                                                         float* __restrict__ positions, float* __restrict__ directions) {
+    const int lane = threadIdx.x & 63;
+    const int S = P.lad.S;
+    const int64_t wave0 = (blockIdx.x * (int64_t)kBlock + threadIdx.x) >> 6;
+    const int64_t n_waves = ((int64_t)gridDim.x * kBlock) >> 6;
+    for (int64_t r = wave0; r < n_rays; r += n_waves) {
+        float o[3], d[3];
+        compact_ray(P, r, o, d);
+        int64_t base = offsets[r];
+        for (int s0 = 0; s0 < S; s0 += 64) {
+            const int s = s0 + lane;
+            const bool valid = s < S;
+            const int64_t i = r * S + s;
+            bool keep = false;
+            float p[3] = {0.0f, 0.0f, 0.0f};
+            if (valid) {
+                const float z = P.z_vals[i];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) p[k] = point_on_ray(o[k], d[k], z);
+                keep = compact_keeps(P, p);
+            }
+            const unsigned long long m = __ballot(keep);
+            const int64_t j = base + (int64_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            const bool store = keep && j < capacity;
+            if (valid) slot[i] = store ? (int32_t)j : -1;
+            if (store) {
+                index[j] = (int32_t)i;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) positions[j * 3 + k] = p[k];
+                if (directions) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) directions[j * 3 + k] = d[k];
+                }
+            }
+            base += __popcll(m);
+        }
+    }
+}
+
 }  // namespace
+
+int64_t occupancy_compact_ws_bytes(int64_t n_rays) { return ((n_rays < 1 ? 1 : n_rays) * 4 + 15) / 16 * 16; }
+
+int launch_occupancy_compact(const TrainRaysDev& r, int64_t n_rays, const OccDev& g, int64_t capacity, int32_t* index, int32_t* slot,
+                             float* positions, float* directions, int64_t* count, void* workspace, hipStream_t s) {
+    if (n_rays <= 0) return NRF_OK;
+    CompactDev P{};
+    P.rays_o = r.rays_o; P.rays_d = r.rays_d; P.pixels = r.pixels; P.cam = r.cam; P.lad = r.lad; P.perturb = r.perturb; P.t_rand = r.t_rand;
+    P.z_in = r.z_in; P.seed = r.seed; P.z_vals = r.z_vals; P.rays_d_out = r.rays_d_out;
+    P.bits = g.bits; P.outside = g.outside;
+    for (int k = 0; k < 3; ++k) { P.res[k] = g.res[k]; P.lo[k] = g.lo[k]; P.scale[k] = g.scale[k]; }
+    int32_t* counts = static_cast<int32_t*>(workspace);
+    const dim3 grid(grid_for(n_rays * 64, kBlock, 16384)), block(kBlock);
+    hipLaunchKernelGGL(occupancy_compact_count_kernel, grid, block, 0, s, P, n_rays, counts);
+    hipLaunchKernelGGL(occupancy_compact_scan_kernel, dim3(1), dim3(1024), 0, s, counts, n_rays, count);
+    hipLaunchKernelGGL(occupancy_compact_write_kernel, grid, block, 0, s, P, n_rays, counts, capacity, index, slot, positions, directions);
+    return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
+}
 
 int launch_occupancy_mark(const float* rays_o, const float* rays_d, const Camera* cam, int64_t ray_begin, int64_t n_rays, int S, const float* z_vals,
                           const float* weights, const int res[3], const float lo[3], const float scale[3], float weight_threshold, float seen_eps,
@@ -1166,7 +1421,7 @@ int launch_composite_mse_backward(const float* rgb, int rgb_stride, const float*
 int launch_composite_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
                                    int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, float* pred, float* d_rgb,
                                    int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n,
-                                   hipStream_t s) {
+                                   hipStream_t s, const int32_t* slot) {
     if (n_rays <= 0 || S > 64 * kMaxSegments) return NRF_EINVAL;
     LossExt ext{};
     ext.noise.std = lt.noise_std; ext.noise.n = lt.noise; ext.noise.seed = lt.rng_seed;
@@ -1174,9 +1429,14 @@ int launch_composite_loss_backward(const float* rgb, int rgb_stride, const float
     ext.gd_scale = lt.target_depth ? lt.depth_weight / (float)n_rays : 0.0f;
     ext.gw_scale = 2.0f * lt.reg_weight / ((float)n_rays * (float)S);
     const int64_t work = std::max(n_rays * 64, (zero_n + 3) / 4);
-    hipLaunchKernelGGL(composite_loss_backward_kernel<true>, dim3(grid_for(work, kBlock, 16384)), dim3(kBlock), 0, s, rgb, rgb_stride, sigma,
-                       sigma_stride, z, rays_d, n_rays, S, white_bkgd, target, lt.rgb_weight, pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride,
-                       ray_terms, zero_buf, zero_n, ext);
+    if (slot)
+        hipLaunchKernelGGL(indexed_loss_backward_kernel, dim3(grid_for(work, kBlock, 16384)), dim3(kBlock), 0, s, rgb, rgb_stride, sigma,
+                           sigma_stride, z, rays_d, n_rays, S, white_bkgd, target, lt.rgb_weight, pred, d_rgb, d_rgb_stride, d_sigma,
+                           d_sigma_stride, ray_terms, zero_buf, zero_n, ext, slot);
+    else
+        hipLaunchKernelGGL(composite_loss_backward_kernel<true>, dim3(grid_for(work, kBlock, 16384)), dim3(kBlock), 0, s, rgb, rgb_stride, sigma,
+                           sigma_stride, z, rays_d, n_rays, S, white_bkgd, target, lt.rgb_weight, pred, d_rgb, d_rgb_stride, d_sigma,
+                           d_sigma_stride, ray_terms, zero_buf, zero_n, ext);
     return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
 }
 

@@ -204,8 +204,15 @@ class NeRFMLP(nn.Module):
         flat = self._flat_on(idx) if same else None
         if flat is not None:
             # parameters live in the flat device vector (training): re-pack the asked-for modes' streams on the device
+            # A re-pack marks the backward weights of every mode outside its mask stale.  When the training mode's streams already
+            # hold THESE parameters (an eval-mode forward between two steps packed them: OccupancyGrid.refresh) and another mode is
+            # asked for at the same version (a validation render), the training mode rides along in the one call, so that the next
+            # step still finds its backward weights current.
+            ride = set()
+            if self._packed == ver and self._packed_modes and self._train_ready and getattr(self, "_train_mode", None) in self._packed_modes:
+                ride = {self._train_mode}
             with torch.cuda.device(idx):
-                L.check(L.lib().nrf_model_update_device(self._handle, L.ptr(flat), sum(1 << k for k in modes), L.stream_ptr()))
+                L.check(L.lib().nrf_model_update_device(self._handle, L.ptr(flat), sum(1 << k for k in modes | ride), L.stream_ptr()))
             self._packed_modes = (modes if self._packed != ver or self._packed_modes is None else self._packed_modes | modes)
             self._packed = ver
             return self._handle

@@ -8,6 +8,10 @@ probed points, which is why skipping is opt-in.  `from_views` / `prune` build a 
 (nrf_occupancy_mark_camera): a cell stays when a sample of weight > weight_threshold fell into it (hit), or -- by default -- when no
 marking ray reached it with transmittance > seen_eps (not seen: behind a surface or outside every frustum, where a held-out view
 may look).  Grids over the same box combine with `&`, `|` and `~`.
+
+Training under a grid (training.FusedStep.step_rays / step_view with occupancy=) needs a grid that follows the field while it
+moves: `full` is the all-ones grid a run starts from, `refresh` re-probes a slab of cells per call and keeps a decaying maximum of
+the densities it has seen per cell.
 """
 from __future__ import annotations
 
@@ -67,7 +71,11 @@ class OccupancyGrid:
         return self.res[0] * self.res[1] * self.res[2]
 
     def to(self, device):
-        return OccupancyGrid(self.bits.to(device), self.res, self.lo, self.hi, self.outside)
+        g = OccupancyGrid(self.bits.to(device), self.res, self.lo, self.hi, self.outside)
+        ema = getattr(self, "ema", None)
+        if ema is not None:                                           # a refreshed grid keeps its per-cell values and its place in the round
+            g.ema, g._cursor, g._refreshes = ema.to(device), self._cursor, self._refreshes
+        return g
 
     # ---- algebra: bitwise operations on the words, on whatever device they live -------------------------
     def _like(self, bits):
@@ -90,6 +98,16 @@ class OccupancyGrid:
         return self._like(torch.bitwise_not(self.bits))
 
     # ---- masks ------------------------------------------------------------------------------------
+    @classmethod
+    def full(cls, res, lo, hi, outside=0, device=None):
+        """The all-ones grid of res = (rx, ry, rz) (or one number) cells over [lo, hi]: every sample is evaluated.  What a training
+        run under a grid starts from (and returns to when it is resumed), before `refresh` has seen the field."""
+        res = tuple(int(r) for r in (res if hasattr(res, "__len__") else (res,) * 3))
+        if len(res) != 3 or not all(1 <= r <= 512 for r in res) or res[0] % 32:
+            raise ValueError("res = (rx, ry, rz): each in 1..512 and rx a multiple of 32")
+        bits = torch.full((res[0] * res[1] * res[2] // 32,), -1, dtype=torch.int32, device=device if device is not None else "cpu")
+        return cls(bits, res, lo, hi, outside)
+
     @classmethod
     def from_mask(cls, mask, lo, hi, outside=0):
         """mask: bool tensor (rz, ry, rx), True = occupied."""
@@ -203,6 +221,67 @@ class OccupancyGrid:
             model.train(was_training)
         grid = cls(bits, res, lo, hi, outside)
         return grid.dilate(dilate) if dilate else grid
+
+    # ---- following a field that is being trained -----------------------------------------------------
+    def refresh(self, model, decay=0.95, threshold=0.0, samples_per_cell=4, cells=None, seed=None, dino=None, mma_mode=None):
+        """Re-probe one slab of the grid, in place, and return (first_cell, n_cells) of the slab.
+
+        The grid keeps one fp32 value per cell (`ema`, zeros before the first refresh).  A call probes `model`'s density at
+        `samples_per_cell` points (cell_points with `seed`) of each of `cells` contiguous cells -- a multiple of 32; default: the
+        whole grid -- through the network itself (_density), sets
+
+            ema[c] = max(decay * ema[c], max over the cell's probes)
+
+        on that slab and re-packs the slab's bits as ema[c] > threshold (nrf_occupancy_pack; a NaN value is occupied).  Cells
+        outside the slab keep their values and bits.  Slabs go round robin: the next call starts where this one ended, the last
+        slab of a round is cut at the end of the grid, so every cell is visited exactly once every ceil(n_cells / cells) calls.
+        seed=None takes the number of refreshes so far, so that a cell is probed at new points in every round.
+
+        Probing the NETWORK -- not the weights the training rays render -- is what lets a cell come back that skipping starved of
+        gradient: a skipped sample passes no gradient, so nothing a step under the grid computes could ever show that the field
+        has grown into an empty cell; the density at the cell's probes does, and the decaying maximum keeps a cell occupied for a
+        while after one probe found it dense.  A V3 grid belongs to ONE source view: dino=dict(features=, pose=, focal=, H=, W=)."""
+        L.require_gpu()
+        if not self.bits.is_cuda:
+            raise ValueError("refresh runs on the GPU: move the grid there first (grid.to(device))")
+        if model.net == L.NRF_NET_V3 and dino is None:
+            raise ValueError("a use_dino model's density depends on the source view: refresh needs dino=dict(features=, pose=, focal=, H=, W=)")
+        if not (0.0 <= float(decay) <= 1.0):
+            raise ValueError("decay must be in [0, 1]")
+        k = int(samples_per_cell)
+        if k < 1:
+            raise ValueError("samples_per_cell must be >= 1")
+        n_cells = self.n_cells
+        cells = n_cells if cells is None else int(cells)
+        if cells < 32 or cells % 32:
+            raise ValueError("cells must be a positive multiple of 32 (a slab starts and ends on a word of the bit array)")
+        dev = self.bits.device
+        if getattr(self, "ema", None) is None or self.ema.device != dev:
+            old = getattr(self, "ema", None)
+            self.ema = old.to(dev) if old is not None else torch.zeros((n_cells,), dtype=torch.float32, device=dev)
+            self._cursor = getattr(self, "_cursor", 0)
+            self._refreshes = getattr(self, "_refreshes", 0)
+        first = self._cursor
+        n = min(cells, n_cells - first)
+        if seed is None:
+            seed = self._refreshes
+        was_training, own_mode = model.training, model.mma_mode
+        model.eval()
+        if mma_mode is not None:
+            model.mma_mode = mma_mode
+        try:
+            with torch.no_grad(), torch.cuda.device(dev):
+                pts = self.cell_points(self.res, self.lo, self.hi, first, n, k, seed, dev).reshape(-1, 3).contiguous()
+                probe = self._density(model, pts, dino).reshape(n, k).max(dim=1).values
+                slab = self.ema[first:first + n]
+                slab.copy_(torch.maximum(slab * float(decay), probe))
+                L.check(L.lib().nrf_occupancy_pack(L.ptr(slab), n, 1, float(threshold), self.bits[first // 32:].data_ptr(), L.stream_ptr()))
+        finally:
+            model.mma_mode = own_mode
+            model.train(was_training)
+        self._cursor = 0 if first + n >= n_cells else first + n
+        self._refreshes += 1
+        return first, n
 
     # ---- building from rendered weights -----------------------------------------------------------
     def _box_args(self):

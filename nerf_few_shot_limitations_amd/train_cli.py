@@ -1,6 +1,8 @@
 """python -m nerf_few_shot_limitations_amd.train_cli --config experiments/baseline.yaml --data data/nerf_synthetic/lego \\
         [--recipe train|multiscale] [--epochs N] [--mode bf16|f16|f32] [--eval-mode f16] [--out DIR] [--checkpoint CKPT]
         [--dino-weights DIR | --dino-maps maps.pt] [--train-extractor] [--fused-inputs] [--seed 0]
+        [--occupancy-res N [--occupancy-box LO HI] [--occupancy-threshold T] [--occupancy-decay D] [--occupancy-refresh-every K]
+         [--occupancy-cells-per-refresh C] [--occupancy-warmup STEPS]]
 
 The training run of `NeRFDINOTrainer` (src/training/train.py:244-292 `train_step`, :344-372 `train`) as a command on the
 HIP path: the YAML loads unchanged; per epoch and training view the rays are cast at the progressive schedule's
@@ -45,6 +47,19 @@ its LoRA matrices would still receive nothing -- refused rather than silently tr
 --fused-inputs: every ray batch is one `FusedStep.step_view` -- the batch's pixel ids go to the saving forward kernel, which casts
 the rays, draws the stratified depths (same seed, same key), encodes and, for use_dino, gathers the features itself; no per-sample
 input tensor is built.  Same shuffle, seeds and sharding as the default route, which stays the default.
+
+--occupancy-res N (0, the default: off) trains under an occupancy grid of N^3 cells over the cube --occupancy-box LO HI (default
+-1.5 1.5): every ray batch is one `FusedStep.step_view(occupancy=grid)` -- the pixel ids go to the compaction kernels, the network,
+its backward and the weight gradients run on the samples in occupied cells alone, a sample in an empty cell composites as empty
+space (include/nerfhip.h: nrf_occupancy_compact_rays).  The grid follows the field: every --occupancy-refresh-every steps (default
+16) `OccupancyGrid.refresh` probes the network's density in the next --occupancy-cells-per-refresh cells (a multiple of 32; default:
+a sixteenth of the grid), keeps max(--occupancy-decay * old, probe) per cell (default 0.95) and marks a cell occupied when that
+exceeds --occupancy-threshold (default 0.01).  Until step --occupancy-warmup (default 256) the steps run under an all-ones grid --
+the same launches, every sample evaluated -- while the refreshes already collect the cells' values.  Unlike the other routes such
+a step reads 8 bytes back from the device.  Refused: a use_dino config (a V3 grid belongs to ONE source view, the batches of a run
+condition on the view they came from), --train-extractor (no per-sample gradients are handed out under a grid), and any
+--occupancy-* flag without --occupancy-res.  The grid is not part of a checkpoint: a resumed run starts again from the all-ones
+grid and its warm-up.
 
 --checkpoint resumes a run: weights, Adam moments and step count, epoch counter and best PSNR (the reference's train.py saves
 these keys, :374-389, but has no resume path); the LR schedule is a function of the epoch.  wandb and LPIPS are not part of
@@ -134,6 +149,70 @@ def extractor_args_error(args, cfg):
     return None
 
 
+OCCUPANCY_FLAGS = ("occupancy_box", "occupancy_threshold", "occupancy_decay", "occupancy_refresh_every", "occupancy_cells_per_refresh",
+                   "occupancy_warmup")
+
+
+def occupancy_args_error(args, cfg):
+    """Why the --occupancy-* arguments cannot run with these arguments / this config (None: they can, or none was given).
+    Decided before any GPU work."""
+    res = int(getattr(args, "occupancy_res", 0) or 0)
+    given = [f for f in OCCUPANCY_FLAGS if getattr(args, f, None) is not None]
+    if res == 0:
+        if given:
+            return "--" + given[0].replace("_", "-") + " needs --occupancy-res N (N > 0): without a grid the flag would be ignored"
+        return None
+    if res < 32 or res > 512 or res % 32:
+        return "--occupancy-res must be a multiple of 32 in 32..512 (0: off)"
+    if bool((cfg.get("model", {}) or {}).get("use_dino", True)):
+        return ("--occupancy-res: this config has use_dino: true -- a grid of such a field belongs to ONE source view, the batches of a run "
+                "condition on the view they came from")
+    if getattr(args, "train_extractor", False):
+        return "--occupancy-res with --train-extractor is refused: a step under a grid hands out no per-sample gradients"
+    box = args.occupancy_box
+    if box is not None and not (box[0] < box[1]):
+        return "--occupancy-box LO HI needs LO < HI"
+    if args.occupancy_decay is not None and not (0.0 <= args.occupancy_decay <= 1.0):
+        return "--occupancy-decay must be in [0, 1]"
+    if args.occupancy_refresh_every is not None and args.occupancy_refresh_every < 1:
+        return "--occupancy-refresh-every must be >= 1"
+    c = args.occupancy_cells_per_refresh
+    if c is not None and (c < 32 or c % 32):
+        return "--occupancy-cells-per-refresh must be a positive multiple of 32"
+    if args.occupancy_warmup is not None and args.occupancy_warmup < 0:
+        return "--occupancy-warmup must be >= 0"
+    return None
+
+
+class OccupancySchedule:
+    """The grid side of --occupancy-res: the all-ones grid of the warm-up, the live grid `OccupancyGrid.refresh` keeps up to date, and
+    the step counter that decides between them and when to refresh."""
+
+    def __init__(self, res, box=(-1.5, 1.5), threshold=0.01, decay=0.95, refresh_every=16, cells_per_refresh=None, warmup=256, device=None):
+        from .occupancy import OccupancyGrid
+        self.full = OccupancyGrid.full(res, box[0], box[1], device=device)
+        self.grid = OccupancyGrid.full(res, box[0], box[1], device=device)
+        self.threshold, self.decay, self.refresh_every, self.warmup = float(threshold), float(decay), int(refresh_every), int(warmup)
+        self.cells = int(cells_per_refresh) if cells_per_refresh else max(32, self.grid.n_cells // 16 // 32 * 32)
+        self.steps = 0
+
+    @classmethod
+    def from_args(cls, args, device):
+        kw = {k: v for k, v in dict(box=args.occupancy_box, threshold=args.occupancy_threshold, decay=args.occupancy_decay,
+                                    refresh_every=args.occupancy_refresh_every, cells_per_refresh=args.occupancy_cells_per_refresh,
+                                    warmup=args.occupancy_warmup).items() if v is not None}
+        return cls(args.occupancy_res, device=device, **kw)
+
+    def current(self):
+        """The grid of the next step: all ones until the warm-up is over."""
+        return self.full if self.steps < self.warmup else self.grid
+
+    def after_step(self, model):
+        self.steps += 1
+        if self.steps % self.refresh_every == 0:
+            self.grid.refresh(model, decay=self.decay, threshold=self.threshold, cells=self.cells)
+
+
 class ExtractorTrainer:
     """The extractor side of --train-extractor: the LoRA parameters (config.lora_trainable_parameters) in a torch.optim.Adam, one
     live map per view and one step per view with the map gradient summed over the view's batches."""
@@ -180,10 +259,12 @@ class ExtractorTrainer:
 
 
 def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, dino_maps=None, max_batches=None, rank=0, world=1,
-                extractor=None, fused_inputs=False):
+                extractor=None, fused_inputs=False, occupancy=None):
     """One pass of train.py:261-290 over the training views; returns (mean loss, ray-samples processed).
     fused_inputs: every batch is one `step.step_view` on its pixel ids (--fused-inputs; module docstring) instead of torch gathers,
     sample_points_along_rays, the expanded directions and fetch_features in front of `step(...)`.
+    occupancy: an OccupancySchedule (--occupancy-res; module docstring) -- the fused_inputs route with `occupancy=` its current grid,
+    and a refresh of the grid when one is due.
     extractor: an ExtractorTrainer (--train-extractor; module docstring) -- the view's map comes from it, live, instead of
     dino_maps[v], and it takes one step per view.
     world > 1 (data parallel, `FusedStep(data_parallel=True)`): every rank draws the SAME shuffle (same generator seed) and
@@ -192,6 +273,10 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
     Ht, Wt, S, batch = schedule_for(cfg, epoch)
     model = step.model
     use_dino = model.net == L.NRF_NET_V3
+    if occupancy is not None:
+        if use_dino or extractor is not None:
+            raise ValueError("training under an occupancy grid is not combined with use_dino models or a trained extractor")
+        fused_inputs = True
     total, n_batches, samples = None, 0, 0
     pts_buf = None
     for v in range(len(images)):
@@ -219,7 +304,11 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
                     if pts_buf is None or pts_buf.shape[0] < n * S:
                         pts_buf = torch.empty((n * S, 3), dtype=torch.float32, device=tgt.device)
                     kw.update(d_dino_out=d_feats, points_out=pts_buf[:n * S])
+                if occupancy is not None:
+                    kw["occupancy"] = occupancy.current()
                 loss = step.step_view(None, c2w, Ht, Wt, f_t, idx, near, far, S, perturb=True, **kw)
+                if occupancy is not None:
+                    occupancy.after_step(model)
                 if extractor is not None:
                     extractor.add_batch(cam, pts_buf[:n * S], d_feats)
                 total = loss if total is None else total + loss
@@ -325,6 +414,15 @@ def main(argv=None):
     ap.add_argument("--fused-inputs", action="store_true",
                     help="cast rays, sample, encode and fetch the DINO features inside the training forward kernel (FusedStep.step_view) instead "
                          "of building per-sample tensors in front of it; same shuffle, seeds and sharding")
+    ap.add_argument("--occupancy-res", type=int, default=0,
+                    help="train under an occupancy grid of N^3 cells (a multiple of 32; 0: off): the network runs on the samples in occupied "
+                         "cells alone, FusedStep.step_view(occupancy=) (module docstring)")
+    ap.add_argument("--occupancy-box", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="the grid's cube (default -1.5 1.5)")
+    ap.add_argument("--occupancy-threshold", type=float, default=None, help="a cell is occupied when its value exceeds this (default 0.01)")
+    ap.add_argument("--occupancy-decay", type=float, default=None, help="value = max(decay * value, probe) per refresh (default 0.95)")
+    ap.add_argument("--occupancy-refresh-every", type=int, default=None, metavar="K", help="refresh the grid every K steps (default 16)")
+    ap.add_argument("--occupancy-cells-per-refresh", type=int, default=None, help="cells probed per refresh, a multiple of 32 (default: 1/16 of the grid)")
+    ap.add_argument("--occupancy-warmup", type=int, default=None, metavar="STEPS", help="steps under an all-ones grid first (default 256)")
     ap.add_argument("--max-test-views", type=int, default=None)
     ap.add_argument("--max-batches", type=int, default=None, help="stop every epoch after this many ray batches (smoke runs)")
     ap.add_argument("--seed", type=int, default=0)
@@ -335,7 +433,7 @@ def main(argv=None):
                     help="--data-parallel on a box with ONE GPU: every rank on cuda:0, the gradient all-reduce over gloo through host memory "
                          "(RCCL refuses two ranks on one card); exercises the sharding and the collective, not multi-GPU speed")
     args = ap.parse_args(argv)
-    problem = extractor_args_error(args, load_config(args.config))
+    problem = extractor_args_error(args, load_config(args.config)) or occupancy_args_error(args, load_config(args.config))
     if problem:
         raise SystemExit(problem)
     rank, world = 0, 1
@@ -400,6 +498,8 @@ def main(argv=None):
                      **({"seed": args.seed} if args.recipe == "multiscale" else {}))
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed)
+    # (not part of a checkpoint: a resumed run starts again from the all-ones grid and its warm-up)
+    occ = OccupancySchedule.from_args(args, dev) if args.occupancy_res else None
     best, log, first_epoch = 0.0, [], 0
     if ckpt is not None:
         first_epoch, best = resume_from(ckpt, model, step)
@@ -411,10 +511,12 @@ def main(argv=None):
             ext.set_lr(lr_at(cfg, epoch))
         t0 = time.perf_counter()
         loss, samples = train_epoch(step, cfg, epoch, images, poses, H, W, focal, rs["near"], rs["far"], gen, dino_maps, args.max_batches, rank, world,
-                                    extractor=ext, fused_inputs=args.fused_inputs)
+                                    extractor=ext, fused_inputs=args.fused_inputs, occupancy=occ)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         rec = {"epoch": epoch + 1, "loss": loss, "lr": step.opt.lr, "seconds": round(dt, 3), "Msamples_per_s": round(world * samples / dt / 1e6, 2)}
+        if occ is not None:
+            rec["occupied_fraction"] = round(occ.current().occupied_fraction, 4)
         if rank != 0:                                                         # every rank holds the same parameters: rank 0 validates and writes
             log.append(rec)
             continue

@@ -115,6 +115,7 @@ def _train_handle(module, dev, mma_mode=None):
             L.check(L.lib().nrf_model_update_device(h, L.ptr(module.flat_params().flat), 1 << mode, L.stream_ptr()))
         module._train_ready = True
         module._packed, module._packed_modes = module._versions(), {mode}
+    module._train_mode = mode            # (nerf_model.handle: the mode whose backward weights a later re-pack must not leave stale)
     return h, mode
 
 
@@ -1060,6 +1061,7 @@ class FusedStep:
         self.white = int(bool(white_bkgd))
         self._loss_vec, self.last_grad_norm = None, None
         self._key = None
+        self.last_count = None              # M of the last step under an occupancy grid (step_rays / step_view with occupancy=)
 
     @property
     def last_losses(self):
@@ -1176,7 +1178,7 @@ class FusedStep:
     # ---- the same step from rays: sampling, encoding and the feature fetch happen inside the saving forward ----------------
     @torch.no_grad()
     def step_rays(self, rays_o, rays_d, target, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False, z_in=None,
-                  dino=None, target_depth=None, noise=None, d_dino_out=None, points_out=None):
+                  dino=None, target_depth=None, noise=None, d_dino_out=None, points_out=None, occupancy=None):
         """One step on rays (R,3) and their target (R,3): what train.py:188-229 builds in front of the network -- stratified
         samples, per-sample directions, projected DINO features, encodings -- is derived inside the forward kernel
         (nrf_mlp_forward_train_rays), so no per-sample input tensor exists.  Depths, points and therefore (V2) every bit of the step
@@ -1192,22 +1194,29 @@ class FusedStep:
         project_fetch_backward needs next to d_dino_out); target_depth, noise, d_dino_out, the returned loss, `last_losses` and
         `last_grad_norm` as in __call__.  `last_z` holds the step's (R,S) depths: a buffer of this object that the next ray step
         of the same shape overwrites -- clone it to keep it.  `dino` may also be the (struct, tensors) pair `renderer.make_dino`
-        returned, for a caller that steps many batches on one source view."""
+        returned, for a caller that steps many batches on one source view.
+
+        occupancy (an occupancy.OccupancyGrid): the step under the grid -- the plain step with every sample in an empty cell
+        composited as colour 0 and effective density -inf (behind the density noise), and the network, its backward and the weight
+        gradients run on the M occupied samples alone (_grid_ray_step).  UNLIKE THE PLAIN STEP IT SYNCHRONISES ONCE: the 8 bytes of
+        M are read back between the compaction and the network.  `last_count` holds M.  Not combined with d_dino_out / points_out."""
         o = L.dev_f32(rays_o).reshape(-1, 3)
         d = L.dev_f32(rays_d, o.device).reshape(-1, 3)
         if d.shape != o.shape:
             raise ValueError("rays_o and rays_d must both be (R,3)")
         return self._ray_step(o.shape[0], o.device, lambda z, d_out, p_out: L.train_rays(rays_o=L.ptr(o), rays_d=L.ptr(d), z_vals=z, points_out=p_out), d,
-                              target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise, d_dino_out, points_out)
+                              target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise, d_dino_out, points_out,
+                              occupancy)
 
     @torch.no_grad()
     def step_view(self, image, pose, H, W, focal, pixels, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False,
-                  z_in=None, dino=None, target_depth=None, noise=None, d_dino_out=None, points_out=None, target=None):
+                  z_in=None, dino=None, target_depth=None, noise=None, d_dino_out=None, points_out=None, target=None, occupancy=None):
         """step_rays on pixels of a pinhole view: `pixels` is an int64 device tensor of ray ids y*W+x of get_rays(H, W, focal, pose),
         whose origins and directions the kernel computes itself.  The target is `target` (R,3) if given, otherwise
         image.reshape(-1,3)[pixels] of the (H,W,3) image: one torch gather.  The jitter of a ray is keyed by its position in
         `pixels`, not by the pixel id: the step equals step_rays on the gathered rays to the bit.  `pose` may also be the 12 floats
-        `ray_sampler._c2w12` made of it (as `dino` may be `make_dino`'s pair): nothing is converted per batch then."""
+        `ray_sampler._c2w12` made of it (as `dino` may be `make_dino`'s pair): nothing is converted per batch then.  occupancy: as in
+        step_rays (one 8-byte read-back per step)."""
         if not (isinstance(pixels, torch.Tensor) and pixels.is_cuda and pixels.dtype == torch.int64 and pixels.dim() == 1):
             raise ValueError("pixels must be a 1-d int64 tensor of ray ids on the GPU")
         pix = pixels.contiguous()
@@ -1222,12 +1231,18 @@ class FusedStep:
         return self._ray_step(pix.shape[0], pix.device,
                               lambda z, d_out, p_out: L.train_rays(pixels=pix.data_ptr(), H=H, W=W, focal=focal, c2w=c2w, z_vals=z, rays_d_out=d_out,
                                                                    points_out=p_out),
-                              None, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise, d_dino_out, points_out)
+                              None, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise, d_dino_out, points_out,
+                              occupancy)
 
     def _ray_step(self, R, dev, make_rays, d, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise,
-                  d_dino_out, points_out):
+                  d_dino_out, points_out, occupancy=None):
         """__call__'s sequence with nrf_mlp_forward_train_rays in front; d is the caller's (R,3) directions or None (pixel mode:
         the kernel writes them for the compositor)."""
+        if occupancy is not None:
+            if d_dino_out is not None or points_out is not None:
+                raise ValueError("occupancy is not combined with d_dino_out / points_out: the step under a grid hands out no per-sample gradients")
+            return self._grid_ray_step(R, dev, make_rays, d, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth,
+                                       noise, occupancy)
         from .renderer import _opts, make_dino
         m = self.model
         S = int(n_samples)
@@ -1314,6 +1329,125 @@ class FusedStep:
                 self._loss_vec, self.last_grad_norm = loss, opt.last_grad_norm
                 loss = loss[0]
             else:
+                L.check(lib.nrf_adam_step_loss(L.ptr(flat), L.ptr(self.grad), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq), flat.numel(), opt.lr,
+                                               opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, opt.step_count, L.ptr(self.ray_loss), R,
+                                               self.rgb_weight, L.ptr(loss), st))
+                self._loss_vec, self.last_grad_norm = loss, None
+        m._gen += 1
+        return loss
+
+    def _grid_ray_step(self, R, dev, make_rays, d, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise,
+                       occupancy):
+        """The step under an occupancy grid (nerfhip.h: nrf_occupancy_compact_rays):
+
+            compact -> read M back -> [V1: encode | V3: project + fetch] of the M points -> saving forward on M rows
+            -> indexed compositor, loss and backward (clears the gradient vector) -> dZ chain + weight gradients on M rows
+            -> [all-reduce] -> the plain step's optimiser launch
+
+        The context and every buffer are sized once for R * S rows (the library accepts a larger context than M needs), so no
+        step allocates.  The read-back of M (8 bytes) is the step's ONLY synchronisation and the one thing the plain step does not
+        have: the launches behind it are sized by M on the host.  M == 0 is a valid step: the network launches nothing, the
+        prediction is the background, the gradient is zero and the optimiser still steps.  With an all-ones grid every bit of the
+        step is the plain step's (V2), or __call__'s on the staged points (V1: nrf_encode; V3: nrf_project_fetch)."""
+        from .occupancy import OccupancyGrid
+        from .renderer import _opts, make_dino
+        if not isinstance(occupancy, OccupancyGrid):
+            raise TypeError("occupancy must be an occupancy.OccupancyGrid")
+        m = self.model
+        S = int(n_samples)
+        n = R * S
+        if R < 1:
+            raise ValueError("a step needs at least one ray")
+        v1, v3 = m.net == L.NRF_NET_V1, m.net == L.NRF_NET_V3
+        tgt = L.dev_f32(target, dev).reshape(R, 3)
+        tr = L.dev_f32(t_rand, dev).reshape(R, S) if t_rand is not None else None
+        zin = L.dev_f32(z_in, dev).reshape(R, S) if z_in is not None else None
+        dn = keep = None
+        if v3:
+            if dino is None:
+                raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
+            dn, keep = make_dino(**dino) if isinstance(dino, dict) else dino
+        lib = L.lib()
+        h, mode = _train_handle(m, dev)
+        with torch.cuda.device(dev):
+            self._buffers(n, R, S, dev, h, mode)
+            if getattr(self, "_ray_key", None) != self._key:
+                self.last_z = torch.empty((R, S), dtype=torch.float32, device=dev)
+                self._rays_d = torch.empty((R, 3), dtype=torch.float32, device=dev)
+                self._ray_key = self._key
+            if getattr(self, "_grid_key", None) != self._key:
+                self._index = torch.empty((n,), dtype=torch.int32, device=dev)
+                self._slot = torch.empty((n,), dtype=torch.int32, device=dev)
+                self._pos = torch.empty((n, 3), dtype=torch.float32, device=dev)
+                self._dirs = None if v1 else torch.empty((n, 3), dtype=torch.float32, device=dev)
+                self._enc = torch.empty((n, 3 * (2 * m.pos_freq + 1)), dtype=torch.float32, device=dev) if v1 else None
+                self._feats = torch.empty((n, m.dino_dim), dtype=torch.float32, device=dev) if v3 else None
+                self._count = torch.zeros((1,), dtype=torch.int64, device=dev)
+                self._cws = torch.empty((int(lib.nrf_occupancy_compact_workspace_bytes(R)),), dtype=torch.uint8, device=dev)
+                self._grid_key = self._key
+            z = self.last_z
+            opts = _opts(near, far, S, perturb, tr, seed, lindisp, 0.0, self.white, L.TRAIN_MODE[m.mma_mode], dn, dev, zin)
+            rays = make_rays(L.ptr(z), L.ptr(self._rays_d), None)
+            if d is None:
+                d = self._rays_d
+            st = L.stream_ptr()
+            occ, occ_keep = occupancy.struct(dev)
+            cp = L.compact(n, self._index.data_ptr(), self._slot.data_ptr(), L.ptr(self._pos), L.ptr(self._dirs), self._count.data_ptr(),
+                           self._cws.data_ptr(), self._cws.numel())
+            L.check(lib.nrf_occupancy_compact_rays(C.byref(rays), R, C.byref(opts), C.byref(occ), C.byref(cp), st))
+            M = int(self._count.item())         # the step's only synchronisation: 8 bytes
+            self.last_count = M
+            ctx = C.c_void_p(self.ctx.data_ptr())
+            o4, d4 = self.out4, self.d_out4
+            if v1:
+                if M:
+                    L.check(lib.nrf_encode(L.ptr(self._pos), M, 3, m.pos_freq, 1, None, L.ptr(self._enc), st))
+                    L.check(lib.nrf_mlp_forward_train_v1(h, mode, L.ptr(self._enc), M, L.ptr(o4), ctx, self.nbytes, st))
+                heads = (L.ptr(o4), 4, C.c_void_p(o4.data_ptr() + 12), 4)
+                d_heads = (L.ptr(d4), 4, C.c_void_p(d4.data_ptr() + 12), 4)
+            else:
+                rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
+                g_rgb, g_den = d4.view(-1)[:3 * n].view(n, 3), d4.view(-1)[3 * n:].view(n, 1)
+                if M:
+                    if v3:
+                        L.check(lib.nrf_project_fetch(C.byref(dn), L.ptr(self._pos), M, L.ptr(self._feats), None, st))
+                    L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(self._pos), L.ptr(self._dirs), L.ptr(self._feats), M, L.ptr(rgb), L.ptr(den),
+                                                      ctx, self.nbytes, st))
+                heads = (L.ptr(rgb), 3, L.ptr(den), 1)
+                d_heads = (L.ptr(g_rgb), 3, L.ptr(g_den), 1)
+            del keep, occ_keep
+            opt = self.opt
+            multi = (self.reg_weight > 0.0 or self.depth_weight > 0.0 or self.noise_std > 0.0 or opt.extended or target_depth is not None
+                     or noise is not None)
+            td = None if target_depth is None else L.dev_f32(target_depth, dev).reshape(R)
+            nz = None if noise is None or self.noise_std == 0.0 else L.dev_f32(noise, dev).reshape(R, S)
+            nseed = 0
+            if self.noise_std > 0.0 and nz is None:
+                if self.seed is None:
+                    self.seed = L.fresh_seed()
+                nseed = self.seed + opt.step_count
+            # the one indexed entry serves both steps: with every option off its bits are the mse kernel's
+            lo = L.loss_opts(self.rgb_weight, self.reg_weight, self.depth_weight, L.ptr(td), self.noise_std, L.ptr(nz), nseed)
+            L.check(lib.nrf_composite_loss_backward_indexed(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo),
+                                                            self._slot.data_ptr(), L.ptr(self.pred), *d_heads, L.ptr(self.ray_loss),
+                                                            L.ptr(self.grad), self.grad.numel(), st))
+            if M:
+                if v1:
+                    L.check(lib.nrf_mlp_backward_v1(h, mode, L.ptr(o4), L.ptr(d4), M, ctx, self.nbytes, L.ptr(self.grad), st))
+                else:
+                    L.check(lib.nrf_mlp_backward(h, mode, L.ptr(rgb), L.ptr(den), L.ptr(g_rgb), L.ptr(g_den), M, ctx, self.nbytes, L.ptr(self.grad), st))
+            if self.data_parallel:
+                _all_reduce_mean(self.grad, self.group)
+            fp, flat = opt._buffers()
+            opt.step_count += 1
+            if multi:
+                loss = torch.empty((4,), dtype=torch.float32, device=dev)
+                opt._update(flat, self.grad, self.ray_loss, R, S, (self.rgb_weight, self.depth_weight if target_depth is not None else 0.0,
+                                                                   self.reg_weight), loss)
+                self._loss_vec, self.last_grad_norm = loss, opt.last_grad_norm
+                loss = loss[0]
+            else:
+                loss = torch.empty((), dtype=torch.float32, device=dev)
                 L.check(lib.nrf_adam_step_loss(L.ptr(flat), L.ptr(self.grad), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq), flat.numel(), opt.lr,
                                                opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, opt.step_count, L.ptr(self.ray_loss), R,
                                                self.rgb_weight, L.ptr(loss), st))
