@@ -120,6 +120,7 @@ class NeRFMLP(nn.Module):
         self._gen = 0                # bumped by optimizers that update the flat vector behind autograd's back
         self._flat = None
         self._train_ready = False
+        self._bwd_modes = set()      # training modes whose BACKWARD stream matches _packed (mirrors the library's per-mode flag)
 
     # ---- parameters in the order include/nerfhip.h documents ------------------------------------
     def linears(self):
@@ -204,16 +205,17 @@ class NeRFMLP(nn.Module):
         flat = self._flat_on(idx) if same else None
         if flat is not None:
             # parameters live in the flat device vector (training): re-pack the asked-for modes' streams on the device
-            # A re-pack marks the backward weights of every mode outside its mask stale.  When the training mode's streams already
-            # hold THESE parameters (an eval-mode forward between two steps packed them: OccupancyGrid.refresh) and another mode is
-            # asked for at the same version (a validation render), the training mode rides along in the one call, so that the next
-            # step still finds its backward weights current.
-            ride = set()
-            if self._packed == ver and self._packed_modes and self._train_ready and getattr(self, "_train_mode", None) in self._packed_modes:
-                ride = {self._train_mode}
+            # A re-pack marks the backward weights of every mode outside its mask stale.  Every training mode whose backward stream
+            # already holds THESE parameters rides along in the one call when another mode is asked for at the same version: the
+            # step's own mode after an eval-mode forward between two steps packed it (OccupancyGrid.refresh) and a validation
+            # render follows; two render_rays(mma_mode=) graphs in different modes with a third mode read before their backward.
+            # _bwd_modes is that set.  At a new version nothing rides: a training step costs one call with one mode bit.
+            ride = self._bwd_modes if self._packed == ver and self._train_ready else set()
+            mask = modes | ride
             with torch.cuda.device(idx):
-                L.check(L.lib().nrf_model_update_device(self._handle, L.ptr(flat), sum(1 << k for k in modes | ride), L.stream_ptr()))
+                L.check(L.lib().nrf_model_update_device(self._handle, L.ptr(flat), sum(1 << k for k in mask), L.stream_ptr()))
             self._packed_modes = (modes if self._packed != ver or self._packed_modes is None else self._packed_modes | modes)
+            self._bwd_modes = {k for k in mask if k < 3} if self._train_ready else set()
             self._packed = ver
             return self._handle
         arr, n, keep = self._host_linears()
@@ -229,11 +231,12 @@ class NeRFMLP(nn.Module):
             self._train_ready = False
         del keep
         self._packed, self._packed_modes = ver, None
+        self._bwd_modes = {0, 1, 2} if self._train_ready else set()      # nrf_model_update packs every backward stream there is
         return self._handle
 
     # native state never travels with a copy: copy.deepcopy / pickle of a module that has rendered or trained would otherwise
     # duplicate the nrf_model* (freed twice) and alias the flat vectors
-    _NATIVE = ("_handle", "_handle_dev", "_packed", "_packed_modes", "_flat", "_flat_grad", "_flat_grad_views", "_linears_cache", "_train_ready")
+    _NATIVE = ("_handle", "_handle_dev", "_packed", "_packed_modes", "_flat", "_flat_grad", "_flat_grad_views", "_linears_cache", "_train_ready", "_bwd_modes")
 
     def __getstate__(self):
         st = self.__dict__.copy()
@@ -245,6 +248,7 @@ class NeRFMLP(nn.Module):
         super().__setstate__(st)
         self._handle = self._handle_dev = self._packed = self._packed_modes = self._flat = None
         self._train_ready = False
+        self._bwd_modes = set()
         self.__dict__.setdefault("_gen", 0)
 
     def release(self):

@@ -115,7 +115,7 @@ def _train_handle(module, dev, mma_mode=None):
             L.check(L.lib().nrf_model_update_device(h, L.ptr(module.flat_params().flat), 1 << mode, L.stream_ptr()))
         module._train_ready = True
         module._packed, module._packed_modes = module._versions(), {mode}
-    module._train_mode = mode            # (nerf_model.handle: the mode whose backward weights a later re-pack must not leave stale)
+        module._bwd_modes = {mode}       # (nerf_model.handle: the modes whose backward weights a later re-pack must not leave stale)
     return h, mode
 
 
