@@ -311,12 +311,10 @@ def density_normals(model: NeRFMLP, points, dino=None):
     if getattr(model, "point_grad", False):
         if dino is None:
             raise ValueError("density_normals of a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
-        from .training import field_input_grad_v3
-        return field_input_grad_v3(model, points, dino)
-    if not getattr(model, "input_grad", False):
+    elif not getattr(model, "input_grad", False):
         raise ValueError("density_normals needs a model built with NeRFMLP(..., input_grad=True) (use_dino form: point_grad=True)")
     from .training import field_input_grad
-    return field_input_grad(model, points)
+    return field_input_grad(model, points, dino)
 
 
 def load_checkpoint_into(model: NeRFMLP, ckpt: dict):

@@ -13,10 +13,13 @@
                      (rgb_weight * mse, Adam) or train_multiscale.py's (density noise, nerf_mlp.NeRFLoss, clipping, AdamW);
   * `all_reduce_gradients`   data-parallel training: ONE collective per step on the flat gradient vector.
 
+Each launch sequence is written once: module-level helpers (_context .. _render_backward) and FusedStep's _launch_loss / _finish.
+
 There is no PyTorch fallback: without libnerfhip.so / a gfx950 GPU every call raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import torch
@@ -101,6 +104,48 @@ def _grad_target(module):
     return None
 
 
+def _context_bytes(h, mode, n):
+    """Bytes of the context a saving forward over n rows fills (call with the device current)."""
+    nbytes = L.lib().nrf_train_context_bytes(h, mode, n)
+    if nbytes < 0:
+        raise L.NrfError(-2, L.lib().nrf_last_error().decode("utf-8", "replace"))
+    return nbytes
+
+
+def _context(h, mode, n, dev):
+    """(buffer, nbytes): the context of a saving forward over n rows, allocated (call with the device current)."""
+    nbytes = _context_bytes(h, mode, n)
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev), nbytes
+
+
+def _heads(o4, n, v1):
+    """The two heads inside an (n,4) buffer of network outputs (or of their gradients) and the compositor's (ptr, stride, ptr, stride)
+    for them.  V1: [r,g,b,sigma] rows, read strided -- (o4, None, args).  V2/V3: rgb (n,3) | density (n,1) packed in the same storage,
+    which is not strided: two plain tensors as views -- (rgb, density, args)."""
+    if v1:
+        return o4, None, (L.ptr(o4), 4, C.c_void_p(o4.data_ptr() + 12), 4)
+    rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
+    return rgb, den, (L.ptr(rgb), 3, L.ptr(den), 1)
+
+
+def _prep(g):
+    """An incoming gradient as the kernels read it; None (an unused output) stays None."""
+    return None if g is None else g.to(torch.float32).contiguous()
+
+
+def _param_grad_target(module, wanted=True):
+    """(the flat vector a backward's weight-gradient kernels add into, what that backward returns for its *params slots).
+    wanted=False (frozen parameters: an input-gradient backward) and a module whose .grad tensors are not ours (_grad_target: None)
+    get a zeroed scratch vector; only the latter hands its per-parameter views to autograd.  Otherwise the kernels accumulate
+    into the parameters' .grad directly and autograd is handed nothing."""
+    fp = module.flat_params()
+    direct = _grad_target(module) if wanted else None
+    if direct is not None:
+        return direct, (None,) * len(fp.offsets)           # already accumulated into the parameters' .grad
+    grad = torch.zeros_like(fp.flat)
+    return grad, (tuple(fp.views(grad)) if wanted else (None,) * len(fp.offsets))
+
+
 def _train_handle(module, dev, mma_mode=None):
     """nrf_model* with forward AND backward streams matching the current parameter values."""
     module.flat_params().ensure()
@@ -110,8 +155,7 @@ def _train_handle(module, dev, mma_mode=None):
     if not module._train_ready:
         # first use: build the backward plan, then pack both directions from the flat vector
         with torch.cuda.device(dev):
-            if L.lib().nrf_train_context_bytes(h, mode, 1) < 0:
-                raise L.NrfError(-2, L.lib().nrf_last_error().decode("utf-8", "replace"))
+            _context_bytes(h, mode, 1)
             L.check(L.lib().nrf_model_update_device(h, L.ptr(module.flat_params().flat), 1 << mode, L.stream_ptr()))
         module._train_ready = True
         module._packed, module._packed_modes = module._versions(), {mode}
@@ -138,30 +182,22 @@ def _live_input(module, t, what, device=None):
 
 
 def _input_grad(module, mode, n, buf, nbytes, dev, positions=None, directions=None, want_x=False, want_p=False, want_d=False):
-    """(d_x_enc, d_positions, d_directions) -- None where not asked for -- of a V1 / V2 module, from the context of a finished
-    nrf_mlp_backward_v1 / nrf_mlp_backward (one launch)."""
+    """(d_x_enc, d_positions, d_directions) -- None where not asked for -- of a module, from the context of a finished
+    nrf_mlp_backward_v1 / nrf_mlp_backward (one launch).  V3: through the positional encodings; there is no d_x_enc, and the share of
+    d_positions through the fetched features is not in it (points_fetch_backward)."""
+    v3 = module.net == L.NRF_NET_V3
+    want_x = want_x and not v3
     if not (want_x or want_p or want_d):
         return None, None, None
-    pe = 3 * (2 * module.pos_freq + 1)
-    d_x = torch.empty((n, pe), dtype=torch.float32, device=dev) if want_x else None
+    d_x = torch.empty((n, 3 * (2 * module.pos_freq + 1)), dtype=torch.float32, device=dev) if want_x else None
     d_p = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_p else None
     d_d = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_d else None
-    L.check(L.lib().nrf_mlp_backward_inputs(module._handle, mode, n, C.c_void_p(buf.data_ptr()), nbytes, L.ptr(positions) if want_p else None,
-                                            L.ptr(directions) if want_d else None, L.ptr(d_x), L.ptr(d_p), L.ptr(d_d), L.stream_ptr()))
+    saved = (module._handle, mode, n, C.c_void_p(buf.data_ptr()), nbytes, L.ptr(positions) if want_p else None, L.ptr(directions) if want_d else None)
+    if v3:
+        L.check(L.lib().nrf_mlp_backward_inputs_v3(*saved, L.ptr(d_p), L.ptr(d_d), L.stream_ptr()))
+    else:
+        L.check(L.lib().nrf_mlp_backward_inputs(*saved, L.ptr(d_x), L.ptr(d_p), L.ptr(d_d), L.stream_ptr()))
     return d_x, d_p, d_d
-
-
-def _input_grad_v3(module, mode, n, buf, nbytes, dev, positions=None, directions=None, want_p=False, want_d=False):
-    """(d_positions, d_directions) -- None where not asked for -- of a V3 module through the positional encodings, from the context
-    of a finished nrf_mlp_backward (one launch).  The share of d_positions through the fetched features is not in it
-    (points_fetch_backward)."""
-    if not (want_p or want_d):
-        return None, None
-    d_p = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_p else None
-    d_d = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_d else None
-    L.check(L.lib().nrf_mlp_backward_inputs_v3(module._handle, mode, n, C.c_void_p(buf.data_ptr()), nbytes, L.ptr(positions) if want_p else None,
-                                               L.ptr(directions) if want_d else None, L.ptr(d_p), L.ptr(d_d), L.stream_ptr()))
-    return d_p, d_d
 
 
 def points_fetch_backward(dino, points, d_feats, d_points=None):
@@ -253,10 +289,7 @@ class _MLPV1Fn(torch.autograd.Function):
         n = x_enc.shape[0]
         out = torch.empty((n, 4), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            nbytes = L.lib().nrf_train_context_bytes(h, mode, n)
-            if nbytes < 0:
-                raise L.NrfError(-2, L.lib().nrf_last_error().decode("utf-8", "replace"))
-            buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+            buf, nbytes = _context(h, mode, n, dev)
             L.check(L.lib().nrf_mlp_forward_train_v1(h, mode, L.ptr(x_enc), n, L.ptr(out), C.c_void_p(buf.data_ptr()), nbytes, L.stream_ptr()))
         ctx.module, ctx.buf, ctx.nbytes, ctx.n, ctx.mode = module, buf, nbytes, n, mode
         ctx.versions = module._versions()
@@ -271,14 +304,8 @@ class _MLPV1Fn(torch.autograd.Function):
                                "no longer match the packed weights")
         out, points = ctx.saved_tensors
         dev = out.device
-        g = g_out.to(torch.float32).contiguous()
-        fp = module.flat_params()
-        wanted = any(ctx.needs_input_grad[3:])
-        if not wanted:                                   # frozen parameters: an input-gradient backward
-            grad, direct = torch.zeros_like(fp.flat), fp.flat
-        else:
-            direct = _grad_target(module)
-            grad = direct if direct is not None else torch.zeros_like(fp.flat)
+        g = _prep(g_out)
+        grad, d_params = _param_grad_target(module, any(ctx.needs_input_grad[3:]))
         with torch.cuda.device(dev):
             L.check(L.lib().nrf_mlp_backward_v1(module._handle, ctx.mode, L.ptr(out), L.ptr(g), ctx.n, C.c_void_p(ctx.buf.data_ptr()), ctx.nbytes,
                                                 L.ptr(grad), L.stream_ptr()))
@@ -286,9 +313,7 @@ class _MLPV1Fn(torch.autograd.Function):
             d_x, d_p, _ = _input_grad(module, ctx.mode, ctx.n, ctx.buf, ctx.nbytes, dev, positions=points,
                                       want_x=ctx.needs_input_grad[1], want_p=ctx.needs_input_grad[2])
         ctx.buf = None
-        if direct is not None:
-            return (None, d_x, d_p) + (None,) * len(fp.offsets)   # already accumulated into the parameters' .grad
-        return (None, d_x, d_p, *fp.views(grad))
+        return (None, d_x, d_p) + d_params
 
 
 class _MLPV2Fn(torch.autograd.Function):
@@ -302,10 +327,7 @@ class _MLPV2Fn(torch.autograd.Function):
         rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
         dens = torch.empty((n, 1), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            nbytes = L.lib().nrf_train_context_bytes(h, mode, n)
-            if nbytes < 0:
-                raise L.NrfError(-2, L.lib().nrf_last_error().decode("utf-8", "replace"))
-            buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+            buf, nbytes = _context(h, mode, n, dev)
             L.check(L.lib().nrf_mlp_forward_train(h, mode, L.ptr(pos), L.ptr(dirs), L.ptr(dino), n, L.ptr(rgb), L.ptr(dens),
                                                   C.c_void_p(buf.data_ptr()), nbytes, L.stream_ptr()))
         ctx.module, ctx.buf, ctx.nbytes, ctx.n, ctx.mode = module, buf, nbytes, n, mode
@@ -321,30 +343,18 @@ class _MLPV2Fn(torch.autograd.Function):
                                "no longer match the packed weights")
         rgb, dens, pos, dirs = ctx.saved_tensors
         dev = rgb.device
-        g_rgb = g_rgb.to(torch.float32).contiguous()
-        g_dens = g_dens.to(torch.float32).contiguous()
-        fp = module.flat_params()
-        if not any(ctx.needs_input_grad[4:]):            # frozen parameters: an input-gradient backward
-            grad, direct = torch.zeros_like(fp.flat), fp.flat
-        else:
-            direct = _grad_target(module)
-            grad = direct if direct is not None else torch.zeros_like(fp.flat)
+        g_rgb, g_dens = _prep(g_rgb), _prep(g_dens)
+        grad, d_params = _param_grad_target(module, any(ctx.needs_input_grad[4:]))
         with torch.cuda.device(dev):
             L.check(L.lib().nrf_mlp_backward(module._handle, ctx.mode, L.ptr(rgb), L.ptr(dens), L.ptr(g_rgb), L.ptr(g_dens), ctx.n,
                                              C.c_void_p(ctx.buf.data_ptr()), ctx.nbytes, L.ptr(grad), L.stream_ptr()))
             # dino_grad modules with features that require grad: one more launch over what the backward saved
             d_dino = _dino_grad(module, ctx.mode, ctx.n, ctx.buf, ctx.nbytes, dev) if ctx.needs_input_grad[3] else None
-            # input_grad modules with positions / directions that require grad: likewise
-            if module.net == L.NRF_NET_V3:               # point_grad modules: the share through the positional encodings
-                d_p, d_d = _input_grad_v3(module, ctx.mode, ctx.n, ctx.buf, ctx.nbytes, dev, positions=pos, directions=dirs,
-                                          want_p=ctx.needs_input_grad[1], want_d=ctx.needs_input_grad[2])
-            else:
-                _, d_p, d_d = _input_grad(module, ctx.mode, ctx.n, ctx.buf, ctx.nbytes, dev, positions=pos, directions=dirs,
-                                          want_p=ctx.needs_input_grad[1], want_d=ctx.needs_input_grad[2])
+            # input_grad / point_grad modules with positions / directions that require grad: likewise
+            _, d_p, d_d = _input_grad(module, ctx.mode, ctx.n, ctx.buf, ctx.nbytes, dev, positions=pos, directions=dirs,
+                                      want_p=ctx.needs_input_grad[1], want_d=ctx.needs_input_grad[2])
         ctx.buf = None
-        if direct is not None:
-            return (None, d_p, d_d, d_dino) + (None,) * len(fp.offsets)
-        return (None, d_p, d_d, d_dino, *fp.views(grad))
+        return (None, d_p, d_d, d_dino) + d_params
 
 
 def mlp_v2_train(module, positions, directions, dino_features=None):
@@ -383,53 +393,23 @@ def mlp_v1_train(module, x_enc, points=None):
     return out.reshape(*x.shape[:-1], 4)
 
 
-def field_input_grad_v3(module, points, dino):
-    """nerf_model.density_normals of a point_grad (V3) module: the fetch, one saving forward, the dZ chain with dL/d sigma = 1 (its
-    parameter gradients go to a scratch vector), dL/d features, the input-gradient kernel and the adjoint of the fetch added onto it."""
-    from .renderer import make_dino
-    pts = L.dev_f32(points).reshape(-1, 3)
-    dev, n = pts.device, pts.shape[0]
-    h, mode = _train_handle(module, dev)
-    lib = L.lib()
-    dn, keep = make_dino(**{**dino, "features": L.dev_f32(dino["features"], dev)})
-    if dn.C != module.dino_dim:
-        raise ValueError("features must be (1,Hp,Wp,dino_dim)")
-    with torch.cuda.device(dev):
-        nbytes = lib.nrf_train_context_bytes(h, mode, n)
-        if nbytes < 0:
-            raise L.NrfError(-2, lib.nrf_last_error().decode("utf-8", "replace"))
-        buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-        scratch = torch.zeros_like(module.flat_params().flat)
-        st, cb = L.stream_ptr(), C.c_void_p(buf.data_ptr())
-        feats = torch.empty((n, dn.C), dtype=torch.float32, device=dev)
-        L.check(lib.nrf_project_fetch(C.byref(dn), L.ptr(pts), n, L.ptr(feats), None, st))
-        dirs = torch.zeros_like(pts)                     # the density does not depend on the view direction
-        rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        sigma = torch.empty((n, 1), dtype=torch.float32, device=dev)
-        L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(pts), L.ptr(dirs), L.ptr(feats), n, L.ptr(rgb), L.ptr(sigma), cb, nbytes, st))
-        g_rgb, g_den = torch.zeros_like(rgb), torch.ones_like(sigma)
-        L.check(lib.nrf_mlp_backward(h, mode, L.ptr(rgb), L.ptr(sigma), L.ptr(g_rgb), L.ptr(g_den), n, cb, nbytes, L.ptr(scratch), st))
-        d_feats = _dino_grad(module, mode, n, buf, nbytes, dev)
-        g, _ = _input_grad_v3(module, mode, n, buf, nbytes, dev, positions=pts, want_p=True)
-        L.check(lib.nrf_project_fetch_backward_points(C.byref(dn), L.ptr(pts), n, L.ptr(d_feats), L.ptr(g), 1, st))
-    del keep
-    norm = g.norm(dim=-1, keepdim=True)
-    normals = torch.where(norm > 0, -g / norm.clamp_min(1e-30), torch.zeros_like(g))
-    return sigma, normals
-
-
-def field_input_grad(module, points):
+def field_input_grad(module, points, dino=None):
     """nerf_model.density_normals: one saving forward, the dZ chain with dL/d sigma = 1 (its parameter gradients go to a scratch
-    vector) and the input-gradient kernel."""
+    vector) and the input-gradient kernel.  A point_grad (V3) module with its source view `dino`: the fetch in front, and behind the
+    chain dL/d features and the adjoint of the fetch added onto the input-gradient kernel's result."""
     pts = L.dev_f32(points).reshape(-1, 3)
     dev, n = pts.device, pts.shape[0]
     h, mode = _train_handle(module, dev)
     lib = L.lib()
+    v3 = module.net == L.NRF_NET_V3
+    dn = keep = None
+    if v3:
+        from .renderer import make_dino
+        dn, keep = make_dino(**{**dino, "features": L.dev_f32(dino["features"], dev)})
+        if dn.C != module.dino_dim:
+            raise ValueError("features must be (1,Hp,Wp,dino_dim)")
     with torch.cuda.device(dev):
-        nbytes = lib.nrf_train_context_bytes(h, mode, n)
-        if nbytes < 0:
-            raise L.NrfError(-2, lib.nrf_last_error().decode("utf-8", "replace"))
-        buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
+        buf, nbytes = _context(h, mode, n, dev)
         scratch = torch.zeros_like(module.flat_params().flat)
         st, cb = L.stream_ptr(), C.c_void_p(buf.data_ptr())
         if module.net == L.NRF_NET_V1:
@@ -440,13 +420,21 @@ def field_input_grad(module, points):
             L.check(lib.nrf_mlp_backward_v1(h, mode, L.ptr(out), L.ptr(g), n, cb, nbytes, L.ptr(scratch), st))
             sigma = out[:, 3:4].contiguous()
         else:
+            feats = None
+            if v3:
+                feats = torch.empty((n, dn.C), dtype=torch.float32, device=dev)
+                L.check(lib.nrf_project_fetch(C.byref(dn), L.ptr(pts), n, L.ptr(feats), None, st))
             dirs = torch.zeros_like(pts)                 # the density does not depend on the view direction
             rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
             sigma = torch.empty((n, 1), dtype=torch.float32, device=dev)
-            L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(pts), L.ptr(dirs), None, n, L.ptr(rgb), L.ptr(sigma), cb, nbytes, st))
+            L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(pts), L.ptr(dirs), L.ptr(feats), n, L.ptr(rgb), L.ptr(sigma), cb, nbytes, st))
             g_rgb, g_den = torch.zeros_like(rgb), torch.ones_like(sigma)          # (named: they must outlive the launch's pointers)
             L.check(lib.nrf_mlp_backward(h, mode, L.ptr(rgb), L.ptr(sigma), L.ptr(g_rgb), L.ptr(g_den), n, cb, nbytes, L.ptr(scratch), st))
+        d_feats = _dino_grad(module, mode, n, buf, nbytes, dev) if v3 else None
         _, g, _ = _input_grad(module, mode, n, buf, nbytes, dev, positions=pts, want_p=True)
+        if v3:
+            L.check(lib.nrf_project_fetch_backward_points(C.byref(dn), L.ptr(pts), n, L.ptr(d_feats), L.ptr(g), 1, st))
+    del keep
     norm = g.norm(dim=-1, keepdim=True)
     normals = torch.where(norm > 0, -g / norm.clamp_min(1e-30), torch.zeros_like(g))
     return sigma, normals
@@ -468,7 +456,7 @@ class _CompositeFn(torch.autograd.Function):
         out_depth = torch.empty((R,), dtype=torch.float32, device=dev)
         out_w = torch.empty((R, S), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            L.check(L.lib().nrf_composite(L.ptr(packed), 4, C.c_void_p(packed.data_ptr() + 12), 4, L.ptr(z), L.ptr(d), R, S,
+            L.check(L.lib().nrf_composite(*_heads(packed, R * S, True)[2], L.ptr(z), L.ptr(d), R, S,
                                           int(bool(white_bkgd)), L.ptr(out_rgb), L.ptr(out_depth), L.ptr(out_w), L.stream_ptr()))
         ctx.save_for_backward(packed, z, d)
         ctx.white, ctx.geom = int(bool(white_bkgd)), bool(geom)
@@ -480,23 +468,19 @@ class _CompositeFn(torch.autograd.Function):
         packed, z, d = ctx.saved_tensors
         R, S = z.shape
         dev = z.device
-
-        def prep(g):
-            return None if g is None else g.to(torch.float32).contiguous()
-        g_rgb, g_depth, g_w = prep(g_rgb), prep(g_depth), prep(g_w)
+        g_rgb, g_depth, g_w = _prep(g_rgb), _prep(g_depth), _prep(g_w)
         d_packed = torch.empty_like(packed)
         if g_rgb is None and g_depth is None and g_w is None:
             return None, None, None, None, None
+        heads, d_heads = _heads(packed, R * S, True)[2], _heads(d_packed, R * S, True)[2]
         with torch.cuda.device(dev):
             if ctx.geom:
                 d_z, d_d = torch.empty_like(z), torch.empty_like(d)
-                L.check(L.lib().nrf_composite_backward_geom(L.ptr(packed), 4, C.c_void_p(packed.data_ptr() + 12), 4, L.ptr(z), L.ptr(d), R, S,
-                                                            ctx.white, L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w), L.ptr(d_packed), 4,
-                                                            C.c_void_p(d_packed.data_ptr() + 12), 4, L.ptr(d_z), L.ptr(d_d), L.stream_ptr()))
+                L.check(L.lib().nrf_composite_backward_geom(*heads, L.ptr(z), L.ptr(d), R, S, ctx.white, L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w),
+                                                            *d_heads, L.ptr(d_z), L.ptr(d_d), L.stream_ptr()))
                 return d_packed, d_z, d_d, None, None
-            L.check(L.lib().nrf_composite_backward(L.ptr(packed), 4, C.c_void_p(packed.data_ptr() + 12), 4, L.ptr(z), L.ptr(d), R, S, ctx.white,
-                                                   L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w), L.ptr(d_packed), 4,
-                                                   C.c_void_p(d_packed.data_ptr() + 12), 4, L.stream_ptr()))
+            L.check(L.lib().nrf_composite_backward(*heads, L.ptr(z), L.ptr(d), R, S, ctx.white, L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w),
+                                                   *d_heads, L.stream_ptr()))
         return d_packed, None, None, None, None
 
 
@@ -511,6 +495,96 @@ def composite(rgb_sigma, z, d, white_bkgd=False, geom_grad=False):
 # ---------------------------------------------------------------------------------------------
 # render_rays with grad enabled: the trainer-shaped entry point (train.py:188-242 inside train_step, :280-287)
 # ---------------------------------------------------------------------------------------------
+def _render_forward(ctx, module, inputs, z, d, white, mma_mode):
+    """The forward the render nodes share: context, o4 (V1: [r,g,b,sigma] rows; V2/V3: rgb (n,3) | density (n,1)) and the three
+    outputs, the family's saving forward, the compositor.  inputs(stream) -> (x, dirs, dino) as the saving forward reads them: a
+    node that derives them (encoding, fetch) launches that here, behind the context query, where it has always run.  Leaves on
+    ctx what _render_backward reads; returns (o4, (rgb, depth, weights))."""
+    dev = z.device
+    R, S = z.shape
+    n = R * S
+    h, mode = _train_handle(module, dev, mma_mode)
+    v1 = module.net == L.NRF_NET_V1
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        buf, nbytes = _context(h, mode, n, dev)
+        o4 = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        out_rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
+        out_depth = torch.empty((R,), dtype=torch.float32, device=dev)
+        out_w = torch.empty((R, S), dtype=torch.float32, device=dev)
+        st, cb = L.stream_ptr(), C.c_void_p(buf.data_ptr())
+        x, dirs, dino = inputs(st)
+        rgb, den, heads = _heads(o4, n, v1)
+        if v1:
+            L.check(lib.nrf_mlp_forward_train_v1(h, mode, L.ptr(x), n, L.ptr(o4), cb, nbytes, st))
+        else:
+            L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(x), L.ptr(dirs), L.ptr(dino), n, L.ptr(rgb), L.ptr(den), cb, nbytes, st))
+        L.check(lib.nrf_composite(*heads, L.ptr(z), L.ptr(d), R, S, white, L.ptr(out_rgb), L.ptr(out_depth), L.ptr(out_w), st))
+    ctx.module, ctx.buf, ctx.nbytes, ctx.mode, ctx.white, ctx.v1, ctx.dev = module, buf, nbytes, mode, white, v1, dev
+    ctx.versions = module._packed                    # the versions handle() just packed (== module._versions(), not recomputed)
+    ctx.set_materialize_grads(False)
+    return o4, (out_rgb, out_depth, out_w)
+
+
+# what _render_backward leaves for the launches a node adds behind it: the saved tensors, rows, stream, what the node returns for
+# its *params slots, and (geom) the compositor's own dL/d z and dL/d rays_d
+_Backward = collections.namedtuple("_Backward", "saved n st d_params d_zc d_dc")
+
+
+def _no_grads(ctx, n_in):
+    """What a render node returns when none of its outputs was used."""
+    return (None,) * (n_in + len(ctx.module.flat_params().offsets))
+
+
+def _render_backward(ctx, g_rgb, g_depth, g_w, n_in, geom):
+    """The opening the render nodes' backwards share (call with ctx.dev current): version check, gradient prep, the gradient
+    target, compositor backward (geom: nrf_composite_backward_geom), network backward.  Returns a _Backward, or None when no
+    output was used: nothing is launched then and the node returns _no_grads."""
+    module = ctx.module
+    if module._versions() != ctx.versions:
+        raise RuntimeError("NeRFMLP parameters were modified between render_rays and backward: the saved activations "
+                           "no longer match the packed weights")
+    saved = ctx.saved_tensors
+    o4, z, d = saved[:3]
+    R, S = z.shape
+    n = R * S
+    lib = L.lib()
+    g_rgb, g_depth, g_w = _prep(g_rgb), _prep(g_depth), _prep(g_w)
+    if g_rgb is None and g_depth is None and g_w is None:
+        return None
+    # geom nodes exist for their input gradients: frozen parameters get a scratch vector.  _RenderFn does not consult
+    # needs_input_grad for the parameters (it always accumulates into their .grad): kept as it is
+    grad, d_params = _param_grad_target(module, not geom or any(ctx.needs_input_grad[n_in:]))
+    d4 = torch.empty_like(o4)
+    d_zc, d_dc = (torch.empty_like(z), torch.empty_like(d)) if geom else (None, None)
+    st, cb = L.stream_ptr(), C.c_void_p(ctx.buf.data_ptr())
+    rgb, den, heads = _heads(o4, n, ctx.v1)
+    d_rgb, d_den, d_heads = _heads(d4, n, ctx.v1)
+    if geom:
+        L.check(lib.nrf_composite_backward_geom(*heads, L.ptr(z), L.ptr(d), R, S, ctx.white, L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w),
+                                                *d_heads, L.ptr(d_zc), L.ptr(d_dc), st))
+    else:
+        L.check(lib.nrf_composite_backward(*heads, L.ptr(z), L.ptr(d), R, S, ctx.white, L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w),
+                                           *d_heads, st))
+    if ctx.v1:
+        L.check(lib.nrf_mlp_backward_v1(module._handle, ctx.mode, L.ptr(o4), L.ptr(d4), n, cb, ctx.nbytes, L.ptr(grad), st))
+    else:
+        L.check(lib.nrf_mlp_backward(module._handle, ctx.mode, L.ptr(rgb), L.ptr(den), L.ptr(d_rgb), L.ptr(d_den), n, cb, ctx.nbytes,
+                                     L.ptr(grad), st))
+    return _Backward(saved, n, st, d_params, d_zc, d_dc)
+
+
+def _ray_grad(d_p, d_dirs, z, d, d_zc, d_dc, z_live, st):
+    """(d_rays_o, d_rays_d, d_z or None): the adjoint of the points and per-sample directions of rays, added to the compositor's own
+    dL/d z and dL/d rays_d (one launch; call with the device current)."""
+    R, S = z.shape
+    d_o, d_d = torch.empty_like(d), torch.empty_like(d)
+    d_z = torch.empty_like(z) if z_live else None
+    L.check(L.lib().nrf_ray_grad(L.ptr(d_p), L.ptr(d_dirs), L.ptr(z), L.ptr(d), L.ptr(d_zc), L.ptr(d_dc), R, S, L.ptr(d_o), L.ptr(d_d),
+                                 L.ptr(d_z), st))
+    return d_o, d_d, d_z
+
+
 class _RenderFn(torch.autograd.Function):
     """Per-sample network inputs + depths + rays -> (rgb (R,3), depth (R,), weights (R,S)), differentiable with respect to the
     parameters: ONE autograd node over the kernels FusedStep runs (saving forward -> composite | composite backward -> dZ
@@ -519,77 +593,19 @@ class _RenderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, x, dirs, dino, z, d, white, mma_mode, *params):
-        dev = z.device
-        R, S = z.shape
-        n = R * S
-        h, mode = _train_handle(module, dev, mma_mode)
-        v1 = module.net == L.NRF_NET_V1
-        lib = L.lib()
-        with torch.cuda.device(dev):
-            nbytes = lib.nrf_train_context_bytes(h, mode, n)
-            if nbytes < 0:
-                raise L.NrfError(-2, lib.nrf_last_error().decode("utf-8", "replace"))
-            buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-            o4 = torch.empty((n, 4), dtype=torch.float32, device=dev)          # V1: [r,g,b,sigma] rows; V2/V3: rgb (n,3) | density (n,1)
-            out_rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
-            out_depth = torch.empty((R,), dtype=torch.float32, device=dev)
-            out_w = torch.empty((R, S), dtype=torch.float32, device=dev)
-            st, cb = L.stream_ptr(), C.c_void_p(buf.data_ptr())
-            if v1:
-                L.check(lib.nrf_mlp_forward_train_v1(h, mode, L.ptr(x), n, L.ptr(o4), cb, nbytes, st))
-                L.check(lib.nrf_composite(L.ptr(o4), 4, C.c_void_p(o4.data_ptr() + 12), 4, L.ptr(z), L.ptr(d), R, S, white,
-                                          L.ptr(out_rgb), L.ptr(out_depth), L.ptr(out_w), st))
-            else:
-                rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
-                L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(x), L.ptr(dirs), L.ptr(dino), n, L.ptr(rgb), L.ptr(den), cb, nbytes, st))
-                L.check(lib.nrf_composite(L.ptr(rgb), 3, L.ptr(den), 1, L.ptr(z), L.ptr(d), R, S, white, L.ptr(out_rgb), L.ptr(out_depth), L.ptr(out_w), st))
-        ctx.module, ctx.buf, ctx.nbytes, ctx.mode, ctx.white, ctx.v1 = module, buf, nbytes, mode, white, v1
-        ctx.versions = module._packed                    # the versions handle() just packed (== module._versions(), not recomputed)
+        o4, outs = _render_forward(ctx, module, lambda st: (x, dirs, dino), z, d, white, mma_mode)
         ctx.save_for_backward(o4, z, d)
-        ctx.set_materialize_grads(False)
-        return out_rgb, out_depth, out_w
+        return outs
 
     @staticmethod
     def backward(ctx, g_rgb, g_depth, g_w):
-        module = ctx.module
-        if module._versions() != ctx.versions:
-            raise RuntimeError("NeRFMLP parameters were modified between render_rays and backward: the saved activations "
-                               "no longer match the packed weights")
-        o4, z, d = ctx.saved_tensors
-        R, S = z.shape
-        n = R * S
-        dev = z.device
-        lib = L.lib()
-
-        def prep(g):
-            return None if g is None else g.to(torch.float32).contiguous()
-        g_rgb, g_depth, g_w = prep(g_rgb), prep(g_depth), prep(g_w)
-        n_in = 8
-        fp = module.flat_params()
-        if g_rgb is None and g_depth is None and g_w is None:
-            return (None,) * (n_in + len(fp.offsets))
-        direct = _grad_target(module)
-        grad = direct if direct is not None else torch.zeros_like(fp.flat)
-        with torch.cuda.device(dev):
-            d4 = torch.empty_like(o4)
-            st, cb = L.stream_ptr(), C.c_void_p(ctx.buf.data_ptr())
-            if ctx.v1:
-                L.check(lib.nrf_composite_backward(L.ptr(o4), 4, C.c_void_p(o4.data_ptr() + 12), 4, L.ptr(z), L.ptr(d), R, S, ctx.white,
-                                                   L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w), L.ptr(d4), 4, C.c_void_p(d4.data_ptr() + 12), 4, st))
-                L.check(lib.nrf_mlp_backward_v1(module._handle, ctx.mode, L.ptr(o4), L.ptr(d4), n, cb, ctx.nbytes, L.ptr(grad), st))
-            else:
-                rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
-                d_rgb, d_den = d4.view(-1)[:3 * n].view(n, 3), d4.view(-1)[3 * n:].view(n, 1)
-                L.check(lib.nrf_composite_backward(L.ptr(rgb), 3, L.ptr(den), 1, L.ptr(z), L.ptr(d), R, S, ctx.white,
-                                                   L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w), L.ptr(d_rgb), 3, L.ptr(d_den), 1, st))
-                L.check(lib.nrf_mlp_backward(module._handle, ctx.mode, L.ptr(rgb), L.ptr(den), L.ptr(d_rgb), L.ptr(d_den), n, cb, ctx.nbytes,
-                                             L.ptr(grad), st))
-            d_dino = _dino_grad(module, ctx.mode, n, ctx.buf, ctx.nbytes, dev) if ctx.needs_input_grad[3] else None      # a live feature map
+        with torch.cuda.device(ctx.dev):
+            b = _render_backward(ctx, g_rgb, g_depth, g_w, 8, False)
+            if b is None:
+                return _no_grads(ctx, 8)
+            d_dino = _dino_grad(ctx.module, ctx.mode, b.n, ctx.buf, ctx.nbytes, ctx.dev) if ctx.needs_input_grad[3] else None      # a live feature map
         ctx.buf = None
-        ins = (None, None, None, d_dino) + (None,) * (n_in - 4)
-        if direct is not None:
-            return ins + (None,) * len(fp.offsets)
-        return ins + tuple(fp.views(grad))
+        return (None, None, None, d_dino) + (None,) * 4 + b.d_params
 
 
 _encoders = {}
@@ -610,88 +626,29 @@ class _RenderGeomFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, o, d, z, z_live, pts, white, mma_mode, *params):
-        dev = z.device
         R, S = z.shape
-        n = R * S
-        h, mode = _train_handle(module, dev, mma_mode)
         v1 = module.net == L.NRF_NET_V1
-        lib = L.lib()
         dirs = None if v1 else d[:, None, :].expand(R, S, 3).reshape(-1, 3).contiguous()
-        with torch.cuda.device(dev):
-            nbytes = lib.nrf_train_context_bytes(h, mode, n)
-            if nbytes < 0:
-                raise L.NrfError(-2, lib.nrf_last_error().decode("utf-8", "replace"))
-            buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-            o4 = torch.empty((n, 4), dtype=torch.float32, device=dev)
-            out_rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
-            out_depth = torch.empty((R,), dtype=torch.float32, device=dev)
-            out_w = torch.empty((R, S), dtype=torch.float32, device=dev)
-            st, cb = L.stream_ptr(), C.c_void_p(buf.data_ptr())
-            if v1:
-                L.check(lib.nrf_mlp_forward_train_v1(h, mode, L.ptr(_encoder(module.pos_freq)(pts)), n, L.ptr(o4), cb, nbytes, st))
-                L.check(lib.nrf_composite(L.ptr(o4), 4, C.c_void_p(o4.data_ptr() + 12), 4, L.ptr(z), L.ptr(d), R, S, white,
-                                          L.ptr(out_rgb), L.ptr(out_depth), L.ptr(out_w), st))
-            else:
-                rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
-                L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(pts), L.ptr(dirs), None, n, L.ptr(rgb), L.ptr(den), cb, nbytes, st))
-                L.check(lib.nrf_composite(L.ptr(rgb), 3, L.ptr(den), 1, L.ptr(z), L.ptr(d), R, S, white, L.ptr(out_rgb), L.ptr(out_depth), L.ptr(out_w), st))
-        ctx.module, ctx.buf, ctx.nbytes, ctx.mode, ctx.white, ctx.v1, ctx.z_live = module, buf, nbytes, mode, white, v1, bool(z_live)
-        ctx.versions = module._packed
+
+        def inputs(st):
+            return (_encoder(module.pos_freq)(pts), None, None) if v1 else (pts, dirs, None)
+        o4, outs = _render_forward(ctx, module, inputs, z, d, white, mma_mode)
+        ctx.z_live = bool(z_live)
         ctx.save_for_backward(o4, z, d, pts, dirs)
-        ctx.set_materialize_grads(False)
-        return out_rgb, out_depth, out_w
+        return outs
 
     @staticmethod
     def backward(ctx, g_rgb, g_depth, g_w):
-        module = ctx.module
-        if module._versions() != ctx.versions:
-            raise RuntimeError("NeRFMLP parameters were modified between render_rays and backward: the saved activations "
-                               "no longer match the packed weights")
-        o4, z, d, pts, dirs = ctx.saved_tensors
-        R, S = z.shape
-        n = R * S
-        dev = z.device
-        lib = L.lib()
-
-        def prep(g):
-            return None if g is None else g.to(torch.float32).contiguous()
-        g_rgb, g_depth, g_w = prep(g_rgb), prep(g_depth), prep(g_w)
-        n_in = 8
-        fp = module.flat_params()
-        if g_rgb is None and g_depth is None and g_w is None:
-            return (None,) * (n_in + len(fp.offsets))
-        direct = None
-        if any(ctx.needs_input_grad[n_in:]):
-            direct = _grad_target(module)
-        grad = direct if direct is not None else torch.zeros_like(fp.flat)      # (frozen parameters: a scratch vector)
-        with torch.cuda.device(dev):
-            d4 = torch.empty_like(o4)
-            d_zc, d_dc = torch.empty_like(z), torch.empty_like(d)
-            st, cb = L.stream_ptr(), C.c_void_p(ctx.buf.data_ptr())
-            if ctx.v1:
-                L.check(lib.nrf_composite_backward_geom(L.ptr(o4), 4, C.c_void_p(o4.data_ptr() + 12), 4, L.ptr(z), L.ptr(d), R, S, ctx.white,
-                                                        L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w), L.ptr(d4), 4, C.c_void_p(d4.data_ptr() + 12), 4,
-                                                        L.ptr(d_zc), L.ptr(d_dc), st))
-                L.check(lib.nrf_mlp_backward_v1(module._handle, ctx.mode, L.ptr(o4), L.ptr(d4), n, cb, ctx.nbytes, L.ptr(grad), st))
-            else:
-                rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
-                d_rgb, d_den = d4.view(-1)[:3 * n].view(n, 3), d4.view(-1)[3 * n:].view(n, 1)
-                L.check(lib.nrf_composite_backward_geom(L.ptr(rgb), 3, L.ptr(den), 1, L.ptr(z), L.ptr(d), R, S, ctx.white,
-                                                        L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w), L.ptr(d_rgb), 3, L.ptr(d_den), 1,
-                                                        L.ptr(d_zc), L.ptr(d_dc), st))
-                L.check(lib.nrf_mlp_backward(module._handle, ctx.mode, L.ptr(rgb), L.ptr(den), L.ptr(d_rgb), L.ptr(d_den), n, cb, ctx.nbytes,
-                                             L.ptr(grad), st))
-            _, d_p, d_dirs = _input_grad(module, ctx.mode, n, ctx.buf, ctx.nbytes, dev, positions=pts, directions=dirs, want_p=True,
+        with torch.cuda.device(ctx.dev):
+            b = _render_backward(ctx, g_rgb, g_depth, g_w, 8, True)
+            if b is None:
+                return _no_grads(ctx, 8)
+            _, z, d, pts, dirs = b.saved
+            _, d_p, d_dirs = _input_grad(ctx.module, ctx.mode, b.n, ctx.buf, ctx.nbytes, ctx.dev, positions=pts, directions=dirs, want_p=True,
                                          want_d=not ctx.v1)
-            d_o, d_d = torch.empty_like(d), torch.empty_like(d)
-            d_z = torch.empty_like(z) if ctx.z_live else None
-            L.check(lib.nrf_ray_grad(L.ptr(d_p), L.ptr(d_dirs), L.ptr(z), L.ptr(d), L.ptr(d_zc), L.ptr(d_dc), R, S, L.ptr(d_o), L.ptr(d_d),
-                                     L.ptr(d_z), st))
+            d_o, d_d, d_z = _ray_grad(d_p, d_dirs, z, d, b.d_zc, b.d_dc, ctx.z_live, b.st)
         ctx.buf = None
-        ins = (None, d_o, d_d, d_z) + (None,) * (n_in - 4)
-        if direct is not None or not any(ctx.needs_input_grad[n_in:]):
-            return ins + (None,) * len(fp.offsets)
-        return ins + tuple(fp.views(grad))
+        return (None, d_o, d_d, d_z) + (None,) * 4 + b.d_params
 
 
 class _RenderPointFn(torch.autograd.Function):
@@ -703,90 +660,43 @@ class _RenderPointFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module, o, d, z, z_live, pts, fmap, dino, white, mma_mode, *params):
         from .renderer import make_dino
-        dev = z.device
         R, S = z.shape
-        n = R * S
-        h, mode = _train_handle(module, dev, mma_mode)
-        lib = L.lib()
         dirs = d[:, None, :].expand(R, S, 3).reshape(-1, 3).contiguous()
         fm = fmap.detach().contiguous()
         dn, keep = make_dino(**{**dino, "features": fm})
-        with torch.cuda.device(dev):
-            nbytes = lib.nrf_train_context_bytes(h, mode, n)
-            if nbytes < 0:
-                raise L.NrfError(-2, lib.nrf_last_error().decode("utf-8", "replace"))
-            buf = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-            o4 = torch.empty((n, 4), dtype=torch.float32, device=dev)
-            out_rgb = torch.empty((R, 3), dtype=torch.float32, device=dev)
-            out_depth = torch.empty((R,), dtype=torch.float32, device=dev)
-            out_w = torch.empty((R, S), dtype=torch.float32, device=dev)
-            feats = torch.empty((n, dn.C), dtype=torch.float32, device=dev)
-            st, cb = L.stream_ptr(), C.c_void_p(buf.data_ptr())
-            L.check(lib.nrf_project_fetch(C.byref(dn), L.ptr(pts), n, L.ptr(feats), None, st))
-            rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
-            L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(pts), L.ptr(dirs), L.ptr(feats), n, L.ptr(rgb), L.ptr(den), cb, nbytes, st))
-            L.check(lib.nrf_composite(L.ptr(rgb), 3, L.ptr(den), 1, L.ptr(z), L.ptr(d), R, S, white, L.ptr(out_rgb), L.ptr(out_depth), L.ptr(out_w), st))
+
+        def fetched(st):
+            feats = torch.empty((R * S, dn.C), dtype=torch.float32, device=z.device)
+            L.check(L.lib().nrf_project_fetch(C.byref(dn), L.ptr(pts), R * S, L.ptr(feats), None, st))
+            return pts, dirs, feats
+        o4, outs = _render_forward(ctx, module, fetched, z, d, white, mma_mode)
         del keep
-        ctx.module, ctx.buf, ctx.nbytes, ctx.mode, ctx.white, ctx.z_live, ctx.dino = module, buf, nbytes, mode, white, bool(z_live), dino
-        ctx.versions = module._packed
+        ctx.z_live, ctx.dino = bool(z_live), dino
         ctx.save_for_backward(o4, z, d, pts, dirs, fm)
-        ctx.set_materialize_grads(False)
-        return out_rgb, out_depth, out_w
+        return outs
 
     @staticmethod
     def backward(ctx, g_rgb, g_depth, g_w):
         from .renderer import make_dino
-        module = ctx.module
-        if module._versions() != ctx.versions:
-            raise RuntimeError("NeRFMLP parameters were modified between render_rays and backward: the saved activations "
-                               "no longer match the packed weights")
-        o4, z, d, pts, dirs, fm = ctx.saved_tensors
-        R, S = z.shape
-        n = R * S
-        dev = z.device
-        lib = L.lib()
-
-        def prep(g):
-            return None if g is None else g.to(torch.float32).contiguous()
-        g_rgb, g_depth, g_w = prep(g_rgb), prep(g_depth), prep(g_w)
-        n_in = 10
-        fp = module.flat_params()
-        if g_rgb is None and g_depth is None and g_w is None:
-            return (None,) * (n_in + len(fp.offsets))
-        direct = None
-        if any(ctx.needs_input_grad[n_in:]):
-            direct = _grad_target(module)
-        grad = direct if direct is not None else torch.zeros_like(fp.flat)      # (frozen parameters: a scratch vector)
-        dn, keep = make_dino(**{**ctx.dino, "features": fm})
-        d_map = None
+        module, dev = ctx.module, ctx.dev
         with torch.cuda.device(dev):
-            d4 = torch.empty_like(o4)
-            d_zc, d_dc = torch.empty_like(z), torch.empty_like(d)
-            st, cb = L.stream_ptr(), C.c_void_p(ctx.buf.data_ptr())
-            rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
-            d_rgb, d_den = d4.view(-1)[:3 * n].view(n, 3), d4.view(-1)[3 * n:].view(n, 1)
-            L.check(lib.nrf_composite_backward_geom(L.ptr(rgb), 3, L.ptr(den), 1, L.ptr(z), L.ptr(d), R, S, ctx.white,
-                                                    L.ptr(g_rgb), L.ptr(g_depth), L.ptr(g_w), L.ptr(d_rgb), 3, L.ptr(d_den), 1,
-                                                    L.ptr(d_zc), L.ptr(d_dc), st))
-            L.check(lib.nrf_mlp_backward(module._handle, ctx.mode, L.ptr(rgb), L.ptr(den), L.ptr(d_rgb), L.ptr(d_den), n, cb, ctx.nbytes,
-                                         L.ptr(grad), st))
+            b = _render_backward(ctx, g_rgb, g_depth, g_w, 10, True)
+            if b is None:
+                return _no_grads(ctx, 10)
+            (_, z, d, pts, dirs, fm), n, st = b.saved, b.n, b.st
+            dn, keep = make_dino(**{**ctx.dino, "features": fm})
+            d_map = None
             d_feats = _dino_grad(module, ctx.mode, n, ctx.buf, ctx.nbytes, dev)
-            d_p, d_dirs = _input_grad_v3(module, ctx.mode, n, ctx.buf, ctx.nbytes, dev, positions=pts, directions=dirs, want_p=True, want_d=True)
-            L.check(lib.nrf_project_fetch_backward_points(C.byref(dn), L.ptr(pts), n, L.ptr(d_feats), L.ptr(d_p), 1, st))
+            _, d_p, d_dirs = _input_grad(module, ctx.mode, n, ctx.buf, ctx.nbytes, dev, positions=pts, directions=dirs, want_p=True, want_d=True)
+            L.check(L.lib().nrf_project_fetch_backward_points(C.byref(dn), L.ptr(pts), n, L.ptr(d_feats), L.ptr(d_p), 1, st))
             if ctx.needs_input_grad[6]:                  # a live feature map
                 d_map = torch.empty_like(fm)
                 ws = fetch_backward_workspace(dn.Hp, dn.Wp, dn.C, n, dev)
-                L.check(lib.nrf_project_fetch_backward(C.byref(dn), L.ptr(pts), n, L.ptr(d_feats), L.ptr(d_map), 0, L.ptr(ws), ws.numel() * 4, st))
-            d_o, d_d = torch.empty_like(d), torch.empty_like(d)
-            d_z = torch.empty_like(z) if ctx.z_live else None
-            L.check(lib.nrf_ray_grad(L.ptr(d_p), L.ptr(d_dirs), L.ptr(z), L.ptr(d), L.ptr(d_zc), L.ptr(d_dc), R, S, L.ptr(d_o), L.ptr(d_d),
-                                     L.ptr(d_z), st))
+                L.check(L.lib().nrf_project_fetch_backward(C.byref(dn), L.ptr(pts), n, L.ptr(d_feats), L.ptr(d_map), 0, L.ptr(ws), ws.numel() * 4, st))
+            d_o, d_d, d_z = _ray_grad(d_p, d_dirs, z, d, b.d_zc, b.d_dc, ctx.z_live, st)
         del keep
         ctx.buf = None
-        ins = (None, d_o, d_d, d_z, None, None, d_map) + (None,) * (n_in - 7)
-        if direct is not None or not any(ctx.needs_input_grad[n_in:]):
-            return ins + (None,) * len(fp.offsets)
-        return ins + tuple(fp.views(grad))
+        return (None, d_o, d_d, d_z, None, None, d_map) + (None,) * 3 + b.d_params
 
 
 def render_rays_train(module, rays_o, rays_d, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False,
@@ -805,75 +715,68 @@ def render_rays_train(module, rays_o, rays_d, near, far, n_samples, perturb=True
         raise ValueError("tail_mode is an inference option: the training kernels have no split-f16 mode (render under "
                          "torch.no_grad() or model.eval())")
     from .ray_sampler import sample_points_along_rays
-    if module._wants_input_grad(rays_o, rays_d, z_in):
+    live_in = module._wants_input_grad(rays_o, rays_d, z_in)
+    if live_in:
         o_live = _live_input(module, rays_o, "render_rays(rays_o)").reshape(-1, 3)
         d_live = _live_input(module, rays_d, "render_rays(rays_d)", o_live.device).reshape(-1, 3)
         o, d = o_live.detach(), d_live.detach()
-        R, S = o.shape[0], int(n_samples)
-        z_live = None
-        if z_in is not None:
+    else:
+        o = L.dev_f32(L.refuse_grad(rays_o, "render_rays(rays_o)")).reshape(-1, 3)
+        d = L.dev_f32(L.refuse_grad(rays_d, "render_rays(rays_d)"), o.device).reshape(-1, 3)
+    R, S = o.shape[0], int(n_samples)
+    z_live = None
+    if z_in is not None:
+        if live_in:
             z_live = _live_input(module, z_in, "render_rays(z_in)", o.device).reshape(R, S)
             z = z_live.detach()
-            pts = o[:, None, :] + d[:, None, :] * z[:, :, None]
         else:
-            pts, z = sample_points_along_rays(o, d, near, far, S, perturb=perturb, lindisp=lindisp, t_rand=t_rand, seed=seed)
-        live = z_live is not None and z_live.requires_grad
-        if module.net == L.NRF_NET_V3:
-            if dino is None:
-                raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
-            fmap = dino.get("features")
-            if torch.is_grad_enabled() and getattr(fmap, "requires_grad", False) and not getattr(module, "dino_grad", False):
-                raise NotImplementedError("no gradient with respect to the DINO feature map is produced by default; detach it, or "
-                                          "build the module with NeRFMLP(..., dino_grad=True)")
-            fmap = torch.as_tensor(fmap)
-            if fmap.dim() != 4 or fmap.shape[0] != 1 or fmap.shape[3] != module.dino_dim:
-                raise ValueError("features must be (1,Hp,Wp,dino_dim)")
-            rgb, depth, w = _RenderPointFn.apply(module, o_live, d_live, z_live if live else z, live, pts.reshape(-1, 3).contiguous(),
-                                                 fmap.to(device=o.device, dtype=torch.float32), {k: v for k, v in dino.items() if k != "features"},
-                                                 int(bool(white_bkgd)), mma_mode, *module.flat_params().params())
-            return {"rgb": rgb, "depth": depth, "weights": w, "z_vals": z_live if live else z}
-        rgb, depth, w = _RenderGeomFn.apply(module, o_live, d_live, z_live if live else z, live, pts.reshape(-1, 3).contiguous(),
-                                            int(bool(white_bkgd)), mma_mode, *module.flat_params().params())
-        return {"rgb": rgb, "depth": depth, "weights": w, "z_vals": z_live if live else z}
-    o = L.dev_f32(L.refuse_grad(rays_o, "render_rays(rays_o)")).reshape(-1, 3)
-    d = L.dev_f32(L.refuse_grad(rays_d, "render_rays(rays_d)"), o.device).reshape(-1, 3)
-    R, S = o.shape[0], int(n_samples)
-    if z_in is not None:
-        z = L.dev_f32(z_in, o.device).reshape(R, S)
+            z = L.dev_f32(z_in, o.device).reshape(R, S)
         pts = o[:, None, :] + d[:, None, :] * z[:, :, None]
     else:
         pts, z = sample_points_along_rays(o, d, near, far, S, perturb=perturb, lindisp=lindisp, t_rand=t_rand, seed=seed)
     pts = pts.reshape(-1, 3)
+    v3 = module.net == L.NRF_NET_V3
+    fmap = view = None
+    if v3:
+        if dino is None:
+            raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
+        fmap = dino.get("features")
+        map_live = torch.is_grad_enabled() and getattr(fmap, "requires_grad", False)
+        if map_live and not getattr(module, "dino_grad", False):
+            raise NotImplementedError("no gradient with respect to the DINO feature map is produced by default; detach it, or "
+                                      "build the module with NeRFMLP(..., dino_grad=True)")
+        if live_in or map_live:           # the map enters an autograd node; a map that is data goes through make_dino, unchecked here
+            if live_in:
+                fmap = torch.as_tensor(fmap)
+            if fmap.dim() != 4 or fmap.shape[0] != 1 or fmap.shape[3] != module.dino_dim:
+                raise ValueError("features must be (1,Hp,Wp,dino_dim)")
+            fmap = fmap.to(device=o.device, dtype=torch.float32)
+            view = {k: v for k, v in dino.items() if k != "features"}
+    white, params = int(bool(white_bkgd)), module.flat_params().params()
+    if live_in:
+        live = z_live is not None and z_live.requires_grad
+        zz = z_live if live else z
+        if v3:
+            rgb, depth, w = _RenderPointFn.apply(module, o_live, d_live, zz, live, pts.contiguous(), fmap, view, white, mma_mode, *params)
+        else:
+            rgb, depth, w = _RenderGeomFn.apply(module, o_live, d_live, zz, live, pts.contiguous(), white, mma_mode, *params)
+        return {"rgb": rgb, "depth": depth, "weights": w, "z_vals": zz}
     dirs = feats = None
     if module.net == L.NRF_NET_V1:
-        from .positional_encoding import PositionalEncoding
-        enc = _encoders.get(module.pos_freq)
-        if enc is None:
-            enc = _encoders[module.pos_freq] = PositionalEncoding(module.pos_freq)
-        x = enc(pts)                                                     # train_minimal.py:101
+        x = _encoder(module.pos_freq)(pts)                               # train_minimal.py:101
     else:
         x = pts
         dirs = d[:, None, :].expand(R, S, 3).reshape(-1, 3).contiguous()          # train.py:225: raw ray directions per sample
-        if module.net == L.NRF_NET_V3:
-            if dino is None:
-                raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
-            fmap = dino.get("features")
-            if torch.is_grad_enabled() and getattr(fmap, "requires_grad", False):
-                if not getattr(module, "dino_grad", False):
-                    raise NotImplementedError("no gradient with respect to the DINO feature map is produced by default; detach it, or "
-                                              "build the module with NeRFMLP(..., dino_grad=True)")
-                if fmap.dim() != 4 or fmap.shape[0] != 1 or fmap.shape[3] != module.dino_dim:
-                    raise ValueError("features must be (1,Hp,Wp,dino_dim)")
-                live = fmap.to(device=o.device, dtype=torch.float32)
-                feats = _ProjectFetchFn.apply(live, pts.contiguous(), {k: v for k, v in dino.items() if k != "features"})
-            else:
-                from .renderer import make_dino
-                dn, keep = make_dino(**dino)
-                feats = torch.empty((R * S, module.dino_dim), dtype=torch.float32, device=o.device)
-                with torch.cuda.device(o.device):
-                    L.check(L.lib().nrf_project_fetch(C.byref(dn), L.ptr(pts), R * S, L.ptr(feats), None, L.stream_ptr()))   # train.py:203-217
-                del keep
-    rgb, depth, w = _RenderFn.apply(module, x, dirs, feats, z, d, int(bool(white_bkgd)), mma_mode, *module.flat_params().params())
+        if v3 and view is not None:
+            feats = _ProjectFetchFn.apply(fmap, pts.contiguous(), view)
+        elif v3:
+            from .renderer import make_dino
+            dn, keep = make_dino(**dino)
+            feats = torch.empty((R * S, module.dino_dim), dtype=torch.float32, device=o.device)
+            with torch.cuda.device(o.device):
+                L.check(L.lib().nrf_project_fetch(C.byref(dn), L.ptr(pts), R * S, L.ptr(feats), None, L.stream_ptr()))   # train.py:203-217
+            del keep
+    rgb, depth, w = _RenderFn.apply(module, x, dirs, feats, z, d, white, mma_mode, *params)
     return {"rgb": rgb, "depth": depth, "weights": w, "z_vals": z}
 
 
@@ -1075,17 +978,100 @@ class FusedStep:
     def _buffers(self, n, R, S, dev, h, mode):
         key = (n, R, S, str(dev), mode)
         if self._key != key:
-            nbytes = L.lib().nrf_train_context_bytes(h, mode, n)
-            if nbytes < 0:
-                raise L.NrfError(-2, L.lib().nrf_last_error().decode("utf-8", "replace"))
             f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-            self.ctx = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=dev)
-            self.nbytes = nbytes
+            self.ctx, self.nbytes = _context(h, mode, n, dev)
             self.out4, self.d_out4 = f(n, 4), f(n, 4)                 # V1: [rgb, sigma] rows; V2: rgb | density packed in the same rows
             self.pred = f(R, 3)
             self.ray_loss = f(3, R)              # row 0: squared rgb errors; rows 1, 2 (multi-term loss): sum of w^2, |depth error|
             self.grad = torch.zeros(self.model.flat_params().flat.numel(), dtype=torch.float32, device=dev)
             self._key = key
+
+    def _check_outputs(self, n, d_dino_out, points_out=None):
+        """The refusals of the per-sample outputs a step over n = R * S samples can be handed."""
+        m = self.model
+        if d_dino_out is not None:
+            if m.net != L.NRF_NET_V3 or not getattr(m, "dino_grad", False):
+                raise ValueError("d_dino_out needs a use_dino model built with dino_grad=True")
+            if (not d_dino_out.is_cuda or d_dino_out.dtype != torch.float32 or not d_dino_out.is_contiguous()
+                    or d_dino_out.numel() != n * m.dino_dim):
+                raise ValueError("d_dino_out must be a contiguous float32 (R*S, dino_dim) tensor on the GPU")
+        if points_out is not None and (not points_out.is_cuda or points_out.dtype != torch.float32 or not points_out.is_contiguous()
+                                       or points_out.numel() != n * 3):
+            raise ValueError("points_out must be a contiguous float32 (R*S, 3) tensor on the GPU")
+
+    def _loss_setup(self, R, S, dev, target_depth, noise, always=False):
+        """(multi, loss_opts, tensors its pointers need alive): multi = the step runs the general compositor/loss kernel and the
+        clipped optimiser; loss_opts is built only then (always=True: the step under a grid, whose one indexed kernel takes it
+        either way).  The noise seed of step t is seed + t: step_count is read before the step increments it."""
+        opt = self.opt
+        multi = (self.reg_weight > 0.0 or self.depth_weight > 0.0 or self.noise_std > 0.0 or opt.extended or target_depth is not None
+                 or noise is not None)
+        if not (multi or always):
+            return False, None, None
+        td = None if target_depth is None else L.dev_f32(target_depth, dev).reshape(R)
+        nz = None if noise is None or self.noise_std == 0.0 else L.dev_f32(noise, dev).reshape(R, S)
+        seed = 0
+        if self.noise_std > 0.0 and nz is None:
+            if self.seed is None:
+                self.seed = L.fresh_seed()
+            seed = self.seed + opt.step_count
+        return multi, L.loss_opts(self.rgb_weight, self.reg_weight, self.depth_weight, L.ptr(td), self.noise_std, L.ptr(nz), seed), (td, nz)
+
+    def _launch_loss(self, heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, slot=None):
+        """compositor -> d loss / d pred = 2 w (pred - target) / (3 R) -> compositor backward, and the flat gradient vector cleared:
+        one launch (a ray's loss gradient needs only its own prediction); the rays' squared errors stay in ray_loss.  slot (the step
+        under a grid): the indexed kernel, for the plain and the multi-term loss alike.  Returns `multi`."""
+        lib = L.lib()
+        multi, lo, keep = self._loss_setup(R, S, dev, target_depth, noise, always=slot is not None)
+        if slot is not None:
+            # the one indexed entry serves both steps: with every option off its bits are the mse kernel's
+            L.check(lib.nrf_composite_loss_backward_indexed(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo),
+                                                            slot.data_ptr(), L.ptr(self.pred), *d_heads, L.ptr(self.ray_loss),
+                                                            L.ptr(self.grad), self.grad.numel(), st))
+        elif multi:
+            L.check(lib.nrf_composite_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), L.ptr(self.pred),
+                                                    *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
+        else:
+            L.check(lib.nrf_composite_mse_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), self.rgb_weight, L.ptr(self.pred),
+                                                   *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
+        del keep                            # (td, nz: alive until the launch that reads them is enqueued)
+        return multi
+
+    def _network_backward(self, h, mode, rows, out, d_out, ctx, st, d_dino_out=None):
+        """dZ chain + weight gradients over the first `rows` rows, added into the flat gradient vector [-> dL/d dino]."""
+        lib = L.lib()
+        if self.model.net == L.NRF_NET_V1:
+            L.check(lib.nrf_mlp_backward_v1(h, mode, L.ptr(out[0]), L.ptr(d_out[0]), rows, ctx, self.nbytes, L.ptr(self.grad), st))
+        else:
+            L.check(lib.nrf_mlp_backward(h, mode, L.ptr(out[0]), L.ptr(out[1]), L.ptr(d_out[0]), L.ptr(d_out[1]), rows, ctx, self.nbytes,
+                                         L.ptr(self.grad), st))
+            if d_dino_out is not None:
+                _dino_grad(self.model, mode, rows, self.ctx, self.nbytes, d_dino_out.device, out=d_dino_out)
+
+    def _finish(self, multi, R, S, dev, target_depth, st):
+        """[all-reduce ->] the optimiser's launch with the loss as its side job, the bookkeeping, and the parameters marked newer than
+        the packed streams (call with the device current).  Returns the step's total loss (a device scalar)."""
+        opt, lib = self.opt, L.lib()
+        if self.data_parallel:
+            _all_reduce_mean(self.grad, self.group)
+        fp, flat = opt._buffers()
+        opt.step_count += 1
+        if multi:
+            # [norm partials ->] clipped Adam / AdamW, and as a side job of its launch the loss terms summed in a fixed order
+            loss = torch.empty((4,), dtype=torch.float32, device=dev)
+            opt._update(flat, self.grad, self.ray_loss, R, S, (self.rgb_weight, self.depth_weight if target_depth is not None else 0.0,
+                                                               self.reg_weight), loss)
+            self._loss_vec, self.last_grad_norm = loss, opt.last_grad_norm
+            loss = loss[0]
+        else:
+            # Adam, and as a side job of its launch the loss value: rgb_weight * sum(ray_loss) / (3 R) in a fixed order
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            L.check(lib.nrf_adam_step_loss(L.ptr(flat), L.ptr(self.grad), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq), flat.numel(), opt.lr,
+                                           opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, opt.step_count, L.ptr(self.ray_loss), R,
+                                           self.rgb_weight, L.ptr(loss), st))
+            self._loss_vec, self.last_grad_norm = loss, None
+        self.model._gen += 1
+        return loss
 
     @torch.no_grad()
     def __call__(self, points, z_vals, rays_d, target, dirs=None, dino=None, target_depth=None, noise=None, d_dino_out=None):
@@ -1094,20 +1080,16 @@ class FusedStep:
         d_dino_out: a preallocated (R*S, dino_dim) fp32 tensor that receives dL/d dino of this step (V3 with model.dino_grad: one
         more launch behind the weight gradients; project_fetch_backward turns it into the feature map's gradient)."""
         m = self.model
-        if d_dino_out is not None:
-            if m.net != L.NRF_NET_V3 or not getattr(m, "dino_grad", False):
-                raise ValueError("d_dino_out needs a use_dino model built with dino_grad=True")
-            if (not d_dino_out.is_cuda or d_dino_out.dtype != torch.float32 or not d_dino_out.is_contiguous()
-                    or d_dino_out.numel() != z_vals.numel() * m.dino_dim):
-                raise ValueError("d_dino_out must be a contiguous float32 (R*S, dino_dim) tensor on the GPU")
+        if d_dino_out is not None:                  # (z_vals may still be a list when there is nothing to check)
+            self._check_outputs(z_vals.numel(), d_dino_out)
         pts = L.dev_f32(points)
         dev = pts.device
         z = L.dev_f32(z_vals, dev)
         R, S = z.shape
         d = L.dev_f32(rays_d, dev).reshape(R, 3)
         tgt = L.dev_f32(target, dev).reshape(R, 3)
-        v2 = m.net != L.NRF_NET_V1                                   # trainer forms: positions + directions (+ DINO features)
-        pts = pts.reshape(R * S, 3 if v2 else 3 * (2 * m.pos_freq + 1))
+        v1 = m.net == L.NRF_NET_V1                                   # otherwise the trainer forms: positions + directions (+ DINO features)
+        pts = pts.reshape(R * S, 3 * (2 * m.pos_freq + 1) if v1 else 3)
         n = R * S
         lib = L.lib()
         h, mode = _train_handle(m, dev)
@@ -1115,65 +1097,17 @@ class FusedStep:
             self._buffers(n, R, S, dev, h, mode)
             st = L.stream_ptr()
             ctx = C.c_void_p(self.ctx.data_ptr())
-            o4, d4 = self.out4, self.d_out4
-            if v2:
-                # rgb -> columns 0..2 of the first 3n/4 rows' worth of storage is not strided: keep two plain tensors as views
-                rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
-                g_rgb, g_den = d4.view(-1)[:3 * n].view(n, 3), d4.view(-1)[3 * n:].view(n, 1)
+            *out, heads = _heads(self.out4, n, v1)
+            *d_out, d_heads = _heads(self.d_out4, n, v1)
+            if v1:
+                L.check(lib.nrf_mlp_forward_train_v1(h, mode, L.ptr(pts), n, L.ptr(out[0]), ctx, self.nbytes, st))
+            else:
                 dirs_d = L.dev_f32(dirs, dev).reshape(n, 3)
                 dino_d = L.dev_f32(dino, dev).reshape(n, m.dino_dim) if m.net == L.NRF_NET_V3 else None
-                L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(pts), L.ptr(dirs_d), L.ptr(dino_d), n, L.ptr(rgb), L.ptr(den), ctx, self.nbytes, st))
-                heads = (L.ptr(rgb), 3, L.ptr(den), 1)
-                d_heads = (L.ptr(g_rgb), 3, L.ptr(g_den), 1)
-            else:
-                L.check(lib.nrf_mlp_forward_train_v1(h, mode, L.ptr(pts), n, L.ptr(o4), ctx, self.nbytes, st))
-                heads = (L.ptr(o4), 4, C.c_void_p(o4.data_ptr() + 12), 4)
-                d_heads = (L.ptr(d4), 4, C.c_void_p(d4.data_ptr() + 12), 4)
-            # compositor -> d loss / d pred = 2 w (pred - target) / (3 R) -> compositor backward, and the flat gradient vector cleared:
-            # one launch (a ray's loss gradient needs only its own prediction); the rays' squared errors stay in ray_loss
-            opt = self.opt
-            multi = (self.reg_weight > 0.0 or self.depth_weight > 0.0 or self.noise_std > 0.0 or opt.extended or target_depth is not None
-                     or noise is not None)
-            if multi:
-                td = None if target_depth is None else L.dev_f32(target_depth, dev).reshape(R)
-                nz = None if noise is None or self.noise_std == 0.0 else L.dev_f32(noise, dev).reshape(R, S)
-                seed = 0
-                if self.noise_std > 0.0 and nz is None:
-                    if self.seed is None:
-                        self.seed = L.fresh_seed()
-                    seed = self.seed + opt.step_count
-                lo = L.loss_opts(self.rgb_weight, self.reg_weight, self.depth_weight, L.ptr(td), self.noise_std, L.ptr(nz), seed)
-                loss = torch.empty((4,), dtype=torch.float32, device=dev)
-                L.check(lib.nrf_composite_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), L.ptr(self.pred),
-                                                        *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
-            else:
-                loss = torch.empty((), dtype=torch.float32, device=dev)
-                L.check(lib.nrf_composite_mse_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), self.rgb_weight, L.ptr(self.pred),
-                                                       *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
-            if v2:
-                L.check(lib.nrf_mlp_backward(h, mode, L.ptr(rgb), L.ptr(den), L.ptr(g_rgb), L.ptr(g_den), n, ctx, self.nbytes, L.ptr(self.grad), st))
-                if d_dino_out is not None:
-                    _dino_grad(m, mode, n, self.ctx, self.nbytes, dev, out=d_dino_out)
-            else:
-                L.check(lib.nrf_mlp_backward_v1(h, mode, L.ptr(o4), L.ptr(d4), n, ctx, self.nbytes, L.ptr(self.grad), st))
-            if self.data_parallel:
-                _all_reduce_mean(self.grad, self.group)
-            fp, flat = opt._buffers()
-            opt.step_count += 1
-            if multi:
-                # [norm partials ->] clipped Adam / AdamW, and as a side job of its launch the loss terms summed in a fixed order
-                opt._update(flat, self.grad, self.ray_loss, R, S, (self.rgb_weight, self.depth_weight if target_depth is not None else 0.0,
-                                                                   self.reg_weight), loss)
-                self._loss_vec, self.last_grad_norm = loss, opt.last_grad_norm
-                loss = loss[0]
-            else:
-                # Adam, and as a side job of its launch the loss value: rgb_weight * sum(ray_loss) / (3 R) in a fixed order
-                L.check(lib.nrf_adam_step_loss(L.ptr(flat), L.ptr(self.grad), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq), flat.numel(), opt.lr,
-                                               opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, opt.step_count, L.ptr(self.ray_loss), R,
-                                               self.rgb_weight, L.ptr(loss), st))
-                self._loss_vec, self.last_grad_norm = loss, None
-        m._gen += 1
-        return loss
+                L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(pts), L.ptr(dirs_d), L.ptr(dino_d), n, L.ptr(out[0]), L.ptr(out[1]), ctx, self.nbytes, st))
+            multi = self._launch_loss(heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st)
+            self._network_backward(h, mode, n, out, d_out, ctx, st, d_dino_out)
+            return self._finish(multi, R, S, dev, target_depth, st)
 
     # ---- the same step from rays: sampling, encoding and the feature fetch happen inside the saving forward ----------------
     @torch.no_grad()
@@ -1198,7 +1132,7 @@ class FusedStep:
 
         occupancy (an occupancy.OccupancyGrid): the step under the grid -- the plain step with every sample in an empty cell
         composited as colour 0 and effective density -inf (behind the density noise), and the network, its backward and the weight
-        gradients run on the M occupied samples alone (_grid_ray_step).  UNLIKE THE PLAIN STEP IT SYNCHRONISES ONCE: the 8 bytes of
+        gradients run on the M occupied samples alone (_grid_forward).  UNLIKE THE PLAIN STEP IT SYNCHRONISES ONCE: the 8 bytes of
         M are read back between the compaction and the network.  `last_count` holds M.  Not combined with d_dino_out / points_out."""
         o = L.dev_f32(rays_o).reshape(-1, 3)
         d = L.dev_f32(rays_d, o.device).reshape(-1, 3)
@@ -1236,28 +1170,22 @@ class FusedStep:
 
     def _ray_step(self, R, dev, make_rays, d, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise,
                   d_dino_out, points_out, occupancy=None):
-        """__call__'s sequence with nrf_mlp_forward_train_rays in front; d is the caller's (R,3) directions or None (pixel mode:
-        the kernel writes them for the compositor)."""
+        """__call__'s sequence with nrf_mlp_forward_train_rays in front -- or, under an occupancy grid, _grid_forward; d is the
+        caller's (R,3) directions or None (pixel mode: the kernel writes them for the compositor)."""
+        from .renderer import _opts, make_dino
         if occupancy is not None:
+            from .occupancy import OccupancyGrid
             if d_dino_out is not None or points_out is not None:
                 raise ValueError("occupancy is not combined with d_dino_out / points_out: the step under a grid hands out no per-sample gradients")
-            return self._grid_ray_step(R, dev, make_rays, d, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth,
-                                       noise, occupancy)
-        from .renderer import _opts, make_dino
+            if not isinstance(occupancy, OccupancyGrid):
+                raise TypeError("occupancy must be an occupancy.OccupancyGrid")
         m = self.model
         S = int(n_samples)
         n = R * S
-        v3 = m.net == L.NRF_NET_V3
+        v1, v3 = m.net == L.NRF_NET_V1, m.net == L.NRF_NET_V3
         if R < 1:
             raise ValueError("a step needs at least one ray")
-        if d_dino_out is not None:
-            if not v3 or not getattr(m, "dino_grad", False):
-                raise ValueError("d_dino_out needs a use_dino model built with dino_grad=True")
-            if (not d_dino_out.is_cuda or d_dino_out.dtype != torch.float32 or not d_dino_out.is_contiguous() or d_dino_out.numel() != n * m.dino_dim):
-                raise ValueError("d_dino_out must be a contiguous float32 (R*S, dino_dim) tensor on the GPU")
-        if points_out is not None and (not points_out.is_cuda or points_out.dtype != torch.float32 or not points_out.is_contiguous()
-                                       or points_out.numel() != n * 3):
-            raise ValueError("points_out must be a contiguous float32 (R*S, 3) tensor on the GPU")
+        self._check_outputs(n, d_dino_out, points_out)
         tgt = L.dev_f32(target, dev).reshape(R, 3)
         tr = L.dev_f32(t_rand, dev).reshape(R, S) if t_rand is not None else None
         zin = L.dev_f32(z_in, dev).reshape(R, S) if z_in is not None else None
@@ -1268,7 +1196,6 @@ class FusedStep:
             dn, keep = make_dino(**dino) if isinstance(dino, dict) else dino
         lib = L.lib()
         h, mode = _train_handle(m, dev)
-        v2 = m.net != L.NRF_NET_V1
         with torch.cuda.device(dev):
             self._buffers(n, R, S, dev, h, mode)
             if getattr(self, "_ray_key", None) != self._key:
@@ -1282,63 +1209,21 @@ class FusedStep:
                 d = self._rays_d
             st = L.stream_ptr()
             ctx = C.c_void_p(self.ctx.data_ptr())
-            o4, d4 = self.out4, self.d_out4
-            if v2:
-                rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
-                g_rgb, g_den = d4.view(-1)[:3 * n].view(n, 3), d4.view(-1)[3 * n:].view(n, 1)
-                L.check(lib.nrf_mlp_forward_train_rays(h, C.byref(rays), R, C.byref(opts), L.ptr(rgb), L.ptr(den), ctx, self.nbytes, st))
-                heads = (L.ptr(rgb), 3, L.ptr(den), 1)
-                d_heads = (L.ptr(g_rgb), 3, L.ptr(g_den), 1)
+            *out, heads = _heads(self.out4, n, v1)
+            *d_out, d_heads = _heads(self.d_out4, n, v1)
+            if occupancy is not None:
+                rows, slot = self._grid_forward(rays, R, S, dev, opts, occupancy, dn, h, mode, out, ctx, st), self._slot
             else:
-                L.check(lib.nrf_mlp_forward_train_rays(h, C.byref(rays), R, C.byref(opts), L.ptr(o4), None, ctx, self.nbytes, st))
-                heads = (L.ptr(o4), 4, C.c_void_p(o4.data_ptr() + 12), 4)
-                d_heads = (L.ptr(d4), 4, C.c_void_p(d4.data_ptr() + 12), 4)
+                L.check(lib.nrf_mlp_forward_train_rays(h, C.byref(rays), R, C.byref(opts), L.ptr(out[0]), L.ptr(out[1]), ctx, self.nbytes, st))
+                rows, slot = n, None
             del keep
-            opt = self.opt
-            multi = (self.reg_weight > 0.0 or self.depth_weight > 0.0 or self.noise_std > 0.0 or opt.extended or target_depth is not None
-                     or noise is not None)
-            if multi:
-                td = None if target_depth is None else L.dev_f32(target_depth, dev).reshape(R)
-                nz = None if noise is None or self.noise_std == 0.0 else L.dev_f32(noise, dev).reshape(R, S)
-                nseed = 0
-                if self.noise_std > 0.0 and nz is None:
-                    if self.seed is None:
-                        self.seed = L.fresh_seed()
-                    nseed = self.seed + opt.step_count
-                lo = L.loss_opts(self.rgb_weight, self.reg_weight, self.depth_weight, L.ptr(td), self.noise_std, L.ptr(nz), nseed)
-                loss = torch.empty((4,), dtype=torch.float32, device=dev)
-                L.check(lib.nrf_composite_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), L.ptr(self.pred),
-                                                        *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
-            else:
-                loss = torch.empty((), dtype=torch.float32, device=dev)
-                L.check(lib.nrf_composite_mse_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), self.rgb_weight, L.ptr(self.pred),
-                                                       *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
-            if v2:
-                L.check(lib.nrf_mlp_backward(h, mode, L.ptr(rgb), L.ptr(den), L.ptr(g_rgb), L.ptr(g_den), n, ctx, self.nbytes, L.ptr(self.grad), st))
-                if d_dino_out is not None:
-                    _dino_grad(m, mode, n, self.ctx, self.nbytes, dev, out=d_dino_out)
-            else:
-                L.check(lib.nrf_mlp_backward_v1(h, mode, L.ptr(o4), L.ptr(d4), n, ctx, self.nbytes, L.ptr(self.grad), st))
-            if self.data_parallel:
-                _all_reduce_mean(self.grad, self.group)
-            fp, flat = opt._buffers()
-            opt.step_count += 1
-            if multi:
-                opt._update(flat, self.grad, self.ray_loss, R, S, (self.rgb_weight, self.depth_weight if target_depth is not None else 0.0,
-                                                                   self.reg_weight), loss)
-                self._loss_vec, self.last_grad_norm = loss, opt.last_grad_norm
-                loss = loss[0]
-            else:
-                L.check(lib.nrf_adam_step_loss(L.ptr(flat), L.ptr(self.grad), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq), flat.numel(), opt.lr,
-                                               opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, opt.step_count, L.ptr(self.ray_loss), R,
-                                               self.rgb_weight, L.ptr(loss), st))
-                self._loss_vec, self.last_grad_norm = loss, None
-        m._gen += 1
-        return loss
+            multi = self._launch_loss(heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, slot)
+            if occupancy is None or rows:
+                self._network_backward(h, mode, rows, out, d_out, ctx, st, d_dino_out)
+            return self._finish(multi, R, S, dev, target_depth, st)
 
-    def _grid_ray_step(self, R, dev, make_rays, d, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise,
-                       occupancy):
-        """The step under an occupancy grid (nerfhip.h: nrf_occupancy_compact_rays):
+    def _grid_forward(self, rays, R, S, dev, opts, occupancy, dn, h, mode, out, ctx, st):
+        """The saving forward of the step under an occupancy grid (nerfhip.h: nrf_occupancy_compact_rays); returns M.  The step:
 
             compact -> read M back -> [V1: encode | V3: project + fetch] of the M points -> saving forward on M rows
             -> indexed compositor, loss and backward (clears the gradient vector) -> dZ chain + weight gradients on M rows
@@ -1349,108 +1234,32 @@ class FusedStep:
         have: the launches behind it are sized by M on the host.  M == 0 is a valid step: the network launches nothing, the
         prediction is the background, the gradient is zero and the optimiser still steps.  With an all-ones grid every bit of the
         step is the plain step's (V2), or __call__'s on the staged points (V1: nrf_encode; V3: nrf_project_fetch)."""
-        from .occupancy import OccupancyGrid
-        from .renderer import _opts, make_dino
-        if not isinstance(occupancy, OccupancyGrid):
-            raise TypeError("occupancy must be an occupancy.OccupancyGrid")
-        m = self.model
-        S = int(n_samples)
-        n = R * S
-        if R < 1:
-            raise ValueError("a step needs at least one ray")
+        m, lib, n = self.model, L.lib(), R * S
         v1, v3 = m.net == L.NRF_NET_V1, m.net == L.NRF_NET_V3
-        tgt = L.dev_f32(target, dev).reshape(R, 3)
-        tr = L.dev_f32(t_rand, dev).reshape(R, S) if t_rand is not None else None
-        zin = L.dev_f32(z_in, dev).reshape(R, S) if z_in is not None else None
-        dn = keep = None
-        if v3:
-            if dino is None:
-                raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
-            dn, keep = make_dino(**dino) if isinstance(dino, dict) else dino
-        lib = L.lib()
-        h, mode = _train_handle(m, dev)
-        with torch.cuda.device(dev):
-            self._buffers(n, R, S, dev, h, mode)
-            if getattr(self, "_ray_key", None) != self._key:
-                self.last_z = torch.empty((R, S), dtype=torch.float32, device=dev)
-                self._rays_d = torch.empty((R, 3), dtype=torch.float32, device=dev)
-                self._ray_key = self._key
-            if getattr(self, "_grid_key", None) != self._key:
-                self._index = torch.empty((n,), dtype=torch.int32, device=dev)
-                self._slot = torch.empty((n,), dtype=torch.int32, device=dev)
-                self._pos = torch.empty((n, 3), dtype=torch.float32, device=dev)
-                self._dirs = None if v1 else torch.empty((n, 3), dtype=torch.float32, device=dev)
-                self._enc = torch.empty((n, 3 * (2 * m.pos_freq + 1)), dtype=torch.float32, device=dev) if v1 else None
-                self._feats = torch.empty((n, m.dino_dim), dtype=torch.float32, device=dev) if v3 else None
-                self._count = torch.zeros((1,), dtype=torch.int64, device=dev)
-                self._cws = torch.empty((int(lib.nrf_occupancy_compact_workspace_bytes(R)),), dtype=torch.uint8, device=dev)
-                self._grid_key = self._key
-            z = self.last_z
-            opts = _opts(near, far, S, perturb, tr, seed, lindisp, 0.0, self.white, L.TRAIN_MODE[m.mma_mode], dn, dev, zin)
-            rays = make_rays(L.ptr(z), L.ptr(self._rays_d), None)
-            if d is None:
-                d = self._rays_d
-            st = L.stream_ptr()
-            occ, occ_keep = occupancy.struct(dev)
-            cp = L.compact(n, self._index.data_ptr(), self._slot.data_ptr(), L.ptr(self._pos), L.ptr(self._dirs), self._count.data_ptr(),
-                           self._cws.data_ptr(), self._cws.numel())
-            L.check(lib.nrf_occupancy_compact_rays(C.byref(rays), R, C.byref(opts), C.byref(occ), C.byref(cp), st))
-            M = int(self._count.item())         # the step's only synchronisation: 8 bytes
-            self.last_count = M
-            ctx = C.c_void_p(self.ctx.data_ptr())
-            o4, d4 = self.out4, self.d_out4
+        if getattr(self, "_grid_key", None) != self._key:
+            self._index = torch.empty((n,), dtype=torch.int32, device=dev)
+            self._slot = torch.empty((n,), dtype=torch.int32, device=dev)
+            self._pos = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            self._dirs = None if v1 else torch.empty((n, 3), dtype=torch.float32, device=dev)
+            self._enc = torch.empty((n, 3 * (2 * m.pos_freq + 1)), dtype=torch.float32, device=dev) if v1 else None
+            self._feats = torch.empty((n, m.dino_dim), dtype=torch.float32, device=dev) if v3 else None
+            self._count = torch.zeros((1,), dtype=torch.int64, device=dev)
+            self._cws = torch.empty((int(lib.nrf_occupancy_compact_workspace_bytes(R)),), dtype=torch.uint8, device=dev)
+            self._grid_key = self._key
+        occ, occ_keep = occupancy.struct(dev)
+        cp = L.compact(n, self._index.data_ptr(), self._slot.data_ptr(), L.ptr(self._pos), L.ptr(self._dirs), self._count.data_ptr(),
+                       self._cws.data_ptr(), self._cws.numel())
+        L.check(lib.nrf_occupancy_compact_rays(C.byref(rays), R, C.byref(opts), C.byref(occ), C.byref(cp), st))
+        M = int(self._count.item())         # the step's only synchronisation: 8 bytes
+        self.last_count = M
+        if M:
             if v1:
-                if M:
-                    L.check(lib.nrf_encode(L.ptr(self._pos), M, 3, m.pos_freq, 1, None, L.ptr(self._enc), st))
-                    L.check(lib.nrf_mlp_forward_train_v1(h, mode, L.ptr(self._enc), M, L.ptr(o4), ctx, self.nbytes, st))
-                heads = (L.ptr(o4), 4, C.c_void_p(o4.data_ptr() + 12), 4)
-                d_heads = (L.ptr(d4), 4, C.c_void_p(d4.data_ptr() + 12), 4)
+                L.check(lib.nrf_encode(L.ptr(self._pos), M, 3, m.pos_freq, 1, None, L.ptr(self._enc), st))
+                L.check(lib.nrf_mlp_forward_train_v1(h, mode, L.ptr(self._enc), M, L.ptr(out[0]), ctx, self.nbytes, st))
             else:
-                rgb, den = o4.view(-1)[:3 * n].view(n, 3), o4.view(-1)[3 * n:].view(n, 1)
-                g_rgb, g_den = d4.view(-1)[:3 * n].view(n, 3), d4.view(-1)[3 * n:].view(n, 1)
-                if M:
-                    if v3:
-                        L.check(lib.nrf_project_fetch(C.byref(dn), L.ptr(self._pos), M, L.ptr(self._feats), None, st))
-                    L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(self._pos), L.ptr(self._dirs), L.ptr(self._feats), M, L.ptr(rgb), L.ptr(den),
-                                                      ctx, self.nbytes, st))
-                heads = (L.ptr(rgb), 3, L.ptr(den), 1)
-                d_heads = (L.ptr(g_rgb), 3, L.ptr(g_den), 1)
-            del keep, occ_keep
-            opt = self.opt
-            multi = (self.reg_weight > 0.0 or self.depth_weight > 0.0 or self.noise_std > 0.0 or opt.extended or target_depth is not None
-                     or noise is not None)
-            td = None if target_depth is None else L.dev_f32(target_depth, dev).reshape(R)
-            nz = None if noise is None or self.noise_std == 0.0 else L.dev_f32(noise, dev).reshape(R, S)
-            nseed = 0
-            if self.noise_std > 0.0 and nz is None:
-                if self.seed is None:
-                    self.seed = L.fresh_seed()
-                nseed = self.seed + opt.step_count
-            # the one indexed entry serves both steps: with every option off its bits are the mse kernel's
-            lo = L.loss_opts(self.rgb_weight, self.reg_weight, self.depth_weight, L.ptr(td), self.noise_std, L.ptr(nz), nseed)
-            L.check(lib.nrf_composite_loss_backward_indexed(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo),
-                                                            self._slot.data_ptr(), L.ptr(self.pred), *d_heads, L.ptr(self.ray_loss),
-                                                            L.ptr(self.grad), self.grad.numel(), st))
-            if M:
-                if v1:
-                    L.check(lib.nrf_mlp_backward_v1(h, mode, L.ptr(o4), L.ptr(d4), M, ctx, self.nbytes, L.ptr(self.grad), st))
-                else:
-                    L.check(lib.nrf_mlp_backward(h, mode, L.ptr(rgb), L.ptr(den), L.ptr(g_rgb), L.ptr(g_den), M, ctx, self.nbytes, L.ptr(self.grad), st))
-            if self.data_parallel:
-                _all_reduce_mean(self.grad, self.group)
-            fp, flat = opt._buffers()
-            opt.step_count += 1
-            if multi:
-                loss = torch.empty((4,), dtype=torch.float32, device=dev)
-                opt._update(flat, self.grad, self.ray_loss, R, S, (self.rgb_weight, self.depth_weight if target_depth is not None else 0.0,
-                                                                   self.reg_weight), loss)
-                self._loss_vec, self.last_grad_norm = loss, opt.last_grad_norm
-                loss = loss[0]
-            else:
-                loss = torch.empty((), dtype=torch.float32, device=dev)
-                L.check(lib.nrf_adam_step_loss(L.ptr(flat), L.ptr(self.grad), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq), flat.numel(), opt.lr,
-                                               opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, opt.step_count, L.ptr(self.ray_loss), R,
-                                               self.rgb_weight, L.ptr(loss), st))
-                self._loss_vec, self.last_grad_norm = loss, None
-        m._gen += 1
-        return loss
+                if v3:
+                    L.check(lib.nrf_project_fetch(C.byref(dn), L.ptr(self._pos), M, L.ptr(self._feats), None, st))
+                L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(self._pos), L.ptr(self._dirs), L.ptr(self._feats), M, L.ptr(out[0]), L.ptr(out[1]),
+                                                  ctx, self.nbytes, st))
+        del occ_keep
+        return M
