@@ -259,7 +259,7 @@ class ExtractorTrainer:
 
 
 def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, dino_maps=None, max_batches=None, rank=0, world=1,
-                extractor=None, fused_inputs=False, occupancy=None):
+                extractor=None, fused_inputs=False, occupancy=None, draws=None):
     """One pass of train.py:261-290 over the training views; returns (mean loss, ray-samples processed).
     fused_inputs: every batch is one `step.step_view` on its pixel ids (--fused-inputs; module docstring) instead of torch gathers,
     sample_points_along_rays, the expanded directions and fetch_features in front of `step(...)`.
@@ -267,6 +267,10 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
     and a refresh of the grid when one is due.
     extractor: an ExtractorTrainer (--train-extractor; module docstring) -- the view's map comes from it, live, instead of
     dino_maps[v], and it takes one step per view.
+    draws: the epoch's random draws as inputs (parity runs against a recorded run of the reference's trainer): an object whose
+    `permutation(v, n)` returns view v's shuffle of its n rays (train.py:272's torch.randperm) and whose `jitter(v, i, n, S)` returns the
+    (n,S) uniforms of the batch starting at position i (ray_utils.py:78's torch.rand), handed on as `t_rand=`.  None: `gen` shuffles and
+    the counter RNG jitters, as before.
     world > 1 (data parallel, `FusedStep(data_parallel=True)`): every rank draws the SAME shuffle (same generator seed) and
     takes rays rank, rank+world, ... of each batch -- the batches are those of one process (the stratified jitter of a ray is
     keyed by its position inside the call, so the sample depths differ from a single-process run's)."""
@@ -289,13 +293,17 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
         view_map = extractor.begin_view(v) if extractor is not None else (dino_maps[v:v + 1] if use_dino else None)
         dino = make_dino(view_map, poses[v], focal, H, W) if use_dino else None                 # train.py:204-206: full-resolution intrinsics
         cam = dict(features=view_map, pose=poses[v], focal=focal, H=H, W=W)
-        order = torch.randperm(n_view, device=dev_v, generator=gen)
+        if draws is None:
+            order = torch.randperm(n_view, device=dev_v, generator=gen)
+        else:
+            order = torch.as_tensor(draws.permutation(v, n_view), dtype=torch.int64).to(dev_v)
         for i in range(0, order.shape[0], batch):
             idx = order[i:i + batch]
             if world > 1:
                 idx = idx[: idx.shape[0] // world * world][rank::world]        # equal shards: the all-reduce averages per-rank means
                 if idx.shape[0] == 0:
                     continue
+            t_rand = None if draws is None else draws.jitter(v, i, idx.shape[0], S)
             if fused_inputs:
                 n = idx.shape[0]
                 kw = dict(dino=dino, seed=epoch * 1_000_003 + v * 10_007 + i, target=tgt[idx])
@@ -306,7 +314,7 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
                     kw.update(d_dino_out=d_feats, points_out=pts_buf[:n * S])
                 if occupancy is not None:
                     kw["occupancy"] = occupancy.current()
-                loss = step.step_view(None, c2w, Ht, Wt, f_t, idx, near, far, S, perturb=True, **kw)
+                loss = step.step_view(None, c2w, Ht, Wt, f_t, idx, near, far, S, perturb=True, t_rand=t_rand, **kw)
                 if occupancy is not None:
                     occupancy.after_step(model)
                 if extractor is not None:
@@ -320,7 +328,7 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
                     return float(total) / n_batches, samples
                 continue
             o, d, t = ro[idx], rd[idx], tgt[idx]
-            pts, z = sample_points_along_rays(o, d, near, far, S, perturb=True, seed=epoch * 1_000_003 + v * 10_007 + i)
+            pts, z = sample_points_along_rays(o, d, near, far, S, perturb=True, t_rand=t_rand, seed=epoch * 1_000_003 + v * 10_007 + i)
             n = idx.shape[0]
             dirs = d[:, None, :].expand(n, S, 3).reshape(-1, 3)                         # train.py:225: raw ray directions per sample
             feats = fetch_features(dino, pts.reshape(-1, 3)) if use_dino else None
