@@ -23,12 +23,18 @@ disparity ladder, the in-kernel jitter and explicit sorted depths:
                              bit-equal to nrf_mlp_forward on the same fp32 features; the staged forward is handed the fetch
                              rounded to f16 -- which makes its two passes exactly that arithmetic -- and the equality asserted is
                              the same bit equality.
-  b. V1                      the staged V1 forward takes an fp32 encoding and the renderer encodes in the kernel: bit equality is
-                             not owed.  A RECORD line per case gives the share of bit-equal open samples and the largest
-                             difference; asserted are the existing bounds (1e-4 for f32 / f16x3; 4e-3 / 4e-2 for f16 / bf16, as
+  b. V1                      the staged V1 forward takes an fp32 encoding and the renderer encodes in the kernel: against the
+                             staged forward on TORCH's encoding, which is what this file feeds it, bit equality is not owed.
+                             A RECORD line per case gives the share of bit-equal open samples and the largest difference;
+                             asserted are the existing bounds (1e-4 for f32 / f16x3; 4e-3 / 4e-2 for f16 / bf16, as
                              test_render_end_to_end_golden_16bit states them for this 'fog' scene) on the colours, and
                              open == (sigma > 0) wherever the staged |sigma| is at or above that bound; and the SPW = 8 and
-                             queue probes are torch.equal to the plain probe (colours and weights).
+                             queue probes are torch.equal to the plain probe (colours and weights).  The bit-level anchor of
+                             the V1 renderers is tests/test_gpu_train_rays_link.py, section 3: the ray-input training forward
+                             saves the kernel's own encoding of these very samples, and on THAT encoding the staged forward
+                             equals the probe colour for colour, open for open, on each of the three routes in f32, f16 and
+                             bf16 (same nets, rays, S and depth kinds as here).  f16x3 has no training kernel, hence no saved
+                             encoding: the 1e-4 bound of this section is what holds it.
   c. compositor and plumbing every net: the S-sample render under the launcher's deal, the uniform deal at SPW = 1 and SPW = 8
                              (NRF_SPW, as tests/test_gpu_even_deal.py) and, for the jittered depths, the ray-queue kernel
                              (ert_eps = 1e-30), with and without the white background: z_vals are the staged sampler's bits; rgb

@@ -1,5 +1,7 @@
 """The saved context of the training path, decoded, and the stage-wise comparer built on it (test infrastructure shared by
-tests/test_gpu_training.py, tests/test_gpu_train_stages.py and the CPU tests of the comparer, tests/test_train_stage_model.py).
+tests/test_gpu_training.py, tests/test_gpu_train_stages.py and the CPU tests of the comparer, tests/test_train_stage_model.py);
+and the bit-for-bit comparer of TWO contexts (context_differences, x_enc_from_input_slot: tests/test_gpu_train_rays_link.py and
+its CPU half, tests/test_train_rays_link_host.py).
 
 Slot sizes, the number of ReLU bit planes and with them the place of the V3 gate pairs come from the plan the library reports
 (nrf_debug_train_plan, parsed by tests/test_training_host.py:train_plan); the context is laid out as train_impl.hpp:fill_slots
@@ -97,15 +99,20 @@ class SavedContext:
         self.mode, self.n = mode, n
         self.tiles32 = (n + 255) // 256 * 8
         self.tb = 4096 if mode == "f32" else 2048
-        self.raw = buf.cpu().numpy() if isinstance(buf, torch.Tensor) else buf
+        self.buf = buf                        # a device tensor stays where it is: a decoder fetches the bytes of its own slot only
         self.slot_off = np.concatenate([[0], np.cumsum(np.asarray(self.slot_tiles, np.int64) * self.tiles32 * self.tb)])
         self.plane_off = int(self.slot_off[-1])
         self.gate_off = self.plane_off + n_planes * self.tiles32 * 1024
 
+    def bytes(self, start, stop):
+        """Bytes start .. stop of the context as a numpy uint8 array on the host."""
+        part = self.buf[int(start):int(stop)]
+        return part.cpu().numpy() if isinstance(part, torch.Tensor) else part
+
     def slot_number(self, slot):
         """Saved-tensor slot -> (features, padded samples) fp32 matrix."""
         T, KT = self.tiles32, self.slot_tiles[slot]
-        raw = self.raw[int(self.slot_off[slot]):int(self.slot_off[slot + 1])]
+        raw = self.bytes(self.slot_off[slot], self.slot_off[slot + 1])
         if self.mode == "f32":
             v = raw.view(np.float32).reshape(T, KT, 4, 2, 32, 4)              # sample tile, tile, vec, lane half, column, e
         else:
@@ -128,7 +135,7 @@ class SavedContext:
         dword m >> 1, accumulator register r at bit 15 - r of that half)."""
         T, KT = self.tiles32, self.slot_tiles[self.slots[name]]
         off = self.plane_off + self.planes[name] * T * 1024
-        w = self.raw[off:off + T * 1024].view(np.uint32).reshape(T, 2, 32, 4)                             # sample tile, half, column, dword
+        w = self.bytes(off, off + T * 1024).view(np.uint32).reshape(T, 2, 32, 4)                          # sample tile, half, column, dword
         out = np.zeros((KT, 32, T, 32), bool)
         for m in range(KT):
             half = (w[..., m >> 1] >> (16 * (m & 1))) & 0xffff
@@ -139,7 +146,7 @@ class SavedContext:
 
     def gate(self):
         """(padded samples, 2) fp32: the V3 softmax gate (w0, w1)."""
-        return self.raw[self.gate_off:self.gate_off + self.tiles32 * 32 * 8].view(np.float32).reshape(-1, 2)
+        return self.bytes(self.gate_off, self.gate_off + self.tiles32 * 32 * 8).view(np.float32).reshape(-1, 2)
 
 
 def _encoder_rows(rows, L, zeros, what):
@@ -186,10 +193,97 @@ def saved_stages(ctx, variant, n_layers, dino_dim=0):
     return st, zeros
 
 
+def x_enc_from_input_slot(ctx, L=10):
+    """V1's `input` slot as the (n, 3(2L+1)) fp32 tensor the staged entry points take (nrf_mlp_forward_train_v1's x_enc), in the
+    reference's column order -- the inverse of kernel_feature_order -- and the slot's padding rows over the real samples, which
+    the kernels promise to be exactly zero.  The values are in the operand type already, so the staged kernel's own rounding of
+    them is the identity (tests/test_train_rays_link_host.py)."""
+    zeros = []
+    x = _encoder_rows(ctx.slot("input")[:, :ctx.n], L, zeros, "input")
+    return torch.from_numpy(x), zeros[0][1]
+
+
+# ---------------------------------------------------------------------------------------------
+# two contexts of the same plan, bit for bit
+# ---------------------------------------------------------------------------------------------
+Difference = namedtuple("Difference", "stage count first")      # first: (row of the slot / plane in operand order, or gate component; sample)
+
+
+def stage_names(variant, n_layers):
+    """oracle.train_stage_names, and V1's chain under the same naming: (forward stages, backward stages) in chain order."""
+    if variant == "v1":
+        return (["input"] + [f"trunk.{j}" for j in range(n_layers)],
+                ["dz_head"] + [f"dz_trunk.{j}" for j in range(n_layers - 1, -1, -1)])
+    return O.train_stage_names(variant, n_layers)
+
+
+def _equal_below_n(a, b, start, unit, inner, n):
+    """Bytes of a region of sample tiles (`unit` bytes per 32 samples from `start`; inside a tile [.., 32 columns, `inner` bytes])
+    over the samples < n: the whole tiles are contiguous, the ragged last one is compared column by column."""
+    full, rem = divmod(n, 32)
+    start = int(start)
+    stop = start + full * unit
+    if not torch.equal(a[start:stop], b[start:stop]):
+        return False
+    if rem:
+        ra, rb = (t[stop:stop + unit].view(-1, 32, inner)[:, :rem] for t in (a, b))
+        return torch.equal(ra, rb)
+    return True
+
+
+def _name_difference(stage, ma, mb, n):
+    """Two decoded (rows, padded samples) matrices -> the Difference over the samples < n (None: bit-equal there)."""
+    bits = lambda m: np.ascontiguousarray(m[:, :n]).view(np.uint8 if m.dtype == bool else np.uint32)
+    d = bits(ma) != bits(mb)
+    if not d.any():
+        return None
+    sample, row = (int(v) for v in np.argwhere(d.T)[0])
+    return Difference(stage, int(d.sum()), (row, sample))
+
+
+def context_differences(ctx_a, ctx_b, variant, n_layers, dino_dim, stages):
+    """The stages (of `stages`, names as stage_names gives them) in which two decoded contexts of the same plan, mode and n hold
+    different BITS: every named slot, the ReLU plane of every named forward stage ('mask.<stage>') and, under 'gate', the V3
+    gate pairs.  One Difference per differing stage, in chain order; [] = the contexts are bit-equal there.
+
+    Only the columns of real samples (< n) are compared.  The padded columns of the last 256-sample group are not owed: a chain
+    kernel runs them on a copy of the LAST real sample's inputs (train_impl.hpp: ChainTile::sid), and a forward that derives its
+    inputs (RaySample on row sid) rather than reading them is free to fill them otherwise; the backward zeroes them on every
+    route (saved_stages' `zeros`).  Inside a real sample's column every byte is compared, the padding rows of an encoder tile
+    and of a head gradient included: they are exact zeros on every route.
+
+    The comparison runs on the raw bytes where the buffers live (on the GPU for device tensors): in each slot the sample tiles
+    wholly below n are contiguous (fill_slots: [sample tile][tile][tile bytes]); only a slot that differs is decoded, to count
+    and name the difference."""
+    assert (ctx_a.mode, ctx_a.n, list(ctx_a.slot_tiles), ctx_a.gate_off) == (ctx_b.mode, ctx_b.n, list(ctx_b.slot_tiles), ctx_b.gate_off)
+    slots, planes, _, _ = slot_numbers(variant, n_layers)
+    assert slots == ctx_a.slots and (variant == "v3") == bool(dino_dim)
+    fwd, bwd = stage_names(variant, n_layers)
+    unknown = set(stages) - set(fwd) - set(bwd)
+    assert not unknown, unknown
+    n, T = ctx_a.n, ctx_a.tiles32
+    a, b = (torch.from_numpy(c.buf) if isinstance(c.buf, np.ndarray) else c.buf for c in (ctx_a, ctx_b))
+    out = []
+    for name in fwd + bwd:
+        if name not in stages:
+            continue
+        if name == "gate":
+            if not _equal_below_n(a, b, ctx_a.gate_off, 32 * 8, 8, n):
+                out.append(_name_difference(name, ctx_a.gate().T, ctx_b.gate().T, n))
+            continue
+        s = slots[name]
+        if not _equal_below_n(a, b, ctx_a.slot_off[s], ctx_a.slot_tiles[s] * ctx_a.tb, 16, n):
+            out.append(_name_difference(name, ctx_a.slot_number(s), ctx_b.slot_number(s), n))
+        if name in planes and not _equal_below_n(a, b, ctx_a.plane_off + planes[name] * T * 1024, 1024, 16, n):
+            out.append(_name_difference("mask." + name, ctx_a.plane(name), ctx_b.plane(name), n))
+    assert None not in out, "the bytes differ where the decoded values do not: a decoder of this file is wrong"
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # the comparer
 # ---------------------------------------------------------------------------------------------
-Finding = namedtuple("Finding", "stage outliers allowed worst differ")      # worst: the largest |a - e| / bound; differ: share of non-zero elements that differ
+Finding =namedtuple("Finding", "stage outliers allowed worst differ")      # worst: the largest |a - e| / bound; differ: share of non-zero elements that differ
 DIFFER_SHARE = 0.10
 
 
