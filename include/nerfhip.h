@@ -311,6 +311,45 @@ int nrf_composite(const float* rgb, int rgb_stride, const float* sigma, int sigm
  * reference's fp32 CPU run would. */
 int nrf_sample_pdf(const float* z_vals, const float* weights, int64_t n_rays, int n_samples, int n_importance,
                    const float* u, int64_t u_ray_stride, float* samples, float* z_union, void* stream);
+/* nrf_sample_pdf with a third optional output: samples_sorted (R,Ni), the new samples in ascending order (equal values keep the
+ * order of u) -- the row the kernel merges into the union.  At least one of the three outputs is given. */
+int nrf_sample_pdf_sorted(const float* z_vals, const float* weights, int64_t n_rays, int n_samples, int n_importance,
+                          const float* u, int64_t u_ray_stride, float* samples, float* samples_sorted, float* z_union, void* stream);
+
+/* ---- hierarchical render that evaluates only the new samples in its fine pass -------------------------------------------
+ * A sample's network output depends on its ray and its depth alone, and the fine pass' sorted union holds the S coarse depths
+ * bit for bit: S of its S + Ni evaluations repeat the coarse pass.  The route below keeps them instead:
+ *   1. nrf_render_rays_emit / nrf_render_camera_emit: the plain render (same rgb, depth, weights, z_vals bits) that also stores,
+ *      for every (ray, sample), the four head outputs its compositor consumes -- r, g, b before the sigmoid, density before the
+ *      ReLU -- as the 16-byte row raw4[(ray * n_samples + s) * 4 ..]; raw4 (R, n_samples, 4), 16-byte aligned.
+ *   2. nrf_sample_pdf_sorted on the coarse weights: the Ni new depths, ascending.
+ *   3. the emitting render again with opts->z_in = the new depths, opts->n_samples = Ni and raw_only = 1: rgb, depth, weights
+ *      and z_vals are ignored (may be NULL), only raw4 (R, Ni, 4) is stored.
+ *   4. nrf_composite_merge / nrf_composite_merge_camera: one lane per ray merges the two ascending depth lists -- the coarse
+ *      sample first among equals, the rule of the sorted union -- and composites the merged order front to back with the fused
+ *      renderer's operations in its order (dist to the next merged depth, 1e10 |d| for the last).  mma_mode: the mode that
+ *      emitted the rows (it selects the compositor's exp / sigmoid as in the renderer).  n_importance = 0 composites the coarse
+ *      rows alone (z_new, raw_new unused).  out_rgbd: rgb is (R,4) rows [r,g,b,depth], 16-byte aligned, depth unused.
+ *      weights, z_union (R, S+Ni): optional.
+ * The result equals, bit for bit, the fine pass rendered on the sorted union through opts->z_in.  The emitting entries take
+ * ert_eps == 0 only (NRF_EINVAL otherwise) and have no tail or occupancy form.
+ * nrf_hier_workspace_bytes: n_rays * (S * (4 + 4 + 16) + Ni * (4 + 16)) -- coarse depths, weights and rows, new depths and rows:
+ * what a caller marching a frame in ray ranges holds per range. */
+int nrf_render_rays_emit(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays,
+                         const nrf_render_opts* opts, float* rgb, float* depth, float* weights, float* z_vals,
+                         float* raw4, int raw_only, void* stream);
+int nrf_render_camera_emit(const nrf_model* m, int H, int W, float focal, const float c2w[12],
+                           int64_t ray_begin, int64_t ray_end, const nrf_render_opts* opts,
+                           float* rgb, float* depth, float* weights, float* z_vals, float* raw4, int raw_only, void* stream);
+int nrf_composite_merge(const float* z_coarse, const float* raw_coarse, const float* z_new, const float* raw_new,
+                        const float* rays_d, int64_t n_rays, int n_samples, int n_importance, int mma_mode, int white_bkgd,
+                        int out_rgbd, float* rgb, float* depth, float* weights, float* z_union, void* stream);
+int nrf_composite_merge_camera(const float* z_coarse, const float* raw_coarse, const float* z_new, const float* raw_new,
+                               int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
+                               int n_samples, int n_importance, int mma_mode, int white_bkgd, int out_rgbd,
+                               float* rgb, float* depth, float* weights, float* z_union, void* stream);
+int64_t nrf_hier_workspace_bytes(int64_t n_rays, int n_samples, int n_importance);
+
 /* ray_utils.py:176-210 + dino_feature_model.py:114-148: points (N,3) -> features (N,C); xy (N,2) may be NULL. */
 int nrf_project_fetch(const nrf_dino* dino, const float* points, int64_t n, float* feats, float* xy, void* stream);
 

@@ -151,6 +151,19 @@ SIGNATURES = {
     "nrf_composite": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrf_sample_pdf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # hierarchical render that evaluates only the new samples: emitting renders, ascending new samples, merging compositor
+    "nrf_sample_pdf_sorted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "nrf_render_rays_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(nrf_render_opts),
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "nrf_render_camera_emit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float * 12, C.c_int64, C.c_int64,
+                                         C.POINTER(nrf_render_opts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "nrf_composite_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_composite_merge_camera": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float * 12,
+                                             C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+    "nrf_hier_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "nrf_debug_pack": (C.c_int, [C.POINTER(nrf_arch), C.POINTER(nrf_linear), C.c_int, C.c_int, C.c_void_p, C.c_int64,
                                  C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "nrf_debug_ray_deal": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]),
@@ -334,6 +347,24 @@ def tail_arg(tail_mode, mma_mode, n_rays, device):
         _tail_ws[key] = ws
     t = nrf_tail(TAIL_MODES[tail_mode], ws.data_ptr(), ws.numel() * 4)
     return t, ws
+
+
+_hier_ws = {}
+
+
+def hier_workspace(n_rays, n_samples, n_importance, device):
+    """The workspace of one ray range of render_camera_hierarchical on `device`: nrf_hier_workspace_bytes(n_rays, S, Ni) bytes as a
+    flat fp32 tensor, cached per (device, stream) and grown on demand -- the chunks of a frame and the frames that follow on the same
+    stream use it in order.  Call with `device` current."""
+    need = lib().nrf_hier_workspace_bytes(int(n_rays), int(n_samples), int(n_importance)) // 4
+    key = (str(device), stream_ptr())
+    ws = _hier_ws.get(key)
+    if ws is None or ws.numel() < need:
+        if len(_hier_ws) > 16:
+            _hier_ws.clear()
+        ws = torch.empty((max(need, 4),), dtype=torch.float32, device=device)
+        _hier_ws[key] = ws
+    return ws
 
 
 def u_row(n_importance, device):

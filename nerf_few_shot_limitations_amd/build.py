@@ -30,7 +30,15 @@ FUSED = [(f"fused_{fam}.hip", f"fused_{fam}_{half}", flags) for fam in ("v1", "v
 TAIL = [("fused_tail.hip", "fused_tail", HALF32)]
 # empty-space skipping (fused_impl.hpp: render_queue_occ_kernel): units of their own, both halves with the flags of their fused_v* siblings
 OCC = [(f"fused_occ_{fam}.hip", f"fused_occ_{fam}_{half}", flags) for fam in ("v1", "v2", "v3", "v3w") for half, flags in (("16", HALF16), ("32", HALF32))]
-SOURCES = FUSED + OCC + TAIL + [(f, os.path.splitext(f)[0], []) for f in
+# The hierarchical render that evaluates only the new samples: the renderer that also emits each sample's raw head outputs
+# (fused_impl.hpp: render_emit_kernel; both halves with the flags of their fused_v* siblings) and its staged kernels (hier_kernels.hip).
+# Their objects and remarks go to a directory of their own, OBJ_HIER: tests/golden/kernel_resources.json is a closed census of the
+# kernels in OBJ (tests/test_train_occupancy_host.py allows no name beside it), so kernels added since are reported per directory --
+# kernel_resources(OBJ_HIER) -- and held to their bars by their own tests (tests/test_hier_reuse_host.py).
+OBJ_HIER = os.path.join(OBJ, "hier")
+HIER = [(f"fused_emit_{fam}.hip", f"hier/fused_emit_{fam}_{half}", flags) for fam in ("v1", "v2", "v3", "v3w") for half, flags in (("16", HALF16), ("32", HALF32))]
+HIER += [("hier_kernels.hip", "hier/hier_kernels", [])]
+SOURCES = FUSED + OCC + HIER + TAIL + [(f, os.path.splitext(f)[0], []) for f in
                    ("fused_kernels.hip", "train_shared.hip", "train_v1.hip", "train_v2.hip", "train_v3.hip", "train_dino_grad.hip", "train_input_grad.hip", "train_input_grad_v3.hip", "staged_kernels.hip", "api.cpp",
                     "packing.cpp")]
 # -Rpass-analysis=kernel-resource-usage: the backend reports every kernel's registers / spills / scratch; kept beside the object
@@ -80,7 +88,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     # source, header and this file
     if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(deps):
         return LIB
-    os.makedirs(OBJ, exist_ok=True)
+    os.makedirs(OBJ_HIER, exist_ok=True)
 
     def one(item):
         src, name, flags = item

@@ -307,19 +307,34 @@ nrf::OccDev make_occ(const nrf_occupancy* g) {
     return d;
 }
 
-// the launch of a render entry point: plain, with a grid, or prefix + tail through the caller's workspace
+// the extra output of the *_emit entry points: raw4 (n_rays, n_samples, 4); raw_only: nothing else is stored
+struct EmitOut {
+    float* raw4;
+    int raw_only;
+};
+
+// what the emitting entries refuse, looked at once the options are known to be sane
+int check_emit(const nrf_render_opts* o, const EmitOut* e) {
+    if (!e->raw4 || (reinterpret_cast<uintptr_t>(e->raw4) & 15u) != 0) return fail(NRF_EINVAL, "raw4 is NULL or not 16-byte aligned (one 16-byte row per sample)");
+    if (o->ert_eps > 0.0f) return fail(NRF_EINVAL, "an emitting render takes ert_eps == 0: a terminated ray would leave rows unwritten");
+    return NRF_OK;
+}
+
+// the launch of a render entry point: plain, emitting, with a grid, or prefix + tail through the caller's workspace
 int launch_any(const nrf_model* m, const nrf_render_opts* opts, const nrf_tail* tail, const nrf_occupancy* occ, const nrf::RenderArgs& a, void* stream,
-               std::string& err) {
+               std::string& err, const EmitOut* emit = nullptr) {
+    if (emit) return nrf::launch_render_emit(m->net, opts->mma_mode, a, emit->raw4, (hipStream_t)stream, err);
     if (occ) return nrf::launch_render_occ(m->net, opts->mma_mode, a, make_occ(occ), (hipStream_t)stream, err);
     if (tail) return nrf::launch_render_tail(m->net, opts->mma_mode, a, static_cast<float*>(tail->workspace), (hipStream_t)stream, err);
     return nrf::launch_render(m->net, opts->mma_mode, a, (hipStream_t)stream, err);
 }
 
 int render_rays_any(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays, const nrf_render_opts* opts,
-                    const nrf_tail* tail, bool tailed, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals, void* stream);
+                    const nrf_tail* tail, bool tailed, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals, void* stream,
+                    const EmitOut* emit = nullptr);
 int render_camera_any(const nrf_model* m, int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
                       const nrf_render_opts* opts, const nrf_tail* tail, bool tailed, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals,
-                      void* stream);
+                      void* stream, const EmitOut* emit = nullptr);
 int render_cameras_tiles_any(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams, int64_t tile_rays,
                              int64_t first_tile, int64_t tile_step, int64_t n_tiles, const nrf_render_opts* opts, const nrf_tail* tail,
                              bool tailed, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals, void* stream);
@@ -426,6 +441,17 @@ int nrf_render_camera_tail(const nrf_model* m, int H, int W, float focal, const 
                            void* stream) {
     return render_camera_any(m, H, W, focal, c2w, ray_begin, ray_end, opts, tail, true, nullptr, rgb, depth, weights, z_vals, stream);
 }
+int nrf_render_rays_emit(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays, const nrf_render_opts* opts,
+                         float* rgb, float* depth, float* weights, float* z_vals, float* raw4, int raw_only, void* stream) {
+    const EmitOut e{raw4, raw_only};
+    return render_rays_any(m, rays_o, rays_d, n_rays, opts, nullptr, false, nullptr, rgb, depth, weights, z_vals, stream, &e);
+}
+int nrf_render_camera_emit(const nrf_model* m, int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
+                           const nrf_render_opts* opts, float* rgb, float* depth, float* weights, float* z_vals, float* raw4, int raw_only,
+                           void* stream) {
+    const EmitOut e{raw4, raw_only};
+    return render_camera_any(m, H, W, focal, c2w, ray_begin, ray_end, opts, nullptr, false, nullptr, rgb, depth, weights, z_vals, stream, &e);
+}
 int nrf_render_cameras_tiles(const nrf_model* m, int H, int W, float focal, const float* c2w, int n_cams, int64_t tile_rays,
                              int64_t first_tile, int64_t tile_step, int64_t n_tiles, const nrf_render_opts* opts, float* rgb, float* depth,
                              float* weights, float* z_vals, void* stream) {
@@ -530,14 +556,18 @@ namespace {
 // The three render entry points, plain (tailed == false) and with a tail (nerfhip.h: nrf_tail), which is checked once the call's
 // ray count is known.
 int render_rays_any(const nrf_model* m, const float* rays_o, const float* rays_d, int64_t n_rays, const nrf_render_opts* opts,
-                    const nrf_tail* tail, bool tailed, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals, void* stream) {
+                    const nrf_tail* tail, bool tailed, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals, void* stream,
+                    const EmitOut* emit) {
+    const bool raw_only = emit && emit->raw_only;
+    if (raw_only) rgb = depth = weights = z_vals = nullptr;
     if (rgbd_misaligned(opts, rgb)) return fail(NRF_EINVAL, kRgbdAlign);
     if (!m) return fail(NRF_EINVAL, "model is NULL");
     if (n_rays < 0) return fail(NRF_EINVAL, "n_rays < 0");
     if (n_rays == 0) return NRF_OK;
     const int rc = check_opts(opts);
     if (rc != NRF_OK) return rc;
-    if (!rays_o || !rays_d || !rgb || (!depth && !opts->out_rgbd)) return fail(NRF_EINVAL, "nrf_render_rays: null ray or output pointer");
+    if (emit && check_emit(opts, emit) != NRF_OK) return NRF_EINVAL;
+    if (!rays_o || !rays_d || (!raw_only && (!rgb || (!depth && !opts->out_rgbd)))) return fail(NRF_EINVAL, "nrf_render_rays: null ray or output pointer");
     if ((int64_t)opts->n_samples * n_rays > (int64_t)1 << 40) return fail(NRF_EINVAL, "ray-sample count too large");
     if (tailed && check_tail(opts, tail, n_rays) != NRF_OK) return NRF_EINVAL;
     nrf::RenderArgs a{};
@@ -548,13 +578,15 @@ int render_rays_any(const nrf_model* m, const float* rays_o, const float* rays_d
     if (m->arch.net == NRF_NET_V3 && !make_dino(opts->dino, m->arch.dino_dim, a.dino, err)) return fail(NRF_EINVAL, err);
     DeviceGuard guard(m->device);
     if (!guard.ok) return fail(NRF_EHIP, "cannot select the model's device");
-    const int r = launch_any(m, opts, tail, occ, a, stream, err);
+    const int r = launch_any(m, opts, tail, occ, a, stream, err, emit);
     return r == NRF_OK ? NRF_OK : fail(r, err);
 }
 
 int render_camera_any(const nrf_model* m, int H, int W, float focal, const float c2w[12], int64_t ray_begin, int64_t ray_end,
                       const nrf_render_opts* opts, const nrf_tail* tail, bool tailed, const nrf_occupancy* occ, float* rgb, float* depth, float* weights, float* z_vals,
-                      void* stream) {
+                      void* stream, const EmitOut* emit) {
+    const bool raw_only = emit && emit->raw_only;
+    if (raw_only) rgb = depth = weights = z_vals = nullptr;
     if (rgbd_misaligned(opts, rgb)) return fail(NRF_EINVAL, kRgbdAlign);
     if (!m) return fail(NRF_EINVAL, "model is NULL");
     if (H < 1 || W < 1 || !(focal > 0.0f) || !c2w) return fail(NRF_EINVAL, "bad camera");
@@ -562,7 +594,8 @@ int render_camera_any(const nrf_model* m, int H, int W, float focal, const float
     if (ray_end == ray_begin) return NRF_OK;
     const int rc = check_opts(opts);
     if (rc != NRF_OK) return rc;
-    if (!rgb || (!depth && !opts->out_rgbd)) return fail(NRF_EINVAL, "nrf_render_camera: null output pointer");
+    if (emit && check_emit(opts, emit) != NRF_OK) return NRF_EINVAL;
+    if (!raw_only && (!rgb || (!depth && !opts->out_rgbd))) return fail(NRF_EINVAL, "nrf_render_camera: null output pointer");
     if (tailed && check_tail(opts, tail, ray_end - ray_begin) != NRF_OK) return NRF_EINVAL;
     nrf::RenderArgs a{};
     a.camera_mode = 1; a.n_cams = 1; a.cams[0] = make_camera(H, W, focal, c2w); a.ray_begin = ray_begin; a.n_rays = ray_end - ray_begin;
@@ -572,7 +605,7 @@ int render_camera_any(const nrf_model* m, int H, int W, float focal, const float
     if (m->arch.net == NRF_NET_V3 && !make_dino(opts->dino, m->arch.dino_dim, a.dino, err)) return fail(NRF_EINVAL, err);
     DeviceGuard guard(m->device);
     if (!guard.ok) return fail(NRF_EHIP, "cannot select the model's device");
-    const int r = launch_any(m, opts, tail, occ, a, stream, err);
+    const int r = launch_any(m, opts, tail, occ, a, stream, err, emit);
     return r == NRF_OK ? NRF_OK : fail(r, err);
 }
 
@@ -1099,6 +1132,67 @@ int nrf_sample_pdf(const float* z_vals, const float* weights, int64_t n_rays, in
     if (u && u_ray_stride != 0 && u_ray_stride < n_importance) return fail(NRF_EINVAL, "u_ray_stride must be 0 (one shared row) or >= n_importance");
     const int r = nrf::launch_sample_pdf(z_vals, weights, n_rays, n_samples, n_importance, u, u_ray_stride, samples, z_union, (hipStream_t)stream);
     return r == NRF_OK ? NRF_OK : fail(r, r == NRF_EINVAL ? "n_samples + n_importance too large for one LDS row" : "sample_pdf launch failed");
+}
+
+int nrf_sample_pdf_sorted(const float* z_vals, const float* weights, int64_t n_rays, int n_samples, int n_importance, const float* u,
+                          int64_t u_ray_stride, float* samples, float* samples_sorted, float* z_union, void* stream) {
+    if (n_rays < 0 || n_samples < 2 || n_importance < 1) return fail(NRF_EINVAL, "bad sizes");
+    if (n_rays == 0) return NRF_OK;
+    if (!z_vals || !weights || (!samples && !samples_sorted && !z_union)) return fail(NRF_EINVAL, "null pointer");
+    if (u && u_ray_stride != 0 && u_ray_stride < n_importance) return fail(NRF_EINVAL, "u_ray_stride must be 0 (one shared row) or >= n_importance");
+    const int r = nrf::launch_sample_pdf_sorted(z_vals, weights, n_rays, n_samples, n_importance, u, u_ray_stride, samples, samples_sorted, z_union,
+                                                (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, r == NRF_EINVAL ? "n_samples + n_importance too large for one LDS row" : "sample_pdf launch failed");
+}
+
+int64_t nrf_hier_workspace_bytes(int64_t n_rays, int n_samples, int n_importance) {
+    if (n_rays < 0 || n_samples < 1 || n_importance < 0) { (void)fail(NRF_EINVAL, "nrf_hier_workspace_bytes: bad sizes"); return -1; }
+    // coarse depths, weights and rows; new depths and rows
+    return n_rays * ((int64_t)n_samples * (4 + 4 + 16) + (int64_t)n_importance * (4 + 16));
+}
+
+extern "C++" {
+namespace {
+
+int composite_merge_any(nrf::MergeArgs& a, int mma_mode, int out_rgbd, void* stream) {
+    if (a.n_rays < 0 || a.S < 1 || a.Ni < 0) return fail(NRF_EINVAL, "bad sizes");
+    if (mma_mode < 0 || mma_mode >= nrf::kModes) return fail(NRF_EINVAL, "unknown mma_mode");
+    if (a.n_rays == 0) return NRF_OK;
+    if (!a.z_coarse || !a.raw_coarse || (a.Ni > 0 && (!a.z_new || !a.raw_new)) || !a.rgb) return fail(NRF_EINVAL, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(a.raw_coarse) & 15u) != 0 || (reinterpret_cast<uintptr_t>(a.raw_new) & 15u) != 0)
+        return fail(NRF_EINVAL, "raw rows must be 16-byte aligned (read with one 16-byte load per sample)");
+    if (out_rgbd && (reinterpret_cast<uintptr_t>(a.rgb) & 15u) != 0) return fail(NRF_EINVAL, kRgbdAlign);
+    a.interleaved = out_rgbd ? 1 : 0;
+    // the compositor's exp / sigmoid follow the arithmetic mode that emitted the rows (mlp_core.hpp: Mode::FAST_EXP)
+    const int r = nrf::launch_composite_merge(a, mma_mode == NRF_MMA_BF16, (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "composite_merge launch failed");
+}
+
+}  // namespace
+}  // extern "C++"
+
+int nrf_composite_merge(const float* z_coarse, const float* raw_coarse, const float* z_new, const float* raw_new, const float* rays_d,
+                        int64_t n_rays, int n_samples, int n_importance, int mma_mode, int white_bkgd, int out_rgbd, float* rgb, float* depth,
+                        float* weights, float* z_union, void* stream) {
+    if (n_rays > 0 && !rays_d) return fail(NRF_EINVAL, "null pointer");
+    nrf::MergeArgs a{};
+    a.z_coarse = z_coarse; a.raw_coarse = raw_coarse; a.z_new = z_new; a.raw_new = raw_new; a.rays_d = rays_d;
+    a.n_rays = n_rays; a.S = n_samples; a.Ni = n_importance; a.white_bkgd = white_bkgd;
+    a.rgb = rgb; a.depth = depth; a.weights = weights; a.z_union = z_union;
+    return composite_merge_any(a, mma_mode, out_rgbd, stream);
+}
+
+int nrf_composite_merge_camera(const float* z_coarse, const float* raw_coarse, const float* z_new, const float* raw_new, int H, int W, float focal,
+                               const float c2w[12], int64_t ray_begin, int64_t ray_end, int n_samples, int n_importance, int mma_mode,
+                               int white_bkgd, int out_rgbd, float* rgb, float* depth, float* weights, float* z_union, void* stream) {
+    if (H < 1 || W < 1 || !(focal > 0.0f) || !c2w) return fail(NRF_EINVAL, "bad camera");
+    if (ray_begin < 0 || ray_end < ray_begin || ray_end > (int64_t)H * W) return fail(NRF_EINVAL, "ray range outside the image");
+    nrf::MergeArgs a{};
+    a.z_coarse = z_coarse; a.raw_coarse = raw_coarse; a.z_new = z_new; a.raw_new = raw_new; a.rays_d = nullptr;
+    a.cam = make_camera(H, W, focal, c2w); a.ray_begin = ray_begin;
+    a.n_rays = ray_end - ray_begin; a.S = n_samples; a.Ni = n_importance; a.white_bkgd = white_bkgd;
+    a.rgb = rgb; a.depth = depth; a.weights = weights; a.z_union = z_union;
+    return composite_merge_any(a, mma_mode, out_rgbd, stream);
 }
 
 int nrf_debug_pack(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int mma_mode, uint8_t* stream_out, int64_t stream_cap,

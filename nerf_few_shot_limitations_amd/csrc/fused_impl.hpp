@@ -53,14 +53,16 @@ struct ForwardKArgs {
     int64_t n_tiles;
 };
 
+// the emitting renderers alone (render_emit_kernel) take the (n_rays, n_samples, 4) row buffer behind the renderer's arguments
+struct EmitKArgs : RenderKArgs {
+    float* raw4 = nullptr;
+};
+
 // the skipping ray-queue kernels alone take the grid (kernels.hpp: OccDev) behind the renderer's arguments
 struct OccKArgs {
     RenderKArgs r;
     OccDev g;
 };
-
-template <bool FAST>
-__device__ __forceinline__ float sigmoid_sel(float x) { return FAST ? sigmoid_fast(x) : sigmoid_precise(x); }
 
 // One of two register values by a (lane-dependent or uniform) flag, as a v_cndmask: left to itself LLVM turns
 // `flag ? out4[1][k] : out4[0][k]` into a dynamically indexed load from a STACK copy of out4 (48 bytes of scratch per lane in the
@@ -113,9 +115,15 @@ constexpr int kLdsState = kLdsRing + kBiasMaxFloats * 4 + 64 + kLadderLds * 4;  
 // prefix + tail are the plain render's bits, and with S == 1 the tail alone is the split-f16 render.
 enum { kWhole = 0, kPrefix = 1, kTail = 2 };
 
-template <class Net, class Mode, int NT, int WAVES, int LP, int LD, int PART>
-__device__ __forceinline__ void render_march(const RenderKArgs& P) {
+// EMIT (render_emit_kernel, the whole march only): every real (ray, sample) also leaves the four head outputs its compositor step is
+// about to consume -- rgb before the sigmoid, density before the ReLU -- as one 16-byte row raw4[ray * S + s], stored in the column
+// phase by the lane that holds the column's head rows.  A hierarchical render composites its fine pass from the coarse pass' rows
+// and the rows of the new depths alone (hier_kernels.hip: composite_merge_kernel).  With a.rgb == NULL the image is not stored
+// (the fine stage keeps raw4 only).  Without EMIT nothing of this is compiled: the plain kernels are what they were.
+template <class Net, class Mode, int NT, int WAVES, int LP, int LD, int PART, bool EMIT = false>
+__device__ __forceinline__ void render_march(const RenderKArgs& P, float* raw4 = nullptr) {
     static_assert(NT == 1 || NT == 2, "a wave marches 32 or 64 sample columns");
+    static_assert(!EMIT || PART == kWhole, "the emitting renderer has no tail form");
     constexpr int COLS = 32 * NT;                  // sample columns of a wave: column q = c + 32 n sits on lanes c, c + 32 of operand tile n
     extern __shared__ __attribute__((aligned(16))) char smem[];
     NRF_LDS char* lds = (NRF_LDS char*)smem;
@@ -325,6 +333,9 @@ __device__ __forceinline__ void render_march(const RenderKArgs& P) {
                 // NT == 2: lane L owns column L = tile h, column c -- and holds that tile's head rows itself
 #pragma unroll
                 for (int k = 0; k < 4; ++k) v[k] = NT == 2 ? pick_reg(out4[0][k], out4[NT - 1][k], h != 0) : out4[0][k];
+                if constexpr (EMIT) {                // (NT == 1: own_valid holds on the low lane of a pair only)
+                    if (own_valid) *(float4*)(raw4 + (rid * S + s) * 4) = make_float4(v[0], v[1], v[2], v[3]);
+                }
                 const float zn = last ? 0.0f : z_ray(rid, s + 1);
                 const float dist = last ? __fmul_rn(1e10f, norm) : __fmul_rn(__fsub_rn(zn, zo), norm);
                 const float w = comp.template add<Mode::FAST_EXP>(v[3], sigmoid_sel<Mode::FAST_EXP>(v[0]), sigmoid_sel<Mode::FAST_EXP>(v[1]),
@@ -350,6 +361,9 @@ __device__ __forceinline__ void render_march(const RenderKArgs& P) {
                     float v[4];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) v[k] = NT == 2 ? pick_reg(out4[0][k], out4[NT - 1][k], h != 0) : out4[0][k];
+                    if constexpr (EMIT) {            // this column's ray is rid (raw: before the clamp of a ragged tile); NT == 1: the low lane of a pair
+                        if (raw < a.n_rays && (NT == 2 || h == 0)) *(float4*)(raw4 + (rid * S + sq) * 4) = make_float4(v[0], v[1], v[2], v[3]);
+                    }
                     cz = z_ray(rid, sq);
                     const float zn = last ? 0.0f : z_ray(rid, sq + 1);
                     const float dist = last ? __fmul_rn(1e10f, norm) : __fmul_rn(__fsub_rn(zn, cz), norm);
@@ -382,7 +396,7 @@ __device__ __forceinline__ void render_march(const RenderKArgs& P) {
                     cy[0] = ST(F_T); cy[a.n_rays] = ST(F_R); cy[2 * a.n_rays] = ST(F_G); cy[3 * a.n_rays] = ST(F_B);
                     cy[4 * a.n_rays] = ST(F_DEPTH); cy[5 * a.n_rays] = ST(F_ACC);
                 }
-            } else if (lane < RPW && raw < a.n_rays) {
+            } else if (lane < RPW && raw < a.n_rays && (!EMIT || a.rgb)) {
                 float r = ST(F_R), g = ST(F_G), b = ST(F_B);
                 if (a.white_bkgd) {                                      // nerf_mlp.py:209-212
                     const float bg = __fsub_rn(1.0f, ST(F_ACC));
@@ -405,6 +419,10 @@ __device__ __forceinline__ void render_march(const RenderKArgs& P) {
 template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
 __global__ void __launch_bounds__(WAVES * 64) render_kernel(const RenderKArgs P) {
     render_march<Net, Mode, NT, WAVES, LP, LD, kWhole>(P);
+}
+template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
+__global__ void __launch_bounds__(WAVES * 64) render_emit_kernel(const EmitKArgs P) {
+    render_march<Net, Mode, NT, WAVES, LP, LD, kWhole, true>(P, P.raw4);
 }
 template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
 __global__ void __launch_bounds__(WAVES * 64) render_hold_kernel(const RenderKArgs P) {
@@ -618,6 +636,18 @@ int run_render_v(const DeviceNet& net, int mode, const RenderArgs& a, hipStream_
     return launch_persistent<render_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, d.items, s, "render", err);
 }
 
+// the emitting renderer: render_kernel's launch and deal, raw4 behind its arguments
+template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
+int run_render_emit(const DeviceNet& net, int mode, const RenderArgs& a, float* raw4, hipStream_t s, std::string& err) {
+    EmitKArgs k;
+    k.a = a;
+    k.raw4 = raw4;
+    const Deal d = pick_deal(a.n_rays, a.n_samples, WAVES, 32 * NT, net.cu_count);
+    k.a.spw_log2 = d.spw_log2;
+    k.even = d.even;
+    return launch_persistent<render_emit_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, d.items, s, "render (emitting)", err);
+}
+
 // tail mode, first launch (16-bit geometry): samples 0 .. S-2 of every ray, compositor state -> carry.  The split is picked for the
 // S-1 samples this launch marches.
 template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
@@ -762,6 +792,12 @@ bool check_net(const DeviceNet& net, int mode, std::string& err) {
     /* empty-space skipping: translation units of their own (fused_occ_v1.hip ... fused_occ_v3w.hip x the two halves) */   \
     int render_occ_##fam##_16(const DeviceNet& net, int mode, const RenderArgs& a, const OccDev& g, hipStream_t s, std::string& err); \
     int render_occ_##fam##_32(const DeviceNet& net, int mode, const RenderArgs& a, const OccDev& g, hipStream_t s, std::string& err); \
+    /* the emitting renderer: translation units of their own (fused_emit_v1.hip ... fused_emit_v3w.hip x the two halves) */ \
+    int render_emit_##fam##_16(const DeviceNet& net, int mode, const RenderArgs& a, float* raw4, hipStream_t s, std::string& err); \
+    int render_emit_##fam##_32(const DeviceNet& net, int mode, const RenderArgs& a, float* raw4, hipStream_t s, std::string& err); \
+    inline int render_emit_##fam(const DeviceNet& net, int mode, const RenderArgs& a, float* raw4, hipStream_t s, std::string& err) { \
+        return (mode == NRF_MMA_BF16 || mode == NRF_MMA_F16) ? render_emit_##fam##_16(net, mode, a, raw4, s, err) : render_emit_##fam##_32(net, mode, a, raw4, s, err); \
+    }                                                                                                                      \
     inline int render_occ_##fam(const DeviceNet& net, int mode, const RenderArgs& a, const OccDev& g, hipStream_t s, std::string& err) { \
         return (mode == NRF_MMA_BF16 || mode == NRF_MMA_F16) ? render_occ_##fam##_16(net, mode, a, g, s, err) : render_occ_##fam##_32(net, mode, a, g, s, err); \
     }                                                                                                                      \

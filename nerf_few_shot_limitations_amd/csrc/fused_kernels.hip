@@ -25,6 +25,17 @@ int launch_render_occ(const DeviceNet& net, int mode, const RenderArgs& a, const
     return NRF_EUNSUPPORTED;
 }
 
+int launch_render_emit(const DeviceNet& net, int mode, const RenderArgs& a, float* raw4, hipStream_t s, std::string& err) {
+    if (!check_net(net, mode, err)) return NRF_EINVAL;
+    if (a.n_rays <= 0) return NRF_OK;
+    if (net.arch.net == NRF_NET_V1 && net.arch.pos_freq == 10) return render_emit_v1(net, mode, a, raw4, s, err);
+    if (net.arch.net == NRF_NET_V2 && net.arch.pos_freq == 10) return render_emit_v2(net, mode, a, raw4, s, err);
+    if (net.arch.net == NRF_NET_V3 && net.arch.pos_freq == 12 && net.arch.dino_dim == 64) return render_emit_v3(net, mode, a, raw4, s, err);
+    if (net.arch.net == NRF_NET_V3 && net.arch.pos_freq == 12 && net.arch.dino_dim == 128) return render_emit_v3w(net, mode, a, raw4, s, err);
+    err = "no fused renderer built for this (net, pos_freq): see nrf_render_rays";
+    return NRF_EUNSUPPORTED;
+}
+
 int launch_render_tail(const DeviceNet& net, int base_mode, const RenderArgs& a, float* carry, hipStream_t s, std::string& err) {
     if (!check_net(net, base_mode, err) || !check_net(net, NRF_MMA_F16X3, err)) return NRF_EINVAL;
     if (a.n_rays <= 0) return NRF_OK;

@@ -85,6 +85,32 @@ struct OccDev {
 };
 // the ray-queue kernel with skipping (ert_eps >= 0: 0 = skipping alone)
 int launch_render_occ(const DeviceNet& net, int mma_mode, const RenderArgs& a, const OccDev& g, hipStream_t s, std::string& err);
+// render_kernel's march (ert_eps == 0) that also stores every real (ray, sample)'s raw head outputs [r, g, b before the sigmoid, density
+// before the ReLU] as the 16-byte row raw4[ray * n_samples + s]; a.rgb == NULL: the image is not stored
+int launch_render_emit(const DeviceNet& net, int mma_mode, const RenderArgs& a, float* raw4, hipStream_t s, std::string& err);
+// The hierarchical fine pass from kept rows (hier_kernels.hip: composite_merge_kernel): per ray the S coarse and the Ni new samples
+// (each list ascending) are merged -- the coarse one first among equals, sample_pdf_kernel's rule -- and composited front to back by one
+// lane with the operations of render_march's SPW = 1 branch.
+struct MergeArgs {
+    const float* z_coarse;      // (R,S)
+    const float* raw_coarse;    // (R,S,4)
+    const float* z_new;         // (R,Ni) ascending; unused with Ni == 0
+    const float* raw_new;       // (R,Ni,4)
+    const float* rays_d;        // (R,3), or NULL: rays ray_begin .. of `cam`
+    Camera cam;
+    int64_t ray_begin;
+    int64_t n_rays;
+    int S, Ni;
+    int white_bkgd, interleaved;
+    float* rgb;                 // (R,3), or (R,4) rows [r,g,b,depth] with `interleaved`
+    float* depth;               // (R), unused with `interleaved`
+    float* weights;             // optional (R,S+Ni)
+    float* z_union;             // optional (R,S+Ni)
+};
+int launch_composite_merge(const MergeArgs& m, bool fast_exp, hipStream_t s);
+// launch_sample_pdf with the new samples in ascending order as a third optional output (R,Ni)
+int launch_sample_pdf_sorted(const float* z, const float* w, int64_t n_rays, int S, int Ni, const float* u, int64_t u_ray_stride, float* samples,
+                             float* samples_sorted, float* z_union, hipStream_t s);
 int launch_forward_v1(const DeviceNet& net, int mma_mode, const float* x_enc, int64_t n, float* out4, hipStream_t s, std::string& err);
 int launch_forward(const DeviceNet& net, int mma_mode, const float* pos, const float* dir, const float* dino, int64_t n,
                    float* rgb, float* density, hipStream_t s, std::string& err);

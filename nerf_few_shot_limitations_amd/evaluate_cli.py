@@ -34,6 +34,10 @@ def main(argv=None):
                     help="with --mode f16 / bf16: evaluate every ray's last sample (composited with dist = 1e10) in split-f16")
     ap.add_argument("--max-views", type=int, default=None)
     ap.add_argument("--ert", type=float, default=0.0)
+    ap.add_argument("--n-importance", type=int, default=0, metavar="N",
+                    help="hierarchical render: N importance samples resampled from the coarse pass' weights on top of the config's sample count "
+                         "(0 = off; not with --tail-mode, --ert or --occupancy-res)")
+    ap.add_argument("--hier-chunk-rays", type=int, default=1 << 15, metavar="M", help="with --n-importance: rays per range of the frame's march")
     ap.add_argument("--occupancy-res", type=int, default=0,
                     help="skip empty space with an occupancy grid of N^3 cells built from the checkpoint (0 = off; N a multiple of 32, <= 512)")
     ap.add_argument("--occupancy-threshold", type=float, default=0.0, help="a cell is occupied when a probed density exceeds this")
@@ -58,6 +62,10 @@ def main(argv=None):
     if pruning and not args.occupancy_res:
         raise SystemExit("--occupancy-prune-views / --occupancy-weight-threshold / --occupancy-seen-eps / --occupancy-unseen prune the grid "
                          "of --occupancy-res: pass --occupancy-res N as well")
+    if args.n_importance < 0 or args.hier_chunk_rays < 1:
+        raise SystemExit("--n-importance must be >= 0 and --hier-chunk-rays >= 1")
+    if args.n_importance and (args.tail_mode or args.ert > 0.0 or args.occupancy_res):
+        raise SystemExit("--n-importance renders every sample of both passes: it takes no --tail-mode, --ert or --occupancy-res")
     if args.occupancy_prune_views < 0:
         raise SystemExit("--occupancy-prune-views must be >= 0")
     if pruning and not args.occupancy_prune_views:
@@ -118,9 +126,11 @@ def main(argv=None):
             prune["occupied_fraction_after"] = grid.occupied_fraction
     res = evaluate_views(model, poses, H, W, focal, rs["near"], rs["far"], rs["n_samples"], targets=targets, out_dir=args.out,
                          white_bkgd=rs["white_bkgd"], mma_mode=args.mode, ert_eps=args.ert, dino=dino, tail_mode=args.tail_mode, occupancy=grid,
-                         return_stats=grid is not None)
+                         return_stats=grid is not None, N_importance=args.n_importance, hier_chunk_rays=args.hier_chunk_rays)
     metrics = {"psnr": res["psnr"], "ssim": res["ssim"], "views": len(res["per_view"]), "per_view": res["per_view"],
                "H": H, "W": W, "n_samples": rs["n_samples"], "mode": args.mode}
+    if args.n_importance:
+        metrics["n_importance"] = args.n_importance
     if args.tail_mode:
         metrics["tail_mode"] = args.tail_mode
     if grid is not None:

@@ -69,15 +69,32 @@ def save_png(path: str, img: torch.Tensor) -> None:
 
 @torch.no_grad()
 def evaluate_views(model, poses, H, W, focal, near, far, N_samples=64, targets=None, out_dir=None, white_bkgd=False,
-                   mma_mode=None, ert_eps=0.0, dino=None, max_png=5, tail_mode=None, occupancy=None, return_stats=False):
+                   mma_mode=None, ert_eps=0.0, dino=None, max_png=5, tail_mode=None, occupancy=None, return_stats=False,
+                   N_importance=0, hier_chunk_rays=1 << 15):
     """Render every test pose (8 views per kernel launch) and, when `targets` (V,H,W,3|4) are given, score them.
     `tail_mode="f16x3"` with a 16-bit mma_mode: every ray's last sample in split-f16 (renderer.render_rays).
     `occupancy=` (an OccupancyGrid; V3: of the source view `dino`): empty cells are skipped; return_stats=True adds 'stats'
     [evaluated (ray, sample) pairs, live MLP passes] and 'evaluated_share' = stats[0] / (V*H*W*N_samples).
+    `N_importance` > 0: every view is a hierarchical render (N_samples coarse + N_importance importance samples) through
+    renderer.render_camera_hierarchical, marched in ray ranges of `hier_chunk_rays`; it takes no tail_mode, occupancy, return_stats or
+    ert_eps > 0 (ValueError).
     Returns {'images' (V,H,W,3), 'depth' (V,H,W), 'psnr', 'ssim' (means), 'per_view': [...]} (train.py:294-342)."""
     model.eval()
     poses = torch.as_tensor(poses)
     V = poses.shape[0]
+    if int(N_importance) > 0:
+        from .renderer import _refuse_reuse, render_camera_hierarchical
+        _refuse_reuse(tail_mode, occupancy, return_stats, ert_eps)
+        images = depth = None
+        for v in range(V):
+            rgb_v, depth_v = render_camera_hierarchical(model, H, W, focal, poses[v], near, far, N_samples, N_importance, chunk_rays=hier_chunk_rays,
+                                                        white_bkgd=white_bkgd, mma_mode=mma_mode, dino=dino)
+            if images is None:
+                images = torch.empty((V, int(H), int(W), 3), dtype=torch.float32, device=rgb_v.device)
+                depth = torch.empty((V, int(H), int(W)), dtype=torch.float32, device=rgb_v.device)
+            images[v] = rgb_v.view(int(H), int(W), 3)
+            depth[v] = depth_v.view(int(H), int(W))
+        return _score_views({"images": images, "depth": depth, "per_view": []}, targets, out_dir, max_png)
     tile_rays = 16 * int(W)
     local = tiles.render_tiles(model, H, W, focal, poses, near, far, N_samples, 0, 1, tile_rays, white_bkgd=white_bkgd,
                                mma_mode=mma_mode, ert_eps=ert_eps, dino=dino, tail_mode=tail_mode, occupancy=occupancy,
@@ -92,6 +109,13 @@ def evaluate_views(model, poses, H, W, focal, near, far, N_samples=64, targets=N
     if stats is not None:
         out["stats"] = [int(v) for v in stats.tolist()]
         out["evaluated_share"] = out["stats"][0] / float(V * int(H) * int(W) * int(N_samples))
+    return _score_views(out, targets, out_dir, max_png)
+
+
+def _score_views(out, targets, out_dir, max_png):
+    """PSNR / SSIM of out['images'] against `targets` and the PNG dumps: the tail of evaluate_views."""
+    images = out["images"]
+    V = images.shape[0]
     if targets is not None:
         for v in range(V):
             t = torch.as_tensor(targets[v]).to(images.device).float()

@@ -187,6 +187,21 @@ def sample_pdf(z_vals, weights, N_importance, u=None):
     return smp, union
 
 
+def sample_pdf_sorted(z_vals, weights, N_importance, u=None, out=None):
+    """The new samples (R,Ni) of sample_pdf in ascending order -- the row the kernel merges into the sorted union (equal values keep
+    the order of `u`).  `out`: a contiguous (R,Ni) fp32 tensor to fill."""
+    L.require_gpu()
+    z = L.dev_f32(z_vals)
+    w = L.dev_f32(weights, z.device)
+    R, S = z.shape
+    Ni = int(N_importance)
+    uu, stride = (L.u_row(Ni, z.device), 0) if u is None else (L.dev_f32(u, z.device).reshape(R, Ni), Ni)
+    with torch.cuda.device(z.device):
+        srt = out if out is not None else torch.empty((R, Ni), dtype=torch.float32, device=z.device)
+        L.check(L.lib().nrf_sample_pdf_sorted(L.ptr(z), L.ptr(w), R, S, Ni, L.ptr(uu), stride, None, L.ptr(srt), None, L.stream_ptr()))
+    return srt
+
+
 def get_ray_batch(rays_o, rays_d, batch_size=1024):
     """ray_utils.py:145-174: host-side chunk generator, kept for callers that still chunk
     (the fused renderer does not need it)."""

@@ -8,6 +8,13 @@
 
     python tools/bench_configs.py [--mode bf16] [--reps 5]
 Prints one JSON line per configuration: ms per frame, M ray-samples/s, fraction of the dense MFMA peak.
+
+    python tools/bench_configs.py --hier [--reps 7]
+C3 three ways, the arms alternating frame by frame in one process (f16 and f16x3, the V2 and the V1 network): the three-call
+render_hierarchical (the yardstick), render_hierarchical(reuse_coarse=True), and render_camera_hierarchical.  One JSON line per
+(network, mode): ms per frame of every arm (mean, min, max) and the ratios to the three-call route.
+    python tools/bench_configs.py --hier-profile [--mode f16]
+ONE frame of the camera route and nothing else: the run to put under `rocprofv3 --kernel-trace --stats`.
 """
 import argparse
 import json
@@ -36,13 +43,64 @@ def timed(fn, reps):
     return (time.perf_counter() - t0) / reps
 
 
+def hier_models(mode, dev):
+    v2 = N.NeRFMLP(pos_freq=10, dir_freq=4, hidden_dim=256, num_density_layers=8, use_dino=False, mma_mode=mode)
+    v2.load_state_dict(O.make_weights("v2", 1, "solid"), strict=False)
+    v1 = N.NeRFMLP(pos_dim=63, hidden_dim=256, n_layers=8, mma_mode=mode)
+    v1.load_state_dict(O.make_weights("v1", 0, "solid"))
+    return {"v2": v2.to(dev).eval(), "v1": v1.to(dev).eval()}
+
+
+def hier_arms(reps, dev, c2w):
+    """C3 (800 x 800, 128 + 64) by the three routes, alternating frame by frame; the three-call route is the yardstick."""
+    H, S, Ni = 800, 128, 64
+    ro, rd = N.get_rays(H, H, O.focal_for(H), c2w)
+    ro, rd = ro.reshape(-1, 3), rd.reshape(-1, 3)
+    with torch.no_grad():
+        for mode in ("f16", "f16x3"):
+            for net, model in hier_models(mode, dev).items():
+                arms = {"three_call": lambda: N.render_hierarchical(model, ro, rd, 2.0, 6.0, S, Ni),
+                        "reuse_coarse": lambda: N.render_hierarchical(model, ro, rd, 2.0, 6.0, S, Ni, reuse_coarse=True),
+                        "camera": lambda: N.render_camera_hierarchical(model, H, H, O.focal_for(H), c2w, 2.0, 6.0, S, Ni)}
+                outs = {}
+                for _ in range(2):                   # warm-up of every arm: code objects, clocks, the allocator's blocks
+                    for name, fn in arms.items():
+                        outs[name] = fn()
+                same = (torch.equal(outs["three_call"]["rgb"], outs["reuse_coarse"]["rgb"]) and torch.equal(outs["three_call"]["rgb"], outs["camera"][0])
+                        and torch.equal(outs["three_call"]["depth"], outs["camera"][1]))
+                del outs
+                ms = {name: [] for name in arms}
+                for _ in range(reps):
+                    for name, fn in arms.items():
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        fn()
+                        torch.cuda.synchronize()
+                        ms[name].append((time.perf_counter() - t0) * 1e3)
+                mean = {k: sum(v) / len(v) for k, v in ms.items()}
+                print(json.dumps({"config": "C3 800x800 128 coarse + 64 fine", "net": net, "mode": mode, "reps": reps, "same_image_bits": same,
+                                  "ms_per_frame": {k: {"mean": round(mean[k], 2), "min": round(min(v), 2), "max": round(max(v), 2)} for k, v in ms.items()},
+                                  "reuse_coarse_over_three_call": round(mean["reuse_coarse"] / mean["three_call"], 4),
+                                  "camera_over_three_call": round(mean["camera"] / mean["three_call"], 4),
+                                  "network_evaluations_per_ray": {"three_call": S + S + Ni, "reuse_coarse": S + Ni, "camera": S + Ni}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="bf16", choices=["bf16", "f16", "f32", "f16x3"])
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--hier", action="store_true", help="C3 by the three hierarchical routes, alternating (f16 and f16x3, V2 and V1)")
+    ap.add_argument("--hier-profile", action="store_true", help="one C3 frame of the camera route (V2, --mode) and nothing else")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     c2w = torch.from_numpy(O.LEGO_LIKE_C2W.copy())
+    if args.hier:
+        return hier_arms(args.reps, dev, c2w)
+    if args.hier_profile:
+        with torch.no_grad():
+            N.render_camera_hierarchical(hier_models(args.mode, dev)["v2"], 800, 800, O.focal_for(800), c2w, 2.0, 6.0, 128, 64)
+            torch.cuda.synchronize()
+        return None
     v2 = N.NeRFMLP(pos_freq=10, dir_freq=4, hidden_dim=256, num_density_layers=8, use_dino=False, mma_mode=args.mode)
     v2.load_state_dict(O.make_weights("v2", 1, "solid"), strict=False)
     v2 = v2.to(dev).eval()
