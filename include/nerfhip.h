@@ -738,6 +738,25 @@ int nrf_composite_loss_backward_indexed(const float* rgb, int rgb_stride, const 
                                         float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride,
                                         float* ray_terms, float* zero_buf, int64_t zero_n, void* stream);
 
+/* nrf_mlp_forward_train_rays on a compacted sample list: the ray route's front end under a grid.  Row j < n_rows of out_a / out_b
+ * and of the saved context is sample index[j] = r*S + s of the ray batch (nrf_compact.index), derived exactly as
+ * nrf_mlp_forward_train_rays derives its row r*S + s: the ray from rays_o / rays_d or from the pixel id and the camera, the position
+ * o + d*z by the same single fp32 operations, the V1 encoding in the kernel, the NRF_NET_V3 feature map gathered in both fusion
+ * passes -- except that the depth is READ from rays->z_vals (R,S), where nrf_occupancy_compact_rays has left the ladder, and is not
+ * drawn again.  The call writes none of the nrf_train_rays outputs (z_vals, rays_d_out, points_out); no encodings, positions,
+ * directions or per-sample features pass through memory.  The context is the ordinary one of
+ * nrf_train_context_bytes(m, mode, n_rows) or larger; nrf_mlp_backward_v1 / nrf_mlp_backward / nrf_mlp_backward_dino run on it with
+ * n = n_rows.  Of `opts` the call reads n_samples, mma_mode and dino (NRF_NET_V3); the sampling fields are checked as
+ * nrf_mlp_forward_train_rays checks them and otherwise unused.
+ * An index entry outside [0, n_rays * n_samples) is the caller's error: the behaviour is undefined (the kernel reads z_vals and the
+ * ray arrays at it unchecked).
+ * NRF_EINVAL, before any launch: index NULL or not 4-byte aligned, n_rows < 0 or n_rows > n_rays * n_samples, a missing
+ * rays->z_vals, a context too small for n_rows, and everything nrf_mlp_forward_train_rays refuses.  n_rows == 0 succeeds and
+ * launches nothing.  Additive to ABI 5. */
+int nrf_mlp_forward_train_rays_indexed(nrf_model* m, const nrf_train_rays* rays, int64_t n_rays, const nrf_render_opts* opts,
+                                       const int32_t* index, int64_t n_rows, float* out_a, float* out_b, void* ctx,
+                                       int64_t ctx_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -235,6 +235,9 @@ SIGNATURES = {
     "nrf_composite_loss_backward_indexed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                                       C.c_void_p, C.POINTER(nrf_loss_opts), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                                       C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    # the ray-input saving forward on the compacted rows: the ray route's front end under a grid
+    "nrf_mlp_forward_train_rays_indexed": (C.c_int, [C.c_void_p, C.POINTER(nrf_train_rays), C.c_int64, C.POINTER(nrf_render_opts), C.c_void_p,
+                                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 _lib = None

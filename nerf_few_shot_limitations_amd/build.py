@@ -38,7 +38,12 @@ OCC = [(f"fused_occ_{fam}.hip", f"fused_occ_{fam}_{half}", flags) for fam in ("v
 OBJ_HIER = os.path.join(OBJ, "hier")
 HIER = [(f"fused_emit_{fam}.hip", f"hier/fused_emit_{fam}_{half}", flags) for fam in ("v1", "v2", "v3", "v3w") for half, flags in (("16", HALF16), ("32", HALF32))]
 HIER += [("hier_kernels.hip", "hier/hier_kernels", [])]
-SOURCES = FUSED + OCC + HIER + TAIL + [(f, os.path.splitext(f)[0], []) for f in
+# The ray-input saving forward on a compacted sample list (train_impl.hpp: IndexedRayInputs), one unit per family with the flags of
+# its train_v* sibling; a directory of its own for the reason OBJ_HIER has one -- kernel_resources(OBJ_RAYS_INDEXED), held to the
+# *_rays_kernel siblings by tests/test_train_occupancy_rays_host.py.
+OBJ_RAYS_INDEXED = os.path.join(OBJ, "rays_indexed")
+RAYS_INDEXED = [(f"train_rays_indexed_{fam}.hip", f"rays_indexed/train_rays_indexed_{fam}", []) for fam in ("v1", "v2", "v3")]
+SOURCES = FUSED + OCC + HIER + RAYS_INDEXED + TAIL + [(f, os.path.splitext(f)[0], []) for f in
                    ("fused_kernels.hip", "train_shared.hip", "train_v1.hip", "train_v2.hip", "train_v3.hip", "train_dino_grad.hip", "train_input_grad.hip", "train_input_grad_v3.hip", "staged_kernels.hip", "api.cpp",
                     "packing.cpp")]
 # -Rpass-analysis=kernel-resource-usage: the backend reports every kernel's registers / spills / scratch; kept beside the object
@@ -89,6 +94,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(deps):
         return LIB
     os.makedirs(OBJ_HIER, exist_ok=True)
+    os.makedirs(OBJ_RAYS_INDEXED, exist_ok=True)
 
     def one(item):
         src, name, flags = item

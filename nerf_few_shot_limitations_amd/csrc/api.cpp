@@ -912,6 +912,53 @@ int nrf_mlp_forward_train_rays(nrf_model* m, const nrf_train_rays* rays, int64_t
     });
 }
 
+int nrf_mlp_forward_train_rays_indexed(nrf_model* m, const nrf_train_rays* rays, int64_t n_rays, const nrf_render_opts* opts, const int32_t* index,
+                                       int64_t n_rows, float* out_a, float* out_b, void* ctx, int64_t ctx_bytes, void* stream) {
+    // the order of nrf_mlp_forward_train_rays, with the row list behind the ray source
+    if (!rays) return fail(NRF_EINVAL, "nrf_mlp_forward_train_rays_indexed: rays is NULL");
+    if (rays->struct_bytes != (int32_t)sizeof(nrf_train_rays)) return fail(NRF_EINVAL, "nrf_train_rays: struct_bytes is not sizeof(nrf_train_rays)");
+    if (n_rays < 0) return fail(NRF_EINVAL, "nrf_mlp_forward_train_rays_indexed: n_rays < 0");
+    const int rc = check_opts(opts);
+    if (rc != NRF_OK) return rc;
+    if (opts->ert_eps > 0.0f) return fail(NRF_EINVAL, "nrf_mlp_forward_train_rays_indexed takes ert_eps == 0: a training step evaluates every kept sample");
+    const bool by_rays = rays->rays_o || rays->rays_d, by_pixels = rays->pixels != nullptr;
+    if (by_rays == by_pixels) return fail(NRF_EINVAL, "nrf_train_rays: give either rays_o and rays_d or pixels, not both and not neither");
+    if (by_rays && (!rays->rays_o || !rays->rays_d)) return fail(NRF_EINVAL, "nrf_train_rays: rays_o and rays_d come together");
+    if (by_pixels && (rays->H < 1 || rays->W < 1 || !(rays->focal > 0.0f))) return fail(NRF_EINVAL, "nrf_train_rays: bad camera for the pixels");
+    if (!rays->z_vals) return fail(NRF_EINVAL, "nrf_mlp_forward_train_rays_indexed: rays->z_vals is required (the depths nrf_occupancy_compact_rays left there)");
+    if (by_pixels && !rays->rays_d_out) return fail(NRF_EINVAL, "nrf_train_rays: output rays_d_out is required in pixel mode");
+    const int64_t n = (int64_t)opts->n_samples * n_rays;
+    if (n > (int64_t)INT32_MAX) return fail(NRF_EINVAL, "ray-sample count too large (n_rays * n_samples < 2^31)");
+    if (!index) return fail(NRF_EINVAL, "nrf_mlp_forward_train_rays_indexed: index is NULL");
+    if ((reinterpret_cast<uintptr_t>(index) & 3u) != 0) return fail(NRF_EINVAL, "nrf_mlp_forward_train_rays_indexed: index must be 4-byte aligned");
+    if (n_rows < 0) return fail(NRF_EINVAL, "nrf_mlp_forward_train_rays_indexed: n_rows < 0");
+    if (n_rows > n) return fail(NRF_EINVAL, "nrf_mlp_forward_train_rays_indexed: n_rows exceeds n_rays * n_samples");
+    if (!m) return fail(NRF_EINVAL, "model is NULL");
+    const int mode = opts->mma_mode == NRF_MMA_F16X3 ? NRF_MMA_F32 : opts->mma_mode;      // the split mode trains in exact fp32
+    const bool v1 = m->arch.net == NRF_NET_V1;
+    nrf::TrainRaysDev r{};
+    std::string derr;
+    if (m->arch.net == NRF_NET_V3 && !make_dino(opts->dino, m->arch.dino_dim, r.dino, derr))
+        return fail(NRF_EINVAL, "nrf_mlp_forward_train_rays_indexed: " + derr);
+    if (n_rows == 0) return NRF_OK;
+    r.rays_o = rays->rays_o; r.rays_d = rays->rays_d; r.pixels = rays->pixels;
+    if (by_pixels) r.cam = make_camera(rays->H, rays->W, rays->focal, rays->c2w);
+    r.lad = nrf::make_ladder(opts->near, opts->far, opts->n_samples, opts->lindisp, opts->z_ladder);      // the kernel takes S from it, no depth
+    r.z_vals = rays->z_vals;                                                                             // read, never written
+    auto wrong = [&]() -> const char* {
+        if (v1 && out_b) return "nrf_mlp_forward_train_rays_indexed: a V1 model writes out_a (n_rows,4) alone, out_b must be NULL";
+        return nullptr;
+    };
+    return train_entry(m, mode, n_rows, !out_a || (!v1 && !out_b) || !ctx, ctx_bytes, false, wrong, [&](std::string& err) {
+        hipStream_t s = (hipStream_t)stream;
+        switch (m->arch.net) {
+            case NRF_NET_V1: return nrf::launch_train_forward_rays_indexed_v1(m->net, m->train, mode, r, index, n_rows, out_a, ctx, s, err);
+            case NRF_NET_V3: return nrf::launch_train_forward_rays_indexed_v3(m->net, m->train, mode, r, index, n_rows, out_a, out_b, ctx, s, err);
+            default:         return nrf::launch_train_forward_rays_indexed_v2(m->net, m->train, mode, r, index, n_rows, out_a, out_b, ctx, s, err);
+        }
+    });
+}
+
 int nrf_composite_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals, const float* rays_d,
                            int64_t n_rays, int n_samples, int white_bkgd, const float* g_rgb, const float* g_depth, const float* g_weights,
                            float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, void* stream) {

@@ -176,6 +176,14 @@ int launch_train_forward_rays_v2(const DeviceNet& net, const TrainDev& t, int mm
                                  float* density, void* ctx, hipStream_t s, std::string& err);
 int launch_train_forward_rays_v3(const DeviceNet& net, const TrainDev& t, int mma_mode, const TrainRaysDev& r, int64_t n, float* rgb,
                                  float* density, void* ctx, hipStream_t s, std::string& err);
+// the same on a compacted sample list (train_impl.hpp: IndexedRayInputs): row j < n_rows is sample index[j] of the ray batch, its depth is
+// read from r.z_vals, and none of r's outputs is written
+int launch_train_forward_rays_indexed_v1(const DeviceNet& net, const TrainDev& t, int mma_mode, const TrainRaysDev& r, const int32_t* index,
+                                         int64_t n_rows, float* out4, void* ctx, hipStream_t s, std::string& err);
+int launch_train_forward_rays_indexed_v2(const DeviceNet& net, const TrainDev& t, int mma_mode, const TrainRaysDev& r, const int32_t* index,
+                                         int64_t n_rows, float* rgb, float* density, void* ctx, hipStream_t s, std::string& err);
+int launch_train_forward_rays_indexed_v3(const DeviceNet& net, const TrainDev& t, int mma_mode, const TrainRaysDev& r, const int32_t* index,
+                                         int64_t n_rows, float* rgb, float* density, void* ctx, hipStream_t s, std::string& err);
 // V3, after launch_train_backward_v3 on the same context: d_dino (n, dino_dim) = dL/d per-sample DINO features
 int launch_dino_grad(const DeviceNet& net, const TrainDev& t, int mma_mode, int64_t n, void* ctx, float* d_dino, hipStream_t s, std::string& err);
 // V1 / V2, after the family's launch_train_backward* on the same context: dL/d encoded inputs (V1), positions, directions (V2); a NULL

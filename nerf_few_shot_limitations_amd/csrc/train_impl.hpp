@@ -52,12 +52,21 @@ struct TrainRayKArgs : TrainKArgs {
     TrainRaysDev rays;
 };
 
+// the ray-input forward on compacted rows: row j < n is sample index[j] of the ray batch (strictly inside it: the caller's duty)
+struct TrainRayIndexKArgs : TrainRayKArgs {
+    const int32_t* index;
+};
+
 // The input source of the saving forward bodies (their last template argument; train_forward*_body, instantiated by the kernel
 // pairs *_kernel / *_rays_kernel).  StagedInputs: the caller's per-sample tensors
 // (x_enc | pos, dir, dino), as nrf_mlp_forward_train* documents them.  RayInputs: rays (or a camera and pixel ids) in P.rays;
 // RaySample below derives what the staged tensors would have held.
-struct StagedInputs { static constexpr bool kRays = false; typedef TrainKArgs KArgs; };
-struct RayInputs { static constexpr bool kRays = true; typedef TrainRayKArgs KArgs; };
+// IndexedRayInputs: RayInputs on a compacted sample list (nerfhip.h: nrf_mlp_forward_train_rays_indexed) -- row j of the outputs and
+// of the context is sample P.index[j] of the ray batch, its depth is read back from rays.z_vals (the compaction left it there), and
+// the kernel stores none of the ray source's outputs.
+struct StagedInputs { static constexpr bool kRays = false, kIndexed = false; typedef TrainKArgs KArgs; };
+struct RayInputs { static constexpr bool kRays = true, kIndexed = false; typedef TrainRayKArgs KArgs; };
+struct IndexedRayInputs { static constexpr bool kRays = true, kIndexed = true; typedef TrainRayIndexKArgs KArgs; };
 
 // ---- host-side helpers shared by the training translation units ---------------------------------------------
 constexpr int kWgSamples = 256;          // the context is laid out for whole 256-sample groups, whatever the geometry
@@ -156,6 +165,27 @@ inline bool check_train_common(const DeviceNet& net, const TrainDev& t, int mode
     return true;
 }
 
+// the family checks of the chain launchers (train_v*.hip and the indexed ray forwards beside them)
+inline bool check_train_v1(const DeviceNet& net, const TrainDev& t, int mode, std::string& err) {
+    if (!check_train_common(net, t, mode, err)) return false;
+    if (net.arch.net != NRF_NET_V1) { err = "nrf_mlp_*_train_v1 needs a V1 model"; return false; }
+    return true;
+}
+inline bool check_train_v2(const DeviceNet& net, const TrainDev& t, int mode, std::string& err) {
+    if (!check_train_common(net, t, mode, err)) return false;
+    if (net.arch.net != NRF_NET_V2 || net.arch.dir_freq != 4) { err = "nrf_mlp_forward_train / nrf_mlp_backward need a V2 model with dir_freq 4"; return false; }
+    return true;
+}
+inline bool check_train_v3(const DeviceNet& net, const TrainDev& t, int mode, std::string& err) {
+    if (!check_train_common(net, t, mode, err)) return false;
+    if (net.arch.net != NRF_NET_V3 || net.arch.dir_freq != 4 || (net.arch.dino_dim != 64 && net.arch.dino_dim != 128)) {
+        err = "V3 training needs dir_freq 4 and dino_dim 64 or 128";
+        return false;
+    }
+    if (net.arch.n_layers > 8) { err = "V3 training: at most 8 trunk layers (saved-tensor slot table)"; return false; }
+    return true;
+}
+
 // dW/db of every Linear from the saved tensors (defined in train_shared.hip; network independent)
 int launch_weight_grad(const DeviceNet& net, const TrainDev& t, int mode, const TrainKArgs& k, float* grad, hipStream_t s, std::string& err);
 
@@ -191,6 +221,14 @@ struct RaySample {
         if (!R.perturb) return ladder_z(R.lad, s);
         const float u = R.t_rand ? R.t_rand[sid] : counter_uniform(R.seed, (uint64_t)ray, (uint32_t)s);
         return ladder_z_jitter(R.lad, s, u);
+    }
+    // the position of a sample whose depth the compaction has left in z_vals (IndexedRayInputs): nothing drawn, nothing stored
+    __device__ __forceinline__ void position_kept(const TrainRaysDev& R, int64_t sid, float (&p)[3]) const {
+        float o[3], d[3];
+        origin_dir(R, o, d);
+        const float z = R.z_vals[sid];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k] = point_on_ray(o[k], d[k], z);
     }
     // the sample's position; `writer` lanes (lane half 0 of a real sample) leave z_vals, points_out and, at s == 0, rays_d_out
     __device__ __forceinline__ void position(const TrainRaysDev& R, int64_t sid, bool writer, float (&p)[3]) const {
@@ -335,10 +373,11 @@ struct ChainTile {
 
     // V2 / V3 colour branch on the trunk output X (nets.hpp:NetV2::tail with stores): density_head, feature_head, PE(dir),
     // colour layers 0 / 2 / 4, with the bias of density_head at boff; write_rgb_density() stores the results.  Src: the kernel's
-    // input source -- the sample's direction is row sid of P.dir or that of its ray in *rays.
+    // input source -- the sample's direction is row sid of P.dir or that of its ray in *rays (IndexedRayInputs: of sample index[sid],
+    // asked for again here rather than held through the trunk, as the ray is).
     template <int LD, class Src = StagedInputs>
     __device__ __forceinline__ void colour_forward(const ColourSlots& cs, const Tiles& X, int boff, float& dens_raw, float (&logit)[3],
-                                                   const TrainRaysDev* rays = nullptr) {
+                                                   const TrainRaysDev* rays = nullptr, const int32_t* index = nullptr) {
         {
             f32x16 dens[1];
             dense_head<Mode, 8, 1>(pipe, bias + boff, h, X, dens);
@@ -348,7 +387,9 @@ struct ChainTile {
         linear<8>(X, in9, cs.in(), boff + 32);
         {
             float dd[3];
-            if constexpr (Src::kRays) {
+            if constexpr (Src::kIndexed) {
+                RaySample(*rays, index[sid]).dir(*rays, dd);
+            } else if constexpr (Src::kRays) {
                 RaySample(*rays, sid).dir(*rays, dd);
             } else {
 #pragma unroll
@@ -446,7 +487,10 @@ int run_chain(const DeviceNet& net, const TrainDev& t, int mode, typename Src::K
     if (!fill_slots(t, mode, n, k, err)) return NRF_EINVAL;
     const int r = dispatch_chain(net, mode, n, [&](auto g) {
         typedef decltype(g) G;
-        if constexpr (FORWARD && Src::kRays)
+        if constexpr (FORWARD && Src::kIndexed)
+            return launch_persistent<F::template forward_indexed<G>, G::kWaves>(net, net_args(net, mode), k, tiles32(n) / G::kWaves, s,
+                                                                                "train forward (indexed rays)", err);
+        else if constexpr (FORWARD && Src::kRays)
             return launch_persistent<F::template forward_rays<G>, G::kWaves>(net, net_args(net, mode), k, tiles32(n) / G::kWaves, s,
                                                                              "train forward (rays)", err);
         else if constexpr (FORWARD)
@@ -473,7 +517,12 @@ __device__ __forceinline__ void train_forward_body(const typename Src::KArgs& P)
         Act A[8][1], B[8][1];
         if constexpr (Src::kRays) {                              // the encoding of the fused renderer's V1 (nets.hpp:encode3) in place of a (n,63) tensor
             float p[3];
-            RaySample(P.rays, T.sid).position(P.rays, T.sid, h == 0 && T.raw < P.n, p);
+            if constexpr (Src::kIndexed) {
+                const int64_t id = P.index[T.sid];
+                RaySample(P.rays, id).position_kept(P.rays, id, p);
+            } else {
+                RaySample(P.rays, T.sid).position(P.rays, T.sid, h == 0 && T.raw < P.n, p);
+            }
             Act e1[KT0], enc[KT0][1];
             encode3<Mode, LP>(p, h, e1);
 #pragma unroll
@@ -522,6 +571,11 @@ __global__ void __launch_bounds__(WAVES * 64) train_forward_kernel(const TrainKA
 template <class Mode, int WAVES, int LP>
 __global__ void __launch_bounds__(WAVES * 64) train_forward_rays_kernel(const TrainRayKArgs P) {
     train_forward_body<Mode, WAVES, LP, RayInputs>(P);
+}
+
+template <class Mode, int WAVES, int LP>
+__global__ void __launch_bounds__(WAVES * 64) train_forward_rays_indexed_kernel(const TrainRayIndexKArgs P) {
+    train_forward_body<Mode, WAVES, LP, IndexedRayInputs>(P);
 }
 
 // ---------------------------------------------------------------------------------------------

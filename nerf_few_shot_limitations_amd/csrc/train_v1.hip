@@ -6,11 +6,7 @@ namespace nrf {
 namespace {
 
 struct V1 {
-    static bool check(const DeviceNet& net, const TrainDev& t, int mode, std::string& err) {
-        if (!check_train_common(net, t, mode, err)) return false;
-        if (net.arch.net != NRF_NET_V1) { err = "nrf_mlp_*_train_v1 needs a V1 model"; return false; }
-        return true;
-    }
+    static bool check(const DeviceNet& net, const TrainDev& t, int mode, std::string& err) { return check_train_v1(net, t, mode, err); }
     template <class G> static constexpr auto forward = train_forward_kernel<typename G::Mode, G::kWaves, 10>;
     template <class G> static constexpr auto forward_rays = train_forward_rays_kernel<typename G::Mode, G::kWaves, 10>;
     template <class G> static constexpr auto backward = train_backward_kernel<typename G::Mode, G::kWaves, 10>;

@@ -6,11 +6,7 @@ namespace nrf {
 namespace {
 
 struct V2 {
-    static bool check(const DeviceNet& net, const TrainDev& t, int mode, std::string& err) {
-        if (!check_train_common(net, t, mode, err)) return false;
-        if (net.arch.net != NRF_NET_V2 || net.arch.dir_freq != 4) { err = "nrf_mlp_forward_train / nrf_mlp_backward need a V2 model with dir_freq 4"; return false; }
-        return true;
-    }
+    static bool check(const DeviceNet& net, const TrainDev& t, int mode, std::string& err) { return check_train_v2(net, t, mode, err); }
     template <class G> static constexpr auto forward = train_forward_v2_kernel<typename G::Mode, G::kWaves, 10, 4>;
     template <class G> static constexpr auto forward_rays = train_forward_v2_rays_kernel<typename G::Mode, G::kWaves, 10, 4>;
     template <class G> static constexpr auto backward = train_backward_v2_kernel<typename G::Mode, G::kWaves, 10>;

@@ -13,13 +13,18 @@ __device__ __forceinline__ void train_forward_v2_body(const typename Src::KArgs&
     typedef typename Mode::Act Act;
     constexpr int KT0 = pe_tiles(LP);
     const TrainRaysDev* rays = nullptr;
+    const int32_t* index = nullptr;
     if constexpr (Src::kRays) rays = &P.rays;
+    if constexpr (Src::kIndexed) index = P.index;
     chain_kernel<Mode, WAVES, true>(P, [&](ChainTile<Mode, WAVES>& T) {
         const SlotsV2 S{P.net.n_layers};
         Act A[8][1], B[8][1];
         {
             float p[3];
-            if constexpr (Src::kRays) {
+            if constexpr (Src::kIndexed) {
+                const int64_t id = P.index[T.sid];
+                RaySample(P.rays, id).position_kept(P.rays, id, p);
+            } else if constexpr (Src::kRays) {
                 RaySample(P.rays, T.sid).position(P.rays, T.sid, T.h == 0 && T.raw < P.n, p);
             } else {
 #pragma unroll
@@ -36,7 +41,7 @@ __device__ __forceinline__ void train_forward_v2_body(const typename Src::KArgs&
         }
         float dens_raw = 0.0f, logit[3];
         int boff = 32 * 8;
-        T.trunk_forward(S, 1, S.n, A, B, boff, [&](const Act (&X)[8][1]) { T.template colour_forward<LD, Src>(S.colour(), X, boff, dens_raw, logit, rays); });
+        T.trunk_forward(S, 1, S.n, A, B, boff, [&](const Act (&X)[8][1]) { T.template colour_forward<LD, Src>(S.colour(), X, boff, dens_raw, logit, rays, index); });
         T.write_rgb_density(dens_raw, logit);
     });
 }
@@ -49,6 +54,11 @@ __global__ void __launch_bounds__(WAVES * 64) train_forward_v2_kernel(const Trai
 template <class Mode, int WAVES, int LP, int LD>
 __global__ void __launch_bounds__(WAVES * 64) train_forward_v2_rays_kernel(const TrainRayKArgs P) {
     train_forward_v2_body<Mode, WAVES, LP, LD, RayInputs>(P);
+}
+
+template <class Mode, int WAVES, int LP, int LD>
+__global__ void __launch_bounds__(WAVES * 64) train_forward_v2_rays_indexed_kernel(const TrainRayIndexKArgs P) {
+    train_forward_v2_body<Mode, WAVES, LP, LD, IndexedRayInputs>(P);
 }
 
 template <class Mode, int WAVES, int LP>

@@ -8,15 +8,7 @@ namespace {
 // DT = dino_dim / 32 operand tiles of per-sample features
 template <int DT>
 struct V3 {
-    static bool check(const DeviceNet& net, const TrainDev& t, int mode, std::string& err) {
-        if (!check_train_common(net, t, mode, err)) return false;
-        if (net.arch.net != NRF_NET_V3 || net.arch.dir_freq != 4 || (net.arch.dino_dim != 64 && net.arch.dino_dim != 128)) {
-            err = "V3 training needs dir_freq 4 and dino_dim 64 or 128";
-            return false;
-        }
-        if (net.arch.n_layers > 8) { err = "V3 training: at most 8 trunk layers (saved-tensor slot table)"; return false; }
-        return true;
-    }
+    static bool check(const DeviceNet& net, const TrainDev& t, int mode, std::string& err) { return check_train_v3(net, t, mode, err); }
     template <class G> static constexpr auto forward = train_forward_v3_kernel<typename G::Mode, G::kWaves, 12, 4, DT>;
     template <class G> static constexpr auto forward_rays = train_forward_v3_rays_kernel<typename G::Mode, G::kWaves, 12, 4, DT>;
     template <class G> static constexpr auto backward = train_backward_v3_kernel<typename G::Mode, G::kWaves, 12, DT>;

@@ -60,12 +60,17 @@ __device__ __forceinline__ void train_forward_v3_body(const typename Src::KArgs&
     typedef typename Mode::Act Act;
     constexpr int PT = pe_tiles(LP), KT0 = PT + DT;
     const TrainRaysDev* rays = nullptr;
+    const int32_t* index = nullptr;
     if constexpr (Src::kRays) rays = &P.rays;
+    if constexpr (Src::kIndexed) index = P.index;
     chain_kernel<Mode, WAVES, true>(P, [&](ChainTile<Mode, WAVES>& T) {
         const SlotsV3 S{P.net.n_layers};
         const int h = T.h;
         float p[3];
-        if constexpr (Src::kRays) {
+        if constexpr (Src::kIndexed) {
+            const int64_t id = P.index[T.sid];
+            RaySample(P.rays, id).position_kept(P.rays, id, p);
+        } else if constexpr (Src::kRays) {
             RaySample(P.rays, T.sid).position(P.rays, T.sid, h == 0 && T.raw < P.n, p);
         } else {
 #pragma unroll
@@ -146,7 +151,7 @@ __device__ __forceinline__ void train_forward_v3_body(const typename Src::KArgs&
         boff += 32 * 8;
 
         float dens_raw = 0.0f, logit[3];
-        T.trunk_forward(S, 0, S.n, A, B, boff, [&](const Act (&X)[8][1]) { T.template colour_forward<LD, Src>(S.colour(), X, boff, dens_raw, logit, rays); });
+        T.trunk_forward(S, 0, S.n, A, B, boff, [&](const Act (&X)[8][1]) { T.template colour_forward<LD, Src>(S.colour(), X, boff, dens_raw, logit, rays, index); });
         T.write_rgb_density(dens_raw, logit);
     });
 }
@@ -159,6 +164,11 @@ __global__ void __launch_bounds__(WAVES * 64) train_forward_v3_kernel(const Trai
 template <class Mode, int WAVES, int LP, int LD, int DT>
 __global__ void __launch_bounds__(WAVES * 64) train_forward_v3_rays_kernel(const TrainRayKArgs P) {
     train_forward_v3_body<Mode, WAVES, LP, LD, DT, RayInputs>(P);
+}
+
+template <class Mode, int WAVES, int LP, int LD, int DT>
+__global__ void __launch_bounds__(WAVES * 64) train_forward_v3_rays_indexed_kernel(const TrainRayIndexKArgs P) {
+    train_forward_v3_body<Mode, WAVES, LP, LD, DT, IndexedRayInputs>(P);
 }
 
 template <class Mode, int WAVES, int LP, int DT>

@@ -2,7 +2,7 @@
         [--recipe train|multiscale] [--epochs N] [--mode bf16|f16|f32] [--eval-mode f16] [--out DIR] [--checkpoint CKPT]
         [--dino-weights DIR | --dino-maps maps.pt] [--train-extractor] [--fused-inputs] [--seed 0]
         [--occupancy-res N [--occupancy-box LO HI] [--occupancy-threshold T] [--occupancy-decay D] [--occupancy-refresh-every K]
-         [--occupancy-cells-per-refresh C] [--occupancy-warmup STEPS]]
+         [--occupancy-cells-per-refresh C] [--occupancy-warmup STEPS] [--occupancy-per-view]]
 
 The training run of `NeRFDINOTrainer` (src/training/train.py:244-292 `train_step`, :344-372 `train`) as a command on the
 HIP path: the YAML loads unchanged; per epoch and training view the rays are cast at the progressive schedule's
@@ -60,6 +60,17 @@ a step reads 8 bytes back from the device.  Refused: a use_dino config (a V3 gri
 condition on the view they came from), --train-extractor (no per-sample gradients are handed out under a grid), and any
 --occupancy-* flag without --occupancy-res.  The grid is not part of a checkpoint: a resumed run starts again from the all-ones
 grid and its warm-up.
+
+--occupancy-per-view (with --occupancy-res, use_dino configs only) lifts the first two refusals: the trainer keeps ONE grid per
+training view (`PerViewOccupancy`: an OccupancySchedule each -- bits, per-cell values, refresh cursor and count, and a step counter
+with its own warm-up, counted in batches of that view).  A batch of view v is one `FusedStep.step_view(occupancy=grid v,
+grid_inputs="rays")` -- the compaction, then the ray-input saving forward on the kept rows (nrf_mlp_forward_train_rays_indexed), which
+gathers view v's map itself -- and after the step grid v is refreshed with `dino=` that view's current map.  With --train-extractor the
+batches also take `d_dino_out` / `points_out` under the grid: their first `last_count` rows are the kept samples, which is what
+`ExtractorTrainer.add_batch` receives (nothing when no sample was kept).  Refused for use_dino: false (a V1 or V2 field does not
+depend on the view: the single grid serves) and without --occupancy-res.  UNLIKE the single grid, the per-view grids ARE part of a
+checkpoint (`occupancy_per_view_state`) and --checkpoint restores them, warm-up counters included.  --data-parallel works as with the
+single grid: every rank refreshes from the same parameters and seeds, so the grids agree; with --train-extractor it stays refused.
 
 --checkpoint resumes a run: weights, Adam moments and step count, epoch counter and best PSNR (the reference's train.py saves
 these keys, :374-389, but has no resume path); the LR schedule is a function of the epoch.  wandb and LPIPS are not part of
@@ -158,16 +169,23 @@ def occupancy_args_error(args, cfg):
     Decided before any GPU work."""
     res = int(getattr(args, "occupancy_res", 0) or 0)
     given = [f for f in OCCUPANCY_FLAGS if getattr(args, f, None) is not None]
+    per_view = bool(getattr(args, "occupancy_per_view", False))
+    use_dino = bool((cfg.get("model", {}) or {}).get("use_dino", True))
+    if per_view and res == 0:
+        return "--occupancy-per-view needs --occupancy-res N (N > 0): without a grid the flag would be ignored"
+    if per_view and not use_dino:
+        return ("--occupancy-per-view: this config has use_dino: false -- such a field does not depend on the view, the single grid of "
+                "--occupancy-res serves every batch")
     if res == 0:
         if given:
             return "--" + given[0].replace("_", "-") + " needs --occupancy-res N (N > 0): without a grid the flag would be ignored"
         return None
     if res < 32 or res > 512 or res % 32:
         return "--occupancy-res must be a multiple of 32 in 32..512 (0: off)"
-    if bool((cfg.get("model", {}) or {}).get("use_dino", True)):
+    if use_dino and not per_view:
         return ("--occupancy-res: this config has use_dino: true -- a grid of such a field belongs to ONE source view, the batches of a run "
                 "condition on the view they came from")
-    if getattr(args, "train_extractor", False):
+    if getattr(args, "train_extractor", False) and not per_view:
         return "--occupancy-res with --train-extractor is refused: a step under a grid hands out no per-sample gradients"
     box = args.occupancy_box
     if box is not None and not (box[0] < box[1]):
@@ -188,9 +206,10 @@ class OccupancySchedule:
     """The grid side of --occupancy-res: the all-ones grid of the warm-up, the live grid `OccupancyGrid.refresh` keeps up to date, and
     the step counter that decides between them and when to refresh."""
 
-    def __init__(self, res, box=(-1.5, 1.5), threshold=0.01, decay=0.95, refresh_every=16, cells_per_refresh=None, warmup=256, device=None):
+    def __init__(self, res, box=(-1.5, 1.5), threshold=0.01, decay=0.95, refresh_every=16, cells_per_refresh=None, warmup=256, device=None,
+                 full=None):
         from .occupancy import OccupancyGrid
-        self.full = OccupancyGrid.full(res, box[0], box[1], device=device)
+        self.full = full if full is not None else OccupancyGrid.full(res, box[0], box[1], device=device)      # (never written: may be shared)
         self.grid = OccupancyGrid.full(res, box[0], box[1], device=device)
         self.threshold, self.decay, self.refresh_every, self.warmup = float(threshold), float(decay), int(refresh_every), int(warmup)
         self.cells = int(cells_per_refresh) if cells_per_refresh else max(32, self.grid.n_cells // 16 // 32 * 32)
@@ -207,10 +226,65 @@ class OccupancySchedule:
         """The grid of the next step: all ones until the warm-up is over."""
         return self.full if self.steps < self.warmup else self.grid
 
-    def after_step(self, model):
+    def after_step(self, model, dino=None):
+        """dino: the source view of a use_dino model's grid (OccupancyGrid.refresh)."""
         self.steps += 1
         if self.steps % self.refresh_every == 0:
-            self.grid.refresh(model, decay=self.decay, threshold=self.threshold, cells=self.cells)
+            self.grid.refresh(model, decay=self.decay, threshold=self.threshold, cells=self.cells, dino=dino)
+
+    def state_dict(self):
+        """What a resumed run needs of the live grid: its bits, the per-cell values (None before the first refresh), the round-robin
+        cursor, the refresh count (the seed of the next probe points) and the step counter of the warm-up."""
+        g = self.grid
+        ema = getattr(g, "ema", None)
+        return {"bits": g.bits.detach().cpu().clone(), "ema": None if ema is None else ema.detach().cpu().clone(),
+                "cursor": int(getattr(g, "_cursor", 0)), "refreshes": int(getattr(g, "_refreshes", 0)), "steps": int(self.steps)}
+
+    def load_state_dict(self, sd):
+        g = self.grid
+        if sd["bits"].dtype != torch.int32 or sd["bits"].numel() != g.bits.numel():
+            raise ValueError("occupancy state: the checkpoint's grid has another resolution")
+        g.bits.copy_(sd["bits"].to(g.bits.device))
+        if sd["ema"] is None:
+            g.ema = None
+        else:
+            g.ema = sd["ema"].to(device=g.bits.device, dtype=torch.float32).clone()
+        g._cursor, g._refreshes = int(sd["cursor"]), int(sd["refreshes"])
+        self.steps = int(sd["steps"])
+
+
+class PerViewOccupancy:
+    """The grid side of --occupancy-per-view: one OccupancySchedule per training view -- the grid of a use_dino field belongs to the
+    source view it is conditioned on -- sharing one all-ones grid for their warm-ups."""
+
+    def __init__(self, n_views, res, device=None, **kw):
+        self.views = []
+        for _ in range(int(n_views)):
+            self.views.append(OccupancySchedule(res, device=device, full=self.views[0].full if self.views else None, **kw))
+
+    @classmethod
+    def from_args(cls, args, n_views, device):
+        kw = {k: v for k, v in dict(box=args.occupancy_box, threshold=args.occupancy_threshold, decay=args.occupancy_decay,
+                                    refresh_every=args.occupancy_refresh_every, cells_per_refresh=args.occupancy_cells_per_refresh,
+                                    warmup=args.occupancy_warmup).items() if v is not None}
+        return cls(n_views, args.occupancy_res, device=device, **kw)
+
+    def view(self, v):
+        return self.views[v]
+
+    @property
+    def occupied_fraction(self):
+        """Mean over the views of the fraction of occupied cells in the grid their next step runs under."""
+        return sum(s.current().occupied_fraction for s in self.views) / max(len(self.views), 1)
+
+    def state_dict(self):
+        return {"views": [s.state_dict() for s in self.views]}
+
+    def load_state_dict(self, sd):
+        if len(sd["views"]) != len(self.views):
+            raise ValueError("occupancy state: the checkpoint holds grids for another number of training views")
+        for s, d in zip(self.views, sd["views"]):
+            s.load_state_dict(d)
 
 
 class ExtractorTrainer:
@@ -264,7 +338,8 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
     fused_inputs: every batch is one `step.step_view` on its pixel ids (--fused-inputs; module docstring) instead of torch gathers,
     sample_points_along_rays, the expanded directions and fetch_features in front of `step(...)`.
     occupancy: an OccupancySchedule (--occupancy-res; module docstring) -- the fused_inputs route with `occupancy=` its current grid,
-    and a refresh of the grid when one is due.
+    and a refresh of the grid when one is due; or a PerViewOccupancy (--occupancy-per-view): view v's batches step under view v's grid
+    with grid_inputs="rays", use_dino models and a trained extractor included.
     extractor: an ExtractorTrainer (--train-extractor; module docstring) -- the view's map comes from it, live, instead of
     dino_maps[v], and it takes one step per view.
     draws: the epoch's random draws as inputs (parity runs against a recorded run of the reference's trainer): an object whose
@@ -277,8 +352,11 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
     Ht, Wt, S, batch = schedule_for(cfg, epoch)
     model = step.model
     use_dino = model.net == L.NRF_NET_V3
+    per_view = isinstance(occupancy, PerViewOccupancy)
     if occupancy is not None:
-        if use_dino or extractor is not None:
+        if per_view and not use_dino:
+            raise ValueError("per-view occupancy grids belong to use_dino models: the other fields do not depend on the view")
+        if not per_view and (use_dino or extractor is not None):
             raise ValueError("training under an occupancy grid is not combined with use_dino models or a trained extractor")
         fused_inputs = True
     total, n_batches, samples = None, 0, 0
@@ -293,6 +371,7 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
         view_map = extractor.begin_view(v) if extractor is not None else (dino_maps[v:v + 1] if use_dino else None)
         dino = make_dino(view_map, poses[v], focal, H, W) if use_dino else None                 # train.py:204-206: full-resolution intrinsics
         cam = dict(features=view_map, pose=poses[v], focal=focal, H=H, W=W)
+        sched = occupancy.view(v) if per_view else occupancy
         if draws is None:
             order = torch.randperm(n_view, device=dev_v, generator=gen)
         else:
@@ -313,12 +392,16 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
                         pts_buf = torch.empty((n * S, 3), dtype=torch.float32, device=tgt.device)
                     kw.update(d_dino_out=d_feats, points_out=pts_buf[:n * S])
                 if occupancy is not None:
-                    kw["occupancy"] = occupancy.current()
+                    kw["occupancy"] = sched.current()
+                if per_view:
+                    kw["grid_inputs"] = "rays"
                 loss = step.step_view(None, c2w, Ht, Wt, f_t, idx, near, far, S, perturb=True, t_rand=t_rand, **kw)
                 if occupancy is not None:
-                    occupancy.after_step(model)
+                    sched.after_step(model, dino=cam if per_view else None)
                 if extractor is not None:
-                    extractor.add_batch(cam, pts_buf[:n * S], d_feats)
+                    rows = step.last_count if per_view else n * S          # under a grid: the kept samples, as dense rows
+                    if rows:
+                        extractor.add_batch(cam, pts_buf[:rows], d_feats[:rows])
                 total = loss if total is None else total + loss
                 n_batches += 1
                 samples += n * S
@@ -364,10 +447,11 @@ def step_options(cfg, recipe="train"):
     return kw
 
 
-def save_checkpoint(path, model, step, epoch, best_psnr, cfg, recipe="train", extractor=None):
+def save_checkpoint(path, model, step, epoch, best_psnr, cfg, recipe="train", extractor=None, occupancy=None):
     """train.py:374-389's dictionary: `nerf_model_state_dict` is what evaluate.py:27 / load_checkpoint_into read; the multiscale
     recipe adds train_multiscale.py:368-376's `nerf_state_dict` (the same tensors); --train-extractor adds
-    `dino_model_state_dict` (train.py:384) and the extractor optimizer's state."""
+    `dino_model_state_dict` (train.py:384) and the extractor optimizer's state; --occupancy-per-view (a PerViewOccupancy) adds
+    `occupancy_per_view_state`.  The single grid of --occupancy-res is not saved."""
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     opt = step.opt
     o = cfg["optimizer"]
@@ -381,6 +465,7 @@ def save_checkpoint(path, model, step, epoch, best_psnr, cfg, recipe="train", ex
                 "scheduler_state_dict": {"last_epoch": epoch + 1, "milestones": list(o["lr_milestones"]), "gamma": float(o["lr_gamma"])},
                 **({"dino_model_state_dict": {k: v.detach().cpu().clone() for k, v in extractor.extractor.state_dict().items()},
                     "dino_optimizer_state_dict": extractor.opt.state_dict()} if extractor is not None else {}),
+                **({"occupancy_per_view_state": occupancy.state_dict()} if isinstance(occupancy, PerViewOccupancy) else {}),
                 "config": cfg}, path)
 
 
@@ -431,6 +516,9 @@ def main(argv=None):
     ap.add_argument("--occupancy-refresh-every", type=int, default=None, metavar="K", help="refresh the grid every K steps (default 16)")
     ap.add_argument("--occupancy-cells-per-refresh", type=int, default=None, help="cells probed per refresh, a multiple of 32 (default: 1/16 of the grid)")
     ap.add_argument("--occupancy-warmup", type=int, default=None, metavar="STEPS", help="steps under an all-ones grid first (default 256)")
+    ap.add_argument("--occupancy-per-view", action="store_true",
+                    help="use_dino configs: one grid per training view, stepped with grid_inputs=\"rays\" and saved in the checkpoint "
+                         "(module docstring); needs --occupancy-res")
     ap.add_argument("--max-test-views", type=int, default=None)
     ap.add_argument("--max-batches", type=int, default=None, help="stop every epoch after this many ray batches (smoke runs)")
     ap.add_argument("--seed", type=int, default=0)
@@ -506,8 +594,13 @@ def main(argv=None):
                      **({"seed": args.seed} if args.recipe == "multiscale" else {}))
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed)
-    # (not part of a checkpoint: a resumed run starts again from the all-ones grid and its warm-up)
-    occ = OccupancySchedule.from_args(args, dev) if args.occupancy_res else None
+    # (the single grid is not part of a checkpoint: a resumed run starts again from the all-ones grid and its warm-up; the per-view
+    # grids are)
+    occ = None
+    if args.occupancy_res:
+        occ = PerViewOccupancy.from_args(args, len(images), dev) if args.occupancy_per_view else OccupancySchedule.from_args(args, dev)
+    if ckpt is not None and isinstance(occ, PerViewOccupancy) and "occupancy_per_view_state" in ckpt:
+        occ.load_state_dict(ckpt["occupancy_per_view_state"])
     best, log, first_epoch = 0.0, [], 0
     if ckpt is not None:
         first_epoch, best = resume_from(ckpt, model, step)
@@ -524,7 +617,7 @@ def main(argv=None):
         dt = time.perf_counter() - t0
         rec = {"epoch": epoch + 1, "loss": loss, "lr": step.opt.lr, "seconds": round(dt, 3), "Msamples_per_s": round(world * samples / dt / 1e6, 2)}
         if occ is not None:
-            rec["occupied_fraction"] = round(occ.current().occupied_fraction, 4)
+            rec["occupied_fraction"] = round(occ.occupied_fraction if args.occupancy_per_view else occ.current().occupied_fraction, 4)
         if rank != 0:                                                         # every rank holds the same parameters: rank 0 validates and writes
             log.append(rec)
             continue
@@ -537,9 +630,9 @@ def main(argv=None):
             rec.update(psnr=m["psnr"], ssim=m["ssim"])
             if m["psnr"] > best:
                 best = m["psnr"]
-                save_checkpoint(os.path.join(out_dir, f"best_{name}.pth"), model, step, epoch, best, cfg, args.recipe, ext)
+                save_checkpoint(os.path.join(out_dir, f"best_{name}.pth"), model, step, epoch, best, cfg, args.recipe, ext, occ)
         if (epoch + 1) % int(cfg["output"]["save_freq"]) == 0:
-            save_checkpoint(os.path.join(out_dir, f"epoch_{epoch + 1}.pth"), model, step, epoch, best, cfg, args.recipe, ext)
+            save_checkpoint(os.path.join(out_dir, f"epoch_{epoch + 1}.pth"), model, step, epoch, best, cfg, args.recipe, ext, occ)
         log.append(rec)
         print(json.dumps(rec), flush=True)
     if rank == 0:

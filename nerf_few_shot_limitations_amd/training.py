@@ -1112,7 +1112,7 @@ class FusedStep:
     # ---- the same step from rays: sampling, encoding and the feature fetch happen inside the saving forward ----------------
     @torch.no_grad()
     def step_rays(self, rays_o, rays_d, target, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False, z_in=None,
-                  dino=None, target_depth=None, noise=None, d_dino_out=None, points_out=None, occupancy=None):
+                  dino=None, target_depth=None, noise=None, d_dino_out=None, points_out=None, occupancy=None, grid_inputs="staged"):
         """One step on rays (R,3) and their target (R,3): what train.py:188-229 builds in front of the network -- stratified
         samples, per-sample directions, projected DINO features, encodings -- is derived inside the forward kernel
         (nrf_mlp_forward_train_rays), so no per-sample input tensor exists.  Depths, points and therefore (V2) every bit of the step
@@ -1133,24 +1133,32 @@ class FusedStep:
         occupancy (an occupancy.OccupancyGrid): the step under the grid -- the plain step with every sample in an empty cell
         composited as colour 0 and effective density -inf (behind the density noise), and the network, its backward and the weight
         gradients run on the M occupied samples alone (_grid_forward).  UNLIKE THE PLAIN STEP IT SYNCHRONISES ONCE: the 8 bytes of
-        M are read back between the compaction and the network.  `last_count` holds M.  Not combined with d_dino_out / points_out."""
+        M are read back between the compaction and the network.  `last_count` holds M.  Not combined with d_dino_out / points_out
+        on the default route.
+
+        grid_inputs (only with occupancy=): "staged" (default) feeds the M compacted points to the staged saving forward (V1:
+        through nrf_encode, V3: through nrf_project_fetch); "rays" keeps the ray route's front end under the grid
+        (nrf_mlp_forward_train_rays_indexed: ray, position, encoding and feature gather derived in the kernel for row index[j]).
+        With "rays" d_dino_out and points_out are accepted: rows [0, M) of both hold the compacted samples in ascending flat-id
+        order (the compaction writes its positions straight into points_out), rows >= M are not written."""
         o = L.dev_f32(rays_o).reshape(-1, 3)
         d = L.dev_f32(rays_d, o.device).reshape(-1, 3)
         if d.shape != o.shape:
             raise ValueError("rays_o and rays_d must both be (R,3)")
         return self._ray_step(o.shape[0], o.device, lambda z, d_out, p_out: L.train_rays(rays_o=L.ptr(o), rays_d=L.ptr(d), z_vals=z, points_out=p_out), d,
                               target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise, d_dino_out, points_out,
-                              occupancy)
+                              occupancy, grid_inputs)
 
     @torch.no_grad()
     def step_view(self, image, pose, H, W, focal, pixels, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False,
-                  z_in=None, dino=None, target_depth=None, noise=None, d_dino_out=None, points_out=None, target=None, occupancy=None):
+                  z_in=None, dino=None, target_depth=None, noise=None, d_dino_out=None, points_out=None, target=None, occupancy=None,
+                  grid_inputs="staged"):
         """step_rays on pixels of a pinhole view: `pixels` is an int64 device tensor of ray ids y*W+x of get_rays(H, W, focal, pose),
         whose origins and directions the kernel computes itself.  The target is `target` (R,3) if given, otherwise
         image.reshape(-1,3)[pixels] of the (H,W,3) image: one torch gather.  The jitter of a ray is keyed by its position in
         `pixels`, not by the pixel id: the step equals step_rays on the gathered rays to the bit.  `pose` may also be the 12 floats
         `ray_sampler._c2w12` made of it (as `dino` may be `make_dino`'s pair): nothing is converted per batch then.  occupancy: as in
-        step_rays (one 8-byte read-back per step)."""
+        step_rays (one 8-byte read-back per step), and so is grid_inputs."""
         if not (isinstance(pixels, torch.Tensor) and pixels.is_cuda and pixels.dtype == torch.int64 and pixels.dim() == 1):
             raise ValueError("pixels must be a 1-d int64 tensor of ray ids on the GPU")
         pix = pixels.contiguous()
@@ -1166,16 +1174,21 @@ class FusedStep:
                               lambda z, d_out, p_out: L.train_rays(pixels=pix.data_ptr(), H=H, W=W, focal=focal, c2w=c2w, z_vals=z, rays_d_out=d_out,
                                                                    points_out=p_out),
                               None, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise, d_dino_out, points_out,
-                              occupancy)
+                              occupancy, grid_inputs)
 
     def _ray_step(self, R, dev, make_rays, d, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise,
-                  d_dino_out, points_out, occupancy=None):
+                  d_dino_out, points_out, occupancy=None, grid_inputs="staged"):
         """__call__'s sequence with nrf_mlp_forward_train_rays in front -- or, under an occupancy grid, _grid_forward; d is the
         caller's (R,3) directions or None (pixel mode: the kernel writes them for the compositor)."""
         from .renderer import _opts, make_dino
+        if grid_inputs not in ("staged", "rays"):
+            raise ValueError('grid_inputs must be "staged" or "rays"')
+        if occupancy is None and grid_inputs != "staged":
+            raise ValueError("grid_inputs chooses the route of a step under a grid: pass occupancy= with it")
+        by_rays = grid_inputs == "rays"
         if occupancy is not None:
             from .occupancy import OccupancyGrid
-            if d_dino_out is not None or points_out is not None:
+            if not by_rays and (d_dino_out is not None or points_out is not None):
                 raise ValueError("occupancy is not combined with d_dino_out / points_out: the step under a grid hands out no per-sample gradients")
             if not isinstance(occupancy, OccupancyGrid):
                 raise TypeError("occupancy must be an occupancy.OccupancyGrid")
@@ -1212,7 +1225,7 @@ class FusedStep:
             *out, heads = _heads(self.out4, n, v1)
             *d_out, d_heads = _heads(self.d_out4, n, v1)
             if occupancy is not None:
-                rows, slot = self._grid_forward(rays, R, S, dev, opts, occupancy, dn, h, mode, out, ctx, st), self._slot
+                rows, slot = self._grid_forward(rays, R, S, dev, opts, occupancy, dn, h, mode, out, ctx, st, by_rays, points_out), self._slot
             else:
                 L.check(lib.nrf_mlp_forward_train_rays(h, C.byref(rays), R, C.byref(opts), L.ptr(out[0]), L.ptr(out[1]), ctx, self.nbytes, st))
                 rows, slot = n, None
@@ -1222,7 +1235,7 @@ class FusedStep:
                 self._network_backward(h, mode, rows, out, d_out, ctx, st, d_dino_out)
             return self._finish(multi, R, S, dev, target_depth, st)
 
-    def _grid_forward(self, rays, R, S, dev, opts, occupancy, dn, h, mode, out, ctx, st):
+    def _grid_forward(self, rays, R, S, dev, opts, occupancy, dn, h, mode, out, ctx, st, by_rays=False, points_out=None):
         """The saving forward of the step under an occupancy grid (nerfhip.h: nrf_occupancy_compact_rays); returns M.  The step:
 
             compact -> read M back -> [V1: encode | V3: project + fetch] of the M points -> saving forward on M rows
@@ -1233,26 +1246,37 @@ class FusedStep:
         step allocates.  The read-back of M (8 bytes) is the step's ONLY synchronisation and the one thing the plain step does not
         have: the launches behind it are sized by M on the host.  M == 0 is a valid step: the network launches nothing, the
         prediction is the background, the gradient is zero and the optimiser still steps.  With an all-ones grid every bit of the
-        step is the plain step's (V2), or __call__'s on the staged points (V1: nrf_encode; V3: nrf_project_fetch)."""
+        step is the plain step's (V2), or __call__'s on the staged points (V1: nrf_encode; V3: nrf_project_fetch).
+
+        by_rays (grid_inputs="rays"): the bracket is gone -- the saving forward is nrf_mlp_forward_train_rays_indexed on the M rows of
+        `index`, which derives every row from the ray source as the plain ray step does and reads neither the compacted positions
+        nor directions.  The compaction still has to leave its positions somewhere: in points_out when the caller passed one.  With
+        an all-ones grid every bit of the step is the plain ray step's, for all three families."""
         m, lib, n = self.model, L.lib(), R * S
         v1, v3 = m.net == L.NRF_NET_V1, m.net == L.NRF_NET_V3
         if getattr(self, "_grid_key", None) != self._key:
             self._index = torch.empty((n,), dtype=torch.int32, device=dev)
             self._slot = torch.empty((n,), dtype=torch.int32, device=dev)
             self._pos = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            self._dirs = None if v1 else torch.empty((n, 3), dtype=torch.float32, device=dev)
-            self._enc = torch.empty((n, 3 * (2 * m.pos_freq + 1)), dtype=torch.float32, device=dev) if v1 else None
-            self._feats = torch.empty((n, m.dino_dim), dtype=torch.float32, device=dev) if v3 else None
+            self._dirs = self._enc = self._feats = None
             self._count = torch.zeros((1,), dtype=torch.int64, device=dev)
             self._cws = torch.empty((int(lib.nrf_occupancy_compact_workspace_bytes(R)),), dtype=torch.uint8, device=dev)
             self._grid_key = self._key
+        if not by_rays and self._dirs is None and self._enc is None:      # the staged route's per-sample inputs, on its first step
+            self._dirs = None if v1 else torch.empty((n, 3), dtype=torch.float32, device=dev)
+            self._enc = torch.empty((n, 3 * (2 * m.pos_freq + 1)), dtype=torch.float32, device=dev) if v1 else None
+            self._feats = torch.empty((n, m.dino_dim), dtype=torch.float32, device=dev) if v3 else None
         occ, occ_keep = occupancy.struct(dev)
-        cp = L.compact(n, self._index.data_ptr(), self._slot.data_ptr(), L.ptr(self._pos), L.ptr(self._dirs), self._count.data_ptr(),
+        pos = points_out if by_rays and points_out is not None else self._pos
+        cp = L.compact(n, self._index.data_ptr(), self._slot.data_ptr(), L.ptr(pos), None if by_rays else L.ptr(self._dirs), self._count.data_ptr(),
                        self._cws.data_ptr(), self._cws.numel())
         L.check(lib.nrf_occupancy_compact_rays(C.byref(rays), R, C.byref(opts), C.byref(occ), C.byref(cp), st))
         M = int(self._count.item())         # the step's only synchronisation: 8 bytes
         self.last_count = M
-        if M:
+        if M and by_rays:
+            L.check(lib.nrf_mlp_forward_train_rays_indexed(h, C.byref(rays), R, C.byref(opts), self._index.data_ptr(), M, L.ptr(out[0]), L.ptr(out[1]),
+                                                           ctx, self.nbytes, st))
+        elif M:
             if v1:
                 L.check(lib.nrf_encode(L.ptr(self._pos), M, 3, m.pos_freq, 1, None, L.ptr(self._enc), st))
                 L.check(lib.nrf_mlp_forward_train_v1(h, mode, L.ptr(self._enc), M, L.ptr(out[0]), ctx, self.nbytes, st))
