@@ -20,32 +20,26 @@ OBJ = os.path.join(PKG, "build")
 LIB = os.path.join(PKG, "libnerfhip.so")
 INCLUDE = os.path.join(os.path.dirname(PKG), "include")
 
-# The fused renderer / forward of every network family is compiled twice (fused_impl.hpp, NRF_TU_HALF): once for the 16-bit
+# Every kind of the fused renderer / forward of every network family is compiled twice (fused_impl.hpp, NRF_TU_HALF): once for the 16-bit
 # MFMA modes -- with VGPR-form MFMAs, so that the pinned walk can park finished operand images in the AGPR half of the register
 # file (mlp_core.hpp NRF_PARK_ACT) -- and once for the fp32-class modes (split-f16, fp32 MFMA) with hipcc's own choice.
 HALF16 = ["-DNRF_TU_HALF=16", "-DNRF_ACT_AGPR=1", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 HALF32 = ["-DNRF_TU_HALF=32"]
-FUSED = [(f"fused_{fam}.hip", f"fused_{fam}_{half}", flags) for fam in ("v1", "v2", "v3", "v3w") for half, flags in (("16", HALF16), ("32", HALF32))]
-# tail mode (fused_impl.hpp: render_march): the last-sample kernels of all four families, split-f16 only
-TAIL = [("fused_tail.hip", "fused_tail", HALF32)]
-# empty-space skipping (fused_impl.hpp: render_queue_occ_kernel): units of their own, both halves with the flags of their fused_v* siblings
-OCC = [(f"fused_occ_{fam}.hip", f"fused_occ_{fam}_{half}", flags) for fam in ("v1", "v2", "v3", "v3w") for half, flags in (("16", HALF16), ("32", HALF32))]
-# The hierarchical render that evaluates only the new samples: the renderer that also emits each sample's raw head outputs
-# (fused_impl.hpp: render_emit_kernel; both halves with the flags of their fused_v* siblings) and its staged kernels (hier_kernels.hip).
-# Their objects and remarks go to a directory of their own, OBJ_HIER: tests/golden/kernel_resources.json is a closed census of the
-# kernels in OBJ (tests/test_train_occupancy_host.py allows no name beside it), so kernels added since are reported per directory --
-# kernel_resources(OBJ_HIER) -- and held to their bars by their own tests (tests/test_hier_reuse_host.py).
-OBJ_HIER = os.path.join(OBJ, "hier")
-HIER = [(f"fused_emit_{fam}.hip", f"hier/fused_emit_{fam}_{half}", flags) for fam in ("v1", "v2", "v3", "v3w") for half, flags in (("16", HALF16), ("32", HALF32))]
-HIER += [("hier_kernels.hip", "hier/hier_kernels", [])]
-# The ray-input saving forward on a compacted sample list (train_impl.hpp: IndexedRayInputs), one unit per family with the flags of
-# its train_v* sibling; a directory of its own for the reason OBJ_HIER has one -- kernel_resources(OBJ_RAYS_INDEXED), held to the
-# *_rays_kernel siblings by tests/test_train_occupancy_rays_host.py.
-OBJ_RAYS_INDEXED = os.path.join(OBJ, "rays_indexed")
-RAYS_INDEXED = [(f"train_rays_indexed_{fam}.hip", f"rays_indexed/train_rays_indexed_{fam}", []) for fam in ("v1", "v2", "v3")]
-SOURCES = FUSED + OCC + HIER + RAYS_INDEXED + TAIL + [(f, os.path.splitext(f)[0], []) for f in
-                   ("fused_kernels.hip", "train_shared.hip", "train_v1.hip", "train_v2.hip", "train_v3.hip", "train_dino_grad.hip", "train_input_grad.hip", "train_input_grad_v3.hip", "staged_kernels.hip", "api.cpp",
-                    "packing.cpp")]
+# The instantiations of the fused renderer are one source, fused_inst.hip, compiled once per (kind, family, half): -DNRF_KIND picks the
+# body, -DNRF_FAMILY the row of the family table (fused_impl.hpp: NRF_FAMILIES -- FAMILIES names its rows), the half's flags the modes.
+# An occ or emit object carries the half flags of its fused_<family> sibling.  Tail mode's last-sample kernels (split-f16 only) are one
+# object for all four families (-DNRF_FAMILY=all).  A new family is a row there and a name here; a new kind a body there and a row of KINDS.
+FAMILIES = ("v1", "v2", "v3", "v3w")
+HALVES = (("16", HALF16), ("32", HALF32))
+# kind: (object name stem, per family and half?)
+KINDS = {"plain": ("fused", True), "occ": ("fused_occ", True), "emit": ("fused_emit", True), "tail": ("fused_tail", False)}
+FUSED = [("fused_inst.hip", f"{stem}_{fam}_{half}", [*flags, f"-DNRF_KIND={kind}", f"-DNRF_FAMILY={fam}"])
+         for kind, (stem, split) in KINDS.items() if split for fam in FAMILIES for half, flags in HALVES]
+FUSED += [("fused_inst.hip", stem, [*HALF32, f"-DNRF_KIND={kind}", "-DNRF_FAMILY=all"]) for kind, (stem, split) in KINDS.items() if not split]
+SOURCES = FUSED + [(f, os.path.splitext(f)[0], []) for f in
+                   ("fused_kernels.hip", "hier_kernels.hip", "train_rays_indexed_v1.hip", "train_rays_indexed_v2.hip", "train_rays_indexed_v3.hip",
+                    "train_shared.hip", "train_v1.hip", "train_v2.hip", "train_v3.hip", "train_dino_grad.hip", "train_input_grad.hip",
+                    "train_input_grad_v3.hip", "staged_kernels.hip", "api.cpp", "packing.cpp")]
 # -Rpass-analysis=kernel-resource-usage: the backend reports every kernel's registers / spills / scratch; kept beside the object
 # (<name>.o.remarks, see kernel_resources()) so that a toolchain or flag change that breaks the AGPR parking or introduces
 # spills in a headline kernel is caught by tests/test_kernel_resources.py
@@ -93,8 +87,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     # source, header and this file
     if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(deps):
         return LIB
-    os.makedirs(OBJ_HIER, exist_ok=True)
-    os.makedirs(OBJ_RAYS_INDEXED, exist_ok=True)
+    os.makedirs(OBJ, exist_ok=True)
 
     def one(item):
         src, name, flags = item

@@ -626,26 +626,31 @@ int launch_persistent(const DeviceNet& net, const NetArgs& na, KArgs k, int64_t 
     return NRF_OK;
 }
 
+// The set-up the persistent render launches share: the arguments, and the deal (pick_deal) of the rays over the `n_samples` samples
+// the launch marches.  Returns the launch's work items.
+template <int NT, int WAVES>
+int64_t deal_render(const DeviceNet& net, const RenderArgs& a, int n_samples, RenderKArgs& k) {
+    k.a = a;
+    const Deal d = pick_deal(a.n_rays, n_samples, WAVES, 32 * NT, net.cu_count);
+    k.a.spw_log2 = d.spw_log2;
+    k.even = d.even;
+    return d.items;
+}
+
 template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
 int run_render_v(const DeviceNet& net, int mode, const RenderArgs& a, hipStream_t s, std::string& err) {
     RenderKArgs k;
-    k.a = a;
-    const Deal d = pick_deal(a.n_rays, a.n_samples, WAVES, 32 * NT, net.cu_count);
-    k.a.spw_log2 = d.spw_log2;
-    k.even = d.even;
-    return launch_persistent<render_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, d.items, s, "render", err);
+    const int64_t items = deal_render<NT, WAVES>(net, a, a.n_samples, k);
+    return launch_persistent<render_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, items, s, "render", err);
 }
 
 // the emitting renderer: render_kernel's launch and deal, raw4 behind its arguments
 template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
 int run_render_emit(const DeviceNet& net, int mode, const RenderArgs& a, float* raw4, hipStream_t s, std::string& err) {
     EmitKArgs k;
-    k.a = a;
     k.raw4 = raw4;
-    const Deal d = pick_deal(a.n_rays, a.n_samples, WAVES, 32 * NT, net.cu_count);
-    k.a.spw_log2 = d.spw_log2;
-    k.even = d.even;
-    return launch_persistent<render_emit_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, d.items, s, "render (emitting)", err);
+    const int64_t items = deal_render<NT, WAVES>(net, a, a.n_samples, k);
+    return launch_persistent<render_emit_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, items, s, "render (emitting)", err);
 }
 
 // tail mode, first launch (16-bit geometry): samples 0 .. S-2 of every ray, compositor state -> carry.  The split is picked for the
@@ -653,12 +658,9 @@ int run_render_emit(const DeviceNet& net, int mode, const RenderArgs& a, float* 
 template <class Net, class Mode, int NT, int WAVES, int LP, int LD>
 int run_render_hold(const DeviceNet& net, int mode, const RenderArgs& a, float* carry, hipStream_t s, std::string& err) {
     RenderKArgs k;
-    k.a = a;
     k.carry = carry;
-    const Deal d = pick_deal(a.n_rays, a.n_samples - 1, WAVES, 32 * NT, net.cu_count);
-    k.a.spw_log2 = d.spw_log2;
-    k.even = d.even;
-    return launch_persistent<render_hold_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, d.items,
+    const int64_t items = deal_render<NT, WAVES>(net, a, a.n_samples - 1, k);
+    return launch_persistent<render_hold_kernel<Net, Mode, NT, WAVES, LP, LD>, WAVES, kLdsBytesQueue>(net, net_args(net, mode), k, items,
                                                                                                       s, "render (tail mode, prefix)", err);
 }
 
@@ -750,8 +752,8 @@ bool check_net(const DeviceNet& net, int mode, std::string& err) {
 //     twice per pass -- is latency one wave per SIMD cannot cover: profiles/r02_ab_v3_geometry.txt).
 //   * fp32 and split-f16: 4 waves x 32 columns (their activations take 16 registers per tile).
 // The images are bit-identical across geometries: a column's arithmetic does not depend on where it sits.
-// Each family's translation unit is compiled twice (build.py): NRF_TU_HALF == 16 holds the two 16-bit modes (VGPR-form MFMAs,
-// operand images parked in AGPRs), NRF_TU_HALF == 32 the fp32-class modes; fused_kernels.hip routes by mode.
+// Every kind of every family (fused_inst.hip) is compiled twice (build.py): NRF_TU_HALF == 16 holds the two 16-bit modes (VGPR-form
+// MFMAs, operand images parked in AGPRs), NRF_TU_HALF == 32 the fp32-class modes; NRF_DECLARE_HALVES below routes by mode.
 #if !defined(NRF_TU_HALF)
 // (fused_kernels.hip: routing only, no kernels)
 #elif NRF_TU_HALF == 16
@@ -761,13 +763,7 @@ bool check_net(const DeviceNet& net, int mode, std::string& err) {
         case NRF_MMA_BF16: return FN<NETT(ModeBF16, 2), ModeBF16, 2, 4, LP, 4>(__VA_ARGS__);          \
         default:           return FN<NETT(ModeF16, 2), ModeF16, 2, 4, LP, 4>(__VA_ARGS__);            \
     }
-// the tail mode's prefix launch exists in the 16-bit half only
-#define NRF_DEFINE_HOLD(fam, NETT, LP)                                                                                              \
-    int render_hold_##fam##_16(const DeviceNet& net, int mode, const RenderArgs& a, float* carry, hipStream_t s, std::string& err) { \
-        NRF_DISPATCH_MODE(run_render_hold, NETT, LP, net, mode, a, carry, s, err)                                                   \
-    }
 #else
-#define NRF_DEFINE_HOLD(fam, NETT, LP)
 #define NRF_TU_NAME(f) f##_32
 #define NRF_DISPATCH_MODE(FN, NETT, LP, ...)                                                         \
     switch (mode) {                                                                                   \
@@ -780,36 +776,34 @@ bool check_net(const DeviceNet& net, int mode, std::string& err) {
 #define NRF_NET_V3_12_64(M, NT) NetV3<M, NT, 12, 2>
 #define NRF_NET_V3_12_128(M, NT) NetV3<M, NT, 12, 4>
 
-// per-family entry points, two translation units each (fused_v1.hip ... fused_v3w.hip x the two halves) so that hipcc builds them in parallel
-#define NRF_DECLARE_FAMILY(fam)                                                                                            \
-    int render_##fam##_16(const DeviceNet& net, int mode, const RenderArgs& a, hipStream_t s, std::string& err);           \
-    int render_##fam##_32(const DeviceNet& net, int mode, const RenderArgs& a, hipStream_t s, std::string& err);           \
-    int forward_##fam##_16(const DeviceNet& net, int mode, ForwardKArgs k, hipStream_t s, std::string& err);               \
-    int forward_##fam##_32(const DeviceNet& net, int mode, ForwardKArgs k, hipStream_t s, std::string& err);               \
-    /* tail mode: the prefix in the 16-bit half of the family's unit, the split-f16 last sample in fused_tail.hip */       \
-    int render_hold_##fam##_16(const DeviceNet& net, int mode, const RenderArgs& a, float* carry, hipStream_t s, std::string& err); \
-    int render_tail_##fam(const DeviceNet& net, const RenderArgs& a, float* carry, hipStream_t s, std::string& err);       \
-    /* empty-space skipping: translation units of their own (fused_occ_v1.hip ... fused_occ_v3w.hip x the two halves) */   \
-    int render_occ_##fam##_16(const DeviceNet& net, int mode, const RenderArgs& a, const OccDev& g, hipStream_t s, std::string& err); \
-    int render_occ_##fam##_32(const DeviceNet& net, int mode, const RenderArgs& a, const OccDev& g, hipStream_t s, std::string& err); \
-    /* the emitting renderer: translation units of their own (fused_emit_v1.hip ... fused_emit_v3w.hip x the two halves) */ \
-    int render_emit_##fam##_16(const DeviceNet& net, int mode, const RenderArgs& a, float* raw4, hipStream_t s, std::string& err); \
-    int render_emit_##fam##_32(const DeviceNet& net, int mode, const RenderArgs& a, float* raw4, hipStream_t s, std::string& err); \
-    inline int render_emit_##fam(const DeviceNet& net, int mode, const RenderArgs& a, float* raw4, hipStream_t s, std::string& err) { \
-        return (mode == NRF_MMA_BF16 || mode == NRF_MMA_F16) ? render_emit_##fam##_16(net, mode, a, raw4, s, err) : render_emit_##fam##_32(net, mode, a, raw4, s, err); \
-    }                                                                                                                      \
-    inline int render_occ_##fam(const DeviceNet& net, int mode, const RenderArgs& a, const OccDev& g, hipStream_t s, std::string& err) { \
-        return (mode == NRF_MMA_BF16 || mode == NRF_MMA_F16) ? render_occ_##fam##_16(net, mode, a, g, s, err) : render_occ_##fam##_32(net, mode, a, g, s, err); \
-    }                                                                                                                      \
-    inline int render_##fam(const DeviceNet& net, int mode, const RenderArgs& a, hipStream_t s, std::string& err) {        \
-        return (mode == NRF_MMA_BF16 || mode == NRF_MMA_F16) ? render_##fam##_16(net, mode, a, s, err) : render_##fam##_32(net, mode, a, s, err); \
-    }                                                                                                                      \
-    inline int forward_##fam(const DeviceNet& net, int mode, ForwardKArgs k, hipStream_t s, std::string& err) {            \
-        return (mode == NRF_MMA_BF16 || mode == NRF_MMA_F16) ? forward_##fam##_16(net, mode, k, s, err) : forward_##fam##_32(net, mode, k, s, err); \
-    }
-NRF_DECLARE_FAMILY(v1)
-NRF_DECLARE_FAMILY(v2)
-NRF_DECLARE_FAMILY(v3)
-NRF_DECLARE_FAMILY(v3w)
+// The family table: X(name, net template macro, LP, then the arch a family serves: net, pos_freq, dino_dim -- 0: any).  Everything per
+// family comes from here: the entry points declared below, family_of (fused_kernels.hip routes by it) and the instantiations of
+// fused_inst.hip, which build.py compiles once per (kind, family, half) with -DNRF_FAMILY=<name> (build.py: FAMILIES lists the names).
+#define NRF_FAMILY_v1(X) X(v1, NRF_NET_V1_10, 10, NRF_NET_V1, 10, 0)
+#define NRF_FAMILY_v2(X) X(v2, NRF_NET_V2_10, 10, NRF_NET_V2, 10, 0)
+#define NRF_FAMILY_v3(X) X(v3, NRF_NET_V3_12_64, 12, NRF_NET_V3, 12, 64)
+#define NRF_FAMILY_v3w(X) X(v3w, NRF_NET_V3_12_128, 12, NRF_NET_V3, 12, 128)
+#define NRF_FAMILIES(X) NRF_FAMILY_v1(X) NRF_FAMILY_v2(X) NRF_FAMILY_v3(X) NRF_FAMILY_v3w(X)
+#define NRF_CAT_(a, b) a##b
+#define NRF_CAT(a, b) NRF_CAT_(a, b)
+
+// An entry point that exists in both halves (fn_16, fn_32: one object each, so that hipcc builds them in parallel), and fn itself,
+// which picks the half by mode.
+#define NRF_DECLARE_HALVES(fn, PARAMS, ARGS) \
+    int fn##_16 PARAMS;                      \
+    int fn##_32 PARAMS;                      \
+    inline int fn PARAMS { return (mode == NRF_MMA_BF16 || mode == NRF_MMA_F16) ? fn##_16 ARGS : fn##_32 ARGS; }
+// A family's entry points by kind (fused_inst.hip defines them).  Tail mode: the prefix exists in the 16-bit half of the plain object
+// only, the split-f16 last sample in fused_tail.
+#define NRF_DECLARE_FAMILY(fam, NETT, LP, NET, PF, DD)                                                                                                \
+    NRF_DECLARE_HALVES(render_##fam, (const DeviceNet& net, int mode, const RenderArgs& a, hipStream_t s, std::string& err), (net, mode, a, s, err))   \
+    NRF_DECLARE_HALVES(forward_##fam, (const DeviceNet& net, int mode, ForwardKArgs k, hipStream_t s, std::string& err), (net, mode, k, s, err))       \
+    NRF_DECLARE_HALVES(render_occ_##fam, (const DeviceNet& net, int mode, const RenderArgs& a, const OccDev& g, hipStream_t s, std::string& err),      \
+                       (net, mode, a, g, s, err))                                                                                                      \
+    NRF_DECLARE_HALVES(render_emit_##fam, (const DeviceNet& net, int mode, const RenderArgs& a, float* raw4, hipStream_t s, std::string& err),         \
+                       (net, mode, a, raw4, s, err))                                                                                                   \
+    int render_hold_##fam##_16(const DeviceNet& net, int mode, const RenderArgs& a, float* carry, hipStream_t s, std::string& err);                    \
+    int render_tail_##fam(const DeviceNet& net, const RenderArgs& a, float* carry, hipStream_t s, std::string& err);
+NRF_FAMILIES(NRF_DECLARE_FAMILY)
 
 }  // namespace nrf

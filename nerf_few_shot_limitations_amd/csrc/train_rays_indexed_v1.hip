@@ -1,5 +1,5 @@
 // train_rays_indexed_v1.hip -- the V1 ray-input saving forward on a compacted sample list (train_impl.hpp: IndexedRayInputs;
-// nerfhip.h: nrf_mlp_forward_train_rays_indexed).  A unit of its own, built into an object directory of its own (build.py).
+// nerfhip.h: nrf_mlp_forward_train_rays_indexed).  A unit of its own (build.py).
 #include "train_impl.hpp"
 
 namespace nrf {

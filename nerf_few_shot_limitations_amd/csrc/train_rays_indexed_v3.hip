@@ -1,6 +1,5 @@
 // train_rays_indexed_v3.hip -- the V3 ray-input saving forward on a compacted sample list, dino_dim 64 / 128 (train_impl.hpp:
-// IndexedRayInputs; nerfhip.h: nrf_mlp_forward_train_rays_indexed).  A unit of its own, built into an object directory of its own
-// (build.py).
+// IndexedRayInputs; nerfhip.h: nrf_mlp_forward_train_rays_indexed).  A unit of its own (build.py).
 #include "train_v3_impl.hpp"
 
 namespace nrf {

@@ -306,6 +306,37 @@ def test_render_link(N, g, net, mode, S, monkeypatch):
     finish(link, f"S={S}")
 
 
+@pytest.mark.parametrize("mode", P.MODES)
+def test_emitting_render_link_at_dino_dim_128(N, g, mode, monkeypatch):
+    """render_emit_kernel of V3 at dino_dim 128 (objects fused_emit_v3w_16 / fused_emit_v3w_32), the one (kind, family) no other GPU
+    test launches: tests/test_gpu_hier_reuse.py emits with V1, V2 and V3 at 64.  300 rays (one full 256-column tile and a ragged one)
+    at 3 explicit depths (odd, more than one): the render's outputs are the plain render's bits, and the emitted rows are the staged
+    forward's outputs sample by sample -- the density in front of the ReLU, and the colour as the compositor reads it out of the row
+    (nrf_composite_merge on one sample, where an open sample weighs exactly 1), torch.equal on every open sample; a sample is open
+    exactly where the staged density is > 0.  The scene opens and closes a fair share of these samples (asserted)."""
+    monkeypatch.delenv("NRF_SPW", raising=False)
+    link, R, S = Link(N, g, "v3w", mode), 300, 3
+    ro, rd = (t[:R].cuda().contiguous() for t in P.frame_rays())
+    z = P.random_depths(R, S).cuda()
+    plain = link.render(ro, rd, S, z_in=z)
+    emit = N.render_rays_emit(link.model, ro, rd, P.NEAR, P.FAR, S, dino=link.src, z_in=z)
+    for k in ("rgb", "depth", "weights", "z_vals"):
+        assert torch.equal(emit[k], plain[k]), k
+    assert torch.equal(emit["z_vals"], z)
+    dirs = rd[:, None, :].expand(-1, S, -1).reshape(-1, 3).contiguous()
+    rgb_f, den_f = link.forward(P.points32(ro, rd, z).cuda().reshape(-1, 3).contiguous(), dirs)
+    rgb_f, den_f = rgb_f.reshape(R, S, 3), den_f.reshape(R, S)
+    raw = emit["raw4"]
+    assert torch.equal(torch.relu(raw[..., 3]).cpu(), den_f)
+    cols = [N.composite_merge(z[:, s:s + 1].contiguous(), raw[:, s:s + 1].contiguous(), rd, mma_mode=mode) for s in range(S)]
+    pr = P.Probe(torch.stack([c["rgb"] for c in cols], 1).cpu(), torch.stack([c["weights"][:, 0] for c in cols], 1).cpu())
+    open_, closed, left = pr.shares()
+    print(f"RECORD emit v3w {mode}: open {open_:.3f} closed {closed:.3f} left out {left:.4f}")
+    assert left <= P.LEFT_OUT_CAP and min(open_, closed) >= P.MIN_SHARE, (open_, closed, left)
+    assert torch.equal(pr.colour[pr.open], rgb_f[pr.open])
+    assert not bool(((pr.open != (den_f > 0)) & ~pr.left_out).any())
+
+
 @pytest.mark.parametrize("S,tag", EVEN_CASES)
 @pytest.mark.parametrize("net,mode", CASES)
 def test_render_link_under_the_even_deal(N, g, net, mode, S, tag, monkeypatch):
