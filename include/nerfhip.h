@@ -757,6 +757,70 @@ int nrf_mlp_forward_train_rays_indexed(nrf_model* m, const nrf_train_rays* rays,
                                        const int32_t* index, int64_t n_rows, float* out_a, float* out_b, void* ctx,
                                        int64_t ctx_bytes, void* stream);
 
+/* ------------------------------------------------------------------------
+ * The hierarchical training step: one network, a coarse and a fine image (NeRF's coarse-to-fine sampling; the render side is
+ * nrf_sample_pdf_sorted / nrf_composite_merge above).  Additive to ABI 5: the struct carries its own size.
+ *   loss = w_coarse * mse(pred_coarse, target) + w_fine * mse(pred_fine, target)
+ * pred_coarse composites the S coarse rows on z_coarse; pred_fine composites the S + Ni rows of both sets in the merged order on
+ * the merged depths.  The merge rule is nrf_sample_pdf's: a coarse depth goes in front of an equal new one, equal new depths keep
+ * their order -- the order of a stable sort of [z_coarse | z_new] -- the interval of a sample runs to the next merged depth, the
+ * last one is 1e10 |d|.  No gradient reaches the depths: the resampling is a constant, as in NeRF.
+ * The sequence between the step's two saving forwards and its two backwards:
+ *   nrf_mlp_forward_train_rays on the S ladder samples -> nrf_composite (the coarse weights) -> nrf_sample_pdf_sorted (Ni new
+ *   depths, ascending) -> nrf_mlp_forward_train_rays with opts->z_in = the new depths, n_samples = Ni, a context of its own
+ *   -> THIS ENTRY -> nrf_mlp_backward* on the coarse context -> nrf_mlp_backward* on the new one (both add into zero_buf)
+ * Each sample is evaluated once forward and once backward: S + Ni network rows per ray.
+ * ------------------------------------------------------------------------ */
+typedef struct nrf_hier_loss {
+    int32_t      struct_bytes;    /* sizeof(nrf_hier_loss): checked by the library */
+    int32_t      white_bkgd;
+    int32_t      rgb_stride;      /* of rgb_* and d_rgb_*: 3, or 4 for [r,g,b,sigma] rows */
+    int32_t      sigma_stride;    /* of sigma_* and d_sigma_*: 1 or 4 */
+    const float* rgb_coarse;      /* the network rows of the coarse samples, (n_rays * S) rows */
+    const float* sigma_coarse;
+    const float* rgb_new;         /* the network rows of the new samples, (n_rays * Ni) rows, laid out the same way */
+    const float* sigma_new;
+    const float* z_coarse;        /* (n_rays, S), ascending */
+    const float* z_new;           /* (n_rays, Ni), ascending (nrf_sample_pdf_sorted: samples_sorted) */
+    const float* rays_d;          /* (n_rays, 3) */
+    const float* target;          /* (n_rays, 3) */
+    float        w_coarse;        /* both >= 0 */
+    float        w_fine;
+    float*       d_rgb_coarse;    /* out: d loss / d rows, the strides of the rows.  Coarse rows receive the coarse term's */
+    float*       d_sigma_coarse;  /*      gradient plus the fine term's (one fp32 addition), new rows the fine term's */
+    float*       d_rgb_new;
+    float*       d_sigma_new;
+    float*       pred_coarse;     /* out, (n_rays, 3), may be NULL */
+    float*       pred_fine;       /* out, (n_rays, 3), may be NULL */
+    float*       ray_loss;        /* out, (n_rays): w_coarse * se_c + w_fine * se_f, se = a ray's squared rgb error; the loss is
+                                     sum(ray_loss) / (3 n_rays): nrf_adam_step_loss with loss_weight = 1 */
+    float*       ray_parts;       /* out, (2, n_rays): se_c | se_f, may be NULL */
+    float*       z_union;         /* out, (n_rays, S + Ni): the merged depths, may be NULL */
+    float*       weights_fine;    /* out, (n_rays, S + Ni): the fine image's weights, may be NULL (costs one more launch) */
+    float*       zero_buf;        /* optional, zero_n floats cleared by the first launch, as in nrf_composite_mse_backward */
+    int64_t      zero_n;
+    void*        workspace;       /* nrf_hier_train_workspace_bytes(n_rays, S, Ni) bytes, 16-byte aligned */
+    int64_t      workspace_bytes;
+} nrf_hier_loss;
+
+/* Bytes of nrf_hier_loss.workspace: the gathered union's rows, their d rows, depths and merge ranks (40 B per sample) and 20 B per
+ * ray, rounded up to 16; -1 for n_rays < 0, n_samples < 1, n_importance < 1 or n_samples + n_importance > 4096. */
+int64_t nrf_hier_train_workspace_bytes(int64_t n_rays, int n_samples, int n_importance);
+
+/* The stage itself.  Four launches on `stream`, five with weights_fine: nrf_composite_mse_backward's kernel on the coarse rows
+ * at weight w_coarse (it clears zero_buf) -> every sample finds its merge rank (coarse a: a + #{new < z_a}, new k: k + #{coarse <= z_k})
+ * by a binary search of the other list and leaves its depth and its row at that place of the workspace -> the same compositor kernel
+ * on the gathered union at weight w_fine -> every sample fetches the fine term's d row from its rank, a new sample stores it, a
+ * coarse sample adds it to the coarse term's.  pred_*, ray_parts, d rows, z_union and weights_fine are therefore the bits of
+ * nrf_composite_mse_backward / nrf_composite on the coarse rows and on the union gathered by a stable sort.  Every element is
+ * written by one thread: no atomics, two runs give the same bits.  Nothing synchronises or allocates.
+ * NRF_EINVAL, before any launch: a NULL, a wrong struct_bytes, n_rays < 0, n_samples < 1, n_importance < 1, n_samples +
+ * n_importance > 4096, strides below 3 / 1, a negative or non-finite weight, a required pointer (rows, depths, rays_d, target, d
+ * rows, ray_loss) that is NULL, any float pointer not 4-byte aligned, zero_n < 0 or zero_n > 0 without zero_buf, a workspace that
+ * is NULL, not 16-byte aligned or too small.  n_rays == 0 is NRF_OK and launches nothing (zero_buf is not cleared: the plain
+ * entry refuses an empty batch, there is no clearing launch to follow). */
+int nrf_composite_hier_loss_backward(const nrf_hier_loss* a, int64_t n_rays, int n_samples, int n_importance, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,31 @@ def compact(capacity=0, index=None, slot=None, positions=None, directions=None, 
     return nrf_compact(C.sizeof(nrf_compact), 0, int(capacity), index, slot, positions, directions, count, workspace, int(workspace_bytes))
 
 
+class nrf_hier_loss(C.Structure):
+    """The arguments of nrf_composite_hier_loss_backward; struct_bytes is filled in by hier_loss()."""
+    _fields_ = [("struct_bytes", C.c_int32), ("white_bkgd", C.c_int32), ("rgb_stride", C.c_int32), ("sigma_stride", C.c_int32),
+                ("rgb_coarse", C.c_void_p), ("sigma_coarse", C.c_void_p), ("rgb_new", C.c_void_p), ("sigma_new", C.c_void_p),
+                ("z_coarse", C.c_void_p), ("z_new", C.c_void_p), ("rays_d", C.c_void_p), ("target", C.c_void_p),
+                ("w_coarse", C.c_float), ("w_fine", C.c_float),
+                ("d_rgb_coarse", C.c_void_p), ("d_sigma_coarse", C.c_void_p), ("d_rgb_new", C.c_void_p), ("d_sigma_new", C.c_void_p),
+                ("pred_coarse", C.c_void_p), ("pred_fine", C.c_void_p), ("ray_loss", C.c_void_p), ("ray_parts", C.c_void_p),
+                ("z_union", C.c_void_p), ("weights_fine", C.c_void_p), ("zero_buf", C.c_void_p), ("zero_n", C.c_int64),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+def hier_loss(**fields):
+    """nrf_hier_loss with its size field set; the pointers are device addresses (ints) or None, everything not named stays 0 / NULL."""
+    a = nrf_hier_loss(struct_bytes=C.sizeof(nrf_hier_loss))
+    for k, v in fields.items():
+        if k not in _HIER_LOSS_FIELDS:
+            raise TypeError(f"nrf_hier_loss has no field {k!r}")
+        setattr(a, k, v)
+    return a
+
+
+_HIER_LOSS_FIELDS = {f for f, _ in nrf_hier_loss._fields_}
+
+
 # name -> (restype, argtypes); tests/test_packing_emulation.py checks this table against include/nerfhip.h
 SIGNATURES = {
     "nrf_abi_version": (C.c_int, []),
@@ -238,6 +263,9 @@ SIGNATURES = {
     # the ray-input saving forward on the compacted rows: the ray route's front end under a grid
     "nrf_mlp_forward_train_rays_indexed": (C.c_int, [C.c_void_p, C.POINTER(nrf_train_rays), C.c_int64, C.POINTER(nrf_render_opts), C.c_void_p,
                                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    # the hierarchical training step: the stage between its two saving forwards and its two backwards
+    "nrf_hier_train_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "nrf_composite_hier_loss_backward": (C.c_int, [C.POINTER(nrf_hier_loss), C.c_int64, C.c_int, C.c_int, C.c_void_p]),
 }
 
 _lib = None

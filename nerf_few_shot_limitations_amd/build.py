@@ -40,6 +40,12 @@ SOURCES = FUSED + [(f, os.path.splitext(f)[0], []) for f in
                    ("fused_kernels.hip", "hier_kernels.hip", "train_rays_indexed_v1.hip", "train_rays_indexed_v2.hip", "train_rays_indexed_v3.hip",
                     "train_shared.hip", "train_v1.hip", "train_v2.hip", "train_v3.hip", "train_dino_grad.hip", "train_input_grad.hip",
                     "train_input_grad_v3.hip", "staged_kernels.hip", "api.cpp", "packing.cpp")]
+# Units built into a sub-directory of the object directory: (source, object name, flags, sub-directory) -- the object, its .d, .cmd and
+# .remarks live there, the object is linked into the same library.  kernel_resources() reads one directory and does not recurse, so
+# such a unit keeps a census of its own (tests/golden/kernel_resources_hier_train.json) beside the closed one of the main directory
+# (tests/golden/kernel_resources.json), and SOURCES stays the table of the main directory's objects.
+HIER_TRAIN_DIR = "hier_train"
+SUBDIR_SOURCES = [("hier_train.hip", "hier_train", [], HIER_TRAIN_DIR)]
 # -Rpass-analysis=kernel-resource-usage: the backend reports every kernel's registers / spills / scratch; kept beside the object
 # (<name>.o.remarks, see kernel_resources()) so that a toolchain or flag change that breaks the AGPR parking or introduces
 # spills in a headline kernel is caught by tests/test_kernel_resources.py
@@ -90,8 +96,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
 
     def one(item):
-        src, name, flags = item
-        obj = os.path.join(OBJ, name + ".o")
+        src, name, flags, *sub = item
+        obj = os.path.join(OBJ, *sub, name + ".o")
+        os.makedirs(os.path.dirname(obj), exist_ok=True)
         cmd = [hipcc(), *FLAGS, *flags, "-MD", "-MF", obj + ".d", "-c", os.path.join(CSRC, src), "-o", obj]
         cmd_key = " ".join(cmd)
         if not force and _obj_fresh(obj, cmd_key):
@@ -108,7 +115,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         return obj, True
 
     with cf.ThreadPoolExecutor(max_workers=os.cpu_count() or 8) as ex:
-        res = list(ex.map(one, SOURCES))
+        res = list(ex.map(one, [*SOURCES, *SUBDIR_SOURCES]))
     objs = [o for o, _ in res]
     if not any(built for _, built in res) and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(objs):
         os.utime(LIB)          # nothing to do (e.g. only a comment of this file changed): restore the fast path

@@ -1087,6 +1087,53 @@ int nrf_composite_loss_backward_indexed(const float* rgb, int rgb_stride, const 
                                        d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream);
 }
 
+int64_t nrf_hier_train_workspace_bytes(int64_t n_rays, int n_samples, int n_importance) {
+    if (n_rays < 0 || n_samples < 1 || n_importance < 1 || (int64_t)n_samples + n_importance > 4096) {
+        (void)fail(NRF_EINVAL, "nrf_hier_train_workspace_bytes: bad sizes");
+        return -1;
+    }
+    return nrf::hier_train_ws_bytes(n_rays, n_samples, n_importance);
+}
+
+int nrf_composite_hier_loss_backward(const nrf_hier_loss* a, int64_t n_rays, int n_samples, int n_importance, void* stream) {
+    const std::string w = "nrf_composite_hier_loss_backward";
+    if (!a) return fail(NRF_EINVAL, w + ": a is NULL");
+    if (a->struct_bytes != (int32_t)sizeof(nrf_hier_loss)) return fail(NRF_EINVAL, w + ": nrf_hier_loss: struct_bytes is not sizeof(nrf_hier_loss)");
+    if (n_rays < 0 || n_rays > ((int64_t)1 << 30)) return fail(NRF_EINVAL, w + ": n_rays < 0 or too large");
+    if (n_samples < 1) return fail(NRF_EINVAL, w + ": n_samples < 1");
+    if (n_importance < 1) return fail(NRF_EINVAL, w + ": n_importance < 1");
+    if ((int64_t)n_samples + n_importance > 4096) return fail(NRF_EINVAL, w + ": n_samples + n_importance > 4096");
+    if (a->rgb_stride < 3 || a->sigma_stride < 1) return fail(NRF_EINVAL, w + ": bad strides");
+    if (!(a->w_coarse >= 0.0f) || !(a->w_fine >= 0.0f) || !std::isfinite(a->w_coarse) || !std::isfinite(a->w_fine))
+        return fail(NRF_EINVAL, w + ": w_coarse and w_fine must be finite and >= 0");
+    if (!a->rgb_coarse || !a->sigma_coarse || !a->rgb_new || !a->sigma_new || !a->z_coarse || !a->z_new || !a->rays_d || !a->target ||
+        !a->d_rgb_coarse || !a->d_sigma_coarse || !a->d_rgb_new || !a->d_sigma_new)
+        return fail(NRF_EINVAL, w + ": null pointer");
+    if (!a->ray_loss) return fail(NRF_EINVAL, w + ": ray_loss is NULL");
+    for (const void* p : {(const void*)a->rgb_coarse, (const void*)a->sigma_coarse, (const void*)a->rgb_new, (const void*)a->sigma_new,
+                          (const void*)a->z_coarse, (const void*)a->z_new, (const void*)a->rays_d, (const void*)a->target,
+                          (const void*)a->d_rgb_coarse, (const void*)a->d_sigma_coarse, (const void*)a->d_rgb_new, (const void*)a->d_sigma_new,
+                          (const void*)a->pred_coarse, (const void*)a->pred_fine, (const void*)a->ray_loss, (const void*)a->ray_parts,
+                          (const void*)a->z_union, (const void*)a->weights_fine, (const void*)a->zero_buf})
+        if ((reinterpret_cast<uintptr_t>(p) & 3u) != 0) return fail(NRF_EINVAL, w + ": float tensors must be 4-byte aligned");
+    if (a->zero_n < 0 || (a->zero_n > 0 && !a->zero_buf)) return fail(NRF_EINVAL, w + ": zero_buf is NULL");
+    if (!a->workspace) return fail(NRF_EINVAL, w + ": workspace is NULL");
+    if ((reinterpret_cast<uintptr_t>(a->workspace) & 15u) != 0) return fail(NRF_EINVAL, w + ": workspace must be 16-byte aligned");
+    if (a->workspace_bytes < nrf::hier_train_ws_bytes(n_rays, n_samples, n_importance))
+        return fail(NRF_EINVAL, w + ": workspace smaller than nrf_hier_train_workspace_bytes");
+    if (n_rays == 0) return NRF_OK;
+    nrf::HierTrainArgs h{};
+    h.white_bkgd = a->white_bkgd; h.rgb_stride = a->rgb_stride; h.sigma_stride = a->sigma_stride;
+    h.rgb_coarse = a->rgb_coarse; h.sigma_coarse = a->sigma_coarse; h.rgb_new = a->rgb_new; h.sigma_new = a->sigma_new;
+    h.z_coarse = a->z_coarse; h.z_new = a->z_new; h.rays_d = a->rays_d; h.target = a->target;
+    h.w_coarse = a->w_coarse; h.w_fine = a->w_fine;
+    h.d_rgb_coarse = a->d_rgb_coarse; h.d_sigma_coarse = a->d_sigma_coarse; h.d_rgb_new = a->d_rgb_new; h.d_sigma_new = a->d_sigma_new;
+    h.pred_coarse = a->pred_coarse; h.pred_fine = a->pred_fine; h.ray_loss = a->ray_loss; h.ray_parts = a->ray_parts;
+    h.z_union = a->z_union; h.weights_fine = a->weights_fine; h.zero_buf = a->zero_buf; h.zero_n = a->zero_n; h.workspace = a->workspace;
+    const int r = nrf::launch_hier_loss_backward(h, n_rays, n_samples, n_importance, (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, w + ": launch failed");
+}
+
 int64_t nrf_occupancy_compact_workspace_bytes(int64_t n_rays) {
     if (n_rays < 0) { (void)fail(NRF_EINVAL, "nrf_occupancy_compact_workspace_bytes: n_rays < 0"); return -1; }
     return nrf::occupancy_compact_ws_bytes(n_rays);

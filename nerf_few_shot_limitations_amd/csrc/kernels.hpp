@@ -201,6 +201,20 @@ int launch_composite_mse_backward(const float* rgb, int rgb_stride, const float*
                                   int64_t n_rays, int S, int white_bkgd, const float* target, float weight, float* pred, float* d_rgb,
                                   int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_loss, float* zero_buf,
                                   int64_t zero_n, hipStream_t s);
+// The hierarchical training step's stage between its forwards and its backwards (hier_train.hip; nerfhip.h: nrf_hier_loss, whose
+// fields these are): launch_composite_mse_backward on the coarse rows, the union gathered in the merged order, the same launch on
+// it, the fine term's d rows scattered back.  workspace: hier_train_ws_bytes, 16-byte aligned.
+struct HierTrainArgs {
+    int white_bkgd, rgb_stride, sigma_stride;
+    const float *rgb_coarse, *sigma_coarse, *rgb_new, *sigma_new, *z_coarse, *z_new, *rays_d, *target;
+    float w_coarse, w_fine;
+    float *d_rgb_coarse, *d_sigma_coarse, *d_rgb_new, *d_sigma_new;
+    float *pred_coarse, *pred_fine, *ray_loss, *ray_parts, *z_union, *weights_fine;      // all but ray_loss may be NULL
+    float* zero_buf; int64_t zero_n;
+    void* workspace;
+};
+int64_t hier_train_ws_bytes(int64_t n_rays, int S, int Ni);
+int launch_hier_loss_backward(const HierTrainArgs& a, int64_t n_rays, int S, int Ni, hipStream_t s);
 // The multiscale trainer's step (train_multiscale.py:207-211,249-266): nerf_mlp.NeRFLoss on a VolumeRenderer in train() mode,
 // clip_grad_norm_, AdamW
 struct LossTerms {

@@ -1,5 +1,5 @@
 """python -m nerf_few_shot_limitations_amd.train_cli --config experiments/baseline.yaml --data data/nerf_synthetic/lego \\
-        [--recipe train|multiscale] [--epochs N] [--mode bf16|f16|f32] [--eval-mode f16] [--out DIR] [--checkpoint CKPT]
+        [--n-importance N [--coarse-weight W]] [--recipe train|multiscale] [--epochs N] [--mode bf16|f16|f32] [--eval-mode f16] [--out DIR] [--checkpoint CKPT]
         [--dino-weights DIR | --dino-maps maps.pt] [--train-extractor] [--fused-inputs] [--seed 0]
         [--occupancy-res N [--occupancy-box LO HI] [--occupancy-threshold T] [--occupancy-decay D] [--occupancy-refresh-every K]
          [--occupancy-cells-per-refresh C] [--occupancy-warmup STEPS] [--occupancy-per-view]]
@@ -71,6 +71,15 @@ batches also take `d_dino_out` / `points_out` under the grid: their first `last_
 depend on the view: the single grid serves) and without --occupancy-res.  UNLIKE the single grid, the per-view grids ARE part of a
 checkpoint (`occupancy_per_view_state`) and --checkpoint restores them, warm-up counters included.  --data-parallel works as with the
 single grid: every rank refreshes from the same parameters and seeds, so the grids agree; with --train-extractor it stays refused.
+
+--n-importance N (0, the default: off, today's run) trains coarse-to-fine on the one network: every ray batch is one
+`FusedStep.step_view_hierarchical` -- the S ladder samples, Ni = N depths resampled from their weights, and the loss
+`rgb_weight * (W * mse(coarse image, target) + mse(fine image, target))` with W = --coarse-weight (default 1.0; 0: the coarse rows
+learn through the fine image alone).  Every sample is evaluated once forward and backward; no gradient reaches the resampled
+depths.  It implies the --fused-inputs route (pixel ids in, no per-sample input tensor), and validation renders hierarchically too:
+`evaluate_views(N_importance=N)`.  Refused before the data set is read: --recipe multiscale (its regulariser, depth term and density
+noise are not part of the hierarchical step), any --occupancy-* flag, --train-extractor (no per-sample gradients are handed out), N < 0,
+W < 0, and --coarse-weight without --n-importance.
 
 --checkpoint resumes a run: weights, Adam moments and step count, epoch counter and best PSNR (the reference's train.py saves
 these keys, :374-389, but has no resume path); the LR schedule is a function of the epoch.  wandb and LPIPS are not part of
@@ -157,6 +166,30 @@ def extractor_args_error(args, cfg):
                 "would receive no gradient")
     if not bool((cfg.get("dino_model", {}) or {}).get("use_lora", True)):
         return "--train-extractor: dino_model.use_lora is false, the trainable set of train.py:105-110 is empty"
+    return None
+
+
+def hierarchical_args_error(args, cfg=None):
+    """Why --n-importance / --coarse-weight cannot run with these arguments (None: they can, or neither was given).  Decided before
+    any GPU work, in the style of occupancy_args_error."""
+    n = int(getattr(args, "n_importance", 0) or 0)
+    w = getattr(args, "coarse_weight", None)
+    if n < 0:
+        return "--n-importance must be >= 0 (0: off)"
+    if w is not None and not w >= 0.0:
+        return "--coarse-weight must be >= 0"
+    if n == 0:
+        if w is not None:
+            return "--coarse-weight needs --n-importance N (N > 0): without the hierarchical step the flag would be ignored"
+        return None
+    if getattr(args, "recipe", "train") == "multiscale":
+        return ("--n-importance with --recipe multiscale is refused: the regulariser, the depth term and the density noise are not part of "
+                "the hierarchical step")
+    if int(getattr(args, "occupancy_res", 0) or 0) or getattr(args, "occupancy_per_view", False) or any(
+            getattr(args, f, None) is not None for f in OCCUPANCY_FLAGS):
+        return "--n-importance is not combined with --occupancy-*: the hierarchical step runs under no grid"
+    if getattr(args, "train_extractor", False):
+        return "--n-importance with --train-extractor is refused: the hierarchical step hands out no per-sample gradients"
     return None
 
 
@@ -333,7 +366,7 @@ class ExtractorTrainer:
 
 
 def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, dino_maps=None, max_batches=None, rank=0, world=1,
-                extractor=None, fused_inputs=False, occupancy=None, draws=None):
+                extractor=None, fused_inputs=False, occupancy=None, draws=None, n_importance=0, coarse_weight=1.0):
     """One pass of train.py:261-290 over the training views; returns (mean loss, ray-samples processed).
     fused_inputs: every batch is one `step.step_view` on its pixel ids (--fused-inputs; module docstring) instead of torch gathers,
     sample_points_along_rays, the expanded directions and fetch_features in front of `step(...)`.
@@ -342,6 +375,8 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
     with grid_inputs="rays", use_dino models and a trained extractor included.
     extractor: an ExtractorTrainer (--train-extractor; module docstring) -- the view's map comes from it, live, instead of
     dino_maps[v], and it takes one step per view.
+    n_importance > 0 (--n-importance; module docstring): every batch is one `step.step_view_hierarchical` with that many resampled
+    depths and `coarse_weight`; the fused_inputs route, without a grid or a trained extractor.
     draws: the epoch's random draws as inputs (parity runs against a recorded run of the reference's trainer): an object whose
     `permutation(v, n)` returns view v's shuffle of its n rays (train.py:272's torch.randperm) and whose `jitter(v, i, n, S)` returns the
     (n,S) uniforms of the batch starting at position i (ray_utils.py:78's torch.rand), handed on as `t_rand=`.  None: `gen` shuffles and
@@ -358,6 +393,11 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
             raise ValueError("per-view occupancy grids belong to use_dino models: the other fields do not depend on the view")
         if not per_view and (use_dino or extractor is not None):
             raise ValueError("training under an occupancy grid is not combined with use_dino models or a trained extractor")
+        fused_inputs = True
+    Ni = int(n_importance)
+    if Ni > 0:
+        if occupancy is not None or extractor is not None:
+            raise ValueError("the hierarchical step is not combined with an occupancy grid or a trained extractor")
         fused_inputs = True
     total, n_batches, samples = None, 0, 0
     pts_buf = None
@@ -395,7 +435,11 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
                     kw["occupancy"] = sched.current()
                 if per_view:
                     kw["grid_inputs"] = "rays"
-                loss = step.step_view(None, c2w, Ht, Wt, f_t, idx, near, far, S, perturb=True, t_rand=t_rand, **kw)
+                if Ni > 0:
+                    loss = step.step_view_hierarchical(None, c2w, Ht, Wt, f_t, idx, near, far, S, Ni, perturb=True, t_rand=t_rand,
+                                                       coarse_weight=coarse_weight, **kw)
+                else:
+                    loss = step.step_view(None, c2w, Ht, Wt, f_t, idx, near, far, S, perturb=True, t_rand=t_rand, **kw)
                 if occupancy is not None:
                     sched.after_step(model, dino=cam if per_view else None)
                 if extractor is not None:
@@ -404,7 +448,7 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
                         extractor.add_batch(cam, pts_buf[:rows], d_feats[:rows])
                 total = loss if total is None else total + loss
                 n_batches += 1
-                samples += n * S
+                samples += n * (S + Ni)
                 if max_batches is not None and n_batches >= max_batches:
                     if extractor is not None:
                         extractor.end_view()
@@ -507,6 +551,11 @@ def main(argv=None):
     ap.add_argument("--fused-inputs", action="store_true",
                     help="cast rays, sample, encode and fetch the DINO features inside the training forward kernel (FusedStep.step_view) instead "
                          "of building per-sample tensors in front of it; same shuffle, seeds and sharding")
+    ap.add_argument("--n-importance", type=int, default=0, metavar="N",
+                    help="train coarse-to-fine: N depths resampled from the coarse weights per ray, FusedStep.step_view_hierarchical per batch, "
+                         "hierarchical validation (module docstring); 0: off")
+    ap.add_argument("--coarse-weight", type=float, default=None, metavar="W",
+                    help="with --n-importance: the coarse image's share of the loss, rgb_weight * (W * mse_coarse + mse_fine) (default 1.0)")
     ap.add_argument("--occupancy-res", type=int, default=0,
                     help="train under an occupancy grid of N^3 cells (a multiple of 32; 0: off): the network runs on the samples in occupied "
                          "cells alone, FusedStep.step_view(occupancy=) (module docstring)")
@@ -529,7 +578,8 @@ def main(argv=None):
                     help="--data-parallel on a box with ONE GPU: every rank on cuda:0, the gradient all-reduce over gloo through host memory "
                          "(RCCL refuses two ranks on one card); exercises the sharding and the collective, not multi-GPU speed")
     args = ap.parse_args(argv)
-    problem = extractor_args_error(args, load_config(args.config)) or occupancy_args_error(args, load_config(args.config))
+    problem = (hierarchical_args_error(args) or extractor_args_error(args, load_config(args.config))
+               or occupancy_args_error(args, load_config(args.config)))
     if problem:
         raise SystemExit(problem)
     rank, world = 0, 1
@@ -612,7 +662,8 @@ def main(argv=None):
             ext.set_lr(lr_at(cfg, epoch))
         t0 = time.perf_counter()
         loss, samples = train_epoch(step, cfg, epoch, images, poses, H, W, focal, rs["near"], rs["far"], gen, dino_maps, args.max_batches, rank, world,
-                                    extractor=ext, fused_inputs=args.fused_inputs, occupancy=occ)
+                                    extractor=ext, fused_inputs=args.fused_inputs, occupancy=occ, n_importance=args.n_importance,
+                                    coarse_weight=1.0 if args.coarse_weight is None else args.coarse_weight)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         rec = {"epoch": epoch + 1, "loss": loss, "lr": step.opt.lr, "seconds": round(dt, 3), "Msamples_per_s": round(world * samples / dt / 1e6, 2)}
@@ -625,7 +676,8 @@ def main(argv=None):
             if ext is not None:                                               # the extractor moved: view 0's map as it is now, under no_grad
                 eval_dino["features"] = precompute_dino_features(ext.extractor, ext.images[0:1]).float()
             m = evaluate_views(model, test_poses, H, W, focal, rs["near"], rs["far"], rs["n_samples"], targets=targets, white_bkgd=rs["white_bkgd"],
-                               mma_mode=args.eval_mode, dino=eval_dino, out_dir=os.path.join(out_dir, f"val_{epoch + 1}"))
+                               mma_mode=args.eval_mode, dino=eval_dino, out_dir=os.path.join(out_dir, f"val_{epoch + 1}"),
+                               N_importance=args.n_importance)
             model.train()
             rec.update(psnr=m["psnr"], ssim=m["ssim"])
             if m["psnr"] > best:

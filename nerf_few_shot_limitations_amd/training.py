@@ -128,6 +128,11 @@ def _heads(o4, n, v1):
     return rgb, den, (L.ptr(rgb), 3, L.ptr(den), 1)
 
 
+def _addr(p):
+    """A device address as an int: _heads hands the V1 density pointer out as a c_void_p, a ctypes struct field takes an int."""
+    return p.value if isinstance(p, C.c_void_p) else p
+
+
 def _prep(g):
     """An incoming gradient as the kernels read it; None (an unused output) stays None."""
     return None if g is None else g.to(torch.float32).contiguous()
@@ -963,6 +968,7 @@ class FusedStep:
         self.seed = None if seed is None else int(seed)
         self.white = int(bool(white_bkgd))
         self._loss_vec, self.last_grad_norm = None, None
+        self._hier_parts = None             # ((2,R) squared errors coarse | fine, R) of the last step when it was a hierarchical one
         self._key = None
         self.last_count = None              # M of the last step under an occupancy grid (step_rays / step_view with occupancy=)
 
@@ -973,6 +979,11 @@ class FusedStep:
         v = self._loss_vec
         if v is None:
             return None
+        if self._hier_parts is not None:    # the hierarchical step: {'total', 'coarse', 'fine'}, the two unweighted mse terms
+            total = v if v.dim() == 0 else v[0]
+            parts, R = self._hier_parts
+            mse = parts.sum(dim=1) / (3.0 * R)              # formed when asked for (torch reductions on the stream: no sync), from the step's buffer
+            return {"total": total, "coarse": mse[0], "fine": mse[1]}
         return {"total": v} if v.dim() == 0 else {"total": v[0], "rgb": v[1], "depth": v[2], "reg": v[3]}
 
     def _buffers(self, n, R, S, dev, h, mode):
@@ -1022,6 +1033,7 @@ class FusedStep:
         one launch (a ray's loss gradient needs only its own prediction); the rays' squared errors stay in ray_loss.  slot (the step
         under a grid): the indexed kernel, for the plain and the multi-term loss alike.  Returns `multi`."""
         lib = L.lib()
+        self._hier_parts = None
         multi, lo, keep = self._loss_setup(R, S, dev, target_depth, noise, always=slot is not None)
         if slot is not None:
             # the one indexed entry serves both steps: with every option off its bits are the mse kernel's
@@ -1037,21 +1049,25 @@ class FusedStep:
         del keep                            # (td, nz: alive until the launch that reads them is enqueued)
         return multi
 
-    def _network_backward(self, h, mode, rows, out, d_out, ctx, st, d_dino_out=None):
-        """dZ chain + weight gradients over the first `rows` rows, added into the flat gradient vector [-> dL/d dino]."""
+    def _network_backward(self, h, mode, rows, out, d_out, ctx, st, d_dino_out=None, nbytes=None):
+        """dZ chain + weight gradients over the first `rows` rows, added into the flat gradient vector [-> dL/d dino].  nbytes: of a
+        context other than the plain step's (the hierarchical step holds two)."""
         lib = L.lib()
+        nbytes = self.nbytes if nbytes is None else nbytes
         if self.model.net == L.NRF_NET_V1:
-            L.check(lib.nrf_mlp_backward_v1(h, mode, L.ptr(out[0]), L.ptr(d_out[0]), rows, ctx, self.nbytes, L.ptr(self.grad), st))
+            L.check(lib.nrf_mlp_backward_v1(h, mode, L.ptr(out[0]), L.ptr(d_out[0]), rows, ctx, nbytes, L.ptr(self.grad), st))
         else:
-            L.check(lib.nrf_mlp_backward(h, mode, L.ptr(out[0]), L.ptr(out[1]), L.ptr(d_out[0]), L.ptr(d_out[1]), rows, ctx, self.nbytes,
+            L.check(lib.nrf_mlp_backward(h, mode, L.ptr(out[0]), L.ptr(out[1]), L.ptr(d_out[0]), L.ptr(d_out[1]), rows, ctx, nbytes,
                                          L.ptr(self.grad), st))
             if d_dino_out is not None:
                 _dino_grad(self.model, mode, rows, self.ctx, self.nbytes, d_dino_out.device, out=d_dino_out)
 
-    def _finish(self, multi, R, S, dev, target_depth, st):
+    def _finish(self, multi, R, S, dev, target_depth, st, loss_weight=None):
         """[all-reduce ->] the optimiser's launch with the loss as its side job, the bookkeeping, and the parameters marked newer than
-        the packed streams (call with the device current).  Returns the step's total loss (a device scalar)."""
+        the packed streams (call with the device current).  Returns the step's total loss (a device scalar).  loss_weight: the factor
+        on sum(ray_loss[0]) / (3 R) when it is not rgb_weight (the hierarchical step's ray_loss carries its two weights already)."""
         opt, lib = self.opt, L.lib()
+        loss_weight = self.rgb_weight if loss_weight is None else loss_weight
         if self.data_parallel:
             _all_reduce_mean(self.grad, self.group)
         fp, flat = opt._buffers()
@@ -1059,7 +1075,7 @@ class FusedStep:
         if multi:
             # [norm partials ->] clipped Adam / AdamW, and as a side job of its launch the loss terms summed in a fixed order
             loss = torch.empty((4,), dtype=torch.float32, device=dev)
-            opt._update(flat, self.grad, self.ray_loss, R, S, (self.rgb_weight, self.depth_weight if target_depth is not None else 0.0,
+            opt._update(flat, self.grad, self.ray_loss, R, S, (loss_weight, self.depth_weight if target_depth is not None else 0.0,
                                                                self.reg_weight), loss)
             self._loss_vec, self.last_grad_norm = loss, opt.last_grad_norm
             loss = loss[0]
@@ -1068,7 +1084,7 @@ class FusedStep:
             loss = torch.empty((), dtype=torch.float32, device=dev)
             L.check(lib.nrf_adam_step_loss(L.ptr(flat), L.ptr(self.grad), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq), flat.numel(), opt.lr,
                                            opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, opt.step_count, L.ptr(self.ray_loss), R,
-                                           self.rgb_weight, L.ptr(loss), st))
+                                           loss_weight, L.ptr(loss), st))
             self._loss_vec, self.last_grad_norm = loss, None
         self.model._gen += 1
         return loss
@@ -1175,6 +1191,174 @@ class FusedStep:
                                                                    points_out=p_out),
                               None, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise, d_dino_out, points_out,
                               occupancy, grid_inputs)
+
+    # ---- the hierarchical step: a coarse and a fine image of one network, every sample evaluated once --------------------------
+    def _hier_check(self, n_samples, n_importance, coarse_weight, occupancy=None, d_dino_out=None, points_out=None):
+        """The refusals of the hierarchical step, all decided on the host before a device is touched; returns (S, Ni, w_coarse,
+        w_fine) with w_coarse = rgb_weight * coarse_weight formed as one fp32 product."""
+        if self.reg_weight > 0.0 or self.depth_weight > 0.0 or self.noise_std > 0.0:
+            raise ValueError("the hierarchical step takes the plain rgb loss: a FusedStep with reg_weight, depth_weight or noise_std > 0 is refused")
+        if occupancy is not None:
+            raise ValueError("the hierarchical step is not combined with occupancy=")
+        if d_dino_out is not None or points_out is not None:
+            raise ValueError("the hierarchical step hands out no per-sample gradients: d_dino_out / points_out are refused")
+        S, Ni = int(n_samples), int(n_importance)
+        if Ni < 1:
+            raise ValueError("n_importance must be >= 1 (step_rays / step_view are the step without resampling)")
+        if S < 2:
+            raise ValueError("n_samples must be >= 2: the resampling needs a bin")
+        if S + Ni > 4096:
+            raise ValueError("n_samples + n_importance must be <= 4096")
+        cw = float(coarse_weight)
+        if not cw >= 0.0:
+            raise ValueError("coarse_weight must be >= 0")
+        f32 = lambda x: C.c_float(x).value
+        return S, Ni, f32(f32(self.rgb_weight) * f32(cw)), f32(self.rgb_weight)      # (the product of two fp32 values is exact in double)
+
+    @torch.no_grad()
+    def step_rays_hierarchical(self, rays_o, rays_d, target, near, far, n_samples, n_importance, perturb=True, t_rand=None, seed=None,
+                               lindisp=False, u=None, dino=None, coarse_weight=1.0, occupancy=None, d_dino_out=None, points_out=None):
+        """One step of NeRF's coarse-to-fine training on ONE network: the loss is
+
+            rgb_weight * (coarse_weight * mse(pred_coarse, target) + mse(pred_fine, target))
+
+        where pred_coarse composites the n_samples ladder samples and pred_fine the sorted union of those and n_importance depths
+        drawn from the coarse weights by inverse-cdf resampling (render_hierarchical's fine pass).  Every sample is evaluated once,
+        forward and backward -- n_samples + n_importance network rows per ray -- and the coarse rows receive the gradient of both
+        images.  No gradient reaches the depths: the resampling is a constant, as in NeRF.  One fixed launch sequence on
+        preallocated buffers, nothing synchronises:
+
+            saving forward on the ladder -> nrf_composite (the coarse weights) -> nrf_sample_pdf_sorted -> saving forward on the
+            new depths (a context of its own) -> nrf_composite_hier_loss_backward (both images, both losses, d rows of both row
+            sets; clears the gradient vector) -> backward on the coarse context -> backward on the new one -> [all-reduce ->]
+            the optimiser
+
+        u: the resampling's uniforms, (R, n_importance) or one shared row (n_importance); default torch.rand on the device with
+        perturb=True, the shared linspace(0, 1, n_importance) row with perturb=False (render_camera_hierarchical's).  t_rand, seed,
+        lindisp, dino as in step_rays.  coarse_weight = 0 is allowed: the coarse rows then learn through the fine image alone.
+        Kept for the caller, as buffers of this object like `last_z`: last_z (R,S), last_weights (R,S: what the resampling read),
+        last_z_new (R,Ni), pred (the fine image), pred_coarse, grad.  `last_losses` = {'total', 'coarse', 'fine'}: the step's loss
+        and the two unweighted mse terms, device scalars (the two terms are summed from the step's buffer when asked for: read them
+        before the next hierarchical step).  max_grad_norm and decoupled_weight_decay act behind the gradient as in
+        the plain step.  Refused with ValueError: a step object with reg_weight, depth_weight or noise_std > 0, occupancy=,
+        d_dino_out=, points_out=, n_importance < 1, n_samples + n_importance > 4096, coarse_weight < 0."""
+        chk = self._hier_check(n_samples, n_importance, coarse_weight, occupancy, d_dino_out, points_out)
+        o = L.dev_f32(rays_o).reshape(-1, 3)
+        d = L.dev_f32(rays_d, o.device).reshape(-1, 3)
+        if d.shape != o.shape:
+            raise ValueError("rays_o and rays_d must both be (R,3)")
+        return self._hier_step(o.shape[0], o.device, lambda z, d_out: L.train_rays(rays_o=L.ptr(o), rays_d=L.ptr(d), z_vals=z), d, target, near, far,
+                               chk, perturb, t_rand, seed, lindisp, u, dino)
+
+    @torch.no_grad()
+    def step_view_hierarchical(self, image, pose, H, W, focal, pixels, near, far, n_samples, n_importance, perturb=True, t_rand=None,
+                               seed=None, lindisp=False, u=None, dino=None, coarse_weight=1.0, target=None, occupancy=None, d_dino_out=None,
+                               points_out=None):
+        """step_rays_hierarchical on pixels of a pinhole view, as step_view is step_rays on them: `pixels` an int64 device tensor of
+        ray ids, the target `target` (R,3) or image.reshape(-1,3)[pixels]; jitter and uniforms are keyed by the position in `pixels`,
+        so the step equals step_rays_hierarchical on the gathered rays to the bit."""
+        chk = self._hier_check(n_samples, n_importance, coarse_weight, occupancy, d_dino_out, points_out)
+        if not (isinstance(pixels, torch.Tensor) and pixels.is_cuda and pixels.dtype == torch.int64 and pixels.dim() == 1):
+            raise ValueError("pixels must be a 1-d int64 tensor of ray ids on the GPU")
+        pix = pixels.contiguous()
+        H, W = int(H), int(W)
+        if target is None:
+            img = L.dev_f32(image, pix.device)
+            if img.numel() != H * W * 3:
+                raise ValueError("image must be (H,W,3) (or pass target=)")
+            target = img.reshape(-1, 3)[pix]
+        from .ray_sampler import _c2w12
+        c2w = pose if isinstance(pose, C.Array) else _c2w12(pose)
+        return self._hier_step(pix.shape[0], pix.device,
+                               lambda z, d_out: L.train_rays(pixels=pix.data_ptr(), H=H, W=W, focal=focal, c2w=c2w, z_vals=z, rays_d_out=d_out),
+                               None, target, near, far, chk, perturb, t_rand, seed, lindisp, u, dino)
+
+    def _hier_buffers(self, R, S, Ni, dev, h, mode):
+        """The hierarchical step's buffers, kept apart from the plain step's (a FusedStep may take both kinds of step); the ones a
+        caller or _finish reads by name -- grad, pred, ray_loss, last_z -- are pointed at them for the step."""
+        key = (R, S, Ni, str(dev), mode)
+        b = getattr(self, "_hb", None)
+        if b is None or b["key"] != key:
+            f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+            b = {"key": key}
+            b["ctx_c"], b["nbytes_c"] = _context(h, mode, R * S, dev)
+            b["ctx_n"], b["nbytes_n"] = _context(h, mode, R * Ni, dev)
+            for k, rows in (("c", R * S), ("n", R * Ni)):
+                b["out4_" + k], b["d_out4_" + k] = f(rows, 4), f(rows, 4)
+            b["pred"], b["pred_coarse"], b["rays_d"] = f(R, 3), f(R, 3), f(R, 3)
+            b["ray_loss"] = torch.zeros((3, R), dtype=torch.float32, device=dev)     # row 0: w_c se_c + w_f se_f; rows 1, 2 stay 0 (the clipped optimiser's side job reads three rows)
+            b["parts"] = f(2, R)
+            b["z"], b["w"], b["z_new"], b["z_new_out"] = f(R, S), f(R, S), f(R, Ni), f(R, Ni)
+            b["ws"] = torch.empty((max(int(L.lib().nrf_hier_train_workspace_bytes(R, S, Ni)), 16) // 4,), dtype=torch.float32, device=dev)
+            b["grad"] = torch.zeros(self.model.flat_params().flat.numel(), dtype=torch.float32, device=dev)
+            self._hb = b
+        self.grad, self.pred, self.pred_coarse, self.ray_loss = b["grad"], b["pred"], b["pred_coarse"], b["ray_loss"]
+        self.last_z, self.last_weights, self.last_z_new = b["z"], b["w"], b["z_new"]
+        self._key = self._ray_key = None    # the plain step's buffers are no longer the ones these names point at: it takes its own again
+        return b
+
+    def _hier_step(self, R, dev, make_rays, d, target, near, far, chk, perturb, t_rand, seed, lindisp, u, dino):
+        """The launch sequence of step_rays_hierarchical; d is the caller's (R,3) directions or None (pixel mode)."""
+        from .renderer import _opts, make_dino
+        S, Ni, w_coarse, w_fine = chk
+        m = self.model
+        v1, v3 = m.net == L.NRF_NET_V1, m.net == L.NRF_NET_V3
+        if R < 1:
+            raise ValueError("a step needs at least one ray")
+        tgt = L.dev_f32(target, dev).reshape(R, 3)
+        tr = L.dev_f32(t_rand, dev).reshape(R, S) if t_rand is not None else None
+        dn = keep = None
+        if v3:
+            if dino is None:
+                raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
+            dn, keep = make_dino(**dino) if isinstance(dino, dict) else dino
+        lib = L.lib()
+        h, mode = _train_handle(m, dev)
+        with torch.cuda.device(dev):
+            if u is None:
+                uu, stride = (torch.rand((R, Ni), dtype=torch.float32, device=dev), Ni) if perturb else (L.u_row(Ni, dev), 0)
+            else:
+                uu = L.dev_f32(u, dev)
+                if uu.numel() == Ni:
+                    uu, stride = uu.reshape(Ni), 0
+                elif uu.numel() == R * Ni:
+                    uu, stride = uu.reshape(R, Ni), Ni
+                else:
+                    raise ValueError("u must be (R, n_importance) or one shared row (n_importance)")
+            b = self._hier_buffers(R, S, Ni, dev, h, mode)
+            z, w, z_new = b["z"], b["w"], b["z_new"]
+            if d is None:
+                d = b["rays_d"]
+            st = L.stream_ptr()
+            train_mode = L.TRAIN_MODE[m.mma_mode]
+            ctx_c, ctx_n = C.c_void_p(b["ctx_c"].data_ptr()), C.c_void_p(b["ctx_n"].data_ptr())
+            *out_c, heads_c = _heads(b["out4_c"], R * S, v1)
+            *d_out_c, d_heads_c = _heads(b["d_out4_c"], R * S, v1)
+            *out_n, heads_n = _heads(b["out4_n"], R * Ni, v1)
+            *d_out_n, d_heads_n = _heads(b["d_out4_n"], R * Ni, v1)
+            # the coarse samples, their weights, the new depths, the new samples
+            opts = _opts(near, far, S, perturb, tr, seed, lindisp, 0.0, self.white, train_mode, dn, dev)
+            rays = make_rays(L.ptr(z), L.ptr(b["rays_d"]))
+            L.check(lib.nrf_mlp_forward_train_rays(h, C.byref(rays), R, C.byref(opts), L.ptr(out_c[0]), L.ptr(out_c[1]), ctx_c, b["nbytes_c"], st))
+            L.check(lib.nrf_composite(*heads_c, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(self.pred_coarse), None, L.ptr(w), st))
+            L.check(lib.nrf_sample_pdf_sorted(L.ptr(z), L.ptr(w), R, S, Ni, L.ptr(uu), stride, None, L.ptr(z_new), None, st))
+            opts_n = _opts(near, far, Ni, False, None, 0, lindisp, 0.0, self.white, train_mode, dn, dev, z_new)
+            rays_n = make_rays(L.ptr(b["z_new_out"]), L.ptr(b["rays_d"]))
+            L.check(lib.nrf_mlp_forward_train_rays(h, C.byref(rays_n), R, C.byref(opts_n), L.ptr(out_n[0]), L.ptr(out_n[1]), ctx_n, b["nbytes_n"], st))
+            del keep, uu
+            # both images, both losses, the d rows of both row sets (the coarse ones: both terms); the gradient vector cleared
+            a = L.hier_loss(white_bkgd=self.white, rgb_stride=heads_c[1], sigma_stride=heads_c[3],
+                            rgb_coarse=heads_c[0], sigma_coarse=_addr(heads_c[2]), rgb_new=heads_n[0], sigma_new=_addr(heads_n[2]),
+                            z_coarse=L.ptr(z), z_new=L.ptr(z_new), rays_d=L.ptr(d), target=L.ptr(tgt), w_coarse=w_coarse, w_fine=w_fine,
+                            d_rgb_coarse=d_heads_c[0], d_sigma_coarse=_addr(d_heads_c[2]), d_rgb_new=d_heads_n[0], d_sigma_new=_addr(d_heads_n[2]),
+                            pred_coarse=L.ptr(self.pred_coarse), pred_fine=L.ptr(self.pred), ray_loss=L.ptr(self.ray_loss), ray_parts=L.ptr(b["parts"]),
+                            zero_buf=L.ptr(self.grad), zero_n=self.grad.numel(), workspace=b["ws"].data_ptr(), workspace_bytes=b["ws"].numel() * 4)
+            L.check(lib.nrf_composite_hier_loss_backward(C.byref(a), R, S, Ni, st))
+            self._network_backward(h, mode, R * S, out_c, d_out_c, ctx_c, st, nbytes=b["nbytes_c"])
+            self._network_backward(h, mode, R * Ni, out_n, d_out_n, ctx_n, st, nbytes=b["nbytes_n"])
+            loss = self._finish(self.opt.extended, R, S + Ni, dev, None, st, loss_weight=1.0)
+            self._hier_parts = (b["parts"], R)
+            return loss
 
     def _ray_step(self, R, dev, make_rays, d, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise,
                   d_dino_out, points_out, occupancy=None, grid_inputs="staged"):
