@@ -821,6 +821,48 @@ int64_t nrf_hier_train_workspace_bytes(int64_t n_rays, int n_samples, int n_impo
  * entry refuses an empty batch, there is no clearing launch to follow). */
 int nrf_composite_hier_loss_backward(const nrf_hier_loss* a, int64_t n_rays, int n_samples, int n_importance, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Few-shot ray regularisers in the fused training step: the distortion loss of mip-NeRF 360 and the occlusion (near-camera
+ * density) penalty of FreeNeRF, both per-ray functions of what the compositor backward holds in registers.  Per ray, with w_i the
+ * compositor's weights (behind the density noise), z_i the depths (non-decreasing), s_i the density the compositor's ReLU sees
+ * (sigma_i + noise_std n_i; -inf for a sample the slot map skips), kappa = dist_inv_span and S = n_samples:
+ *   m_i = kappa (z_i + z_{i+1}) / 2,  delta_i = kappa (z_{i+1} - z_i)   for i < S-1
+ *   m_{S-1} = kappa z_{S-1},          delta_{S-1} = 0                   (the compositor's last interval is 1e10: no width here)
+ *   D = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i
+ *   O = (1/M') sum_{i<M'} relu(s_i),   M' = min(occ_samples, S)
+ *   loss = nrf_composite_loss_backward's + dist_weight mean_r D_r + occ_weight mean_r O_r
+ * Depths carry no gradient.  Additive to ABI 5: the struct carries its own size, nrf_abi_sizeof knows nothing of it.
+ * ------------------------------------------------------------------------ */
+typedef struct nrf_ray_reg {
+    int32_t struct_bytes;   /* sizeof(nrf_ray_reg): checked by the library */
+    float   dist_weight;    /* >= 0; 0: the distortion term is not computed, its row of ray_terms is 0 */
+    float   dist_inv_span;  /* kappa, 1 / (far - near) for depths in [near, far]; finite and > 0 when dist_weight > 0 */
+    float   occ_weight;     /* >= 0; 0: the occlusion term is not computed, its row of ray_terms is 0 */
+    int32_t occ_samples;    /* >= 1 when occ_weight > 0; clamped to n_samples */
+} nrf_ray_reg;
+
+/* nrf_composite_loss_backward (slot == NULL) or nrf_composite_loss_backward_indexed (slot = nrf_compact.slot) with the two terms,
+ * still ONE launch: dL/dw_i gains dist_weight / R (2 sum_j w_j |m_i - m_j| + (2/3) w_i delta_i) where the regulariser's
+ * 2 reg_weight w_i / (R S) enters, d_sigma_i gains occ_weight / (R M') [s_i > 0] for i < M'.  The double sum costs O(S) per ray:
+ * prefix and suffix scans of w and w m over the ray's 64-sample segments.  With both weights 0 pred, d_rgb, d_sigma and the first
+ * three rows of ray_terms are the bits of the entry without the terms.
+ *   ray_terms : 5 * n_rays floats: the three rows of nrf_composite_loss_backward | D_r | O_r
+ * NRF_EINVAL, before any launch: what nrf_composite_loss_backward refuses (n_samples > 4096 among it), reg NULL or of a wrong
+ * struct_bytes, a negative or non-finite weight, dist_weight > 0 with a dist_inv_span that is not finite and > 0, occ_weight > 0
+ * with occ_samples < 1, a slot that is not 4-byte aligned. */
+int nrf_composite_reg_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride,
+                                    const float* z_vals, const float* rays_d, int64_t n_rays, int n_samples, int white_bkgd,
+                                    const float* target, const nrf_loss_opts* loss, const nrf_ray_reg* reg, const int32_t* slot,
+                                    float* pred, float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride,
+                                    float* ray_terms, float* zero_buf, int64_t zero_n, void* stream);
+
+/* One small launch behind nrf_adamw_step_loss (which was handed the same ray_terms and left losses4 = total, rgb, depth, reg):
+ *   losses6 = [total + dist_weight mean D + occ_weight mean O, rgb, depth, reg, mean D, mean O]
+ * Rows 3 and 4 of ray_terms are added up by one workgroup in a fixed order: no atomics, two runs give the same bits.  losses4 and
+ * losses6 are device pointers and may not overlap.  NRF_EINVAL: a NULL, n_rays < 1, and what the entry above refuses of reg. */
+int nrf_ray_terms_finish(const float* ray_terms, int64_t n_rays, const nrf_ray_reg* reg, const float* losses4, float* losses6,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

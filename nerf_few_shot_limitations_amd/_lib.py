@@ -79,6 +79,17 @@ def loss_opts(rgb_weight=1.0, reg_weight=0.0, depth_weight=0.0, target_depth=Non
     return nrf_loss_opts(C.sizeof(nrf_loss_opts), rgb_weight, reg_weight, depth_weight, target_depth, noise_std, noise, int(rng_seed) & (2 ** 64 - 1))
 
 
+class nrf_ray_reg(C.Structure):
+    """The two few-shot ray regularisers of nrf_composite_reg_loss_backward; struct_bytes is filled in by ray_reg()."""
+    _fields_ = [("struct_bytes", C.c_int32), ("dist_weight", C.c_float), ("dist_inv_span", C.c_float), ("occ_weight", C.c_float),
+                ("occ_samples", C.c_int32)]
+
+
+def ray_reg(dist_weight=0.0, dist_inv_span=0.0, occ_weight=0.0, occ_samples=0):
+    """nrf_ray_reg with its size field set."""
+    return nrf_ray_reg(C.sizeof(nrf_ray_reg), float(dist_weight), float(dist_inv_span), float(occ_weight), int(occ_samples))
+
+
 class nrf_train_rays(C.Structure):
     """The ray source of nrf_mlp_forward_train_rays; struct_bytes is filled in by train_rays()."""
     _fields_ = [("struct_bytes", C.c_int32), ("reserved", C.c_int32), ("rays_o", C.c_void_p), ("rays_d", C.c_void_p), ("pixels", C.c_void_p),
@@ -266,6 +277,11 @@ SIGNATURES = {
     # the hierarchical training step: the stage between its two saving forwards and its two backwards
     "nrf_hier_train_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "nrf_composite_hier_loss_backward": (C.c_int, [C.POINTER(nrf_hier_loss), C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    # few-shot ray regularisers in the fused step: the loss launch with the distortion and occlusion terms, and the launch that sums them
+    "nrf_composite_reg_loss_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                                  C.c_void_p, C.POINTER(nrf_loss_opts), C.POINTER(nrf_ray_reg), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "nrf_ray_terms_finish": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(nrf_ray_reg), C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -1043,11 +1043,25 @@ int nrf_adam_step_loss(float* params, const float* grads, float* exp_avg, float*
 
 extern "C++" {
 namespace {
-// nrf_composite_loss_backward and its indexed form (slot != NULL: rgb / sigma / d_rgb / d_sigma hold compacted rows)
+// nrf_ray_reg as the launches take it; false (with the message set) on a refusal
+bool ray_reg_terms(const nrf_ray_reg* reg, nrf::RayRegTerms& rt) {
+    if (!reg) return fail(NRF_EINVAL, "reg is NULL"), false;
+    if (reg->struct_bytes != (int32_t)sizeof(nrf_ray_reg)) return fail(NRF_EINVAL, "nrf_ray_reg.struct_bytes is not sizeof(nrf_ray_reg)"), false;
+    if (!(reg->dist_weight >= 0.0f) || !(reg->occ_weight >= 0.0f) || !std::isfinite(reg->dist_weight) || !std::isfinite(reg->occ_weight))
+        return fail(NRF_EINVAL, "dist_weight and occ_weight must be finite and >= 0"), false;
+    if (reg->dist_weight > 0.0f && !(std::isfinite(reg->dist_inv_span) && reg->dist_inv_span > 0.0f))
+        return fail(NRF_EINVAL, "dist_inv_span must be finite and > 0 when dist_weight > 0"), false;
+    if (reg->occ_weight > 0.0f && reg->occ_samples < 1) return fail(NRF_EINVAL, "occ_samples must be >= 1 when occ_weight > 0"), false;
+    rt.dist_weight = reg->dist_weight; rt.dist_inv_span = reg->dist_inv_span; rt.occ_weight = reg->occ_weight; rt.occ_samples = reg->occ_samples;
+    return true;
+}
+
+// nrf_composite_loss_backward and its indexed form (slot != NULL: rgb / sigma / d_rgb / d_sigma hold compacted rows); rt != NULL:
+// nrf_composite_reg_loss_backward (ray_terms holds five rows)
 int composite_loss_backward_any(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals, const float* rays_d,
                                 int64_t n_rays, int n_samples, int white_bkgd, const float* target, const nrf_loss_opts* loss, const int32_t* slot,
                                 float* pred, float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf,
-                                int64_t zero_n, void* stream) {
+                                int64_t zero_n, void* stream, const nrf::RayRegTerms* rt = nullptr) {
     if (!loss) return fail(NRF_EINVAL, "nrf_composite_loss_backward: loss is NULL");
     if (loss->struct_bytes != (int32_t)sizeof(nrf_loss_opts)) return fail(NRF_EINVAL, "nrf_loss_opts.struct_bytes is not sizeof(nrf_loss_opts)");
     if (!(loss->rgb_weight >= 0.0f) || !(loss->reg_weight >= 0.0f) || !(loss->depth_weight >= 0.0f) || !std::isfinite(loss->rgb_weight) ||
@@ -1061,9 +1075,12 @@ int composite_loss_backward_any(const float* rgb, int rgb_stride, const float* s
     nrf::LossTerms lt{};
     lt.rgb_weight = loss->rgb_weight; lt.reg_weight = loss->reg_weight; lt.depth_weight = loss->depth_weight;
     lt.target_depth = loss->target_depth; lt.noise_std = loss->noise_std; lt.noise = loss->noise; lt.rng_seed = loss->rng_seed;
-    const int r = nrf::launch_composite_loss_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, lt,
-                                                      pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n,
-                                                      (hipStream_t)stream, slot);
+    const int r = rt ? nrf::launch_composite_reg_loss_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd,
+                                                               target, lt, *rt, slot, pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms,
+                                                               zero_buf, zero_n, (hipStream_t)stream)
+                     : nrf::launch_composite_loss_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, lt,
+                                                           pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n,
+                                                           (hipStream_t)stream, slot);
     return r == NRF_OK ? NRF_OK : fail(r, "composite + loss + backward launch failed");
 }
 }  // namespace
@@ -1085,6 +1102,27 @@ int nrf_composite_loss_backward_indexed(const float* rgb, int rgb_stride, const 
     if ((reinterpret_cast<uintptr_t>(slot) & 3u) != 0) return fail(NRF_EINVAL, "nrf_composite_loss_backward_indexed: slot must be 4-byte aligned");
     return composite_loss_backward_any(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, loss, slot, pred,
                                        d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream);
+}
+
+int nrf_composite_reg_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals,
+                                    const float* rays_d, int64_t n_rays, int n_samples, int white_bkgd, const float* target,
+                                    const nrf_loss_opts* loss, const nrf_ray_reg* reg, const int32_t* slot, float* pred, float* d_rgb,
+                                    int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n,
+                                    void* stream) {
+    nrf::RayRegTerms rt{};
+    if (!ray_reg_terms(reg, rt)) return NRF_EINVAL;
+    if (slot && (reinterpret_cast<uintptr_t>(slot) & 3u) != 0) return fail(NRF_EINVAL, "nrf_composite_reg_loss_backward: slot must be 4-byte aligned");
+    return composite_loss_backward_any(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, loss, slot, pred,
+                                       d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream, &rt);
+}
+
+int nrf_ray_terms_finish(const float* ray_terms, int64_t n_rays, const nrf_ray_reg* reg, const float* losses4, float* losses6, void* stream) {
+    nrf::RayRegTerms rt{};
+    if (!ray_reg_terms(reg, rt)) return NRF_EINVAL;
+    if (n_rays <= 0 || n_rays > ((int64_t)1 << 30)) return fail(NRF_EINVAL, "nrf_ray_terms_finish: bad sizes");
+    if (!ray_terms || !losses4 || !losses6) return fail(NRF_EINVAL, "null pointer");
+    const int r = nrf::launch_ray_terms_finish(ray_terms, n_rays, rt.dist_weight, rt.occ_weight, losses4, losses6, (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "ray terms finish launch failed");
 }
 
 int64_t nrf_hier_train_workspace_bytes(int64_t n_rays, int n_samples, int n_importance) {

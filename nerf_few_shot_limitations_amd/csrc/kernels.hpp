@@ -229,6 +229,15 @@ int launch_composite_loss_backward(const float* rgb, int rgb_stride, const float
                                    int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, float* pred, float* d_rgb,
                                    int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n,
                                    hipStream_t s, const int32_t* slot = nullptr);      // slot (R,S): the indexed form, rgb / sigma / d_* hold compacted rows
+// The same launch with the two few-shot ray regularisers (ray_reg.hip; nerfhip.h: nrf_ray_reg, whose fields these are); ray_terms
+// (5,R): the three rows above | D_r | O_r.  launch_ray_terms_finish: losses6 from rows 3, 4 and the optimiser launch's four values.
+struct RayRegTerms { float dist_weight, dist_inv_span, occ_weight; int occ_samples; };
+int launch_composite_reg_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
+                                       int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, const RayRegTerms& rt,
+                                       const int32_t* slot, float* pred, float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride,
+                                       float* ray_terms, float* zero_buf, int64_t zero_n, hipStream_t s);
+int launch_ray_terms_finish(const float* ray_terms, int64_t n_rays, float dist_weight, float occ_weight, const float* losses4, float* losses6,
+                            hipStream_t s);
 // partial sums of squares of a flat vector (one float per workgroup, fixed order); the optimiser launch adds them up
 constexpr int kMaxSqnormPartials = 1024;
 inline int sqnorm_partials(int64_t n) {

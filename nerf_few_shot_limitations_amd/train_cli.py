@@ -1,5 +1,5 @@
 """python -m nerf_few_shot_limitations_amd.train_cli --config experiments/baseline.yaml --data data/nerf_synthetic/lego \\
-        [--n-importance N [--coarse-weight W]] [--recipe train|multiscale] [--epochs N] [--mode bf16|f16|f32] [--eval-mode f16] [--out DIR] [--checkpoint CKPT]
+        [--n-importance N [--coarse-weight W]] [--dist-weight W] [--occ-weight W --occ-samples K] [--recipe train|multiscale] [--epochs N] [--mode bf16|f16|f32] [--eval-mode f16] [--out DIR] [--checkpoint CKPT]
         [--dino-weights DIR | --dino-maps maps.pt] [--train-extractor] [--fused-inputs] [--seed 0]
         [--occupancy-res N [--occupancy-box LO HI] [--occupancy-threshold T] [--occupancy-decay D] [--occupancy-refresh-every K]
          [--occupancy-cells-per-refresh C] [--occupancy-warmup STEPS] [--occupancy-per-view]]
@@ -81,6 +81,15 @@ depths.  It implies the --fused-inputs route (pixel ids in, no per-sample input 
 noise are not part of the hierarchical step), any --occupancy-* flag, --train-extractor (no per-sample gradients are handed out), N < 0,
 W < 0, and --coarse-weight without --n-importance.
 
+--dist-weight W / --occ-weight W --occ-samples K (0, the default: off) add the two few-shot ray regularisers to the step's loss
+(`FusedStep(dist_weight=, occ_weight=, occ_samples=)`; nerfhip.h: nrf_ray_reg): W * the distortion loss of mip-NeRF 360 -- sum_ij
+w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i on the weights and the interval midpoints scaled by 1 / (far - near), against
+floaters -- and W * the occlusion penalty of FreeNeRF -- the mean rectified density of every ray's first K samples, against a wall
+of density in front of the cameras.  Both work with either recipe, with --fused-inputs and with --occupancy-*; the step is then
+the multi-term one (clipped optimiser entry) with one small launch more.  Refused before the data set is read: a negative weight,
+--occ-weight > 0 without --occ-samples K >= 1, --occ-samples without --occ-weight, and either weight together with --n-importance
+(the hierarchical step takes the plain rgb loss).
+
 --checkpoint resumes a run: weights, Adam moments and step count, epoch counter and best PSNR (the reference's train.py saves
 these keys, :374-389, but has no resume path); the LR schedule is a function of the epoch.  wandb and LPIPS are not part of
 this command.
@@ -90,6 +99,7 @@ from __future__ import annotations
 import argparse
 import ctypes as C
 import json
+import math
 import os
 import time
 
@@ -191,6 +201,31 @@ def hierarchical_args_error(args, cfg=None):
     if getattr(args, "train_extractor", False):
         return "--n-importance with --train-extractor is refused: the hierarchical step hands out no per-sample gradients"
     return None
+
+
+def ray_reg_args_error(args):
+    """Why --dist-weight / --occ-weight / --occ-samples cannot run with these arguments (None: they can, or none was given).  Decided
+    before any GPU work, like hierarchical_args_error."""
+    dw, ow = float(getattr(args, "dist_weight", 0.0) or 0.0), float(getattr(args, "occ_weight", 0.0) or 0.0)
+    k = getattr(args, "occ_samples", None)
+    if not (dw >= 0.0 and ow >= 0.0 and math.isfinite(dw) and math.isfinite(ow)):
+        return "--dist-weight and --occ-weight must be finite and >= 0 (0: off)"
+    if ow > 0.0 and (k is None or int(k) < 1):
+        return "--occ-weight needs --occ-samples K (K >= 1): the number of samples at the front of every ray the penalty covers"
+    if ow == 0.0 and k is not None:
+        return "--occ-samples needs --occ-weight W (W > 0): without the occlusion term the flag would be ignored"
+    if (dw > 0.0 or ow > 0.0) and int(getattr(args, "n_importance", 0) or 0) > 0:
+        return "--dist-weight / --occ-weight with --n-importance is refused: the hierarchical step takes the plain rgb loss"
+    return None
+
+
+def ray_reg_options(args, near, far):
+    """FusedStep's keywords of --dist-weight / --occ-weight / --occ-samples ({} when both are off); dist_span = far - near, so that the
+    per-sample route (`step(points, z_vals, ...)`, which has no near / far) scales the midpoints as the ray routes do."""
+    dw, ow = float(getattr(args, "dist_weight", 0.0) or 0.0), float(getattr(args, "occ_weight", 0.0) or 0.0)
+    if dw == 0.0 and ow == 0.0:
+        return {}
+    return dict(dist_weight=dw, occ_weight=ow, occ_samples=int(getattr(args, "occ_samples", None) or 0), dist_span=float(far) - float(near))
 
 
 OCCUPANCY_FLAGS = ("occupancy_box", "occupancy_threshold", "occupancy_decay", "occupancy_refresh_every", "occupancy_cells_per_refresh",
@@ -556,6 +591,13 @@ def main(argv=None):
                          "hierarchical validation (module docstring); 0: off")
     ap.add_argument("--coarse-weight", type=float, default=None, metavar="W",
                     help="with --n-importance: the coarse image's share of the loss, rgb_weight * (W * mse_coarse + mse_fine) (default 1.0)")
+    ap.add_argument("--dist-weight", type=float, default=0.0, metavar="W",
+                    help="add W * the distortion loss of mip-NeRF 360 (weights against interval midpoints scaled by 1 / (far - near)) to the "
+                         "step's loss: FusedStep(dist_weight=W) (module docstring); 0: off")
+    ap.add_argument("--occ-weight", type=float, default=0.0, metavar="W",
+                    help="add W * the occlusion penalty of FreeNeRF (mean rectified density of every ray's first --occ-samples samples): "
+                         "FusedStep(occ_weight=W, occ_samples=K) (module docstring); 0: off")
+    ap.add_argument("--occ-samples", type=int, default=None, metavar="K", help="with --occ-weight: the samples at the front of every ray it covers")
     ap.add_argument("--occupancy-res", type=int, default=0,
                     help="train under an occupancy grid of N^3 cells (a multiple of 32; 0: off): the network runs on the samples in occupied "
                          "cells alone, FusedStep.step_view(occupancy=) (module docstring)")
@@ -578,7 +620,7 @@ def main(argv=None):
                     help="--data-parallel on a box with ONE GPU: every rank on cuda:0, the gradient all-reduce over gloo through host memory "
                          "(RCCL refuses two ranks on one card); exercises the sharding and the collective, not multi-GPU speed")
     args = ap.parse_args(argv)
-    problem = (hierarchical_args_error(args) or extractor_args_error(args, load_config(args.config))
+    problem = (hierarchical_args_error(args) or ray_reg_args_error(args) or extractor_args_error(args, load_config(args.config))
                or occupancy_args_error(args, load_config(args.config)))
     if problem:
         raise SystemExit(problem)
@@ -641,7 +683,7 @@ def main(argv=None):
     model.dino_grad = ext is not None
     model = model.to(dev).train()
     step = FusedStep(model, white_bkgd=rs["white_bkgd"], data_parallel=world > 1, **step_options(cfg, args.recipe),
-                     **({"seed": args.seed} if args.recipe == "multiscale" else {}))
+                     **({"seed": args.seed} if args.recipe == "multiscale" else {}), **ray_reg_options(args, rs["near"], rs["far"]))
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed)
     # (the single grid is not part of a checkpoint: a resumed run starts again from the all-ones grid and its warm-up; the per-view

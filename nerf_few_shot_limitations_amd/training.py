@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import math
 
 import torch
 
@@ -945,11 +946,21 @@ class FusedStep:
     is the norm's partial sums (with max_grad_norm).  The returned value is the total loss; `last_losses` holds the components
     ({'total', 'rgb', 'depth', 'reg'}: device scalars, the reference's `losses` dict) and `last_grad_norm` the pre-clip norm
     (device scalar, None without clipping).  Nothing synchronises.
+
+    Few-shot ray regularisers (nerfhip.h: nrf_ray_reg), on __call__, step_rays and step_view, with or without occupancy=:
+
+        step = FusedStep(model, lr=5e-4, dist_weight=1e-2, occ_weight=1e-2, occ_samples=4)
+
+    dist_weight * mean_r D_r is mip-NeRF 360's distortion loss on the weights and the interval midpoints scaled by 1 / dist_span
+    (None: far - near of the step), occ_weight * mean_r O_r FreeNeRF's penalty on the density of every ray's first occ_samples
+    samples.  With either weight on the step is the multi-term one with nrf_composite_reg_loss_backward as its loss launch and
+    one small launch (nrf_ray_terms_finish) behind the optimiser; `last_losses` gains 'dist' and 'occ' (unweighted; 0 for a term
+    whose weight is 0), 'total' and the returned loss include both.  With both weights 0 (the default) nothing changes.
     """
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rgb_weight=1.0, white_bkgd=False,
                  process_group=None, data_parallel=False, reg_weight=0.0, depth_weight=0.0, noise_std=0.0, max_grad_norm=None,
-                 decoupled_weight_decay=False, seed=None):
+                 decoupled_weight_decay=False, seed=None, dist_weight=0.0, occ_weight=0.0, occ_samples=0, dist_span=None):
         """data_parallel=True (inside an initialised torch.distributed job): every rank passes ITS shard of the ray batch
         (equal sizes), the flat gradient vector is averaged over the ranks with one all-reduce before Adam (the norm of
         max_grad_norm is taken behind it, so all ranks clip alike), and the returned loss is this rank's.
@@ -959,12 +970,22 @@ class FusedStep:
             raise NotImplementedError("FusedStep: unknown network family")
         if min(float(rgb_weight), float(reg_weight), float(depth_weight), float(noise_std)) < 0.0:
             raise ValueError("FusedStep: loss weights and noise_std must be >= 0")
+        if not (float(dist_weight) >= 0.0 and float(occ_weight) >= 0.0 and math.isfinite(float(dist_weight)) and math.isfinite(float(occ_weight))):
+            raise ValueError("FusedStep: dist_weight and occ_weight must be finite and >= 0")
+        if int(occ_samples) < 0 or (float(occ_weight) > 0.0 and int(occ_samples) < 1):
+            raise ValueError("FusedStep: occ_samples must be >= 1 with occ_weight > 0 (and never negative)")
+        if dist_span is not None and not (math.isfinite(float(dist_span)) and float(dist_span) > 0.0):
+            raise ValueError("FusedStep: dist_span must be finite and > 0 (None: far - near of the step)")
         self.model = model
         self.data_parallel = bool(data_parallel)
         self.group = process_group
         self.opt = Adam(model, lr, betas, eps, weight_decay, decoupled=decoupled_weight_decay, max_grad_norm=max_grad_norm)
         self.rgb_weight = float(rgb_weight)
         self.reg_weight, self.depth_weight, self.noise_std = float(reg_weight), float(depth_weight), float(noise_std)
+        self.dist_weight, self.occ_weight, self.occ_samples = float(dist_weight), float(occ_weight), int(occ_samples)
+        self.dist_span = None if dist_span is None else float(dist_span)
+        self.ray_reg = self.dist_weight > 0.0 or self.occ_weight > 0.0        # the step with the two few-shot terms
+        self._reg = None                    # nrf_ray_reg of the last regularised loss launch: _finish hands it to nrf_ray_terms_finish
         self.seed = None if seed is None else int(seed)
         self.white = int(bool(white_bkgd))
         self._loss_vec, self.last_grad_norm = None, None
@@ -975,7 +996,8 @@ class FusedStep:
     @property
     def last_losses(self):
         """The last step's loss terms as device scalars (no sync): {'total'} of the plain step, {'total', 'rgb', 'depth', 'reg'}
-        (nerf_mlp.NeRFLoss's dict, unweighted components) of the multi-term one; None before the first step."""
+        (nerf_mlp.NeRFLoss's dict, unweighted components) of the multi-term one, and 'dist', 'occ' behind them of the step with the
+        few-shot ray regularisers; None before the first step."""
         v = self._loss_vec
         if v is None:
             return None
@@ -984,6 +1006,8 @@ class FusedStep:
             parts, R = self._hier_parts
             mse = parts.sum(dim=1) / (3.0 * R)              # formed when asked for (torch reductions on the stream: no sync), from the step's buffer
             return {"total": total, "coarse": mse[0], "fine": mse[1]}
+        if v.dim() == 1 and v.numel() == 6:
+            return {"total": v[0], "rgb": v[1], "depth": v[2], "reg": v[3], "dist": v[4], "occ": v[5]}
         return {"total": v} if v.dim() == 0 else {"total": v[0], "rgb": v[1], "depth": v[2], "reg": v[3]}
 
     def _buffers(self, n, R, S, dev, h, mode):
@@ -993,7 +1017,8 @@ class FusedStep:
             self.ctx, self.nbytes = _context(h, mode, n, dev)
             self.out4, self.d_out4 = f(n, 4), f(n, 4)                 # V1: [rgb, sigma] rows; V2: rgb | density packed in the same rows
             self.pred = f(R, 3)
-            self.ray_loss = f(3, R)              # row 0: squared rgb errors; rows 1, 2 (multi-term loss): sum of w^2, |depth error|
+            # row 0: squared rgb errors; rows 1, 2 (multi-term loss): sum of w^2, |depth error|; rows 3, 4 (ray regularisers): D_r, O_r
+            self.ray_loss = f(5 if self.ray_reg else 3, R)
             self.grad = torch.zeros(self.model.flat_params().flat.numel(), dtype=torch.float32, device=dev)
             self._key = key
 
@@ -1016,7 +1041,7 @@ class FusedStep:
         either way).  The noise seed of step t is seed + t: step_count is read before the step increments it."""
         opt = self.opt
         multi = (self.reg_weight > 0.0 or self.depth_weight > 0.0 or self.noise_std > 0.0 or opt.extended or target_depth is not None
-                 or noise is not None)
+                 or noise is not None or self.ray_reg)
         if not (multi or always):
             return False, None, None
         td = None if target_depth is None else L.dev_f32(target_depth, dev).reshape(R)
@@ -1028,14 +1053,24 @@ class FusedStep:
             seed = self.seed + opt.step_count
         return multi, L.loss_opts(self.rgb_weight, self.reg_weight, self.depth_weight, L.ptr(td), self.noise_std, L.ptr(nz), seed), (td, nz)
 
-    def _launch_loss(self, heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, slot=None):
+    def _launch_loss(self, heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, slot=None, span=None):
         """compositor -> d loss / d pred = 2 w (pred - target) / (3 R) -> compositor backward, and the flat gradient vector cleared:
         one launch (a ray's loss gradient needs only its own prediction); the rays' squared errors stay in ray_loss.  slot (the step
-        under a grid): the indexed kernel, for the plain and the multi-term loss alike.  Returns `multi`."""
+        under a grid): the indexed kernel, for the plain and the multi-term loss alike.  With the few-shot ray regularisers on, the
+        one entry that carries them (dense or indexed); span: the depth range their midpoints are scaled by.  Returns `multi`."""
         lib = L.lib()
         self._hier_parts = None
         multi, lo, keep = self._loss_setup(R, S, dev, target_depth, noise, always=slot is not None)
-        if slot is not None:
+        if self.ray_reg:
+            span = self.dist_span if self.dist_span is not None else span
+            if self.dist_weight > 0.0 and not (span is not None and math.isfinite(span) and span > 0.0):
+                raise ValueError("dist_weight > 0 needs a depth range: pass dist_span= to FusedStep (__call__ has no near / far), "
+                                 "or step with far > near")
+            self._reg = L.ray_reg(self.dist_weight, 1.0 / span if self.dist_weight > 0.0 else 0.0, self.occ_weight, self.occ_samples)
+            L.check(lib.nrf_composite_reg_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), C.byref(self._reg),
+                                                        None if slot is None else slot.data_ptr(), L.ptr(self.pred), *d_heads,
+                                                        L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
+        elif slot is not None:
             # the one indexed entry serves both steps: with every option off its bits are the mse kernel's
             L.check(lib.nrf_composite_loss_backward_indexed(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo),
                                                             slot.data_ptr(), L.ptr(self.pred), *d_heads, L.ptr(self.ray_loss),
@@ -1077,6 +1112,10 @@ class FusedStep:
             loss = torch.empty((4,), dtype=torch.float32, device=dev)
             opt._update(flat, self.grad, self.ray_loss, R, S, (loss_weight, self.depth_weight if target_depth is not None else 0.0,
                                                                self.reg_weight), loss)
+            if self.ray_reg:
+                # one small launch more: the two new terms summed in a fixed order and appended to the four
+                loss4, loss = loss, torch.empty((6,), dtype=torch.float32, device=dev)
+                L.check(lib.nrf_ray_terms_finish(L.ptr(self.ray_loss), R, C.byref(self._reg), L.ptr(loss4), L.ptr(loss), st))
             self._loss_vec, self.last_grad_norm = loss, opt.last_grad_norm
             loss = loss[0]
         else:
@@ -1096,6 +1135,8 @@ class FusedStep:
         d_dino_out: a preallocated (R*S, dino_dim) fp32 tensor that receives dL/d dino of this step (V3 with model.dino_grad: one
         more launch behind the weight gradients; project_fetch_backward turns it into the feature map's gradient)."""
         m = self.model
+        if self.dist_weight > 0.0 and self.dist_span is None:
+            raise ValueError("dist_weight > 0 needs dist_span= on a FusedStep that is called with depths: there is no near / far to take it from")
         if d_dino_out is not None:                  # (z_vals may still be a list when there is nothing to check)
             self._check_outputs(z_vals.numel(), d_dino_out)
         pts = L.dev_f32(points)
@@ -1198,6 +1239,8 @@ class FusedStep:
         w_fine) with w_coarse = rgb_weight * coarse_weight formed as one fp32 product."""
         if self.reg_weight > 0.0 or self.depth_weight > 0.0 or self.noise_std > 0.0:
             raise ValueError("the hierarchical step takes the plain rgb loss: a FusedStep with reg_weight, depth_weight or noise_std > 0 is refused")
+        if self.ray_reg:
+            raise ValueError("the hierarchical step takes the plain rgb loss: a FusedStep with dist_weight or occ_weight > 0 is refused")
         if occupancy is not None:
             raise ValueError("the hierarchical step is not combined with occupancy=")
         if d_dino_out is not None or points_out is not None:
@@ -1414,7 +1457,7 @@ class FusedStep:
                 L.check(lib.nrf_mlp_forward_train_rays(h, C.byref(rays), R, C.byref(opts), L.ptr(out[0]), L.ptr(out[1]), ctx, self.nbytes, st))
                 rows, slot = n, None
             del keep
-            multi = self._launch_loss(heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, slot)
+            multi = self._launch_loss(heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, slot, span=float(far) - float(near))
             if occupancy is None or rows:
                 self._network_backward(h, mode, rows, out, d_out, ctx, st, d_dino_out)
             return self._finish(multi, R, S, dev, target_depth, st)

@@ -64,9 +64,10 @@ def standin_feature_maps(images, dim=64, grid=9):
     return torch.stack(maps).contiguous()
 
 
-def train_field(net, cfg, scene_dir, train_mode, seed=0, epoch_scale=1.0, sigma_bias=None, v1_batch=None):
+def train_field(net, cfg, scene_dir, train_mode, seed=0, epoch_scale=1.0, sigma_bias=None, v1_batch=None, step_options=None):
     """Train on the scene's train split; returns (model, info).  The progressive schedule's stage boundaries (epochs 50 / 100,
-    train.py:249-259) scale with `epoch_scale` when fewer than the YAML's 200 epochs are run."""
+    train.py:249-259) scale with `epoch_scale` when fewer than the YAML's 200 epochs are run.  step_options: further keywords of the
+    FusedStep (tools/few_shot_ray_reg.py: the ray regularisers)."""
     import nerf_few_shot_limitations_amd as N
     from nerf_few_shot_limitations_amd import train_cli
     from nerf_few_shot_limitations_amd.training import FusedStep
@@ -94,7 +95,7 @@ def train_field(net, cfg, scene_dir, train_mode, seed=0, epoch_scale=1.0, sigma_
             head.bias.fill_(float(sigma_bias))
     model = model.to(dev).train()
     o = cfg["optimizer"]
-    step = FusedStep(model, lr=float(o["lr"]), weight_decay=float(o["weight_decay"]), rgb_weight=1.0)
+    step = FusedStep(model, lr=float(o["lr"]), weight_decay=float(o["weight_decay"]), rgb_weight=1.0, **(step_options or {}))
     gen = torch.Generator(device=dev)
     gen.manual_seed(seed)
     epochs = int(cfg["training"]["epochs"])
