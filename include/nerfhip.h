@@ -424,6 +424,10 @@ int nrf_debug_pack_input_grad(const nrf_arch* arch, const nrf_linear* linears, i
 int nrf_debug_pack_input_grad_v3(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int mma_mode,
                                  uint8_t* stream_out, int64_t stream_cap, int64_t* stream_bytes);
 
+/* Host-only: the frequency mask's scale id of every flat parameter (nrf_model_set_freq_mask): position column c is id c, direction
+ * column c is id 3*(2*pos_freq+1) + c, -1 = the parameter is not scaled.  out (may be NULL to query n_ids): nrf_param_count values. */
+int nrf_debug_freq_mask_ids(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int8_t* out, int64_t cap, int64_t* n_ids);
+
 /* Host-only: how render_kernel / render_hold_kernel deal a launch of n_rays rays x n_samples samples to the workgroups of a device
  * with n_cu compute units, for a geometry of cols_per_wave sample columns per wave (64: NRF_MMA_BF16 / F16, 32: the fp32-class modes).
  * head[4] = { 1: the even deal / 0: equal tiles round-robin, log2 of the uniform deal's samples per ray and pass, workgroups,
@@ -466,6 +470,24 @@ int64_t nrf_param_count(const nrf_model* m);
  * ONE mask -- a second call for the other mode would mark the first one's backward weights
  * stale. */
 int nrf_model_update_device(nrf_model* m, const float* flat_params, int mode_mask, void* stream);
+
+/* Per-column scale of the positional encodings (FreeNeRF's frequency mask, general form).
+ * pos_scale: HOST, 3*(2*pos_freq+1) floats in the encoder's column order [x | sin f0 | cos f0 | sin f1 | ...], or NULL = all ones.
+ * dir_scale: HOST, 3*(2*dir_freq+1) floats, or NULL; must be NULL for NRF_NET_V1.
+ * Values finite and in [0,1], otherwise NRF_EINVAL.  A mask that is all ones (or both NULL) clears the mask.
+ *
+ * A mask m on an encoding is a column scale of the Linears that read it, W (m . enc) = (W diag m) enc: layers.0 (V1),
+ * density_layers.0 and the direction columns of color_layers.0 (V2), the position columns of dino_fusion.fusion.0 and the same
+ * columns of color_layers.0 (V3).  The setter only RECORDS the mask in the handle: no GPU call, no copy, no synchronisation.
+ * It takes effect at the next pack -- nrf_model_update_device (the modes in its mask), nrf_model_update or nrf_model_create
+ * (every mode) -- which writes the streams a pack of parameters holding the fp32 products weight * scale would write; every render,
+ * forward and backward entry reads those streams.  Each mode remembers the mask its streams were last packed with and scales the
+ * weight gradients of nrf_mlp_backward* with that one (dW = (dZ enc^T) diag m; biases are never scaled), so a forward, its backward
+ * and its weight gradients agree; a hidden column (scale 0) receives gradient exactly 0.  Setting a mask that differs from the
+ * recorded one marks the backward weights of all modes stale: nrf_mlp_backward* refuses a mode until it has been re-packed.
+ * The getter returns the recorded mask (either pointer may be NULL) and active = 1 unless it is all ones. */
+int nrf_model_set_freq_mask(nrf_model* m, const float* pos_scale, const float* dir_scale);
+int nrf_model_get_freq_mask(const nrf_model* m, float* pos_scale, float* dir_scale, int* active);
 
 /* Bytes of saved tensors ("context") a forward_train/backward pair needs for n
  * samples; the caller allocates it (device) and keeps it until backward ran.  It holds

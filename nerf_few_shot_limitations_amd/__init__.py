@@ -7,7 +7,7 @@ surface.  Everything numeric runs in libnerfhip.so
 contain '-'.)
 """
 from .ray_sampler import get_rays, sample_points_along_rays, hierarchical_sampling, sample_pdf, sample_pdf_sorted, get_ray_batch
-from .positional_encoding import PositionalEncoding
+from .positional_encoding import PositionalEncoding, freq_mask_columns, freq_mask_visible
 from .nerf_model import NeRFMLP, density_normals, load_checkpoint_into
 from .volume_renderer import VolumeRenderer, volume_render_radiance
 from .renderer import (render_rays, render_camera, render_hierarchical, render_camera_hierarchical, render_rays_emit, composite_merge,
@@ -22,7 +22,7 @@ from .dino_feature_model import LoRALinear, SpatialDINOFeatures, MultiScaleDINOF
 from .dino_backbone import Dinov2Backbone, build_backbone, load_backbone_weights
 
 __all__ = ["get_rays", "sample_points_along_rays", "hierarchical_sampling", "sample_pdf", "sample_pdf_sorted", "get_ray_batch",
-           "PositionalEncoding", "NeRFMLP", "density_normals", "load_checkpoint_into", "VolumeRenderer", "volume_render_radiance",
+           "PositionalEncoding", "freq_mask_columns", "freq_mask_visible", "NeRFMLP", "density_normals", "load_checkpoint_into", "VolumeRenderer", "volume_render_radiance",
            "render_rays", "render_camera", "render_hierarchical", "render_camera_hierarchical", "render_rays_emit",
            "composite_merge", "NeRFRenderer", "make_dino", "OccupancyGrid",
            "load_config", "resolve_near_far", "model_from_config", "render_settings",

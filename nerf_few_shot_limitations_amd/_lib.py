@@ -235,6 +235,9 @@ SIGNATURES = {
     # training path
     "nrf_param_count": (C.c_int64, [C.c_void_p]),
     "nrf_model_update_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "nrf_model_set_freq_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrf_model_get_freq_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "nrf_debug_freq_mask_ids": (C.c_int, [C.POINTER(nrf_arch), C.POINTER(nrf_linear), C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
     "nrf_train_context_bytes": (C.c_int64, [C.c_void_p, C.c_int, C.c_int64]),
     "nrf_mlp_forward_train_v1": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "nrf_mlp_backward_v1": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

@@ -50,6 +50,9 @@ SUBDIR_SOURCES = [("hier_train.hip", "hier_train", [], HIER_TRAIN_DIR)]
 # (tests/golden/kernel_resources_ray_reg.json).
 RAY_REG_DIR = "ray_reg"
 RAY_REG_SOURCES = [("ray_reg.hip", "ray_reg", [], RAY_REG_DIR)]
+# The frequency mask's re-pack and weight-gradient reduce (freq_mask.hip): likewise (tests/golden/kernel_resources_freq_mask.json).
+FREQ_MASK_DIR = "freq_mask"
+FREQ_MASK_SOURCES = [("freq_mask.hip", "freq_mask", [], FREQ_MASK_DIR)]
 # -Rpass-analysis=kernel-resource-usage: the backend reports every kernel's registers / spills / scratch; kept beside the object
 # (<name>.o.remarks, see kernel_resources()) so that a toolchain or flag change that breaks the AGPR parking or introduces
 # spills in a headline kernel is caught by tests/test_kernel_resources.py
@@ -119,7 +122,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         return obj, True
 
     with cf.ThreadPoolExecutor(max_workers=os.cpu_count() or 8) as ex:
-        res = list(ex.map(one, [*SOURCES, *SUBDIR_SOURCES, *RAY_REG_SOURCES]))
+        res = list(ex.map(one, [*SOURCES, *SUBDIR_SOURCES, *RAY_REG_SOURCES, *FREQ_MASK_SOURCES]))
     objs = [o for o, _ in res]
     if not any(built for _, built in res) and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(objs):
         os.utime(LIB)          # nothing to do (e.g. only a comment of this file changed): restore the fast path

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/nerfhip.h"
+#include "freq_mask.hpp"
 #include "kernels.hpp"
 #include "packing.hpp"
 #include "ray_deal.hpp"
@@ -112,23 +113,51 @@ struct nrf_model {
     int32_t* d_src[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};   // [forward|backward][packing.hpp stream kind] element sources
     int64_t n_src[2][3] = {{0, 0, 0}, {0, 0, 0}};                                        // (no backward stream in the split mode)
     int32_t* d_bias_src = nullptr;
+    // frequency mask (freq_mask.hpp): the recorded one takes effect at the next pack; each mode remembers what its streams were
+    // last packed with, and its weight gradients scale with that (train.freq[mode]), so a forward, its backward and its weight
+    // gradients always agree
+    nrf::FreqMaskArgs freq{};
+    bool freq_active = false;
+    nrf::FreqMaskArgs freq_packed[nrf::kModes]{};
+    bool freq_packed_active[nrf::kModes] = {false, false, false, false};
+    int8_t* d_freq_ids = nullptr;
 };
 
 namespace {
 
+// the streams of `mode` now hold the recorded mask
+void mark_packed(nrf_model* m, int mode) {
+    m->freq_packed[mode] = m->freq;
+    m->freq_packed_active[mode] = m->freq_active;
+    if (mode < 3) m->train.freq[mode] = m->freq_active ? &m->freq_packed[mode] : nullptr;
+}
+
+bool same_mask(const nrf::FreqMaskArgs& a, const nrf::FreqMaskArgs& b) { return std::memcmp(a.scale, b.scale, sizeof(a.scale)) == 0; }
+
+// what the host packer reads: the Linears themselves, or under a mask a copy with the masked columns multiplied in fp32
+const std::vector<nrf::HostLinear>& pack_source(const nrf_model* m, bool active, const nrf::FreqMaskArgs& f, std::vector<nrf::HostLinear>& scaled) {
+    if (!active) return m->lin;
+    scaled = m->lin;
+    nrf::freq_scale_linears(m->arch, scaled, f.scale);
+    return scaled;
+}
+
 int upload(nrf_model* m, hipStream_t s, bool allocate) {
+    std::vector<nrf::HostLinear> scaled;
+    const std::vector<nrf::HostLinear>& lin = pack_source(m, m->freq_active, m->freq, scaled);
     for (int mode = 0; mode < nrf::kModes; ++mode) {
-        m->h_stream[mode] = nrf::pack_stream(m->plan, m->lin, mode);
+        m->h_stream[mode] = nrf::pack_stream(m->plan, lin, mode);
         const size_t bytes = m->h_stream[mode].bytes.size();
         if (allocate) NRF_HIP(hipMalloc(&m->d_stream[mode], bytes));
         NRF_HIP(hipMemcpyAsync(m->d_stream[mode], m->h_stream[mode].bytes.data(), bytes, hipMemcpyHostToDevice, s));
         m->net.stream[mode] = m->d_stream[mode];
         m->net.n_chunks[mode] = m->h_stream[mode].n_chunks;
+        mark_packed(m, mode);
     }
     m->lin_stale = false;
     if (m->train_ready) {
         for (int mode = 0; mode < 3; ++mode) {
-            const nrf::PackedStream ps = nrf::pack_stream(m->bplan, m->lin, mode);      // (with the W0d^T layer: ensure_train)
+            const nrf::PackedStream ps = nrf::pack_stream(m->bplan, lin, mode);         // (with the W0d^T layer: ensure_train)
             NRF_HIP(hipMemcpyAsync(m->d_bstream[mode], ps.bytes.data(), ps.bytes.size(), hipMemcpyHostToDevice, s));
             NRF_HIP(hipStreamSynchronize(s));
             m->bfresh[mode] = true;
@@ -161,6 +190,13 @@ int ensure_sources(nrf_model* m) {
     const std::vector<int32_t> bsrc = nrf::bias_sources(m->plan, m->layout);
     NRF_HIP(hipMalloc((void**)&m->d_bias_src, bsrc.size() * sizeof(int32_t)));
     NRF_HIP(hipMemcpy(m->d_bias_src, bsrc.data(), bsrc.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    // flat parameter index -> scale id of the frequency mask: one table for every segment of the masked re-pack and for the
+    // masked weight-gradient reduce
+    const std::vector<int8_t> ids = nrf::freq_scale_ids(m->arch, m->layout);
+    NRF_HIP(hipMalloc((void**)&m->d_freq_ids, ids.size()));
+    NRF_HIP(hipMemcpy(m->d_freq_ids, ids.data(), ids.size(), hipMemcpyHostToDevice));
+    m->freq.ids = m->d_freq_ids;
+    for (int mode = 0; mode < nrf::kModes; ++mode) m->freq_packed[mode].ids = m->d_freq_ids;
     return NRF_OK;
 }
 
@@ -197,7 +233,9 @@ int ensure_train(nrf_model* m) {
         }
     }
     for (int mode = 0; mode < 3; ++mode) {
-        const nrf::PackedStream ps = nrf::pack_stream(m->bplan, m->lin, mode);
+        // under the mask the mode's forward stream holds; current only if that is also the recorded one
+        std::vector<nrf::HostLinear> scaled;
+        const nrf::PackedStream ps = nrf::pack_stream(m->bplan, pack_source(m, m->freq_packed_active[mode], m->freq_packed[mode], scaled), mode);
         NRF_HIP(hipMalloc(&m->d_bstream[mode], ps.bytes.size()));
         NRF_HIP(hipMemcpy(m->d_bstream[mode], ps.bytes.data(), ps.bytes.size(), hipMemcpyHostToDevice));
         // the layer is whole chunks: 16 fragments per chunk, DT * 16 (16-bit) or DT * 32 (fp32) fragments
@@ -208,7 +246,8 @@ int ensure_train(nrf_model* m) {
         m->train.n_bchunks[mode] = ps.n_chunks - g_chunks - i_chunks;
         m->train.gstream[mode] = g_chunks ? static_cast<const char*>(m->d_bstream[mode]) + (size_t)m->train.n_bchunks[mode] * 16 * 1024 : nullptr;
         m->train.istream[mode] = i_chunks ? static_cast<const char*>(m->d_bstream[mode]) + ((size_t)m->train.n_bchunks[mode] + g_chunks) * 16 * 1024 : nullptr;
-        m->bfresh[mode] = !m->lin_stale;
+        m->bfresh[mode] = !m->lin_stale && same_mask(m->freq_packed[mode], m->freq);
+        m->train.freq[mode] = m->freq_packed_active[mode] ? &m->freq_packed[mode] : nullptr;
     }
     for (int f32 = 0; f32 < 2; ++f32) {
         const std::vector<int32_t> src = nrf::stream_sources(m->bplan, m->layout, f32);
@@ -378,6 +417,7 @@ int nrf_model_create(nrf_model** out, int device, const nrf_arch* arch, const nr
         delete m;
         return fail(NRF_EUNSUPPORTED, std::string("libnerfhip is built for gfx950 only, device is ") + prop.gcnArchName);
     }
+    for (float& v : m->freq.scale) v = 1.0f;
     m->net.arch = *arch;
     m->net.device = device;
     m->net.cu_count = prop.multiProcessorCount;
@@ -414,6 +454,7 @@ void nrf_model_destroy(nrf_model* m) {
             if (m->d_src[i][j]) (void)hipFree(m->d_src[i][j]);
     if (m->d_maps) (void)hipFree(m->d_maps);
     if (m->d_bias_src) (void)hipFree(m->d_bias_src);
+    if (m->d_freq_ids) (void)hipFree(m->d_freq_ids);
     delete m;
 }
 
@@ -732,12 +773,46 @@ int nrf_model_update_device(nrf_model* m, const float* flat_params, int mode_mas
         const int64_t n[3] = {m->n_src[0][kind], bwd ? m->n_src[1][kind] : 0, bias ? m->plan.n_bias : 0};
         const int modes[3] = {mode, mode, NRF_MMA_F32};
         void* out[3] = {m->d_stream[mode], bwd ? m->d_bstream[mode] : nullptr, bias ? m->d_bias : nullptr};
-        rc = nrf::launch_repack3(flat_params, src, n, modes, out, s);
+        rc = nrf::launch_repack3(flat_params, src, n, modes, out, s, m->freq_active ? &m->freq : nullptr);
         if (rc != NRF_OK) return fail(rc, "repack launch failed");
+        mark_packed(m, mode);
         bias = false;
     }
     m->lin_stale = true;
     for (int k = 0; k < 3; ++k) m->bfresh[k] = (mode_mask & (1 << k)) && m->train_ready;
+    return NRF_OK;
+}
+
+int nrf_model_set_freq_mask(nrf_model* m, const float* pos_scale, const float* dir_scale) {
+    if (!m) return fail(NRF_EINVAL, "nrf_model_set_freq_mask: model is NULL");
+    if (dir_scale && m->arch.net == NRF_NET_V1) return fail(NRF_EINVAL, "nrf_model_set_freq_mask: a V1 model reads no direction encoding (dir_scale must be NULL)");
+    const int np = nrf::freq_pos_cols(m->arch), nd = nrf::freq_dir_cols(m->arch);
+    if (np + nd > nrf::kFreqCols) return fail(NRF_EUNSUPPORTED, "nrf_model_set_freq_mask: too many encoding columns");
+    nrf::FreqMaskArgs f = m->freq;
+    for (float& v : f.scale) v = 1.0f;
+    bool active = false;
+    for (int part = 0; part < 2; ++part) {
+        const float* in = part ? dir_scale : pos_scale;
+        const int n = part ? nd : np, id0 = part ? np : 0;
+        for (int c = 0; in && c < n; ++c) {
+            if (!std::isfinite(in[c]) || in[c] < 0.0f || in[c] > 1.0f) return fail(NRF_EINVAL, "nrf_model_set_freq_mask: scales must be finite and in [0,1]");
+            f.scale[id0 + c] = in[c] == 0.0f ? 0.0f : in[c];            // (-0 is recorded as +0)
+            active = active || in[c] != 1.0f;
+        }
+    }
+    if (same_mask(f, m->freq)) return NRF_OK;
+    m->freq = f;
+    m->freq_active = active;
+    for (int k = 0; k < 3; ++k) m->bfresh[k] = false;           // every mode's backward weights are older than the mask now
+    return NRF_OK;
+}
+
+int nrf_model_get_freq_mask(const nrf_model* m, float* pos_scale, float* dir_scale, int* active) {
+    if (!m) return fail(NRF_EINVAL, "nrf_model_get_freq_mask: model is NULL");
+    const int np = nrf::freq_pos_cols(m->arch), nd = nrf::freq_dir_cols(m->arch);
+    if (pos_scale) std::memcpy(pos_scale, m->freq.scale, sizeof(float) * np);
+    if (dir_scale) std::memcpy(dir_scale, m->freq.scale + np, sizeof(float) * nd);
+    if (active) *active = m->freq_active ? 1 : 0;
     return NRF_OK;
 }
 
@@ -1521,6 +1596,21 @@ int nrf_debug_train_plan(const nrf_arch* arch, const nrf_linear* linears, int n_
     if (out) {
         if (cap < (int64_t)v.size()) return fail(NRF_EINVAL, "out too small");
         std::memcpy(out, v.data(), v.size() * sizeof(int32_t));
+    }
+    return NRF_OK;
+}
+
+int nrf_debug_freq_mask_ids(const nrf_arch* arch, const nrf_linear* linears, int n_linear, int8_t* out, int64_t cap, int64_t* n_ids) {
+    if (!arch || !linears || n_linear <= 0) return fail(NRF_EINVAL, "nrf_debug_freq_mask_ids: null argument");
+    std::string err;
+    std::vector<nrf::HostLinear> lin;
+    nrf::NetPlan plan;
+    if (!copy_linears(linears, n_linear, lin, err) || !nrf::make_plan(*arch, lin, plan, err)) return fail(NRF_EINVAL, err);
+    const std::vector<int8_t> ids = nrf::freq_scale_ids(*arch, nrf::param_layout(lin));
+    if (n_ids) *n_ids = (int64_t)ids.size();
+    if (out) {
+        if (cap < (int64_t)ids.size()) return fail(NRF_EINVAL, "out too small");
+        std::memcpy(out, ids.data(), ids.size());
     }
     return NRF_OK;
 }

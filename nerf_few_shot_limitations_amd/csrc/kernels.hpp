@@ -121,6 +121,7 @@ constexpr int kMaxJobs = 24;
 constexpr int kMaxMaskSlots = 20;
 constexpr int kMapStride = 3 * 320;      // per weight-gradient job: row_w[320] | row_b[320] | col[320]
 
+struct FreqMaskArgs;             // freq_mask.hpp
 struct TrainDev {
     const void* bstream[3];     // backward-chain (transposed) streams by NRF_MMA_*
     uint32_t n_bchunks[3];
@@ -136,6 +137,7 @@ struct TrainDev {
     const void* gstream[3];     // V3: the W0d^T fragments of dino_grad_kernel (train_dino_grad_impl.hpp), behind the chain's layers in bstream
     const void* istream[3];     // V1, V2: the W0^T (and color_layers.0^T) fragments of input_grad_kernel (train_input_grad_impl.hpp), likewise;
                                 // V3: the W0p^T and color_layers.0^T fragments of input_grad_v3_kernel (train_input_grad_v3_impl.hpp), behind gstream's
+    const FreqMaskArgs* freq[3];  // HOST: the frequency mask the mode's streams were last packed with, NULL = none: its weight gradients scale with it
 };
 
 int64_t train_ctx_bytes(const TrainDev& t, int mma_mode, int64_t n);
@@ -257,7 +259,9 @@ struct AdamExt {
 };
 int launch_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps, float wd, int step,
                  const AdamExt& ext, hipStream_t s);
-int launch_repack3(const float* flat, const int32_t* const src[3], const int64_t n_elems[3], const int modes[3], void* const out[3], hipStream_t s);
+// freq: the recorded frequency mask (freq_mask.hpp), or NULL: masked elements are converted from the fp32 product with their scale
+int launch_repack3(const float* flat, const int32_t* const src[3], const int64_t n_elems[3], const int modes[3], void* const out[3], hipStream_t s,
+                   const FreqMaskArgs* freq = nullptr);
 int launch_composite_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
                               int64_t n_rays, int S, int white_bkgd, const float* g_rgb, const float* g_depth, const float* g_w,
                               float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, hipStream_t s);

@@ -1,35 +1,13 @@
 // train_shared.hip -- what the training paths of all network families share: parameter re-pack, Adam, the weight gradients
 // (train_impl.hpp: weight_grad_kernel) and the size of the saved-tensor context
-#include "train_impl.hpp"
+#include "train_shared_core.hpp"
+#include "freq_mask_launch.hpp"
 
 namespace nrf {
 
 // ---------------------------------------------------------------------------------------------
 // parameter re-pack and Adam
 // ---------------------------------------------------------------------------------------------
-// out element i = convert(flat[src[i]]) (0 where src < 0); mode selects the operand type
-// one 16-bit operand pair of the stream: bf16, f16, or the split mode's hi / lo part (pair i lies in fragment i/256; odd
-// fragments carry the low parts: packing.cpp:pack_stream)
-__device__ __forceinline__ uint32_t convert_pair(float a, float b, int mode, int64_t pair) {
-    if (mode == NRF_MMA_BF16) return (uint32_t)pack_pair<bf16x2, false>(a, b);
-    a = __builtin_amdgcn_fmed3f(a, -65504.0f, 65504.0f);      // f16-typed streams saturate (packing.cpp:pack_stream does the same on the host)
-    b = __builtin_amdgcn_fmed3f(b, -65504.0f, 65504.0f);
-    if (mode == NRF_MMA_F16X3 && ((pair >> 8) & 1)) {
-        const f32x2 ab = {a, b};
-        const f32x2 hf = __builtin_convertvector(__builtin_convertvector(ab, f16x2), f32x2);
-        return (uint32_t)pack_pair<f16x2, false>(__fsub_rn(a, hf[0]), __fsub_rn(b, hf[1]));
-    }
-    return (uint32_t)pack_pair<f16x2, false>(a, b);
-}
-
-// forward stream, backward stream and bias table in ONE launch (an optimisation step re-packs all three): segment k holds
-// n[k] work items -- pairs of 16-bit elements, or single fp32 values when mode[k] is NRF_MMA_F32
-struct Repack3Args {
-    const int32_t* src[3];
-    void* out[3];
-    int64_t n[3];
-    int mode[3];
-};
 __global__ void __launch_bounds__(256) repack3_kernel(const float* __restrict__ flat, const Repack3Args a) {
     const int64_t total = a.n[0] + a.n[1] + a.n[2];
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -162,63 +140,7 @@ __global__ void __launch_bounds__(256) grad_sqnorm_partials_kernel(const float* 
 // lanes.  The only atomics left are the adds into `grad` (a weight shared by two jobs -- the fusion block of V3 -- receives
 // two of them; a + b = b + a, so the result does not depend on their order): gradients are bit-reproducible run to run.
 __global__ void __launch_bounds__(256) weight_grad_reduce_kernel(const GradKArgs P) {
-    const int job = blockIdx.x >> 6, wt = blockIdx.x & 63, wave = wt >> 3, tile = wt & 7;
-    const GradJob J = P.jobs[job];
-    constexpr int RT = 2, CT = 4;
-    const int i = tile / CT, j = tile % CT;
-    const int row0 = (wave & 3) * RT, col0 = (wave >> 2) * CT;
-    const int b0 = P.first_block[job], b1 = P.first_block[job + 1];
-    const int32_t* row_w = P.maps + J.map_off;
-    const int32_t* row_b = row_w + 320;
-    const int32_t* colm = row_b + 320;
-    if (row0 + i < J.MT && col0 + j < J.KT) {
-        // thread t: register group q = t >> 6, lane = t & 63: the 16 bytes that lane stored for registers 4q .. 4q+3
-        const int q = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
-        const f32x4* src = (const f32x4*)(P.partial + (int64_t)b0 * kPartialFloats + (wave * 8 + tile) * 16 * 64) + threadIdx.x;
-        // the partial sums are added in workgroup order (fixed: bit-reproducible), but LOADED sixteen at a time: one load per
-        // iteration and a wait on it is 32 HBM latencies in a row at the reference's batch (25 us for 61 MB, round-3 trace)
-        f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
-        constexpr int64_t kStep = kPartialFloats / 4;
-        int b = b0;
-        for (; b + 16 <= b1; b += 16, src += 16 * kStep) {
-            f32x4 v[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) v[k] = src[k * kStep];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) s += v[k];
-        }
-        for (; b + 4 <= b1; b += 4, src += 4 * kStep) {
-            f32x4 v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = src[k * kStep];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s += v[k];
-        }
-        for (; b < b1; ++b, src += kStep) s += *src;
-        const int col = colm[32 * (col0 + j) + c];
-#pragma unroll
-        for (int sub = 0; sub < 4; ++sub) {
-            const int r = 4 * q + sub;
-            const int o = 32 * (row0 + i) + (r & 3) + 8 * (r >> 2) + 4 * h;
-            const int w = row_w[o];
-            if (w >= 0 && col >= 0) unsafeAtomicAdd(P.grad + w + col, s[sub]);
-        }
-    }
-    if (tile == 0 && wave < J.MT && threadIdx.x < 32) {
-        const float* src = P.partial + (int64_t)b0 * kPartialFloats + 8 * 8 * 16 * 64 + 32 * wave + threadIdx.x;
-        float s = 0.0f;
-        int b = b0;
-        for (; b + 16 <= b1; b += 16, src += 16 * (int64_t)kPartialFloats) {
-            float v[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) v[k] = src[k * (int64_t)kPartialFloats];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) s += v[k];
-        }
-        for (; b < b1; ++b, src += kPartialFloats) s += *src;
-        const int bo = row_b[32 * wave + threadIdx.x];
-        if (bo >= 0) unsafeAtomicAdd(P.grad + bo, s);
-    }
+    weight_grad_reduce_body(P, NoScale{});
 }
 
 namespace {
@@ -248,7 +170,8 @@ int run_weight_grad(const DeviceNet& net, const TrainDev& t, const TrainKArgs& k
     const unsigned grid = (unsigned)wgrad_grid(t, mode_of<Mode>(), g.n_tiles32, g.first_block);
     g.partial = (float*)(k.ctx + k.partial_off);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), kLds, s, g);
-    hipLaunchKernelGGL(weight_grad_reduce_kernel, dim3((unsigned)(64 * t.n_jobs)), dim3(256), 0, s, g);
+    if (const FreqMaskArgs* f = t.freq[mode_of<Mode>()]) launch_weight_grad_reduce_masked(g, *f, s);     // the mode's streams were packed under a mask
+    else hipLaunchKernelGGL(weight_grad_reduce_kernel, dim3((unsigned)(64 * t.n_jobs)), dim3(256), 0, s, g);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { err = std::string("weight gradient launch: ") + hipGetErrorString(e); return NRF_EHIP; }
     return NRF_OK;
@@ -273,7 +196,8 @@ int launch_weight_grad(const DeviceNet& net, const TrainDev& t, int mode, const 
     }
 }
 
-int launch_repack3(const float* flat, const int32_t* const src[3], const int64_t n_elems[3], const int modes[3], void* const out[3], hipStream_t s) {
+int launch_repack3(const float* flat, const int32_t* const src[3], const int64_t n_elems[3], const int modes[3], void* const out[3], hipStream_t s,
+                   const FreqMaskArgs* freq) {
     Repack3Args a{};
     int64_t total = 0;
     for (int k = 0; k < 3; ++k) {
@@ -283,7 +207,8 @@ int launch_repack3(const float* flat, const int32_t* const src[3], const int64_t
     }
     if (total <= 0) return NRF_OK;
     const int64_t blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(repack3_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, flat, a);
+    if (freq) launch_repack3_masked(flat, a, (unsigned)(blocks < 4096 ? blocks : 4096), *freq, s);
+    else hipLaunchKernelGGL(repack3_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s, flat, a);
     return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
 }
 

@@ -4,6 +4,8 @@
 What `NeRFDINOTrainer.evaluate` does (src/training/train.py:294-342) for a use_dino=False config, on the fused renderer:
 load the YAML unchanged, the Blender split, the checkpoint (either key set), render every view (8 per launch), score
 PSNR/SSIM, dump PNGs and a metrics.json.  Without --checkpoint the weights are the module's random init (smoke use).
+A checkpoint written under a frequency mask (train_cli --freq-reg-end: keys `freq_mask_pos` / `freq_mask_dirs` beside the raw
+weights) is rendered under that mask (load_checkpoint_into applies it).
 use_dino configs condition every test view on the feature map and pose of TRAINING view 0 (train.py:203-208: `feat_idx = 0` outside
 training).  The map comes from the config's extractor (config.dino_model_from_config) run once on that view -- --dino-weights
 names a local transformers Dinov2Model checkpoint, --dino-random-init builds it with random weights (the published weights are

@@ -121,6 +121,72 @@ class NeRFMLP(nn.Module):
         self._flat = None
         self._train_ready = False
         self._bwd_modes = set()      # training modes whose BACKWARD stream matches _packed (mirrors the library's per-mode flag)
+        self._freq_mask = (None, None)   # host copies of the frequency mask (set_freq_mask); not a parameter or buffer
+
+    # ---- frequency mask (nerfhip.h: nrf_model_set_freq_mask) ---------------------------------------
+    def _freq_cols(self):
+        return 3 * (2 * self.pos_freq + 1), (0 if self.net == L.NRF_NET_V1 else 3 * (2 * self.dir_freq + 1))
+
+    def set_freq_mask(self, pos=None, dirs=None):
+        """Scale the columns of the positional encodings: pos (3 * (2 * pos_freq + 1),), dirs (3 * (2 * dir_freq + 1),; not for the
+        legacy form), values in [0, 1], None = all ones (positional_encoding.freq_mask_columns makes FreeNeRF's).  The mask is a
+        column scale of the Linears that read the encodings, applied where the weights are packed and where their gradient is
+        formed: every render and training route of this module evaluates the masked field from the next call on, hidden columns
+        receive gradient exactly 0.  It is no parameter or buffer: the state_dict keeps the raw weights (effective_state_dict has
+        the masked ones).  An all-ones mask clears it."""
+        n_pos, n_dir = self._freq_cols()
+        new = []
+        for name, v, n in (("pos", pos, n_pos), ("dirs", dirs, n_dir)):
+            if v is None:
+                new.append(None)
+                continue
+            if n == 0:
+                raise ValueError("set_freq_mask: the legacy form (V1) reads no direction encoding: dirs must be None")
+            a = np.ascontiguousarray(torch.as_tensor(v).detach().to("cpu", torch.float32).numpy()).reshape(-1).copy()
+            if a.shape[0] != n:
+                raise ValueError(f"set_freq_mask: {name} must hold {n} values, got {a.shape[0]}")
+            if not (np.isfinite(a).all() and (a >= 0.0).all() and (a <= 1.0).all()):
+                raise ValueError(f"set_freq_mask: {name} must be finite and in [0, 1]")
+            new.append(None if (a == 1.0).all() else a + np.float32(0.0))
+        old = self.__dict__.get("_freq_mask", (None, None))
+        same = all((a is None and b is None) or (a is not None and b is not None and np.array_equal(a, b)) for a, b in zip(old, new))
+        if same:
+            return
+        self._freq_mask = tuple(new)
+        if self._handle is not None:
+            self._push_freq_mask()
+        self._gen += 1                   # handle() re-packs before the next use on every route; a pending backward is refused
+
+    def _push_freq_mask(self):
+        pos, dirs = self.__dict__.get("_freq_mask", (None, None))
+        p = None if pos is None else pos.ctypes.data_as(C.c_void_p)
+        d = None if dirs is None else dirs.ctypes.data_as(C.c_void_p)
+        L.check(L.lib().nrf_model_set_freq_mask(self._handle, p, d))
+
+    @property
+    def freq_mask(self):
+        """(pos, dirs) of the current mask as float32 CPU tensors, None for a part that is all ones."""
+        return tuple(None if a is None else torch.from_numpy(a.copy()) for a in self.__dict__.get("_freq_mask", (None, None)))
+
+    def _freq_targets(self):
+        """[(Linear, first column, part index)] of the Linears that read the encodings (freq_mask.hpp's table)."""
+        lins = self.linears()
+        out = [(lins[0], 0, 0)]
+        if self.net != L.NRF_NET_V1:
+            out.append((self.color_mlp.color_layers[0], self.hidden_dim, 1))
+        return out
+
+    def effective_state_dict(self):
+        """state_dict() with the mask multiplied into the weight columns it scales (fp32 products): what a consumer that knows
+        nothing of masks must load to evaluate the same field."""
+        sd = {k: v.detach().clone() for k, v in self.state_dict().items()}
+        names = {id(p): k for k, p in self.named_parameters()}
+        for lin, c0, part in self._freq_targets():
+            a = self.__dict__.get("_freq_mask", (None, None))[part]
+            if a is not None:
+                w = sd[names[id(lin.weight)]]
+                w[:, c0:c0 + a.shape[0]] *= torch.from_numpy(a).to(w.device)
+        return sd
 
     # ---- parameters in the order include/nerfhip.h documents ------------------------------------
     def linears(self):
@@ -229,6 +295,11 @@ class NeRFMLP(nn.Module):
             L.check(L.lib().nrf_model_create(C.byref(h), idx, C.byref(arch), arr, n))
             self._handle, self._handle_dev = h, idx
             self._train_ready = False
+            if any(a is not None for a in self.__dict__.get("_freq_mask", (None, None))):
+                # a mask set before the handle existed: record it, then pack under it
+                self._push_freq_mask()
+                with torch.cuda.device(idx):
+                    L.check(L.lib().nrf_model_update(self._handle, arr, n, L.stream_ptr()))
         del keep
         self._packed, self._packed_modes = ver, None
         self._bwd_modes = {0, 1, 2} if self._train_ready else set()      # nrf_model_update packs every backward stream there is
@@ -250,6 +321,7 @@ class NeRFMLP(nn.Module):
         self._train_ready = False
         self._bwd_modes = set()
         self.__dict__.setdefault("_gen", 0)
+        self.__dict__.setdefault("_freq_mask", (None, None))
 
     def release(self):
         if getattr(self, "_handle", None) is not None:
@@ -319,7 +391,11 @@ def density_normals(model: NeRFMLP, points, dino=None):
 
 def load_checkpoint_into(model: NeRFMLP, ckpt: dict):
     """Accept both checkpoint key sets the reference writes: `nerf_model_state_dict`
-    (train.py:378) and `nerf_state_dict` (train_multiscale.py:368-376, read by evaluate.py:27)."""
+    (train.py:378) and `nerf_state_dict` (train_multiscale.py:368-376, read by evaluate.py:27).
+    A checkpoint written under a frequency mask (train_cli --freq-reg-end) holds the raw weights and the mask beside them
+    (`freq_mask_pos`, `freq_mask_dirs`): the mask is applied to the model, an absent one clears it."""
+    if "nerf_model_state_dict" in ckpt or "nerf_state_dict" in ckpt:
+        model.set_freq_mask(ckpt.get("freq_mask_pos"), ckpt.get("freq_mask_dirs"))
     for key in ("nerf_model_state_dict", "nerf_state_dict"):
         if key in ckpt:
             return model.load_state_dict(ckpt[key])

@@ -8,6 +8,25 @@ import torch.nn as nn
 from . import _lib as L
 
 
+def freq_mask_columns(num_freqs, visible, include_input=True):
+    """FreeNeRF's frequency mask as a per-column scale of PositionalEncoding(num_freqs) on 3-d inputs, float32 (3 * (2 L + 1),)
+    or (6 L,) without the input: the raw input columns are 1 and band l -- its sin and its cos, all three axes -- gets
+    clamp(visible - l, 0, 1).  Column order is the encoder's: [x | sin f0 | cos f0 | sin f1 | ...]."""
+    L_ = int(num_freqs)
+    band = (float(visible) - torch.arange(L_, dtype=torch.float64)).clamp_(0.0, 1.0).to(torch.float32)
+    cols = band.repeat_interleave(6)
+    return torch.cat([torch.ones(3, dtype=torch.float32), cols]) if include_input else cols
+
+
+def freq_mask_visible(step, end_step, num_freqs):
+    """Bands visible at `step` of FreeNeRF's linear schedule over `end_step` steps: min(L, 1 + L * step / end_step).  Taken on whole
+    bands (a band's sin and cos sit side by side in the encoding); equals L from end_step * (L - 1) / L on."""
+    L_ = int(num_freqs)
+    if end_step <= 0:
+        return float(L_)
+    return min(float(L_), 1.0 + L_ * float(step) / float(end_step))
+
+
 class PositionalEncoding(nn.Module):
     def __init__(self, num_freqs=10, include_input=True, log_sampling=True):
         super().__init__()

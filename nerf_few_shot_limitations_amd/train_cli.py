@@ -1,5 +1,5 @@
 """python -m nerf_few_shot_limitations_amd.train_cli --config experiments/baseline.yaml --data data/nerf_synthetic/lego \\
-        [--n-importance N [--coarse-weight W]] [--dist-weight W] [--occ-weight W --occ-samples K] [--recipe train|multiscale] [--epochs N] [--mode bf16|f16|f32] [--eval-mode f16] [--out DIR] [--checkpoint CKPT]
+        [--n-importance N [--coarse-weight W]] [--freq-reg-end N [--no-freq-reg-dirs]] [--dist-weight W] [--occ-weight W --occ-samples K] [--recipe train|multiscale] [--epochs N] [--mode bf16|f16|f32] [--eval-mode f16] [--out DIR] [--checkpoint CKPT]
         [--dino-weights DIR | --dino-maps maps.pt] [--train-extractor] [--fused-inputs] [--seed 0]
         [--occupancy-res N [--occupancy-box LO HI] [--occupancy-threshold T] [--occupancy-decay D] [--occupancy-refresh-every K]
          [--occupancy-cells-per-refresh C] [--occupancy-warmup STEPS] [--occupancy-per-view]]
@@ -89,6 +89,13 @@ of density in front of the cameras.  Both work with either recipe, with --fused-
 the multi-term one (clipped optimiser entry) with one small launch more.  Refused before the data set is read: a negative weight,
 --occ-weight > 0 without --occ-samples K >= 1, --occ-samples without --occ-weight, and either weight together with --n-importance
 (the hierarchical step takes the plain rgb loss).
+
+--freq-reg-end N (0, the default: off) is FreeNeRF's frequency regularisation (`FusedStep(freq_reg_end=N)`; nerfhip.h:
+nrf_model_set_freq_mask): step t trains and validates the field whose positional encodings show min(L, 1 + L t / N) bands (the
+direction encoding too, unless --no-freq-reg-dirs).  The mask is a column scale of the Linears that read the encodings, applied
+in the re-pack and in the weight gradients: no launch more, and it goes with every recipe, route and the other flags.  Hidden
+columns receive gradient exactly 0 (under weight decay they still decay).  From step N (L - 1) / L on the run is the plain one.
+Checkpoints hold the raw weights and the active mask (`freq_mask_pos`, `freq_mask_dirs`); --checkpoint and evaluate_cli apply it.
 
 --checkpoint resumes a run: weights, Adam moments and step count, epoch counter and best PSNR (the reference's train.py saves
 these keys, :374-389, but has no resume path); the LR schedule is a function of the epoch.  wandb and LPIPS are not part of
@@ -226,6 +233,23 @@ def ray_reg_options(args, near, far):
     if dw == 0.0 and ow == 0.0:
         return {}
     return dict(dist_weight=dw, occ_weight=ow, occ_samples=int(getattr(args, "occ_samples", None) or 0), dist_span=float(far) - float(near))
+
+
+def freq_reg_args_error(args):
+    """Why --freq-reg-end / --no-freq-reg-dirs cannot run with these arguments (None: they can, or neither was given).  The mask
+    goes with every recipe and route: it lives in the re-pack and the weight gradients, which all of them share."""
+    n = getattr(args, "freq_reg_end", 0) or 0
+    if int(n) < 0:
+        return "--freq-reg-end must be >= 0 (0: off)"
+    if int(n) == 0 and getattr(args, "no_freq_reg_dirs", False):
+        return "--no-freq-reg-dirs needs --freq-reg-end N (N > 0): without the frequency mask the flag would be ignored"
+    return None
+
+
+def freq_reg_options(args):
+    """FusedStep's keywords of --freq-reg-end / --no-freq-reg-dirs ({} when off)."""
+    n = int(getattr(args, "freq_reg_end", 0) or 0)
+    return dict(freq_reg_end=n, freq_reg_dirs=not getattr(args, "no_freq_reg_dirs", False)) if n > 0 else {}
 
 
 OCCUPANCY_FLAGS = ("occupancy_box", "occupancy_threshold", "occupancy_decay", "occupancy_refresh_every", "occupancy_cells_per_refresh",
@@ -530,7 +554,9 @@ def save_checkpoint(path, model, step, epoch, best_psnr, cfg, recipe="train", ex
     """train.py:374-389's dictionary: `nerf_model_state_dict` is what evaluate.py:27 / load_checkpoint_into read; the multiscale
     recipe adds train_multiscale.py:368-376's `nerf_state_dict` (the same tensors); --train-extractor adds
     `dino_model_state_dict` (train.py:384) and the extractor optimizer's state; --occupancy-per-view (a PerViewOccupancy) adds
-    `occupancy_per_view_state`.  The single grid of --occupancy-res is not saved."""
+    `occupancy_per_view_state`.  The single grid of --occupancy-res is not saved.  Under a frequency mask (--freq-reg-end) the weights
+    are the RAW ones, as resuming needs them, and the active mask is saved beside them as `freq_mask_pos` / `freq_mask_dirs`
+    (load_checkpoint_into applies it; NeRFMLP.effective_state_dict() is the masked field for a consumer that knows no masks)."""
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     opt = step.opt
     o = cfg["optimizer"]
@@ -545,6 +571,7 @@ def save_checkpoint(path, model, step, epoch, best_psnr, cfg, recipe="train", ex
                 **({"dino_model_state_dict": {k: v.detach().cpu().clone() for k, v in extractor.extractor.state_dict().items()},
                     "dino_optimizer_state_dict": extractor.opt.state_dict()} if extractor is not None else {}),
                 **({"occupancy_per_view_state": occupancy.state_dict()} if isinstance(occupancy, PerViewOccupancy) else {}),
+                **{k: v for k, v in zip(("freq_mask_pos", "freq_mask_dirs"), model.freq_mask) if v is not None},
                 "config": cfg}, path)
 
 
@@ -598,6 +625,10 @@ def main(argv=None):
                     help="add W * the occlusion penalty of FreeNeRF (mean rectified density of every ray's first --occ-samples samples): "
                          "FusedStep(occ_weight=W, occ_samples=K) (module docstring); 0: off")
     ap.add_argument("--occ-samples", type=int, default=None, metavar="K", help="with --occ-weight: the samples at the front of every ray it covers")
+    ap.add_argument("--freq-reg-end", type=int, default=0, metavar="N",
+                    help="FreeNeRF's frequency regularisation: reveal the bands of the positional encodings linearly over the first N steps "
+                         "(FusedStep(freq_reg_end=N); a column scale in the re-pack and the weight gradients, no launch more); 0: off")
+    ap.add_argument("--no-freq-reg-dirs", action="store_true", help="with --freq-reg-end: mask the position encoding only")
     ap.add_argument("--occupancy-res", type=int, default=0,
                     help="train under an occupancy grid of N^3 cells (a multiple of 32; 0: off): the network runs on the samples in occupied "
                          "cells alone, FusedStep.step_view(occupancy=) (module docstring)")
@@ -620,7 +651,7 @@ def main(argv=None):
                     help="--data-parallel on a box with ONE GPU: every rank on cuda:0, the gradient all-reduce over gloo through host memory "
                          "(RCCL refuses two ranks on one card); exercises the sharding and the collective, not multi-GPU speed")
     args = ap.parse_args(argv)
-    problem = (hierarchical_args_error(args) or ray_reg_args_error(args) or extractor_args_error(args, load_config(args.config))
+    problem = (hierarchical_args_error(args) or ray_reg_args_error(args) or freq_reg_args_error(args) or extractor_args_error(args, load_config(args.config))
                or occupancy_args_error(args, load_config(args.config)))
     if problem:
         raise SystemExit(problem)
@@ -683,7 +714,8 @@ def main(argv=None):
     model.dino_grad = ext is not None
     model = model.to(dev).train()
     step = FusedStep(model, white_bkgd=rs["white_bkgd"], data_parallel=world > 1, **step_options(cfg, args.recipe),
-                     **({"seed": args.seed} if args.recipe == "multiscale" else {}), **ray_reg_options(args, rs["near"], rs["far"]))
+                     **({"seed": args.seed} if args.recipe == "multiscale" else {}), **ray_reg_options(args, rs["near"], rs["far"]),
+                     **freq_reg_options(args))
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed)
     # (the single grid is not part of a checkpoint: a resumed run starts again from the all-ones grid and its warm-up; the per-view

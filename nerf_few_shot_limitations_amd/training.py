@@ -956,11 +956,23 @@ class FusedStep:
     samples.  With either weight on the step is the multi-term one with nrf_composite_reg_loss_backward as its loss launch and
     one small launch (nrf_ray_terms_finish) behind the optimiser; `last_losses` gains 'dist' and 'occ' (unweighted; 0 for a term
     whose weight is 0), 'total' and the returned loss include both.  With both weights 0 (the default) nothing changes.
+
+    Frequency regularisation (FreeNeRF's coarse-to-fine mask on the positional encodings), on every step method:
+
+        step = FusedStep(model, lr=5e-4, freq_reg_end=9000)
+
+    Step t (opt.step_count before the step) runs under model.set_freq_mask(freq_mask_columns(pos_freq, freq_mask_visible(t,
+    freq_reg_end, pos_freq))), and the same on the direction encoding unless freq_reg_dirs=False, set before anything of the step
+    is packed.  The mask costs no launch: it rides in the re-pack and in the weight gradients' second stage.  Hidden columns
+    receive gradient exactly 0 (with weight_decay = 0 their weights keep their bits; under decay they decay like any weight).
+    Once all bands are visible the mask is cleared and the step is the plain one, launch for launch and bit for bit.  The mask is
+    a function of the step count alone, so data_parallel ranks agree on it.
     """
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rgb_weight=1.0, white_bkgd=False,
                  process_group=None, data_parallel=False, reg_weight=0.0, depth_weight=0.0, noise_std=0.0, max_grad_norm=None,
-                 decoupled_weight_decay=False, seed=None, dist_weight=0.0, occ_weight=0.0, occ_samples=0, dist_span=None):
+                 decoupled_weight_decay=False, seed=None, dist_weight=0.0, occ_weight=0.0, occ_samples=0, dist_span=None,
+                 freq_reg_end=0, freq_reg_dirs=True):
         """data_parallel=True (inside an initialised torch.distributed job): every rank passes ITS shard of the ray batch
         (equal sizes), the flat gradient vector is averaged over the ranks with one all-reduce before Adam (the norm of
         max_grad_norm is taken behind it, so all ranks clip alike), and the returned loss is this rank's.
@@ -976,7 +988,10 @@ class FusedStep:
             raise ValueError("FusedStep: occ_samples must be >= 1 with occ_weight > 0 (and never negative)")
         if dist_span is not None and not (math.isfinite(float(dist_span)) and float(dist_span) > 0.0):
             raise ValueError("FusedStep: dist_span must be finite and > 0 (None: far - near of the step)")
+        if int(freq_reg_end) < 0:
+            raise ValueError("FusedStep: freq_reg_end must be >= 0 (0: no frequency regularisation)")
         self.model = model
+        self.freq_reg_end, self.freq_reg_dirs = int(freq_reg_end), bool(freq_reg_dirs)
         self.data_parallel = bool(data_parallel)
         self.group = process_group
         self.opt = Adam(model, lr, betas, eps, weight_decay, decoupled=decoupled_weight_decay, max_grad_norm=max_grad_norm)
@@ -992,6 +1007,18 @@ class FusedStep:
         self._hier_parts = None             # ((2,R) squared errors coarse | fine, R) of the last step when it was a hierarchical one
         self._key = None
         self.last_count = None              # M of the last step under an occupancy grid (step_rays / step_view with occupancy=)
+
+    def _freq_reg(self):
+        """The frequency mask of the step about to run, set on the model before anything of the step is packed."""
+        if self.freq_reg_end <= 0:
+            return
+        from .positional_encoding import freq_mask_columns, freq_mask_visible
+        m, t = self.model, self.opt.step_count
+        pos = freq_mask_columns(m.pos_freq, freq_mask_visible(t, self.freq_reg_end, m.pos_freq))
+        dirs = None
+        if self.freq_reg_dirs and m.net != L.NRF_NET_V1:
+            dirs = freq_mask_columns(m.dir_freq, freq_mask_visible(t, self.freq_reg_end, m.dir_freq))
+        m.set_freq_mask(pos, dirs)
 
     @property
     def last_losses(self):
@@ -1149,6 +1176,7 @@ class FusedStep:
         pts = pts.reshape(R * S, 3 * (2 * m.pos_freq + 1) if v1 else 3)
         n = R * S
         lib = L.lib()
+        self._freq_reg()
         h, mode = _train_handle(m, dev)
         with torch.cuda.device(dev):
             self._buffers(n, R, S, dev, h, mode)
@@ -1356,6 +1384,7 @@ class FusedStep:
                 raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
             dn, keep = make_dino(**dino) if isinstance(dino, dict) else dino
         lib = L.lib()
+        self._freq_reg()
         h, mode = _train_handle(m, dev)
         with torch.cuda.device(dev):
             if u is None:
@@ -1435,6 +1464,7 @@ class FusedStep:
                 raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
             dn, keep = make_dino(**dino) if isinstance(dino, dict) else dino
         lib = L.lib()
+        self._freq_reg()
         h, mode = _train_handle(m, dev)
         with torch.cuda.device(dev):
             self._buffers(n, R, S, dev, h, mode)

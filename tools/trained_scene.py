@@ -131,7 +131,7 @@ def train_field(net, cfg, scene_dir, train_mode, seed=0, epoch_scale=1.0, sigma_
             curve.append(round(loss, 5))
     torch.cuda.synchronize()
     info = {"net": net, "train_mode": train_mode, "epochs": epochs, "train_views": len(images), "resolution": int(H),
-            "train_seconds": round(time.perf_counter() - t0, 2), "ray_samples_trained": samples,
+            "train_seconds": round(time.perf_counter() - t0, 2), "ray_samples_trained": samples, "steps": step.opt.step_count,
             "loss_first_epoch": round(first, 6), "loss_last_epoch": round(last, 6), "loss_curve": curve}
     # the side channel of each training view (its own map + camera: what the field was trained with, train.py:203-206) and the one the
     # reference's evaluate() uses for every test view (view 0's, train.py:207-208)
