@@ -885,6 +885,55 @@ int nrf_composite_reg_loss_backward(const float* rgb, int rgb_stride, const floa
 int nrf_ray_terms_finish(const float* ray_terms, int64_t n_rays, const nrf_ray_reg* reg, const float* losses4, float* losses6,
                          void* stream);
 
+/* ------------------------------------------------------------------------
+ * Patch regulariser: RegNeRF's depth-smoothness loss on small patches rendered from poses nobody observed.  A batch of R = n_rays
+ * rays is R_s supervised rays followed by N_p = n_patches patches of P x P rays (P = patch_size), R = R_s + N_p P^2, patch-major and
+ * row-major inside a patch: ray (i, j) of patch p is row R_s + p P^2 + i P + j.  target and loss->target_depth hold R_s rows.
+ * With d(p,i,j) the compositor's depth sum_k w_k z_k of a patch ray (behind the density noise):
+ *   DS_p   = sum_{i<P-1, j<P-1} (d(i,j) - d(i,j+1))^2 + (d(i,j) - d(i+1,j))^2
+ *   smooth = sum_p DS_p / (N_p (P-1)^2)                                       (RegNeRF's compute_tv_norm(...).mean())
+ *   loss   = rgb_weight mse (R_s rays, divisor 3 R_s) + depth_weight l1 (R_s rays, divisor R_s) + reg_weight mean w^2 (R rays)
+ *            + dist_weight mean D + occ_weight mean O (R rays) + depth_smooth_weight smooth
+ * A patch ray has no target: its colour gradient is 0, it takes the three target-free terms like any ray, and its dL/d depth is
+ *   (2 depth_smooth_weight / (N_p (P-1)^2)) ([i<P-1, j<P-1] ((d(i,j) - d(i,j+1)) + (d(i,j) - d(i+1,j)))
+ *                                            - [i<P-1, j>0] (d(i,j-1) - d(i,j)) - [i>0, j<P-1] (d(i-1,j) - d(i,j)))
+ * formed in single fp32 operations in this order.  Depths and poses carry no gradient.  Additive to ABI 5, as nrf_ray_reg is.
+ * ------------------------------------------------------------------------ */
+typedef struct nrf_patch_reg {
+    int32_t struct_bytes;          /* sizeof(nrf_patch_reg): checked by the library */
+    float   depth_smooth_weight;   /* >= 0 */
+    int32_t patch_size;            /* P, 2 ... 16 */
+    int32_t n_patches;             /* N_p >= 0, N_p P^2 < n_rays: a batch keeps at least one supervised ray */
+} nrf_patch_reg;
+
+/* nrf_composite_reg_loss_backward with the patch term, still ONE launch: the supervised rays are that entry's code, one wave per
+ * ray; a workgroup owns a patch, composites its rays, exchanges their depths through LDS, and runs the compositor backward of every
+ * patch ray with the dL/d depth above.  No atomics: two runs give the same bits.  With n_patches = 0 every output is
+ * nrf_composite_reg_loss_backward's, bit for bit.  With n_patches > 0 every ray's compositor forms a sample's transmittance factor
+ * as e + 1e-10 from e = exp(-relu(s) dist) itself and its suffix sums without a subtraction -- the same values in exact arithmetic,
+ * better conditioned behind a nearly opaque sample -- so pred and d rows differ from the other loss entries' in the last digits.
+ *   ray_terms   : 5 * n_rays floats, as there; rows 0 and 2 of a patch ray are 0
+ *   patch_terms : n_patches floats: DS_p
+ *   patch_depth : n_patches * P * P floats: d(p,i,j), or NULL
+ *   pred        : n_rays * 3 floats (or NULL): the patch rays' colours too
+ * NRF_EINVAL, before any launch: what nrf_composite_reg_loss_backward refuses, patch NULL or of a wrong struct_bytes, a negative or
+ * non-finite depth_smooth_weight, patch_size outside 2 ... 16, n_patches < 0, n_patches * patch_size^2 >= n_rays, patch_terms NULL
+ * with n_patches > 0. */
+int nrf_composite_patch_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride,
+                                      const float* z_vals, const float* rays_d, int64_t n_rays, int n_samples, int white_bkgd,
+                                      const float* target, const nrf_loss_opts* loss, const nrf_ray_reg* reg, const int32_t* slot,
+                                      float* pred, float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride,
+                                      float* ray_terms, float* zero_buf, int64_t zero_n, void* stream, const nrf_patch_reg* patch,
+                                      float* patch_terms, float* patch_depth);
+
+/* One small launch behind the optimiser (whose own four loss values divide every term by R and are not the step's with patches):
+ *   losses7 = [total, rgb, depth, reg, mean D, mean O, smooth]
+ * formed by one workgroup from the five rows of ray_terms and from patch_terms with the divisors above, in a fixed order; the depth
+ * term counts only with loss->target_depth set, as in the loss launch.  NRF_EINVAL: a NULL (patch_terms may be NULL with
+ * n_patches = 0), n_rays < 1, n_samples outside 1 ... 4096, and what the entry above refuses of loss, reg and patch. */
+int nrf_patch_terms_finish(const float* ray_terms, int64_t n_rays, int n_samples, const nrf_loss_opts* loss, const nrf_ray_reg* reg,
+                           const nrf_patch_reg* patch, const float* patch_terms, float* losses7, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

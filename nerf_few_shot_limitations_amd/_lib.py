@@ -90,6 +90,16 @@ def ray_reg(dist_weight=0.0, dist_inv_span=0.0, occ_weight=0.0, occ_samples=0):
     return nrf_ray_reg(C.sizeof(nrf_ray_reg), float(dist_weight), float(dist_inv_span), float(occ_weight), int(occ_samples))
 
 
+class nrf_patch_reg(C.Structure):
+    """The patch-based depth-smoothness term of nrf_composite_patch_loss_backward; struct_bytes is filled in by patch_reg()."""
+    _fields_ = [("struct_bytes", C.c_int32), ("depth_smooth_weight", C.c_float), ("patch_size", C.c_int32), ("n_patches", C.c_int32)]
+
+
+def patch_reg(depth_smooth_weight=0.0, patch_size=8, n_patches=0):
+    """nrf_patch_reg with its size field set."""
+    return nrf_patch_reg(C.sizeof(nrf_patch_reg), float(depth_smooth_weight), int(patch_size), int(n_patches))
+
+
 class nrf_train_rays(C.Structure):
     """The ray source of nrf_mlp_forward_train_rays; struct_bytes is filled in by train_rays()."""
     _fields_ = [("struct_bytes", C.c_int32), ("reserved", C.c_int32), ("rays_o", C.c_void_p), ("rays_d", C.c_void_p), ("pixels", C.c_void_p),
@@ -285,6 +295,13 @@ SIGNATURES = {
                                                   C.c_void_p, C.POINTER(nrf_loss_opts), C.POINTER(nrf_ray_reg), C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "nrf_ray_terms_finish": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(nrf_ray_reg), C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the same loss launch with the depth-smoothness term on patches of unseen views, and the launch that forms the seven loss values
+    "nrf_composite_patch_loss_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                                    C.c_void_p, C.POINTER(nrf_loss_opts), C.POINTER(nrf_ray_reg), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                    C.POINTER(nrf_patch_reg), C.c_void_p, C.c_void_p]),
+    "nrf_patch_terms_finish": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(nrf_loss_opts), C.POINTER(nrf_ray_reg), C.POINTER(nrf_patch_reg),
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

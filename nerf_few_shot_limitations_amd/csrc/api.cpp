@@ -1131,12 +1131,27 @@ bool ray_reg_terms(const nrf_ray_reg* reg, nrf::RayRegTerms& rt) {
     return true;
 }
 
+// nrf_patch_reg as the launches take it, checked against the batch it splits; false (with the message set) on a refusal
+bool patch_reg_terms(const nrf_patch_reg* patch, int64_t n_rays, nrf::PatchRegTerms& pt) {
+    if (!patch) return fail(NRF_EINVAL, "patch is NULL"), false;
+    if (patch->struct_bytes != (int32_t)sizeof(nrf_patch_reg)) return fail(NRF_EINVAL, "nrf_patch_reg.struct_bytes is not sizeof(nrf_patch_reg)"), false;
+    if (!(patch->depth_smooth_weight >= 0.0f) || !std::isfinite(patch->depth_smooth_weight))
+        return fail(NRF_EINVAL, "depth_smooth_weight must be finite and >= 0"), false;
+    if (patch->patch_size < 2 || patch->patch_size > 16) return fail(NRF_EINVAL, "patch_size must be in 2 ... 16"), false;
+    if (patch->n_patches < 0) return fail(NRF_EINVAL, "n_patches must be >= 0"), false;
+    if ((int64_t)patch->n_patches * patch->patch_size * patch->patch_size >= n_rays)
+        return fail(NRF_EINVAL, "n_patches * patch_size^2 must be < n_rays: a batch needs at least one supervised ray"), false;
+    pt.depth_smooth_weight = patch->depth_smooth_weight; pt.patch_size = patch->patch_size; pt.n_patches = patch->n_patches;
+    return true;
+}
+
 // nrf_composite_loss_backward and its indexed form (slot != NULL: rgb / sigma / d_rgb / d_sigma hold compacted rows); rt != NULL:
-// nrf_composite_reg_loss_backward (ray_terms holds five rows)
+// nrf_composite_reg_loss_backward (ray_terms holds five rows); pt != NULL (with rt): nrf_composite_patch_loss_backward
 int composite_loss_backward_any(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals, const float* rays_d,
                                 int64_t n_rays, int n_samples, int white_bkgd, const float* target, const nrf_loss_opts* loss, const int32_t* slot,
                                 float* pred, float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf,
-                                int64_t zero_n, void* stream, const nrf::RayRegTerms* rt = nullptr) {
+                                int64_t zero_n, void* stream, const nrf::RayRegTerms* rt = nullptr, const nrf::PatchRegTerms* pt = nullptr,
+                                float* patch_terms = nullptr, float* patch_depth = nullptr) {
     if (!loss) return fail(NRF_EINVAL, "nrf_composite_loss_backward: loss is NULL");
     if (loss->struct_bytes != (int32_t)sizeof(nrf_loss_opts)) return fail(NRF_EINVAL, "nrf_loss_opts.struct_bytes is not sizeof(nrf_loss_opts)");
     if (!(loss->rgb_weight >= 0.0f) || !(loss->reg_weight >= 0.0f) || !(loss->depth_weight >= 0.0f) || !std::isfinite(loss->rgb_weight) ||
@@ -1150,7 +1165,10 @@ int composite_loss_backward_any(const float* rgb, int rgb_stride, const float* s
     nrf::LossTerms lt{};
     lt.rgb_weight = loss->rgb_weight; lt.reg_weight = loss->reg_weight; lt.depth_weight = loss->depth_weight;
     lt.target_depth = loss->target_depth; lt.noise_std = loss->noise_std; lt.noise = loss->noise; lt.rng_seed = loss->rng_seed;
-    const int r = rt ? nrf::launch_composite_reg_loss_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd,
+    const int r = pt ? nrf::launch_composite_patch_loss_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd,
+                                                                 target, lt, *rt, *pt, slot, pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride,
+                                                                 ray_terms, zero_buf, zero_n, patch_terms, patch_depth, (hipStream_t)stream)
+                  : rt ? nrf::launch_composite_reg_loss_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd,
                                                                target, lt, *rt, slot, pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms,
                                                                zero_buf, zero_n, (hipStream_t)stream)
                      : nrf::launch_composite_loss_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, lt,
@@ -1198,6 +1216,41 @@ int nrf_ray_terms_finish(const float* ray_terms, int64_t n_rays, const nrf_ray_r
     if (!ray_terms || !losses4 || !losses6) return fail(NRF_EINVAL, "null pointer");
     const int r = nrf::launch_ray_terms_finish(ray_terms, n_rays, rt.dist_weight, rt.occ_weight, losses4, losses6, (hipStream_t)stream);
     return r == NRF_OK ? NRF_OK : fail(r, "ray terms finish launch failed");
+}
+
+int nrf_composite_patch_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals,
+                                      const float* rays_d, int64_t n_rays, int n_samples, int white_bkgd, const float* target,
+                                      const nrf_loss_opts* loss, const nrf_ray_reg* reg, const int32_t* slot, float* pred, float* d_rgb,
+                                      int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n,
+                                      void* stream, const nrf_patch_reg* patch, float* patch_terms, float* patch_depth) {
+    nrf::RayRegTerms rt{};
+    if (!ray_reg_terms(reg, rt)) return NRF_EINVAL;
+    nrf::PatchRegTerms pt{};
+    if (!patch_reg_terms(patch, n_rays, pt)) return NRF_EINVAL;
+    if (pt.n_patches > 0 && !patch_terms) return fail(NRF_EINVAL, "nrf_composite_patch_loss_backward: patch_terms is NULL");
+    if (slot && (reinterpret_cast<uintptr_t>(slot) & 3u) != 0) return fail(NRF_EINVAL, "nrf_composite_patch_loss_backward: slot must be 4-byte aligned");
+    return composite_loss_backward_any(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, loss, slot, pred,
+                                       d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream, &rt, &pt, patch_terms,
+                                       patch_depth);
+}
+
+int nrf_patch_terms_finish(const float* ray_terms, int64_t n_rays, int n_samples, const nrf_loss_opts* loss, const nrf_ray_reg* reg,
+                           const nrf_patch_reg* patch, const float* patch_terms, float* losses7, void* stream) {
+    nrf::RayRegTerms rt{};
+    if (!ray_reg_terms(reg, rt)) return NRF_EINVAL;
+    nrf::PatchRegTerms pt{};
+    if (!patch_reg_terms(patch, n_rays, pt)) return NRF_EINVAL;
+    if (!loss) return fail(NRF_EINVAL, "nrf_patch_terms_finish: loss is NULL");
+    if (loss->struct_bytes != (int32_t)sizeof(nrf_loss_opts)) return fail(NRF_EINVAL, "nrf_loss_opts.struct_bytes is not sizeof(nrf_loss_opts)");
+    if (!(loss->rgb_weight >= 0.0f) || !(loss->reg_weight >= 0.0f) || !(loss->depth_weight >= 0.0f) || !std::isfinite(loss->rgb_weight) ||
+        !std::isfinite(loss->reg_weight) || !std::isfinite(loss->depth_weight))
+        return fail(NRF_EINVAL, "loss weights must be finite and >= 0");
+    if (n_rays <= 0 || n_rays > ((int64_t)1 << 30) || n_samples < 1 || n_samples > 4096) return fail(NRF_EINVAL, "nrf_patch_terms_finish: bad sizes");
+    if (!ray_terms || !losses7 || (pt.n_patches > 0 && !patch_terms)) return fail(NRF_EINVAL, "null pointer");
+    nrf::LossTerms lt{};
+    lt.rgb_weight = loss->rgb_weight; lt.reg_weight = loss->reg_weight; lt.depth_weight = loss->depth_weight; lt.target_depth = loss->target_depth;
+    const int r = nrf::launch_patch_terms_finish(ray_terms, n_rays, n_samples, lt, rt, pt, patch_terms, losses7, (hipStream_t)stream);
+    return r == NRF_OK ? NRF_OK : fail(r, "patch terms finish launch failed");
 }
 
 int64_t nrf_hier_train_workspace_bytes(int64_t n_rays, int n_samples, int n_importance) {

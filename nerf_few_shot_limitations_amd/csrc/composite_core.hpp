@@ -42,8 +42,12 @@ __device__ __forceinline__ float sigma_eff(float sigma, const NoiseSrc& ns, int6
 // samples alone, sample i of the (R,S) ladder reads row slot[i]; slot[i] < 0 is a skipped sample, composited as colour (0,0,0) and
 // effective density -inf -- behind the noise, so that no draw brings it back.  The instantiations without IDX are the code the
 // kernels had before it existed.
+// FINE (the loss launch with patches, patch_reg.hip): the factor a sample leaves of the transmittance is formed as e + 1e-10 from
+// e = exp(-relu(sigma) dist) itself, not as (1 - alpha) + 1e-10 from alpha = 1 - e rounded to fp32 -- the same number in exact
+// arithmetic, but behind a nearly opaque sample (e = 1e-5) the rounding of alpha costs everything later 6e-3 of its value.  The
+// instantiations without FINE are the code the kernels had before it existed.
 struct RaySums { float r, g, b, depth, acc, w2; };
-template <bool EXT = false, bool IDX = false>
+template <bool EXT = false, bool IDX = false, bool FINE = false>
 __device__ __forceinline__ RaySums composite_ray(const float* __restrict__ rgb, int rgb_stride, const float* __restrict__ sigma, int sigma_stride,
                                                  const float* __restrict__ z, const float* __restrict__ rays_d, int64_t r, int S, int lane,
                                                  float* __restrict__ out_w, const NoiseSrc ns = NoiseSrc{},
@@ -62,9 +66,18 @@ __device__ __forceinline__ RaySums composite_ray(const float* __restrict__ rgb, 
         const bool last = (s + 1 == S);
         const float dist = last ? __fmul_rn(1e10f, norm) : __fmul_rn(__fsub_rn(zn, zc), norm);
         float alpha = 0.0f;
+        float e_fine = 1.0f;                             // FINE: exp(-relu(sigma) dist), 1 beyond the ray
         int64_t row = i;                                 // the sample's row of rgb / sigma
         if constexpr (IDX) row = slot[i];
-        if constexpr (IDX) {
+        if constexpr (FINE) {
+            if (valid) {
+                float sg;
+                if constexpr (IDX) sg = row < 0 ? -__builtin_huge_valf() : sigma_eff<EXT>(sigma[row * sigma_stride], ns, i, r, s);
+                else sg = sigma_eff<EXT>(sigma[i * sigma_stride], ns, i, r, s);
+                e_fine = expf(__fmul_rn(-fmaxf(sg, 0.0f), dist));
+                alpha = __fsub_rn(1.0f, e_fine);
+            }
+        } else if constexpr (IDX) {
             if (valid) {
                 const float sg = row < 0 ? -__builtin_huge_valf() : sigma_eff<EXT>(sigma[row * sigma_stride], ns, i, r, s);
                 alpha = __fsub_rn(1.0f, expf(__fmul_rn(-fmaxf(sg, 0.0f), dist)));
@@ -72,7 +85,7 @@ __device__ __forceinline__ RaySums composite_ray(const float* __restrict__ rgb, 
         } else {
             if (valid) alpha = __fsub_rn(1.0f, expf(__fmul_rn(-fmaxf(sigma_eff<EXT>(sigma[i * sigma_stride], ns, i, r, s), 0.0f), dist)));
         }
-        const float f = valid ? __fadd_rn(__fsub_rn(1.0f, alpha), 1e-10f) : 1.0f;
+        const float f = valid ? __fadd_rn(FINE ? e_fine : __fsub_rn(1.0f, alpha), 1e-10f) : 1.0f;
         const float incl = wave_incl_prod(f, lane);
         float excl = __shfl_up(incl, 1, 64);
         if (lane == 0) excl = 1.0f;
@@ -159,7 +172,10 @@ struct RayReg {
 // sums C, Dm: O(S).  Pass 1 leaves the prefix sums entering every segment beside seg_T (rays of one segment have none: it skips the
 // two sums), pass 2 carries the suffix sums as it carries `carry`; both sides are true scans.  The instantiations without REG are
 // the code the kernels had before it existed.
-template <bool EXT = false, bool GEOM = false, bool IDX = false, bool REG = false>
+// FINE: as in composite_ray, and the sum over the strictly later samples is the neighbour's inclusive sum, not `inclusive - own`:
+// behind an opaque sample the later samples' w v (1e-11) vanish in that subtraction against the own (1e-1), and the divisor there is
+// 1e-10.  The instantiations without FINE are the code the kernels had before it existed.
+template <bool EXT = false, bool GEOM = false, bool IDX = false, bool REG = false, bool FINE = false>
 __device__ __forceinline__ void composite_backward_ray(const float* __restrict__ rgb, int rgb_stride, const float* __restrict__ sigma,
                                                        int sigma_stride, const float* __restrict__ z, const float* __restrict__ rays_d,
                                                        int64_t r, int S, int lane, int white_bkgd, float gr, float gg, float gb, float gd,
@@ -190,7 +206,7 @@ __device__ __forceinline__ void composite_backward_ray(const float* __restrict__
         }
         e = valid ? expf(__fmul_rn(-fmaxf(sg, 0.0f), dist)) : 1.0f;
         alpha = valid ? __fsub_rn(1.0f, e) : 0.0f;
-        f = valid ? __fadd_rn(__fsub_rn(1.0f, alpha), 1e-10f) : 1.0f;
+        f = valid ? __fadd_rn(FINE ? e : __fsub_rn(1.0f, alpha), 1e-10f) : 1.0f;
     };
     // REG: m_i and delta_i of the lane's sample from (z_{i+1} - z_i) as `sample` formed it
     auto interval = [&](int s0, float zc, int64_t i, float& m, float& delta) {
@@ -273,7 +289,14 @@ __device__ __forceinline__ void composite_backward_ray(const float* __restrict__
         }
         const float wv_ = valid ? __fmul_rn(w, v) : 0.0f;
         const float incl_rev = wave_incl_sum_rev(wv_, lane);
-        const float suffix = __fadd_rn(__fsub_rn(incl_rev, wv_), carry);     // strictly later samples
+        float suffix;                                    // strictly later samples
+        if constexpr (FINE) {
+            float later = __shfl_down(incl_rev, 1, 64);
+            if (lane == 63) later = 0.0f;
+            suffix = __fadd_rn(later, carry);
+        } else {
+            suffix = __fadd_rn(__fsub_rn(incl_rev, wv_), carry);
+        }
         carry = __fadd_rn(carry, __shfl(incl_rev, 0, 64));
         if (IDX ? (valid && row >= 0) : valid) {
             const int64_t o = IDX ? row : i;

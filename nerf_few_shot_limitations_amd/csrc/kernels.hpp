@@ -240,6 +240,17 @@ int launch_composite_reg_loss_backward(const float* rgb, int rgb_stride, const f
                                        float* ray_terms, float* zero_buf, int64_t zero_n, hipStream_t s);
 int launch_ray_terms_finish(const float* ray_terms, int64_t n_rays, float dist_weight, float occ_weight, const float* losses4, float* losses6,
                             hipStream_t s);
+// The same launch with RegNeRF's depth-smoothness term on patches as well (patch_reg.hip; nerfhip.h: nrf_patch_reg, whose fields
+// these are): the last n_patches patch_size^2 rays are patch rays, target and target_depth hold the other rows.  patch_terms (N_p):
+// DS_p; patch_depth (N_p, P, P) or NULL.  launch_patch_terms_finish: losses7 from the five rows of ray_terms and patch_terms.
+struct PatchRegTerms { float depth_smooth_weight; int patch_size; int64_t n_patches; };
+int launch_composite_patch_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
+                                         int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, const RayRegTerms& rt,
+                                         const PatchRegTerms& pt, const int32_t* slot, float* pred, float* d_rgb, int d_rgb_stride, float* d_sigma,
+                                         int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n, float* patch_terms,
+                                         float* patch_depth, hipStream_t s);
+int launch_patch_terms_finish(const float* ray_terms, int64_t n_rays, int S, const LossTerms& lt, const RayRegTerms& rt, const PatchRegTerms& pt,
+                              const float* patch_terms, float* losses7, hipStream_t s);
 // partial sums of squares of a flat vector (one float per workgroup, fixed order); the optimiser launch adds them up
 constexpr int kMaxSqnormPartials = 1024;
 inline int sqnorm_partials(int64_t n) {

@@ -202,6 +202,73 @@ def sample_pdf_sorted(z_vals, weights, N_importance, u=None, out=None):
     return srt
 
 
+# ---- patches of unseen views (RegNeRF's depth-smoothness term: FusedStep(depth_smooth_weight=), n_patches=) -- plain torch ----------
+def patch_pixels(H, W, patch_size, n_patches, generator=None, stride=1):
+    """int64 ray ids y*W+x of n_patches random windows of patch_size x patch_size pixels that lie inside an (H,W) image, flat in the
+    batch layout of the patch term: patch-major, row-major inside a patch (id k of patch p is element p*P*P + k).  stride dilates a
+    window: neighbouring patch pixels are `stride` image pixels apart.  The draw comes from `generator` (a CPU torch.Generator; None:
+    torch's global one), so it repeats under a seed."""
+    H, W, P, n, st = int(H), int(W), int(patch_size), int(n_patches), int(stride)
+    if P < 2 or P > 16:
+        raise ValueError("patch_size must be in 2 ... 16")
+    if n < 0 or st < 1:
+        raise ValueError("n_patches must be >= 0 and stride >= 1")
+    ext = (P - 1) * st + 1
+    if ext > H or ext > W:
+        raise ValueError(f"a {P} x {P} window of stride {st} spans {ext} pixels: it does not fit a {H} x {W} image")
+    y0 = torch.randint(0, H - ext + 1, (n,), generator=generator, dtype=torch.int64)
+    x0 = torch.randint(0, W - ext + 1, (n,), generator=generator, dtype=torch.int64)
+    k = torch.arange(P, dtype=torch.int64) * st
+    ids = (y0[:, None, None] + k[None, :, None]) * W + (x0[:, None, None] + k[None, None, :])
+    return ids.reshape(-1)
+
+
+def sample_patch_poses(train_poses, n, generator=None, focus_jitter=0.125):
+    """n camera-to-world matrices (n,4,4) of views nobody observed, from the (V,4,4) / (V,3,4) training poses: positions uniform in
+    the bounding box of the training cameras' positions and rescaled to their mean distance from the origin, every camera looking
+    at the origin + N(0, focus_jitter^2), up the mean training up vector.  The columns are the camera's right, up and backward axes
+    (it looks down -z, as get_rays has it): orthonormal, det = +1.  Returned on the CPU in float32."""
+    p = torch.as_tensor(train_poses).detach().to("cpu", torch.float64)
+    if p.dim() != 3 or tuple(p.shape[1:]) not in ((4, 4), (3, 4)):
+        raise ValueError("train_poses must be (V,4,4) or (V,3,4)")
+    n = int(n)
+    pos = p[:, :3, 3]
+    lo, hi = pos.amin(dim=0), pos.amax(dim=0)
+    radius = pos.norm(dim=1).mean()
+    up = p[:, :3, 1].mean(dim=0)
+    up = up / up.norm().clamp_min(1e-12)
+    u = torch.rand((n, 3), generator=generator, dtype=torch.float64)
+    c = lo + (hi - lo) * u
+    c = c * (radius / c.norm(dim=1, keepdim=True).clamp_min(1e-12))
+    focus = torch.randn((n, 3), generator=generator, dtype=torch.float64) * float(focus_jitter)
+    zax = c - focus
+    zax = zax / zax.norm(dim=1, keepdim=True).clamp_min(1e-12)
+    xax = torch.linalg.cross(up.expand(n, 3), zax)
+    xax = xax / xax.norm(dim=1, keepdim=True).clamp_min(1e-12)
+    yax = torch.linalg.cross(zax, xax)
+    out = torch.zeros((n, 4, 4), dtype=torch.float64)
+    out[:, :3, 0], out[:, :3, 1], out[:, :3, 2], out[:, :3, 3] = xax, yax, zax, c
+    out[:, 3, 3] = 1.0
+    return out.to(torch.float32)
+
+
+def patch_rays(H, W, focal, poses, patch_size, generator=None, stride=1):
+    """(rays_o, rays_d), each (n * P * P, 3) in the patch term's batch layout: one window of patch_pixels per pose of `poses`
+    (n,4,4) / (n,3,4), the rays written with get_rays' formula -- rays_d = R ((x - W/2) / focal, -(y - H/2) / focal, -1), rays_o = t --
+    on the device of `poses`.  The windows are patch_pixels(H, W, patch_size, n, generator, stride)."""
+    c2w = torch.as_tensor(poses).to(torch.float32)
+    if c2w.dim() != 3 or tuple(c2w.shape[1:]) not in ((4, 4), (3, 4)):
+        raise ValueError("poses must be (n,4,4) or (n,3,4)")
+    n, P = c2w.shape[0], int(patch_size)
+    ids = patch_pixels(H, W, P, n, generator, stride).reshape(n, P * P).to(c2w.device)
+    x, y = (ids % int(W)).to(torch.float32), (ids // int(W)).to(torch.float32)
+    cam = torch.stack([(x - int(W) * 0.5) / float(focal), -(y - int(H) * 0.5) / float(focal), -torch.ones_like(x)], dim=-1)      # (n, P*P, 3)
+    rot = c2w[:, None, :3, :3]
+    rays_d = cam[..., 0:1] * rot[..., 0] + cam[..., 1:2] * rot[..., 1] + cam[..., 2:3] * rot[..., 2]
+    rays_o = c2w[:, None, :3, 3].expand(n, P * P, 3)
+    return rays_o.reshape(-1, 3).contiguous(), rays_d.reshape(-1, 3).contiguous()
+
+
 def get_ray_batch(rays_o, rays_d, batch_size=1024):
     """ray_utils.py:145-174: host-side chunk generator, kept for callers that still chunk
     (the fused renderer does not need it)."""

@@ -90,6 +90,18 @@ the multi-term one (clipped optimiser entry) with one small launch more.  Refuse
 --occ-weight > 0 without --occ-samples K >= 1, --occ-samples without --occ-weight, and either weight together with --n-importance
 (the hierarchical step takes the plain rgb loss).
 
+--depth-smooth-weight W (0, the default: off) adds RegNeRF's depth-smoothness loss on patches of unseen views
+(`FusedStep(depth_smooth_weight=W, patch_size=P)`; nerfhip.h: nrf_patch_reg): every batch of the default (staged) route gets
+--patches-per-step N (default 16) patches of --patch-size P x P rays (default 8; 2 ... 16) behind its supervised rays, one patch per
+freshly drawn pose (`ray_sampler.sample_patch_poses`: positions in the bounding box of the training cameras at their mean radius,
+looking at the jittered origin) at the epoch's schedule resolution, neighbouring patch pixels --patch-stride K (default 1) image
+pixels apart.  The term is W * the mean over patches and anchors of the squared differences between a patch ray's rendered depth
+and those of its right and lower neighbours; patch rays have no colour term and take the other target-free terms like any ray.
+One launch sequence as with --dist-weight: the patch rays' depths meet in LDS inside the loss launch.  It goes with both recipes,
+--dist-weight / --occ-weight, --freq-reg-end and --data-parallel (every rank draws its own patches).  Refused before the config or
+the data set is read: --depth-smooth-weight together with --n-importance, --fused-inputs (a view step has one pose), any
+--occupancy-* flag or --train-extractor; a negative weight, P outside 2 ... 16, N < 1, K < 1.
+
 --freq-reg-end N (0, the default: off) is FreeNeRF's frequency regularisation (`FusedStep(freq_reg_end=N)`; nerfhip.h:
 nrf_model_set_freq_mask): step t trains and validates the field whose positional encodings show min(L, 1 + L t / N) bands (the
 direction encoding too, unless --no-freq-reg-dirs).  The mask is a column scale of the Linears that read the encodings, applied
@@ -233,6 +245,39 @@ def ray_reg_options(args, near, far):
     if dw == 0.0 and ow == 0.0:
         return {}
     return dict(dist_weight=dw, occ_weight=ow, occ_samples=int(getattr(args, "occ_samples", None) or 0), dist_span=float(far) - float(near))
+
+
+def patch_reg_args_error(args):
+    """Why --depth-smooth-weight and its companions cannot run with these arguments (None: they can, or the weight is 0).  Decided
+    before a config or a data set is read, like ray_reg_args_error."""
+    w = float(getattr(args, "depth_smooth_weight", 0.0) or 0.0)
+    if not (w >= 0.0 and math.isfinite(w)):
+        return "--depth-smooth-weight must be finite and >= 0 (0: off)"
+    if w == 0.0:
+        return None
+    P, n, k = (getattr(args, a, d) for a, d in (("patch_size", 8), ("patches_per_step", 16), ("patch_stride", 1)))
+    if not 2 <= int(P) <= 16:
+        return "--patch-size must be in 2 ... 16"
+    if int(n) < 1:
+        return "--patches-per-step must be >= 1"
+    if int(k) < 1:
+        return "--patch-stride must be >= 1"
+    if int(getattr(args, "n_importance", 0) or 0) > 0:
+        return "--depth-smooth-weight with --n-importance is refused: the hierarchical step takes the plain rgb loss"
+    if getattr(args, "fused_inputs", False):
+        return "--depth-smooth-weight with --fused-inputs is refused: a view step has one pose, the patches come from poses of their own"
+    if int(getattr(args, "occupancy_res", 0) or 0) or getattr(args, "occupancy_per_view", False) or any(
+            getattr(args, f, None) is not None for f in OCCUPANCY_FLAGS):
+        return "--depth-smooth-weight is not combined with --occupancy-*: the trainer's grid route steps view by view"
+    if getattr(args, "train_extractor", False):
+        return "--depth-smooth-weight with --train-extractor is refused: the patch rays belong to no view whose map could take their gradient"
+    return None
+
+
+def patch_reg_options(args):
+    """FusedStep's keywords of --depth-smooth-weight / --patch-size ({} when off)."""
+    w = float(getattr(args, "depth_smooth_weight", 0.0) or 0.0)
+    return dict(depth_smooth_weight=w, patch_size=int(getattr(args, "patch_size", 8))) if w > 0.0 else {}
 
 
 def freq_reg_args_error(args):
@@ -425,7 +470,7 @@ class ExtractorTrainer:
 
 
 def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, dino_maps=None, max_batches=None, rank=0, world=1,
-                extractor=None, fused_inputs=False, occupancy=None, draws=None, n_importance=0, coarse_weight=1.0):
+                extractor=None, fused_inputs=False, occupancy=None, draws=None, n_importance=0, coarse_weight=1.0, patches=None):
     """One pass of train.py:261-290 over the training views; returns (mean loss, ray-samples processed).
     fused_inputs: every batch is one `step.step_view` on its pixel ids (--fused-inputs; module docstring) instead of torch gathers,
     sample_points_along_rays, the expanded directions and fetch_features in front of `step(...)`.
@@ -440,6 +485,9 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
     `permutation(v, n)` returns view v's shuffle of its n rays (train.py:272's torch.randperm) and whose `jitter(v, i, n, S)` returns the
     (n,S) uniforms of the batch starting at position i (ray_utils.py:78's torch.rand), handed on as `t_rand=`.  None: `gen` shuffles and
     the counter RNG jitters, as before.
+    patches: dict(n=, stride=, generator=) (--depth-smooth-weight; module docstring) -- every batch of the staged route gets n patches
+    of step.patch_size^2 rays from freshly drawn poses behind its supervised rays, drawn from the CPU generator.  Refused with
+    fused_inputs, occupancy, n_importance, extractor and draws (a recorded run holds no jitter for the patch rays).
     world > 1 (data parallel, `FusedStep(data_parallel=True)`): every rank draws the SAME shuffle (same generator seed) and
     takes rays rank, rank+world, ... of each batch -- the batches are those of one process (the stratified jitter of a ray is
     keyed by its position inside the call, so the sample depths differ from a single-process run's)."""
@@ -458,8 +506,14 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
         if occupancy is not None or extractor is not None:
             raise ValueError("the hierarchical step is not combined with an occupancy grid or a trained extractor")
         fused_inputs = True
+    if patches is not None and (fused_inputs or occupancy is not None or Ni > 0 or extractor is not None):
+        raise ValueError("patches go with the staged route alone: not with fused_inputs, an occupancy grid, the hierarchical step or a trained extractor")
+    if patches is not None and draws is not None:
+        raise ValueError("patches are not combined with draws: a recorded run holds no jitter for the patch rays")
+    train_poses = torch.stack([p.detach().cpu() for p in poses]) if patches is not None else None      # what the unseen poses are drawn around
     total, n_batches, samples = None, 0, 0
     pts_buf = None
+    f_s = focal if (Ht, Wt) == (H, W) else focal * (Ht / H)                    # the focal length of the schedule's rays (view_target)
     for v in range(len(images)):
         if fused_inputs:
             tgt, f_t = view_target(images[v], H, W, focal, Ht, Wt)
@@ -514,8 +568,15 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
                     return float(total) / n_batches, samples
                 continue
             o, d, t = ro[idx], rd[idx], tgt[idx]
+            n_p = 0
+            if patches is not None:
+                from .ray_sampler import patch_rays, sample_patch_poses
+                n_p = int(patches["n"])
+                pp = sample_patch_poses(train_poses, n_p, patches["generator"]).to(o.device)
+                o_p, d_p = patch_rays(Ht, Wt, f_s, pp, step.patch_size, patches["generator"], patches["stride"])
+                o, d = torch.cat([o, o_p]), torch.cat([d, d_p])
             pts, z = sample_points_along_rays(o, d, near, far, S, perturb=True, t_rand=t_rand, seed=epoch * 1_000_003 + v * 10_007 + i)
-            n = idx.shape[0]
+            n = o.shape[0]
             dirs = d[:, None, :].expand(n, S, 3).reshape(-1, 3)                         # train.py:225: raw ray directions per sample
             feats = fetch_features(dino, pts.reshape(-1, 3)) if use_dino else None
             if extractor is not None:
@@ -523,7 +584,7 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
                 loss = step(pts.reshape(-1, 3), z, d, t, dirs=dirs, dino=feats, d_dino_out=d_feats)
                 extractor.add_batch(cam, pts.reshape(-1, 3), d_feats)
             else:
-                loss = step(pts.reshape(-1, 3), z, d, t, dirs=dirs, dino=feats)
+                loss = step(pts.reshape(-1, 3), z, d, t, dirs=dirs, dino=feats, **({"n_patches": n_p} if n_p else {}))
             total = loss if total is None else total + loss
             n_batches += 1
             samples += n * S
@@ -625,6 +686,12 @@ def main(argv=None):
                     help="add W * the occlusion penalty of FreeNeRF (mean rectified density of every ray's first --occ-samples samples): "
                          "FusedStep(occ_weight=W, occ_samples=K) (module docstring); 0: off")
     ap.add_argument("--occ-samples", type=int, default=None, metavar="K", help="with --occ-weight: the samples at the front of every ray it covers")
+    ap.add_argument("--depth-smooth-weight", type=float, default=0.0, metavar="W",
+                    help="add W * RegNeRF's depth-smoothness loss on patches rendered from unseen poses to the step's loss: "
+                         "FusedStep(depth_smooth_weight=W, patch_size=P) (module docstring); 0: off")
+    ap.add_argument("--patch-size", type=int, default=8, metavar="P", help="with --depth-smooth-weight: a patch is P x P rays (2 ... 16)")
+    ap.add_argument("--patches-per-step", type=int, default=16, metavar="N", help="with --depth-smooth-weight: patches behind every batch's supervised rays")
+    ap.add_argument("--patch-stride", type=int, default=1, metavar="K", help="with --depth-smooth-weight: neighbouring patch pixels are K image pixels apart")
     ap.add_argument("--freq-reg-end", type=int, default=0, metavar="N",
                     help="FreeNeRF's frequency regularisation: reveal the bands of the positional encodings linearly over the first N steps "
                          "(FusedStep(freq_reg_end=N); a column scale in the re-pack and the weight gradients, no launch more); 0: off")
@@ -651,7 +718,7 @@ def main(argv=None):
                     help="--data-parallel on a box with ONE GPU: every rank on cuda:0, the gradient all-reduce over gloo through host memory "
                          "(RCCL refuses two ranks on one card); exercises the sharding and the collective, not multi-GPU speed")
     args = ap.parse_args(argv)
-    problem = (hierarchical_args_error(args) or ray_reg_args_error(args) or freq_reg_args_error(args) or extractor_args_error(args, load_config(args.config))
+    problem = (hierarchical_args_error(args) or ray_reg_args_error(args) or patch_reg_args_error(args) or freq_reg_args_error(args) or extractor_args_error(args, load_config(args.config))
                or occupancy_args_error(args, load_config(args.config)))
     if problem:
         raise SystemExit(problem)
@@ -715,9 +782,12 @@ def main(argv=None):
     model = model.to(dev).train()
     step = FusedStep(model, white_bkgd=rs["white_bkgd"], data_parallel=world > 1, **step_options(cfg, args.recipe),
                      **({"seed": args.seed} if args.recipe == "multiscale" else {}), **ray_reg_options(args, rs["near"], rs["far"]),
-                     **freq_reg_options(args))
+                     **freq_reg_options(args), **patch_reg_options(args))
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed)
+    patches = None
+    if step.patch_reg:                                    # the patch draws: a CPU generator of their own, another stream on every rank
+        patches = dict(n=args.patches_per_step, stride=args.patch_stride, generator=torch.Generator().manual_seed(args.seed * 1_000_003 + 7919 * (rank + 1)))
     # (the single grid is not part of a checkpoint: a resumed run starts again from the all-ones grid and its warm-up; the per-view
     # grids are)
     occ = None
@@ -737,7 +807,7 @@ def main(argv=None):
         t0 = time.perf_counter()
         loss, samples = train_epoch(step, cfg, epoch, images, poses, H, W, focal, rs["near"], rs["far"], gen, dino_maps, args.max_batches, rank, world,
                                     extractor=ext, fused_inputs=args.fused_inputs, occupancy=occ, n_importance=args.n_importance,
-                                    coarse_weight=1.0 if args.coarse_weight is None else args.coarse_weight)
+                                    coarse_weight=1.0 if args.coarse_weight is None else args.coarse_weight, patches=patches)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         rec = {"epoch": epoch + 1, "loss": loss, "lr": step.opt.lr, "seconds": round(dt, 3), "Msamples_per_s": round(world * samples / dt / 1e6, 2)}

@@ -957,6 +957,23 @@ class FusedStep:
     one small launch (nrf_ray_terms_finish) behind the optimiser; `last_losses` gains 'dist' and 'occ' (unweighted; 0 for a term
     whose weight is 0), 'total' and the returned loss include both.  With both weights 0 (the default) nothing changes.
 
+    Patch regulariser (RegNeRF's depth-smoothness loss on patches of unseen views; nerfhip.h: nrf_patch_reg), on __call__ and
+    step_rays, with or without occupancy=:
+
+        step = FusedStep(model, lr=5e-4, depth_smooth_weight=0.1, patch_size=8)
+        o_p, d_p = patch_rays(H, W, focal, sample_patch_poses(train_poses, 16), 8)                   # ray_sampler
+        loss = step.step_rays(torch.cat([rays_o, o_p]), torch.cat([rays_d, d_p]), target, near, far, 64, n_patches=16)
+
+    The last n_patches * patch_size^2 rays of the batch are patch rays -- patch-major, row-major inside a patch -- and `target`
+    (and target_depth) hold the rows of the R_s rays in front of them.  A patch ray has no colour term; it takes reg_weight,
+    dist_weight and occ_weight like any ray, and depth_smooth_weight * mean over patches and anchors of the squared depth
+    differences to its right and lower neighbour.  The step is the multi-term one with nrf_composite_patch_loss_backward as its
+    loss launch -- a workgroup owns a patch and its rays' depths meet in LDS between the compositor forward and its backward -- and
+    nrf_patch_terms_finish behind the optimiser: as many launches as a step with dist_weight > 0.  `last_losses` gains 'smooth'
+    (seven keys; rgb and depth are means over the R_s supervised rays), `last_patch_depth` is the (n_patches, P, P) view of a
+    buffer of this object with the rendered depths.  step_view and the hierarchical steps refuse such a step object.  With
+    depth_smooth_weight = 0 (the default) nothing changes, launch for launch.
+
     Frequency regularisation (FreeNeRF's coarse-to-fine mask on the positional encodings), on every step method:
 
         step = FusedStep(model, lr=5e-4, freq_reg_end=9000)
@@ -972,7 +989,7 @@ class FusedStep:
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rgb_weight=1.0, white_bkgd=False,
                  process_group=None, data_parallel=False, reg_weight=0.0, depth_weight=0.0, noise_std=0.0, max_grad_norm=None,
                  decoupled_weight_decay=False, seed=None, dist_weight=0.0, occ_weight=0.0, occ_samples=0, dist_span=None,
-                 freq_reg_end=0, freq_reg_dirs=True):
+                 freq_reg_end=0, freq_reg_dirs=True, depth_smooth_weight=0.0, patch_size=8):
         """data_parallel=True (inside an initialised torch.distributed job): every rank passes ITS shard of the ray batch
         (equal sizes), the flat gradient vector is averaged over the ranks with one all-reduce before Adam (the norm of
         max_grad_norm is taken behind it, so all ranks clip alike), and the returned loss is this rank's.
@@ -990,6 +1007,10 @@ class FusedStep:
             raise ValueError("FusedStep: dist_span must be finite and > 0 (None: far - near of the step)")
         if int(freq_reg_end) < 0:
             raise ValueError("FusedStep: freq_reg_end must be >= 0 (0: no frequency regularisation)")
+        if not (float(depth_smooth_weight) >= 0.0 and math.isfinite(float(depth_smooth_weight))):
+            raise ValueError("FusedStep: depth_smooth_weight must be finite and >= 0")
+        if int(patch_size) != patch_size or not 2 <= int(patch_size) <= 16:
+            raise ValueError("FusedStep: patch_size must be an integer in 2 ... 16")
         self.model = model
         self.freq_reg_end, self.freq_reg_dirs = int(freq_reg_end), bool(freq_reg_dirs)
         self.data_parallel = bool(data_parallel)
@@ -1001,6 +1022,11 @@ class FusedStep:
         self.dist_span = None if dist_span is None else float(dist_span)
         self.ray_reg = self.dist_weight > 0.0 or self.occ_weight > 0.0        # the step with the two few-shot terms
         self._reg = None                    # nrf_ray_reg of the last regularised loss launch: _finish hands it to nrf_ray_terms_finish
+        self.depth_smooth_weight, self.patch_size = float(depth_smooth_weight), int(patch_size)
+        self.patch_reg = self.depth_smooth_weight > 0.0                       # the step with the patch-based depth-smoothness term
+        self._patch = self._patch_lo = None # nrf_patch_reg and nrf_loss_opts of the last patch loss launch, for nrf_patch_terms_finish
+        self._patch_terms = self._patch_depth = None
+        self.last_patch_depth = None        # (n_patches, P, P) view of a buffer of this object: the last patch step's rendered depths
         self.seed = None if seed is None else int(seed)
         self.white = int(bool(white_bkgd))
         self._loss_vec, self.last_grad_norm = None, None
@@ -1024,7 +1050,7 @@ class FusedStep:
     def last_losses(self):
         """The last step's loss terms as device scalars (no sync): {'total'} of the plain step, {'total', 'rgb', 'depth', 'reg'}
         (nerf_mlp.NeRFLoss's dict, unweighted components) of the multi-term one, and 'dist', 'occ' behind them of the step with the
-        few-shot ray regularisers; None before the first step."""
+        few-shot ray regularisers, and 'smooth' behind those of the step with the patch term; None before the first step."""
         v = self._loss_vec
         if v is None:
             return None
@@ -1033,6 +1059,8 @@ class FusedStep:
             parts, R = self._hier_parts
             mse = parts.sum(dim=1) / (3.0 * R)              # formed when asked for (torch reductions on the stream: no sync), from the step's buffer
             return {"total": total, "coarse": mse[0], "fine": mse[1]}
+        if v.dim() == 1 and v.numel() == 7:     # the step with the patch term: 'smooth' behind the six
+            return {"total": v[0], "rgb": v[1], "depth": v[2], "reg": v[3], "dist": v[4], "occ": v[5], "smooth": v[6]}
         if v.dim() == 1 and v.numel() == 6:
             return {"total": v[0], "rgb": v[1], "depth": v[2], "reg": v[3], "dist": v[4], "occ": v[5]}
         return {"total": v} if v.dim() == 0 else {"total": v[0], "rgb": v[1], "depth": v[2], "reg": v[3]}
@@ -1045,7 +1073,7 @@ class FusedStep:
             self.out4, self.d_out4 = f(n, 4), f(n, 4)                 # V1: [rgb, sigma] rows; V2: rgb | density packed in the same rows
             self.pred = f(R, 3)
             # row 0: squared rgb errors; rows 1, 2 (multi-term loss): sum of w^2, |depth error|; rows 3, 4 (ray regularisers): D_r, O_r
-            self.ray_loss = f(5 if self.ray_reg else 3, R)
+            self.ray_loss = f(5 if self.ray_reg or self.patch_reg else 3, R)
             self.grad = torch.zeros(self.model.flat_params().flat.numel(), dtype=torch.float32, device=dev)
             self._key = key
 
@@ -1062,16 +1090,16 @@ class FusedStep:
                                        or points_out.numel() != n * 3):
             raise ValueError("points_out must be a contiguous float32 (R*S, 3) tensor on the GPU")
 
-    def _loss_setup(self, R, S, dev, target_depth, noise, always=False):
+    def _loss_setup(self, R, S, dev, target_depth, noise, always=False, n_sup=None):
         """(multi, loss_opts, tensors its pointers need alive): multi = the step runs the general compositor/loss kernel and the
         clipped optimiser; loss_opts is built only then (always=True: the step under a grid, whose one indexed kernel takes it
         either way).  The noise seed of step t is seed + t: step_count is read before the step increments it."""
         opt = self.opt
         multi = (self.reg_weight > 0.0 or self.depth_weight > 0.0 or self.noise_std > 0.0 or opt.extended or target_depth is not None
-                 or noise is not None or self.ray_reg)
+                 or noise is not None or self.ray_reg or self.patch_reg)
         if not (multi or always):
             return False, None, None
-        td = None if target_depth is None else L.dev_f32(target_depth, dev).reshape(R)
+        td = None if target_depth is None else L.dev_f32(target_depth, dev).reshape(R if n_sup is None else n_sup)
         nz = None if noise is None or self.noise_std == 0.0 else L.dev_f32(noise, dev).reshape(R, S)
         seed = 0
         if self.noise_std > 0.0 and nz is None:
@@ -1080,20 +1108,45 @@ class FusedStep:
             seed = self.seed + opt.step_count
         return multi, L.loss_opts(self.rgb_weight, self.reg_weight, self.depth_weight, L.ptr(td), self.noise_std, L.ptr(nz), seed), (td, nz)
 
-    def _launch_loss(self, heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, slot=None, span=None):
+    def _patch_check(self, R, n_patches):
+        """The refusals of n_patches on a batch of R rays; returns R_s, the number of supervised rays in front of the patch rays."""
+        n_patches = int(n_patches)
+        if n_patches < 0:
+            raise ValueError("n_patches must be >= 0")
+        if n_patches > 0 and not self.patch_reg:
+            raise ValueError("n_patches > 0 needs a FusedStep built with depth_smooth_weight > 0")
+        Rs = R - n_patches * self.patch_size ** 2
+        if Rs < 1:
+            raise ValueError("the last n_patches * patch_size^2 rays of the batch are patch rays: at least one supervised ray must stand in front of them")
+        return Rs
+
+    def _launch_loss(self, heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, slot=None, span=None, n_patches=0):
         """compositor -> d loss / d pred = 2 w (pred - target) / (3 R) -> compositor backward, and the flat gradient vector cleared:
         one launch (a ray's loss gradient needs only its own prediction); the rays' squared errors stay in ray_loss.  slot (the step
         under a grid): the indexed kernel, for the plain and the multi-term loss alike.  With the few-shot ray regularisers on, the
         one entry that carries them (dense or indexed); span: the depth range their midpoints are scaled by.  Returns `multi`."""
         lib = L.lib()
         self._hier_parts = None
-        multi, lo, keep = self._loss_setup(R, S, dev, target_depth, noise, always=slot is not None)
-        if self.ray_reg:
+        multi, lo, keep = self._loss_setup(R, S, dev, target_depth, noise, always=slot is not None, n_sup=R - n_patches * self.patch_size ** 2)
+        if self.ray_reg or self.patch_reg:
             span = self.dist_span if self.dist_span is not None else span
             if self.dist_weight > 0.0 and not (span is not None and math.isfinite(span) and span > 0.0):
                 raise ValueError("dist_weight > 0 needs a depth range: pass dist_span= to FusedStep (__call__ has no near / far), "
                                  "or step with far > near")
             self._reg = L.ray_reg(self.dist_weight, 1.0 / span if self.dist_weight > 0.0 else 0.0, self.occ_weight, self.occ_samples)
+        if self.patch_reg:
+            # the one entry with the patch term (dense or indexed): the rays' depths meet in LDS between its forward and its backward
+            P = self.patch_size
+            if self._patch_terms is None or self._patch_terms.numel() != max(n_patches, 1) or self._patch_terms.device != dev:
+                self._patch_terms = torch.zeros((max(n_patches, 1),), dtype=torch.float32, device=dev)
+                self._patch_depth = torch.zeros((max(n_patches, 1) * P * P,), dtype=torch.float32, device=dev)
+            self.last_patch_depth = self._patch_depth[: n_patches * P * P].view(n_patches, P, P)
+            self._patch, self._patch_lo = L.patch_reg(self.depth_smooth_weight, P, n_patches), lo
+            L.check(lib.nrf_composite_patch_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), C.byref(self._reg),
+                                                          None if slot is None else slot.data_ptr(), L.ptr(self.pred), *d_heads,
+                                                          L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st, C.byref(self._patch),
+                                                          L.ptr(self._patch_terms), L.ptr(self._patch_depth)))
+        elif self.ray_reg:
             L.check(lib.nrf_composite_reg_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), C.byref(self._reg),
                                                         None if slot is None else slot.data_ptr(), L.ptr(self.pred), *d_heads,
                                                         L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
@@ -1139,7 +1192,12 @@ class FusedStep:
             loss = torch.empty((4,), dtype=torch.float32, device=dev)
             opt._update(flat, self.grad, self.ray_loss, R, S, (loss_weight, self.depth_weight if target_depth is not None else 0.0,
                                                                self.reg_weight), loss)
-            if self.ray_reg:
+            if self.patch_reg:
+                # one small launch more: all seven values with the divisors of the batch layout (the optimiser's four divide by R)
+                loss = torch.empty((7,), dtype=torch.float32, device=dev)
+                L.check(lib.nrf_patch_terms_finish(L.ptr(self.ray_loss), R, S, C.byref(self._patch_lo), C.byref(self._reg), C.byref(self._patch),
+                                                   L.ptr(self._patch_terms), L.ptr(loss), st))      # (loss_opts.target_depth: a flag here, not read)
+            elif self.ray_reg:
                 # one small launch more: the two new terms summed in a fixed order and appended to the four
                 loss4, loss = loss, torch.empty((6,), dtype=torch.float32, device=dev)
                 L.check(lib.nrf_ray_terms_finish(L.ptr(self.ray_loss), R, C.byref(self._reg), L.ptr(loss4), L.ptr(loss), st))
@@ -1156,11 +1214,13 @@ class FusedStep:
         return loss
 
     @torch.no_grad()
-    def __call__(self, points, z_vals, rays_d, target, dirs=None, dino=None, target_depth=None, noise=None, d_dino_out=None):
+    def __call__(self, points, z_vals, rays_d, target, dirs=None, dino=None, target_depth=None, noise=None, d_dino_out=None, n_patches=0):
         """target_depth (R): switches the depth term on (with depth_weight); noise (R,S): the standard normals of the density noise
         (with noise_std) instead of the in-kernel RNG -- what torch.randn_like would have drawn, for parity runs.
         d_dino_out: a preallocated (R*S, dino_dim) fp32 tensor that receives dL/d dino of this step (V3 with model.dino_grad: one
-        more launch behind the weight gradients; project_fetch_backward turns it into the feature map's gradient)."""
+        more launch behind the weight gradients; project_fetch_backward turns it into the feature map's gradient).
+        n_patches (a step built with depth_smooth_weight > 0): the last n_patches * patch_size^2 rays of the batch are patch rays
+        (patch-major, row-major inside a patch); target and target_depth hold the rows of the other rays."""
         m = self.model
         if self.dist_weight > 0.0 and self.dist_span is None:
             raise ValueError("dist_weight > 0 needs dist_span= on a FusedStep that is called with depths: there is no near / far to take it from")
@@ -1171,7 +1231,8 @@ class FusedStep:
         z = L.dev_f32(z_vals, dev)
         R, S = z.shape
         d = L.dev_f32(rays_d, dev).reshape(R, 3)
-        tgt = L.dev_f32(target, dev).reshape(R, 3)
+        n_patches = int(n_patches)
+        tgt = L.dev_f32(target, dev).reshape(self._patch_check(R, n_patches), 3)
         v1 = m.net == L.NRF_NET_V1                                   # otherwise the trainer forms: positions + directions (+ DINO features)
         pts = pts.reshape(R * S, 3 * (2 * m.pos_freq + 1) if v1 else 3)
         n = R * S
@@ -1190,14 +1251,14 @@ class FusedStep:
                 dirs_d = L.dev_f32(dirs, dev).reshape(n, 3)
                 dino_d = L.dev_f32(dino, dev).reshape(n, m.dino_dim) if m.net == L.NRF_NET_V3 else None
                 L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(pts), L.ptr(dirs_d), L.ptr(dino_d), n, L.ptr(out[0]), L.ptr(out[1]), ctx, self.nbytes, st))
-            multi = self._launch_loss(heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st)
+            multi = self._launch_loss(heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, n_patches=n_patches)
             self._network_backward(h, mode, n, out, d_out, ctx, st, d_dino_out)
             return self._finish(multi, R, S, dev, target_depth, st)
 
     # ---- the same step from rays: sampling, encoding and the feature fetch happen inside the saving forward ----------------
     @torch.no_grad()
     def step_rays(self, rays_o, rays_d, target, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False, z_in=None,
-                  dino=None, target_depth=None, noise=None, d_dino_out=None, points_out=None, occupancy=None, grid_inputs="staged"):
+                  dino=None, target_depth=None, noise=None, d_dino_out=None, points_out=None, occupancy=None, grid_inputs="staged", n_patches=0):
         """One step on rays (R,3) and their target (R,3): what train.py:188-229 builds in front of the network -- stratified
         samples, per-sample directions, projected DINO features, encodings -- is derived inside the forward kernel
         (nrf_mlp_forward_train_rays), so no per-sample input tensor exists.  Depths, points and therefore (V2) every bit of the step
@@ -1225,14 +1286,17 @@ class FusedStep:
         through nrf_encode, V3: through nrf_project_fetch); "rays" keeps the ray route's front end under the grid
         (nrf_mlp_forward_train_rays_indexed: ray, position, encoding and feature gather derived in the kernel for row index[j]).
         With "rays" d_dino_out and points_out are accepted: rows [0, M) of both hold the compacted samples in ascending flat-id
-        order (the compaction writes its positions straight into points_out), rows >= M are not written."""
+        order (the compaction writes its positions straight into points_out), rows >= M are not written.
+
+        n_patches: as in __call__ -- the last n_patches * patch_size^2 rays are patch rays (ray_sampler.patch_rays writes them), target
+        (R_s,3) and target_depth (R_s) belong to the rays in front of them; with or without occupancy=, on both grid_inputs routes."""
         o = L.dev_f32(rays_o).reshape(-1, 3)
         d = L.dev_f32(rays_d, o.device).reshape(-1, 3)
         if d.shape != o.shape:
             raise ValueError("rays_o and rays_d must both be (R,3)")
         return self._ray_step(o.shape[0], o.device, lambda z, d_out, p_out: L.train_rays(rays_o=L.ptr(o), rays_d=L.ptr(d), z_vals=z, points_out=p_out), d,
                               target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise, d_dino_out, points_out,
-                              occupancy, grid_inputs)
+                              occupancy, grid_inputs, n_patches)
 
     @torch.no_grad()
     def step_view(self, image, pose, H, W, focal, pixels, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False,
@@ -1243,7 +1307,10 @@ class FusedStep:
         image.reshape(-1,3)[pixels] of the (H,W,3) image: one torch gather.  The jitter of a ray is keyed by its position in
         `pixels`, not by the pixel id: the step equals step_rays on the gathered rays to the bit.  `pose` may also be the 12 floats
         `ray_sampler._c2w12` made of it (as `dino` may be `make_dino`'s pair): nothing is converted per batch then.  occupancy: as in
-        step_rays (one 8-byte read-back per step), and so is grid_inputs."""
+        step_rays (one 8-byte read-back per step), and so is grid_inputs.  A step built with depth_smooth_weight > 0 is refused: a
+        view has one pose, and the patches come from poses of their own (step_rays)."""
+        if self.patch_reg:
+            raise ValueError("step_view takes one pose per call: a FusedStep with depth_smooth_weight > 0 steps through step_rays or __call__")
         if not (isinstance(pixels, torch.Tensor) and pixels.is_cuda and pixels.dtype == torch.int64 and pixels.dim() == 1):
             raise ValueError("pixels must be a 1-d int64 tensor of ray ids on the GPU")
         pix = pixels.contiguous()
@@ -1269,6 +1336,8 @@ class FusedStep:
             raise ValueError("the hierarchical step takes the plain rgb loss: a FusedStep with reg_weight, depth_weight or noise_std > 0 is refused")
         if self.ray_reg:
             raise ValueError("the hierarchical step takes the plain rgb loss: a FusedStep with dist_weight or occ_weight > 0 is refused")
+        if self.patch_reg:
+            raise ValueError("the hierarchical step takes the plain rgb loss: a FusedStep with depth_smooth_weight > 0 is refused")
         if occupancy is not None:
             raise ValueError("the hierarchical step is not combined with occupancy=")
         if d_dino_out is not None or points_out is not None:
@@ -1433,7 +1502,7 @@ class FusedStep:
             return loss
 
     def _ray_step(self, R, dev, make_rays, d, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise,
-                  d_dino_out, points_out, occupancy=None, grid_inputs="staged"):
+                  d_dino_out, points_out, occupancy=None, grid_inputs="staged", n_patches=0):
         """__call__'s sequence with nrf_mlp_forward_train_rays in front -- or, under an occupancy grid, _grid_forward; d is the
         caller's (R,3) directions or None (pixel mode: the kernel writes them for the compositor)."""
         from .renderer import _opts, make_dino
@@ -1455,7 +1524,8 @@ class FusedStep:
         if R < 1:
             raise ValueError("a step needs at least one ray")
         self._check_outputs(n, d_dino_out, points_out)
-        tgt = L.dev_f32(target, dev).reshape(R, 3)
+        n_patches = int(n_patches)
+        tgt = L.dev_f32(target, dev).reshape(self._patch_check(R, n_patches), 3)
         tr = L.dev_f32(t_rand, dev).reshape(R, S) if t_rand is not None else None
         zin = L.dev_f32(z_in, dev).reshape(R, S) if z_in is not None else None
         dn = keep = None
@@ -1487,7 +1557,7 @@ class FusedStep:
                 L.check(lib.nrf_mlp_forward_train_rays(h, C.byref(rays), R, C.byref(opts), L.ptr(out[0]), L.ptr(out[1]), ctx, self.nbytes, st))
                 rows, slot = n, None
             del keep
-            multi = self._launch_loss(heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, slot, span=float(far) - float(near))
+            multi = self._launch_loss(heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, slot, span=float(far) - float(near), n_patches=n_patches)
             if occupancy is None or rows:
                 self._network_backward(h, mode, rows, out, d_out, ctx, st, d_dino_out)
             return self._finish(multi, R, S, dev, target_depth, st)

@@ -64,10 +64,11 @@ def standin_feature_maps(images, dim=64, grid=9):
     return torch.stack(maps).contiguous()
 
 
-def train_field(net, cfg, scene_dir, train_mode, seed=0, epoch_scale=1.0, sigma_bias=None, v1_batch=None, step_options=None):
+def train_field(net, cfg, scene_dir, train_mode, seed=0, epoch_scale=1.0, sigma_bias=None, v1_batch=None, step_options=None, patches=None):
     """Train on the scene's train split; returns (model, info).  The progressive schedule's stage boundaries (epochs 50 / 100,
     train.py:249-259) scale with `epoch_scale` when fewer than the YAML's 200 epochs are run.  step_options: further keywords of the
-    FusedStep (tools/few_shot_ray_reg.py: the ray regularisers)."""
+    FusedStep (tools/few_shot_ray_reg.py: the ray regularisers); patches: train_cli.train_epoch's dict (tools/few_shot_patch_reg.py: the
+    patches of unseen views behind every batch, V2 / V3)."""
     import nerf_few_shot_limitations_amd as N
     from nerf_few_shot_limitations_amd import train_cli
     from nerf_few_shot_limitations_amd.training import FusedStep
@@ -108,7 +109,7 @@ def train_field(net, cfg, scene_dir, train_mode, seed=0, epoch_scale=1.0, sigma_
         sched_epoch = int(epoch / epoch_scale)                   # which stage of the 200-epoch schedule this epoch stands for
         step.opt.lr = train_cli.lr_at(cfg, sched_epoch)
         if net in ("v2", "v3"):
-            loss, n = train_cli.train_epoch(step, cfg, sched_epoch, images, poses, H, W, focal, 2.0, 6.0, gen, dino_maps)
+            loss, n = train_cli.train_epoch(step, cfg, sched_epoch, images, poses, H, W, focal, 2.0, 6.0, gen, dino_maps, patches=patches)
         else:
             Ht, Wt, S, batch = train_cli.schedule_for(cfg, sched_epoch)
             batch = v1_batch or batch
