@@ -934,6 +934,69 @@ int nrf_composite_patch_loss_backward(const float* rgb, int rgb_stride, const fl
 int nrf_patch_terms_finish(const float* ray_terms, int64_t n_rays, int n_samples, const nrf_loss_opts* loss, const nrf_ray_reg* reg,
                            const nrf_patch_reg* patch, const float* patch_terms, float* losses7, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Information regularisers: InfoNeRF's ray-entropy loss on every ray and its information-gain (KL) loss between neighbouring
+ * rays, here the neighbouring rays of the patches of nrf_patch_reg.  Both act on the per-sample distribution of a ray.  For ray r
+ * with S samples, s_i the density the ReLU sees (behind the density noise; -inf for a sample skipped under an occupancy grid),
+ * dist_i as the compositor forms it, over the S - 1 samples i = 0 ... S-2 with a finite interval (the last sample, whose dist is
+ * 1e10 |d|, takes no part), eps = 1e-10, tau = ent_threshold, natural logarithms:
+ *   x_i = relu(s_i) dist_i      a_i = -expm1(-x_i)      A = sum_i a_i      p_i = a_i / (A + eps)
+ *   H_r = -sum_i p_i ln(p_i + eps)                       m_r = [A > tau]   (a constant: no gradient)
+ *   KL(p || q) = sum_i p_i (ln(p_i + eps) - ln(q_i + eps))
+ *   entropy = (1/R) sum_r m_r H_r                        over all R rays of the batch, the patch rays included
+ *   K_p     = sum_{i<P-1, j<P-1} m(i,j) m(i,j+1) KL(p(i,j) || p(i,j+1)) + m(i,j) m(i+1,j) KL(p(i,j) || p(i+1,j))
+ *   kl      = sum_p K_p / (N_p (P-1)^2)
+ *   loss    = nrf_composite_patch_loss_backward's + ent_weight entropy + kl_weight kl
+ * The gradient flows into both arguments of every KL, to the densities alone: with G_i = dL/dp_i summed over a ray's roles
+ * (entropy: -ln(p_i+eps) - p_i/(p_i+eps); first argument of a KL: ln(p_i+eps) - ln(q_i+eps) + p_i/(p_i+eps); second argument,
+ * p' the first: -p'_i/(p_i+eps)), M = sum_i p_i G_i,
+ *   dL/ds_j += [s_j > 0] dist_j exp(-x_j) (G_j - M) / (A + eps).
+ * a_i comes from expm1, not from the compositor's alpha = 1 - e: next to e = 1 that subtraction keeps three digits of a_i.  The
+ * compositor's own alpha is what it was.  A ray with S = 1, a masked ray (A <= tau) and a sample with s_j <= 0 receive exactly
+ * nothing from the two terms.  Additive to ABI 5, as nrf_patch_reg is.
+ * ------------------------------------------------------------------------ */
+typedef struct nrf_info_reg {
+    int32_t struct_bytes;          /* sizeof(nrf_info_reg): checked by the library */
+    float   ent_weight;            /* >= 0; 0: the entropy term is not computed */
+    float   ent_threshold;         /* tau >= 0: rays with A <= tau take part in neither term */
+    float   kl_weight;             /* >= 0; 0: the KL term is not computed */
+} nrf_info_reg;
+
+/* The KL term keeps a patch's distributions in LDS between the two phases of the loss launch: patch_size^2 * n_samples floats
+ * (P^2 rows of S - 1 values and their sums), sized at launch.  A request with kl_weight > 0 and patch_size^2 * n_samples above
+ * this is refused; it admits P = 8 at S = 192 and P = 16 at S = 48.  The entropy term alone has no such cap. */
+#define NRF_INFO_KL_MAX_LDS_FLOATS 12288
+
+/* nrf_composite_patch_loss_backward with the two terms, still ONE launch and its walk: a wave that has run the compositor
+ * backward of a ray forms G and M for it, LANE <-> sample (M a wave reduction per 64-sample segment, the segments added front to
+ * back; rays of S - 1 <= 64 keep everything in registers, longer ones walk their segments once more), and adds
+ *   fl(fl(dist_j e_j) * fl(fl(G_j - M) / fl(A + eps)))
+ * in one rounded addition to the d_sigma entry that the compositor backward has just stored, regularisers included.  With
+ * kl_weight > 0 phase 1 of a patch leaves every ray's a_i and A in LDS, and phase 2 reads up to four neighbours' rows.  No atomics:
+ * two runs give the same bits.  With ent_weight = kl_weight = 0 every output is nrf_composite_patch_loss_backward's, bit for bit
+ * (n_patches = 0 or not), and the launch carries no dynamic LDS.  A term whose weight is 0 is not computed and its output is 0.
+ *   info_terms : n_rays floats: m_r H_r       (may be NULL with ent_weight = 0)
+ *   patch_kl   : n_patches floats: K_p        (may be NULL with kl_weight = 0)
+ * NRF_EINVAL, before any launch: what nrf_composite_patch_loss_backward refuses; info NULL or of a wrong struct_bytes; a negative
+ * or non-finite ent_weight, ent_threshold or kl_weight; kl_weight > 0 with n_patches = 0; kl_weight > 0 with
+ * patch_size^2 * n_samples > NRF_INFO_KL_MAX_LDS_FLOATS; info_terms NULL with ent_weight > 0; patch_kl NULL with kl_weight > 0. */
+int nrf_composite_info_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride,
+                                     const float* z_vals, const float* rays_d, int64_t n_rays, int n_samples, int white_bkgd,
+                                     const float* target, const nrf_loss_opts* loss, const nrf_ray_reg* reg, const int32_t* slot,
+                                     float* pred, float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride,
+                                     float* ray_terms, float* zero_buf, int64_t zero_n, void* stream, const nrf_patch_reg* patch,
+                                     float* patch_terms, float* patch_depth, const nrf_info_reg* info, float* info_terms,
+                                     float* patch_kl);
+
+/* nrf_patch_terms_finish with the two terms:
+ *   losses9 = [total, rgb, depth, reg, mean D, mean O, smooth, entropy, kl]
+ * unweighted components with the divisors above (entropy: R; kl: N_p (P-1)^2, 0 with n_patches = 0), the total with both weighted
+ * terms, one workgroup, a fixed order.  NRF_EINVAL: what nrf_patch_terms_finish refuses, what the entry above refuses of info,
+ * info_terms NULL with ent_weight > 0, patch_kl NULL with kl_weight > 0. */
+int nrf_info_terms_finish(const float* ray_terms, int64_t n_rays, int n_samples, const nrf_loss_opts* loss, const nrf_ray_reg* reg,
+                          const nrf_patch_reg* patch, const float* patch_terms, const nrf_info_reg* info, const float* info_terms,
+                          const float* patch_kl, float* losses9, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

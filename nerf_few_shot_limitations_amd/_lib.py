@@ -100,6 +100,19 @@ def patch_reg(depth_smooth_weight=0.0, patch_size=8, n_patches=0):
     return nrf_patch_reg(C.sizeof(nrf_patch_reg), float(depth_smooth_weight), int(patch_size), int(n_patches))
 
 
+class nrf_info_reg(C.Structure):
+    """The ray-entropy and patch-KL terms of nrf_composite_info_loss_backward; struct_bytes is filled in by info_reg()."""
+    _fields_ = [("struct_bytes", C.c_int32), ("ent_weight", C.c_float), ("ent_threshold", C.c_float), ("kl_weight", C.c_float)]
+
+
+def info_reg(ent_weight=0.0, ent_threshold=0.01, kl_weight=0.0):
+    """nrf_info_reg with its size field set."""
+    return nrf_info_reg(C.sizeof(nrf_info_reg), float(ent_weight), float(ent_threshold), float(kl_weight))
+
+
+INFO_KL_MAX_LDS_FLOATS = 12288          # nerfhip.h: NRF_INFO_KL_MAX_LDS_FLOATS -- kl_weight > 0 needs patch_size^2 * n_samples <= this
+
+
 class nrf_train_rays(C.Structure):
     """The ray source of nrf_mlp_forward_train_rays; struct_bytes is filled in by train_rays()."""
     _fields_ = [("struct_bytes", C.c_int32), ("reserved", C.c_int32), ("rays_o", C.c_void_p), ("rays_d", C.c_void_p), ("pixels", C.c_void_p),
@@ -302,6 +315,14 @@ SIGNATURES = {
                                                     C.POINTER(nrf_patch_reg), C.c_void_p, C.c_void_p]),
     "nrf_patch_terms_finish": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(nrf_loss_opts), C.POINTER(nrf_ray_reg), C.POINTER(nrf_patch_reg),
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the same two with InfoNeRF's ray entropy and patch KL terms (nine loss values)
+    "nrf_composite_info_loss_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                                   C.c_void_p, C.POINTER(nrf_loss_opts), C.POINTER(nrf_ray_reg), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                   C.POINTER(nrf_patch_reg), C.c_void_p, C.c_void_p, C.POINTER(nrf_info_reg), C.c_void_p,
+                                                   C.c_void_p]),
+    "nrf_info_terms_finish": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.POINTER(nrf_loss_opts), C.POINTER(nrf_ray_reg), C.POINTER(nrf_patch_reg),
+                                        C.c_void_p, C.POINTER(nrf_info_reg), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

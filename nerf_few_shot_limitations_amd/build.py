@@ -56,6 +56,9 @@ FREQ_MASK_SOURCES = [("freq_mask.hip", "freq_mask", [], FREQ_MASK_DIR)]
 # The loss launch with the patch-based depth-smoothness term (patch_reg.hip): likewise (tests/golden/kernel_resources_patch_reg.json).
 PATCH_REG_DIR = "patch_reg"
 PATCH_REG_SOURCES = [("patch_reg.hip", "patch_reg", [], PATCH_REG_DIR)]
+# The loss launch with InfoNeRF's ray entropy and patch KL terms (info_reg.hip): likewise (tests/golden/kernel_resources_info_reg.json).
+INFO_REG_DIR = "info_reg"
+INFO_REG_SOURCES = [("info_reg.hip", "info_reg", [], INFO_REG_DIR)]
 # -Rpass-analysis=kernel-resource-usage: the backend reports every kernel's registers / spills / scratch; kept beside the object
 # (<name>.o.remarks, see kernel_resources()) so that a toolchain or flag change that breaks the AGPR parking or introduces
 # spills in a headline kernel is caught by tests/test_kernel_resources.py
@@ -125,7 +128,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         return obj, True
 
     with cf.ThreadPoolExecutor(max_workers=os.cpu_count() or 8) as ex:
-        res = list(ex.map(one, [*SOURCES, *SUBDIR_SOURCES, *RAY_REG_SOURCES, *FREQ_MASK_SOURCES, *PATCH_REG_SOURCES]))
+        res = list(ex.map(one, [*SOURCES, *SUBDIR_SOURCES, *RAY_REG_SOURCES, *FREQ_MASK_SOURCES, *PATCH_REG_SOURCES, *INFO_REG_SOURCES]))
     objs = [o for o, _ in res]
     if not any(built for _, built in res) and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(objs):
         os.utime(LIB)          # nothing to do (e.g. only a comment of this file changed): restore the fast path

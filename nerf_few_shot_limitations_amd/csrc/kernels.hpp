@@ -251,6 +251,17 @@ int launch_composite_patch_loss_backward(const float* rgb, int rgb_stride, const
                                          float* patch_depth, hipStream_t s);
 int launch_patch_terms_finish(const float* ray_terms, int64_t n_rays, int S, const LossTerms& lt, const RayRegTerms& rt, const PatchRegTerms& pt,
                               const float* patch_terms, float* losses7, hipStream_t s);
+// The same launch with InfoNeRF's ray entropy and patch KL terms on top (info_reg.hip; nerfhip.h: nrf_info_reg, whose fields these
+// are).  info_terms (R): m_r H_r; patch_kl (N_p): K_p.  launch_info_terms_finish: losses9 from ray_terms, patch_terms and those two.
+struct InfoRegTerms { float ent_weight, ent_threshold, kl_weight; };
+int launch_composite_info_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
+                                        int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, const RayRegTerms& rt,
+                                        const PatchRegTerms& pt, const InfoRegTerms& it, const int32_t* slot, float* pred, float* d_rgb,
+                                        int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n,
+                                        float* patch_terms, float* patch_depth, float* info_terms, float* patch_kl, hipStream_t s);
+int launch_info_terms_finish(const float* ray_terms, int64_t n_rays, int S, const LossTerms& lt, const RayRegTerms& rt, const PatchRegTerms& pt,
+                             const InfoRegTerms& it, const float* patch_terms, const float* info_terms, const float* patch_kl, float* losses9,
+                             hipStream_t s);
 // partial sums of squares of a flat vector (one float per workgroup, fixed order); the optimiser launch adds them up
 constexpr int kMaxSqnormPartials = 1024;
 inline int sqnorm_partials(int64_t n) {

@@ -102,6 +102,18 @@ One launch sequence as with --dist-weight: the patch rays' depths meet in LDS in
 the data set is read: --depth-smooth-weight together with --n-importance, --fused-inputs (a view step has one pose), any
 --occupancy-* flag or --train-extractor; a negative weight, P outside 2 ... 16, N < 1, K < 1.
 
+--entropy-weight W (0, the default: off) adds InfoNeRF's ray-entropy loss (`FusedStep(ent_weight=W, ent_threshold=T)`; nerfhip.h:
+nrf_info_reg): W * the mean over every ray of the batch of the entropy of the ray's per-sample distribution p_i = a_i / sum a, rays
+whose sum a is at most --entropy-threshold T (default 0.01) left out.  It goes wherever --dist-weight goes (the staged route,
+--fused-inputs, the occupancy routes) and is refused with --n-importance.  --entropy-unseen also draws patches of unseen poses behind
+every batch (--patches-per-step / --patch-size / --patch-stride, as --depth-smooth-weight does), so that the entropy acts on rays
+nobody observed; it has --depth-smooth-weight's refusals.  --kl-weight W (0: off) adds InfoNeRF's information-gain loss
+(`FusedStep(kl_weight=W, patch_size=P)`): W * the mean over patches and anchors of KL(p_anchor || p_right) + KL(p_anchor || p_below) on
+the same patches, neighbouring rays --patch-stride K pixels apart; it draws the patches itself and has --depth-smooth-weight's
+refusals: --n-importance, --fused-inputs, any --occupancy-* flag, --train-extractor, and P^2 * n_samples above 12288 (the patch's
+distributions meet in LDS).  All of this is decided before the config or the data set is read, except the last, which the step
+object refuses.  The launch count is --depth-smooth-weight's.
+
 --freq-reg-end N (0, the default: off) is FreeNeRF's frequency regularisation (`FusedStep(freq_reg_end=N)`; nerfhip.h:
 nrf_model_set_freq_mask): step t trains and validates the field whose positional encodings show min(L, 1 + L t / N) bands (the
 direction encoding too, unless --no-freq-reg-dirs).  The mask is a column scale of the Linears that read the encodings, applied
@@ -255,6 +267,11 @@ def patch_reg_args_error(args):
         return "--depth-smooth-weight must be finite and >= 0 (0: off)"
     if w == 0.0:
         return None
+    return patch_draw_error(args, "--depth-smooth-weight")
+
+
+def patch_draw_error(args, flag):
+    """Why the trainer cannot draw patches for `flag` (--depth-smooth-weight, --kl-weight, --entropy-unseen) with these arguments."""
     P, n, k = (getattr(args, a, d) for a, d in (("patch_size", 8), ("patches_per_step", 16), ("patch_stride", 1)))
     if not 2 <= int(P) <= 16:
         return "--patch-size must be in 2 ... 16"
@@ -263,15 +280,59 @@ def patch_reg_args_error(args):
     if int(k) < 1:
         return "--patch-stride must be >= 1"
     if int(getattr(args, "n_importance", 0) or 0) > 0:
-        return "--depth-smooth-weight with --n-importance is refused: the hierarchical step takes the plain rgb loss"
+        return f"{flag} with --n-importance is refused: the hierarchical step takes the plain rgb loss"
     if getattr(args, "fused_inputs", False):
-        return "--depth-smooth-weight with --fused-inputs is refused: a view step has one pose, the patches come from poses of their own"
+        return f"{flag} with --fused-inputs is refused: a view step has one pose, the patches come from poses of their own"
     if int(getattr(args, "occupancy_res", 0) or 0) or getattr(args, "occupancy_per_view", False) or any(
             getattr(args, f, None) is not None for f in OCCUPANCY_FLAGS):
-        return "--depth-smooth-weight is not combined with --occupancy-*: the trainer's grid route steps view by view"
+        return f"{flag} is not combined with --occupancy-*: the trainer's grid route steps view by view"
     if getattr(args, "train_extractor", False):
-        return "--depth-smooth-weight with --train-extractor is refused: the patch rays belong to no view whose map could take their gradient"
+        return f"{flag} with --train-extractor is refused: the patch rays belong to no view whose map could take their gradient"
     return None
+
+
+def info_reg_args_error(args):
+    """Why --entropy-weight / --entropy-threshold / --entropy-unseen / --kl-weight cannot run with these arguments (None: they can, or
+    none was given).  Decided before a config or a data set is read: the entropy flag has --dist-weight's refusals, the KL flag and
+    --entropy-unseen, which draw patches, --depth-smooth-weight's."""
+    ew, kw = float(getattr(args, "entropy_weight", 0.0) or 0.0), float(getattr(args, "kl_weight", 0.0) or 0.0)
+    th = getattr(args, "entropy_threshold", None)
+    unseen = bool(getattr(args, "entropy_unseen", False))
+    if not (ew >= 0.0 and kw >= 0.0 and math.isfinite(ew) and math.isfinite(kw)):
+        return "--entropy-weight and --kl-weight must be finite and >= 0 (0: off)"
+    if th is not None and not (float(th) >= 0.0 and math.isfinite(float(th))):
+        return "--entropy-threshold must be finite and >= 0"
+    if th is not None and ew == 0.0 and kw == 0.0:
+        return "--entropy-threshold needs --entropy-weight or --kl-weight: without either term the flag would be ignored"
+    if unseen and ew == 0.0:
+        return "--entropy-unseen needs --entropy-weight W (W > 0): it draws patches of unseen poses for the entropy term"
+    if ew > 0.0 and int(getattr(args, "n_importance", 0) or 0) > 0:
+        return "--entropy-weight with --n-importance is refused: the hierarchical step takes the plain rgb loss"
+    if kw > 0.0:
+        return patch_draw_error(args, "--kl-weight")
+    if unseen:
+        return patch_draw_error(args, "--entropy-unseen")
+    return None
+
+
+def info_reg_options(args):
+    """FusedStep's keywords of --entropy-weight / --entropy-threshold / --kl-weight ({} when both weights are 0); patch_size with them
+    when the step draws patches for these terms alone (--depth-smooth-weight hands it over itself)."""
+    ew, kw = float(getattr(args, "entropy_weight", 0.0) or 0.0), float(getattr(args, "kl_weight", 0.0) or 0.0)
+    if ew == 0.0 and kw == 0.0:
+        return {}
+    th = getattr(args, "entropy_threshold", None)
+    out = dict(ent_weight=ew, ent_threshold=0.01 if th is None else float(th), kl_weight=kw)
+    if draws_patches(args) and not float(getattr(args, "depth_smooth_weight", 0.0) or 0.0) > 0.0:
+        out["patch_size"] = int(getattr(args, "patch_size", 8))
+    return out
+
+
+def draws_patches(args):
+    """Whether every batch gets patches of unseen poses behind its supervised rays: --depth-smooth-weight, --kl-weight, or
+    --entropy-weight with --entropy-unseen."""
+    return (float(getattr(args, "depth_smooth_weight", 0.0) or 0.0) > 0.0 or float(getattr(args, "kl_weight", 0.0) or 0.0) > 0.0
+            or (float(getattr(args, "entropy_weight", 0.0) or 0.0) > 0.0 and bool(getattr(args, "entropy_unseen", False))))
 
 
 def patch_reg_options(args):
@@ -692,6 +753,16 @@ def main(argv=None):
     ap.add_argument("--patch-size", type=int, default=8, metavar="P", help="with --depth-smooth-weight: a patch is P x P rays (2 ... 16)")
     ap.add_argument("--patches-per-step", type=int, default=16, metavar="N", help="with --depth-smooth-weight: patches behind every batch's supervised rays")
     ap.add_argument("--patch-stride", type=int, default=1, metavar="K", help="with --depth-smooth-weight: neighbouring patch pixels are K image pixels apart")
+    ap.add_argument("--entropy-weight", type=float, default=0.0, metavar="W",
+                    help="add W * InfoNeRF's ray entropy (mean over every ray of the batch of the entropy of its per-sample distribution): "
+                         "FusedStep(ent_weight=W, ent_threshold=T) (module docstring); 0: off")
+    ap.add_argument("--entropy-threshold", type=float, default=None, metavar="T",
+                    help="with --entropy-weight / --kl-weight: rays whose summed opacity is at most T take no part (default 0.01)")
+    ap.add_argument("--entropy-unseen", action="store_true",
+                    help="with --entropy-weight: also draw --patches-per-step patches of unseen poses per batch, as --depth-smooth-weight does")
+    ap.add_argument("--kl-weight", type=float, default=0.0, metavar="W",
+                    help="add W * InfoNeRF's information-gain loss, the KL divergence between neighbouring rays of patches from unseen poses: "
+                         "FusedStep(kl_weight=W, patch_size=P) (module docstring); 0: off")
     ap.add_argument("--freq-reg-end", type=int, default=0, metavar="N",
                     help="FreeNeRF's frequency regularisation: reveal the bands of the positional encodings linearly over the first N steps "
                          "(FusedStep(freq_reg_end=N); a column scale in the re-pack and the weight gradients, no launch more); 0: off")
@@ -718,7 +789,7 @@ def main(argv=None):
                     help="--data-parallel on a box with ONE GPU: every rank on cuda:0, the gradient all-reduce over gloo through host memory "
                          "(RCCL refuses two ranks on one card); exercises the sharding and the collective, not multi-GPU speed")
     args = ap.parse_args(argv)
-    problem = (hierarchical_args_error(args) or ray_reg_args_error(args) or patch_reg_args_error(args) or freq_reg_args_error(args) or extractor_args_error(args, load_config(args.config))
+    problem = (hierarchical_args_error(args) or ray_reg_args_error(args) or patch_reg_args_error(args) or info_reg_args_error(args) or freq_reg_args_error(args) or extractor_args_error(args, load_config(args.config))
                or occupancy_args_error(args, load_config(args.config)))
     if problem:
         raise SystemExit(problem)
@@ -782,11 +853,11 @@ def main(argv=None):
     model = model.to(dev).train()
     step = FusedStep(model, white_bkgd=rs["white_bkgd"], data_parallel=world > 1, **step_options(cfg, args.recipe),
                      **({"seed": args.seed} if args.recipe == "multiscale" else {}), **ray_reg_options(args, rs["near"], rs["far"]),
-                     **freq_reg_options(args), **patch_reg_options(args))
+                     **freq_reg_options(args), **patch_reg_options(args), **info_reg_options(args))
     gen = torch.Generator(device=dev)
     gen.manual_seed(args.seed)
     patches = None
-    if step.patch_reg:                                    # the patch draws: a CPU generator of their own, another stream on every rank
+    if draws_patches(args):                               # the patch draws: a CPU generator of their own, another stream on every rank
         patches = dict(n=args.patches_per_step, stride=args.patch_stride, generator=torch.Generator().manual_seed(args.seed * 1_000_003 + 7919 * (rank + 1)))
     # (the single grid is not part of a checkpoint: a resumed run starts again from the all-ones grid and its warm-up; the per-view
     # grids are)

@@ -974,6 +974,21 @@ class FusedStep:
     buffer of this object with the rendered depths.  step_view and the hierarchical steps refuse such a step object.  With
     depth_smooth_weight = 0 (the default) nothing changes, launch for launch.
 
+    Information regularisers (InfoNeRF's ray entropy and its KL between neighbouring rays; nerfhip.h: nrf_info_reg):
+
+        step = FusedStep(model, lr=5e-4, ent_weight=1e-3, ent_threshold=0.01, kl_weight=1e-5, patch_size=8)
+        loss = step.step_rays(torch.cat([rays_o, o_p]), torch.cat([rays_d, d_p]), target, near, far, 64, n_patches=16)
+
+    Both act on a ray's distribution p_i = a_i / sum a over its S - 1 finite intervals, a_i = 1 - exp(-relu(sigma_i) dist_i): ent_weight
+    times the mean over ALL rays of the batch (patch rays included) of the entropy of p, for rays whose sum a exceeds ent_threshold;
+    kl_weight times the mean over patches and anchors of KL(p_anchor || p_right) + KL(p_anchor || p_below), both rays above the
+    threshold, the gradient into both arguments.  ent_weight goes wherever dist_weight does (__call__, step_rays with or without
+    occupancy=, step_view); kl_weight wherever depth_smooth_weight does, on the patch rays behind n_patches= (patch_size^2 *
+    n_samples <= 12288: the patch's distributions meet in LDS); n_patches > 0 is accepted with any of the three weights.  The step is
+    the patch step with nrf_composite_info_loss_backward as its loss launch and nrf_info_terms_finish behind the optimiser: the same
+    launch count.  `last_losses` gains 'entropy' and 'kl' (nine keys, unweighted).  The hierarchical steps refuse both weights.  With
+    both 0 (the default) nothing changes, launch for launch and bit for bit.
+
     Frequency regularisation (FreeNeRF's coarse-to-fine mask on the positional encodings), on every step method:
 
         step = FusedStep(model, lr=5e-4, freq_reg_end=9000)
@@ -989,7 +1004,8 @@ class FusedStep:
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, rgb_weight=1.0, white_bkgd=False,
                  process_group=None, data_parallel=False, reg_weight=0.0, depth_weight=0.0, noise_std=0.0, max_grad_norm=None,
                  decoupled_weight_decay=False, seed=None, dist_weight=0.0, occ_weight=0.0, occ_samples=0, dist_span=None,
-                 freq_reg_end=0, freq_reg_dirs=True, depth_smooth_weight=0.0, patch_size=8):
+                 freq_reg_end=0, freq_reg_dirs=True, depth_smooth_weight=0.0, patch_size=8, ent_weight=0.0, ent_threshold=0.01,
+                 kl_weight=0.0):
         """data_parallel=True (inside an initialised torch.distributed job): every rank passes ITS shard of the ray batch
         (equal sizes), the flat gradient vector is averaged over the ranks with one all-reduce before Adam (the norm of
         max_grad_norm is taken behind it, so all ranks clip alike), and the returned loss is this rank's.
@@ -1011,6 +1027,9 @@ class FusedStep:
             raise ValueError("FusedStep: depth_smooth_weight must be finite and >= 0")
         if int(patch_size) != patch_size or not 2 <= int(patch_size) <= 16:
             raise ValueError("FusedStep: patch_size must be an integer in 2 ... 16")
+        for name, v in (("ent_weight", ent_weight), ("ent_threshold", ent_threshold), ("kl_weight", kl_weight)):
+            if not (float(v) >= 0.0 and math.isfinite(float(v))):
+                raise ValueError(f"FusedStep: {name} must be finite and >= 0")
         self.model = model
         self.freq_reg_end, self.freq_reg_dirs = int(freq_reg_end), bool(freq_reg_dirs)
         self.data_parallel = bool(data_parallel)
@@ -1026,6 +1045,10 @@ class FusedStep:
         self.patch_reg = self.depth_smooth_weight > 0.0                       # the step with the patch-based depth-smoothness term
         self._patch = self._patch_lo = None # nrf_patch_reg and nrf_loss_opts of the last patch loss launch, for nrf_patch_terms_finish
         self._patch_terms = self._patch_depth = None
+        self.ent_weight, self.ent_threshold, self.kl_weight = float(ent_weight), float(ent_threshold), float(kl_weight)
+        self.info_reg = self.ent_weight > 0.0 or self.kl_weight > 0.0         # the step with InfoNeRF's ray entropy and / or patch KL term
+        self._info = None                   # nrf_info_reg of the last such loss launch, for nrf_info_terms_finish
+        self._info_terms = self._patch_kl = None
         self.last_patch_depth = None        # (n_patches, P, P) view of a buffer of this object: the last patch step's rendered depths
         self.seed = None if seed is None else int(seed)
         self.white = int(bool(white_bkgd))
@@ -1050,7 +1073,8 @@ class FusedStep:
     def last_losses(self):
         """The last step's loss terms as device scalars (no sync): {'total'} of the plain step, {'total', 'rgb', 'depth', 'reg'}
         (nerf_mlp.NeRFLoss's dict, unweighted components) of the multi-term one, and 'dist', 'occ' behind them of the step with the
-        few-shot ray regularisers, and 'smooth' behind those of the step with the patch term; None before the first step."""
+        few-shot ray regularisers, and 'smooth' behind those of the step with the patch term, and 'entropy' and 'kl' behind that of
+        the step with ent_weight or kl_weight > 0; None before the first step."""
         v = self._loss_vec
         if v is None:
             return None
@@ -1059,6 +1083,8 @@ class FusedStep:
             parts, R = self._hier_parts
             mse = parts.sum(dim=1) / (3.0 * R)              # formed when asked for (torch reductions on the stream: no sync), from the step's buffer
             return {"total": total, "coarse": mse[0], "fine": mse[1]}
+        if v.dim() == 1 and v.numel() == 9:     # the step with the information terms: 'entropy' and 'kl' behind the seven
+            return {"total": v[0], "rgb": v[1], "depth": v[2], "reg": v[3], "dist": v[4], "occ": v[5], "smooth": v[6], "entropy": v[7], "kl": v[8]}
         if v.dim() == 1 and v.numel() == 7:     # the step with the patch term: 'smooth' behind the six
             return {"total": v[0], "rgb": v[1], "depth": v[2], "reg": v[3], "dist": v[4], "occ": v[5], "smooth": v[6]}
         if v.dim() == 1 and v.numel() == 6:
@@ -1073,7 +1099,7 @@ class FusedStep:
             self.out4, self.d_out4 = f(n, 4), f(n, 4)                 # V1: [rgb, sigma] rows; V2: rgb | density packed in the same rows
             self.pred = f(R, 3)
             # row 0: squared rgb errors; rows 1, 2 (multi-term loss): sum of w^2, |depth error|; rows 3, 4 (ray regularisers): D_r, O_r
-            self.ray_loss = f(5 if self.ray_reg or self.patch_reg else 3, R)
+            self.ray_loss = f(5 if self.ray_reg or self.patch_reg or self.info_reg else 3, R)
             self.grad = torch.zeros(self.model.flat_params().flat.numel(), dtype=torch.float32, device=dev)
             self._key = key
 
@@ -1096,7 +1122,7 @@ class FusedStep:
         either way).  The noise seed of step t is seed + t: step_count is read before the step increments it."""
         opt = self.opt
         multi = (self.reg_weight > 0.0 or self.depth_weight > 0.0 or self.noise_std > 0.0 or opt.extended or target_depth is not None
-                 or noise is not None or self.ray_reg or self.patch_reg)
+                 or noise is not None or self.ray_reg or self.patch_reg or self.info_reg)
         if not (multi or always):
             return False, None, None
         td = None if target_depth is None else L.dev_f32(target_depth, dev).reshape(R if n_sup is None else n_sup)
@@ -1113,8 +1139,10 @@ class FusedStep:
         n_patches = int(n_patches)
         if n_patches < 0:
             raise ValueError("n_patches must be >= 0")
-        if n_patches > 0 and not self.patch_reg:
-            raise ValueError("n_patches > 0 needs a FusedStep built with depth_smooth_weight > 0")
+        if n_patches > 0 and not (self.patch_reg or self.info_reg):
+            raise ValueError("n_patches > 0 needs a FusedStep built with depth_smooth_weight, kl_weight or ent_weight > 0")
+        if n_patches == 0 and self.kl_weight > 0.0:
+            raise ValueError("kl_weight > 0 acts on patch rays: pass n_patches > 0")
         Rs = R - n_patches * self.patch_size ** 2
         if Rs < 1:
             raise ValueError("the last n_patches * patch_size^2 rays of the batch are patch rays: at least one supervised ray must stand in front of them")
@@ -1128,20 +1156,36 @@ class FusedStep:
         lib = L.lib()
         self._hier_parts = None
         multi, lo, keep = self._loss_setup(R, S, dev, target_depth, noise, always=slot is not None, n_sup=R - n_patches * self.patch_size ** 2)
-        if self.ray_reg or self.patch_reg:
+        if self.ray_reg or self.patch_reg or self.info_reg:
             span = self.dist_span if self.dist_span is not None else span
             if self.dist_weight > 0.0 and not (span is not None and math.isfinite(span) and span > 0.0):
                 raise ValueError("dist_weight > 0 needs a depth range: pass dist_span= to FusedStep (__call__ has no near / far), "
                                  "or step with far > near")
             self._reg = L.ray_reg(self.dist_weight, 1.0 / span if self.dist_weight > 0.0 else 0.0, self.occ_weight, self.occ_samples)
-        if self.patch_reg:
+        if self.patch_reg or self.info_reg:
             # the one entry with the patch term (dense or indexed): the rays' depths meet in LDS between its forward and its backward
             P = self.patch_size
+            if self.kl_weight > 0.0 and P * P * S > L.INFO_KL_MAX_LDS_FLOATS:
+                raise ValueError(f"kl_weight > 0 keeps a patch's distributions in LDS: patch_size^2 * n_samples = {P * P * S} exceeds "
+                                 f"{L.INFO_KL_MAX_LDS_FLOATS}")
             if self._patch_terms is None or self._patch_terms.numel() != max(n_patches, 1) or self._patch_terms.device != dev:
                 self._patch_terms = torch.zeros((max(n_patches, 1),), dtype=torch.float32, device=dev)
                 self._patch_depth = torch.zeros((max(n_patches, 1) * P * P,), dtype=torch.float32, device=dev)
             self.last_patch_depth = self._patch_depth[: n_patches * P * P].view(n_patches, P, P)
             self._patch, self._patch_lo = L.patch_reg(self.depth_smooth_weight, P, n_patches), lo
+        if self.info_reg:
+            # the same entry with the ray entropy and the patch KL term: the same launch count, the patch's distributions meet in LDS
+            if self._info_terms is None or self._info_terms.numel() != R or self._info_terms.device != dev:
+                self._info_terms = torch.zeros((R,), dtype=torch.float32, device=dev)
+            if self._patch_kl is None or self._patch_kl.numel() != max(n_patches, 1) or self._patch_kl.device != dev:
+                self._patch_kl = torch.zeros((max(n_patches, 1),), dtype=torch.float32, device=dev)
+            self._info = L.info_reg(self.ent_weight, self.ent_threshold, self.kl_weight)
+            L.check(lib.nrf_composite_info_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), C.byref(self._reg),
+                                                         None if slot is None else slot.data_ptr(), L.ptr(self.pred), *d_heads,
+                                                         L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st, C.byref(self._patch),
+                                                         L.ptr(self._patch_terms), L.ptr(self._patch_depth), C.byref(self._info),
+                                                         L.ptr(self._info_terms), L.ptr(self._patch_kl)))
+        elif self.patch_reg:
             L.check(lib.nrf_composite_patch_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), C.byref(self._reg),
                                                           None if slot is None else slot.data_ptr(), L.ptr(self.pred), *d_heads,
                                                           L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st, C.byref(self._patch),
@@ -1192,7 +1236,13 @@ class FusedStep:
             loss = torch.empty((4,), dtype=torch.float32, device=dev)
             opt._update(flat, self.grad, self.ray_loss, R, S, (loss_weight, self.depth_weight if target_depth is not None else 0.0,
                                                                self.reg_weight), loss)
-            if self.patch_reg:
+            if self.info_reg:
+                # one small launch more, in the patch step's place: all nine values with the divisors of the batch layout
+                loss = torch.empty((9,), dtype=torch.float32, device=dev)
+                L.check(lib.nrf_info_terms_finish(L.ptr(self.ray_loss), R, S, C.byref(self._patch_lo), C.byref(self._reg), C.byref(self._patch),
+                                                  L.ptr(self._patch_terms), C.byref(self._info), L.ptr(self._info_terms), L.ptr(self._patch_kl),
+                                                  L.ptr(loss), st))
+            elif self.patch_reg:
                 # one small launch more: all seven values with the divisors of the batch layout (the optimiser's four divide by R)
                 loss = torch.empty((7,), dtype=torch.float32, device=dev)
                 L.check(lib.nrf_patch_terms_finish(L.ptr(self.ray_loss), R, S, C.byref(self._patch_lo), C.byref(self._reg), C.byref(self._patch),
@@ -1309,8 +1359,8 @@ class FusedStep:
         `ray_sampler._c2w12` made of it (as `dino` may be `make_dino`'s pair): nothing is converted per batch then.  occupancy: as in
         step_rays (one 8-byte read-back per step), and so is grid_inputs.  A step built with depth_smooth_weight > 0 is refused: a
         view has one pose, and the patches come from poses of their own (step_rays)."""
-        if self.patch_reg:
-            raise ValueError("step_view takes one pose per call: a FusedStep with depth_smooth_weight > 0 steps through step_rays or __call__")
+        if self.patch_reg or self.kl_weight > 0.0:
+            raise ValueError("step_view takes one pose per call: a FusedStep with depth_smooth_weight or kl_weight > 0 steps through step_rays or __call__")
         if not (isinstance(pixels, torch.Tensor) and pixels.is_cuda and pixels.dtype == torch.int64 and pixels.dim() == 1):
             raise ValueError("pixels must be a 1-d int64 tensor of ray ids on the GPU")
         pix = pixels.contiguous()
@@ -1338,6 +1388,8 @@ class FusedStep:
             raise ValueError("the hierarchical step takes the plain rgb loss: a FusedStep with dist_weight or occ_weight > 0 is refused")
         if self.patch_reg:
             raise ValueError("the hierarchical step takes the plain rgb loss: a FusedStep with depth_smooth_weight > 0 is refused")
+        if self.info_reg:
+            raise ValueError("the hierarchical step takes the plain rgb loss: a FusedStep with ent_weight or kl_weight > 0 is refused")
         if occupancy is not None:
             raise ValueError("the hierarchical step is not combined with occupancy=")
         if d_dino_out is not None or points_out is not None:
