@@ -1145,42 +1145,67 @@ bool patch_reg_terms(const nrf_patch_reg* patch, int64_t n_rays, nrf::PatchRegTe
     return true;
 }
 
-// the two information terms and their outputs (io != NULL, with rt and pt: nrf_composite_info_loss_backward)
-struct InfoOut { const nrf::InfoRegTerms* it; float* info_terms; float* patch_kl; };
+// nrf_info_reg as the launches take it, checked against the patches it acts on; false (with the message set) on a refusal
+bool info_reg_terms(const nrf_info_reg* info, const nrf::PatchRegTerms& pt, int n_samples, nrf::InfoRegTerms& it) {
+    if (!info) return fail(NRF_EINVAL, "info is NULL"), false;
+    if (info->struct_bytes != (int32_t)sizeof(nrf_info_reg)) return fail(NRF_EINVAL, "nrf_info_reg.struct_bytes is not sizeof(nrf_info_reg)"), false;
+    for (const float v : {info->ent_weight, info->ent_threshold, info->kl_weight})
+        if (!(v >= 0.0f) || !std::isfinite(v)) return fail(NRF_EINVAL, "ent_weight, ent_threshold and kl_weight must be finite and >= 0"), false;
+    if (info->kl_weight > 0.0f && pt.n_patches < 1) return fail(NRF_EINVAL, "kl_weight > 0 needs n_patches > 0: the KL term acts on patch rays"), false;
+    if (info->kl_weight > 0.0f && (int64_t)pt.patch_size * pt.patch_size * n_samples > NRF_INFO_KL_MAX_LDS_FLOATS)
+        return fail(NRF_EINVAL, "kl_weight > 0: patch_size^2 * n_samples exceeds NRF_INFO_KL_MAX_LDS_FLOATS"), false;
+    it.ent_weight = info->ent_weight; it.ent_threshold = info->ent_threshold; it.kl_weight = info->kl_weight;
+    return true;
+}
 
-// nrf_composite_loss_backward and its indexed form (slot != NULL: rgb / sigma / d_rgb / d_sigma hold compacted rows); rt != NULL:
-// nrf_composite_reg_loss_backward (ray_terms holds five rows); pt != NULL (with rt): nrf_composite_patch_loss_backward
+// nrf_loss_opts as the launches take it, for the entry `who`; false (with the message set) on a refusal
+bool loss_terms(const char* who, const nrf_loss_opts* loss, nrf::LossTerms& lt) {
+    if (!loss) return fail(NRF_EINVAL, std::string(who) + ": loss is NULL"), false;
+    if (loss->struct_bytes != (int32_t)sizeof(nrf_loss_opts)) return fail(NRF_EINVAL, "nrf_loss_opts.struct_bytes is not sizeof(nrf_loss_opts)"), false;
+    if (!(loss->rgb_weight >= 0.0f) || !(loss->reg_weight >= 0.0f) || !(loss->depth_weight >= 0.0f) || !std::isfinite(loss->rgb_weight) ||
+        !std::isfinite(loss->reg_weight) || !std::isfinite(loss->depth_weight))
+        return fail(NRF_EINVAL, "loss weights must be finite and >= 0"), false;
+    lt.rgb_weight = loss->rgb_weight; lt.reg_weight = loss->reg_weight; lt.depth_weight = loss->depth_weight;
+    lt.target_depth = loss->target_depth; lt.noise_std = loss->noise_std; lt.noise = loss->noise; lt.rng_seed = loss->rng_seed;
+    return true;
+}
+
+bool slot_aligned(const char* who, const int32_t* slot) {
+    if ((reinterpret_cast<uintptr_t>(slot) & 3u) != 0) return fail(NRF_EINVAL, std::string(who) + ": slot must be 4-byte aligned"), false;
+    return true;
+}
+
+bool sizes_ok(const char* who, int64_t n_rays, int n_samples) {
+    if (n_rays <= 0 || n_rays > ((int64_t)1 << 30) || n_samples < 1 || n_samples > 4096) return fail(NRF_EINVAL, std::string(who) + ": bad sizes"), false;
+    return true;
+}
+
+// What the entries with regularisers hand over on top of the common arguments: rt != NULL: nrf_composite_reg_loss_backward (ray_terms
+// holds five rows); pt != NULL (with rt): nrf_composite_patch_loss_backward; it != NULL (with both): nrf_composite_info_loss_backward
+struct LossRegs {
+    const nrf::RayRegTerms* rt; const nrf::PatchRegTerms* pt; const nrf::InfoRegTerms* it;
+    float *patch_terms, *patch_depth, *info_terms, *patch_kl;
+};
+
+// nrf_composite_loss_backward and its indexed form (slot != NULL: rgb / sigma / d_rgb / d_sigma hold compacted rows), and the entries
+// with regularisers
 int composite_loss_backward_any(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals, const float* rays_d,
                                 int64_t n_rays, int n_samples, int white_bkgd, const float* target, const nrf_loss_opts* loss, const int32_t* slot,
                                 float* pred, float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf,
-                                int64_t zero_n, void* stream, const nrf::RayRegTerms* rt = nullptr, const nrf::PatchRegTerms* pt = nullptr,
-                                float* patch_terms = nullptr, float* patch_depth = nullptr, const InfoOut* io = nullptr) {
-    if (!loss) return fail(NRF_EINVAL, "nrf_composite_loss_backward: loss is NULL");
-    if (loss->struct_bytes != (int32_t)sizeof(nrf_loss_opts)) return fail(NRF_EINVAL, "nrf_loss_opts.struct_bytes is not sizeof(nrf_loss_opts)");
-    if (!(loss->rgb_weight >= 0.0f) || !(loss->reg_weight >= 0.0f) || !(loss->depth_weight >= 0.0f) || !std::isfinite(loss->rgb_weight) ||
-        !std::isfinite(loss->reg_weight) || !std::isfinite(loss->depth_weight))
-        return fail(NRF_EINVAL, "loss weights must be finite and >= 0");
+                                int64_t zero_n, void* stream, const LossRegs& g) {
+    nrf::LossLaunch a{rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, {}, slot, pred,
+                      d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, (hipStream_t)stream};
+    if (!loss_terms("nrf_composite_loss_backward", loss, a.lt)) return NRF_EINVAL;
     if (!(loss->noise_std >= 0.0f) || !std::isfinite(loss->noise_std)) return fail(NRF_EINVAL, "noise_std must be finite and >= 0");
-    if (n_rays <= 0 || n_rays > ((int64_t)1 << 30) || n_samples < 1 || n_samples > 4096) return fail(NRF_EINVAL, "nrf_composite_loss_backward: bad sizes");
+    if (!sizes_ok("nrf_composite_loss_backward", n_rays, n_samples)) return NRF_EINVAL;
     if (rgb_stride < 3 || sigma_stride < 1 || d_rgb_stride < 3 || d_sigma_stride < 1) return fail(NRF_EINVAL, "bad strides");
     if (!rgb || !sigma || !z_vals || !rays_d || !target || !d_rgb || !d_sigma || !ray_terms) return fail(NRF_EINVAL, "null pointer");
     if (zero_n < 0 || (zero_n > 0 && !zero_buf)) return fail(NRF_EINVAL, "zero_buf is NULL");
-    nrf::LossTerms lt{};
-    lt.rgb_weight = loss->rgb_weight; lt.reg_weight = loss->reg_weight; lt.depth_weight = loss->depth_weight;
-    lt.target_depth = loss->target_depth; lt.noise_std = loss->noise_std; lt.noise = loss->noise; lt.rng_seed = loss->rng_seed;
-    const int r = io ? nrf::launch_composite_info_loss_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd,
-                                                                target, lt, *rt, *pt, *io->it, slot, pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride,
-                                                                ray_terms, zero_buf, zero_n, patch_terms, patch_depth, io->info_terms, io->patch_kl,
-                                                                (hipStream_t)stream)
-                  : pt ? nrf::launch_composite_patch_loss_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd,
-                                                                 target, lt, *rt, *pt, slot, pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride,
-                                                                 ray_terms, zero_buf, zero_n, patch_terms, patch_depth, (hipStream_t)stream)
-                  : rt ? nrf::launch_composite_reg_loss_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd,
-                                                               target, lt, *rt, slot, pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms,
-                                                               zero_buf, zero_n, (hipStream_t)stream)
-                     : nrf::launch_composite_loss_backward(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, lt,
-                                                           pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n,
-                                                           (hipStream_t)stream, slot);
+    int r;
+    if (g.it) r = nrf::launch_composite_info_loss_backward(a, *g.rt, *g.pt, *g.it, g.patch_terms, g.patch_depth, g.info_terms, g.patch_kl);
+    else if (g.pt) r = nrf::launch_composite_patch_loss_backward(a, *g.rt, *g.pt, g.patch_terms, g.patch_depth);
+    else if (g.rt) r = nrf::launch_composite_reg_loss_backward(a, *g.rt);
+    else r = nrf::launch_composite_loss_backward(a);
     return r == NRF_OK ? NRF_OK : fail(r, "composite + loss + backward launch failed");
 }
 }  // namespace
@@ -1191,7 +1216,7 @@ int nrf_composite_loss_backward(const float* rgb, int rgb_stride, const float* s
                                 float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf,
                                 int64_t zero_n, void* stream) {
     return composite_loss_backward_any(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, loss, nullptr,
-                                       pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream);
+                                       pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream, {});
 }
 
 int nrf_composite_loss_backward_indexed(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals,
@@ -1199,9 +1224,9 @@ int nrf_composite_loss_backward_indexed(const float* rgb, int rgb_stride, const 
                                         const nrf_loss_opts* loss, const int32_t* slot, float* pred, float* d_rgb, int d_rgb_stride,
                                         float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n, void* stream) {
     if (!slot) return fail(NRF_EINVAL, "nrf_composite_loss_backward_indexed: slot is NULL");
-    if ((reinterpret_cast<uintptr_t>(slot) & 3u) != 0) return fail(NRF_EINVAL, "nrf_composite_loss_backward_indexed: slot must be 4-byte aligned");
+    if (!slot_aligned("nrf_composite_loss_backward_indexed", slot)) return NRF_EINVAL;
     return composite_loss_backward_any(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, loss, slot, pred,
-                                       d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream);
+                                       d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream, {});
 }
 
 int nrf_composite_reg_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals,
@@ -1211,9 +1236,9 @@ int nrf_composite_reg_loss_backward(const float* rgb, int rgb_stride, const floa
                                     void* stream) {
     nrf::RayRegTerms rt{};
     if (!ray_reg_terms(reg, rt)) return NRF_EINVAL;
-    if (slot && (reinterpret_cast<uintptr_t>(slot) & 3u) != 0) return fail(NRF_EINVAL, "nrf_composite_reg_loss_backward: slot must be 4-byte aligned");
+    if (!slot_aligned("nrf_composite_reg_loss_backward", slot)) return NRF_EINVAL;
     return composite_loss_backward_any(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, loss, slot, pred,
-                                       d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream, &rt);
+                                       d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream, {&rt});
 }
 
 int nrf_ray_terms_finish(const float* ray_terms, int64_t n_rays, const nrf_ray_reg* reg, const float* losses4, float* losses6, void* stream) {
@@ -1235,10 +1260,10 @@ int nrf_composite_patch_loss_backward(const float* rgb, int rgb_stride, const fl
     nrf::PatchRegTerms pt{};
     if (!patch_reg_terms(patch, n_rays, pt)) return NRF_EINVAL;
     if (pt.n_patches > 0 && !patch_terms) return fail(NRF_EINVAL, "nrf_composite_patch_loss_backward: patch_terms is NULL");
-    if (slot && (reinterpret_cast<uintptr_t>(slot) & 3u) != 0) return fail(NRF_EINVAL, "nrf_composite_patch_loss_backward: slot must be 4-byte aligned");
+    if (!slot_aligned("nrf_composite_patch_loss_backward", slot)) return NRF_EINVAL;
     return composite_loss_backward_any(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, loss, slot, pred,
-                                       d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream, &rt, &pt, patch_terms,
-                                       patch_depth);
+                                       d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream,
+                                       {&rt, &pt, nullptr, patch_terms, patch_depth});
 }
 
 int nrf_patch_terms_finish(const float* ray_terms, int64_t n_rays, int n_samples, const nrf_loss_opts* loss, const nrf_ray_reg* reg,
@@ -1247,33 +1272,13 @@ int nrf_patch_terms_finish(const float* ray_terms, int64_t n_rays, int n_samples
     if (!ray_reg_terms(reg, rt)) return NRF_EINVAL;
     nrf::PatchRegTerms pt{};
     if (!patch_reg_terms(patch, n_rays, pt)) return NRF_EINVAL;
-    if (!loss) return fail(NRF_EINVAL, "nrf_patch_terms_finish: loss is NULL");
-    if (loss->struct_bytes != (int32_t)sizeof(nrf_loss_opts)) return fail(NRF_EINVAL, "nrf_loss_opts.struct_bytes is not sizeof(nrf_loss_opts)");
-    if (!(loss->rgb_weight >= 0.0f) || !(loss->reg_weight >= 0.0f) || !(loss->depth_weight >= 0.0f) || !std::isfinite(loss->rgb_weight) ||
-        !std::isfinite(loss->reg_weight) || !std::isfinite(loss->depth_weight))
-        return fail(NRF_EINVAL, "loss weights must be finite and >= 0");
-    if (n_rays <= 0 || n_rays > ((int64_t)1 << 30) || n_samples < 1 || n_samples > 4096) return fail(NRF_EINVAL, "nrf_patch_terms_finish: bad sizes");
-    if (!ray_terms || !losses7 || (pt.n_patches > 0 && !patch_terms)) return fail(NRF_EINVAL, "null pointer");
     nrf::LossTerms lt{};
-    lt.rgb_weight = loss->rgb_weight; lt.reg_weight = loss->reg_weight; lt.depth_weight = loss->depth_weight; lt.target_depth = loss->target_depth;
+    if (!loss_terms("nrf_patch_terms_finish", loss, lt)) return NRF_EINVAL;          // (loss->target_depth: a flag here, not read)
+    if (!sizes_ok("nrf_patch_terms_finish", n_rays, n_samples)) return NRF_EINVAL;
+    if (!ray_terms || !losses7 || (pt.n_patches > 0 && !patch_terms)) return fail(NRF_EINVAL, "null pointer");
     const int r = nrf::launch_patch_terms_finish(ray_terms, n_rays, n_samples, lt, rt, pt, patch_terms, losses7, (hipStream_t)stream);
     return r == NRF_OK ? NRF_OK : fail(r, "patch terms finish launch failed");
 }
-
-namespace {
-// nrf_info_reg as the launches take it, checked against the patches it acts on; false (with the message set) on a refusal
-bool info_reg_terms(const nrf_info_reg* info, const nrf::PatchRegTerms& pt, int n_samples, nrf::InfoRegTerms& it) {
-    if (!info) return fail(NRF_EINVAL, "info is NULL"), false;
-    if (info->struct_bytes != (int32_t)sizeof(nrf_info_reg)) return fail(NRF_EINVAL, "nrf_info_reg.struct_bytes is not sizeof(nrf_info_reg)"), false;
-    for (const float v : {info->ent_weight, info->ent_threshold, info->kl_weight})
-        if (!(v >= 0.0f) || !std::isfinite(v)) return fail(NRF_EINVAL, "ent_weight, ent_threshold and kl_weight must be finite and >= 0"), false;
-    if (info->kl_weight > 0.0f && pt.n_patches < 1) return fail(NRF_EINVAL, "kl_weight > 0 needs n_patches > 0: the KL term acts on patch rays"), false;
-    if (info->kl_weight > 0.0f && (int64_t)pt.patch_size * pt.patch_size * n_samples > NRF_INFO_KL_MAX_LDS_FLOATS)
-        return fail(NRF_EINVAL, "kl_weight > 0: patch_size^2 * n_samples exceeds NRF_INFO_KL_MAX_LDS_FLOATS"), false;
-    it.ent_weight = info->ent_weight; it.ent_threshold = info->ent_threshold; it.kl_weight = info->kl_weight;
-    return true;
-}
-}  // namespace
 
 int nrf_composite_info_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z_vals,
                                      const float* rays_d, int64_t n_rays, int n_samples, int white_bkgd, const float* target,
@@ -1290,11 +1295,10 @@ int nrf_composite_info_loss_backward(const float* rgb, int rgb_stride, const flo
     if (pt.n_patches > 0 && !patch_terms) return fail(NRF_EINVAL, "nrf_composite_info_loss_backward: patch_terms is NULL");
     if (it.ent_weight > 0.0f && !info_terms) return fail(NRF_EINVAL, "nrf_composite_info_loss_backward: info_terms is NULL with ent_weight > 0");
     if (it.kl_weight > 0.0f && !patch_kl) return fail(NRF_EINVAL, "nrf_composite_info_loss_backward: patch_kl is NULL with kl_weight > 0");
-    if (slot && (reinterpret_cast<uintptr_t>(slot) & 3u) != 0) return fail(NRF_EINVAL, "nrf_composite_info_loss_backward: slot must be 4-byte aligned");
-    const InfoOut io{&it, info_terms, patch_kl};
+    if (!slot_aligned("nrf_composite_info_loss_backward", slot)) return NRF_EINVAL;
     return composite_loss_backward_any(rgb, rgb_stride, sigma, sigma_stride, z_vals, rays_d, n_rays, n_samples, white_bkgd, target, loss, slot, pred,
-                                       d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream, &rt, &pt, patch_terms,
-                                       patch_depth, &io);
+                                       d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, stream,
+                                       {&rt, &pt, &it, patch_terms, patch_depth, info_terms, patch_kl});
 }
 
 int nrf_info_terms_finish(const float* ray_terms, int64_t n_rays, int n_samples, const nrf_loss_opts* loss, const nrf_ray_reg* reg,
@@ -1306,16 +1310,11 @@ int nrf_info_terms_finish(const float* ray_terms, int64_t n_rays, int n_samples,
     if (!patch_reg_terms(patch, n_rays, pt)) return NRF_EINVAL;
     nrf::InfoRegTerms it{};
     if (!info_reg_terms(info, pt, n_samples, it)) return NRF_EINVAL;
-    if (!loss) return fail(NRF_EINVAL, "nrf_info_terms_finish: loss is NULL");
-    if (loss->struct_bytes != (int32_t)sizeof(nrf_loss_opts)) return fail(NRF_EINVAL, "nrf_loss_opts.struct_bytes is not sizeof(nrf_loss_opts)");
-    if (!(loss->rgb_weight >= 0.0f) || !(loss->reg_weight >= 0.0f) || !(loss->depth_weight >= 0.0f) || !std::isfinite(loss->rgb_weight) ||
-        !std::isfinite(loss->reg_weight) || !std::isfinite(loss->depth_weight))
-        return fail(NRF_EINVAL, "loss weights must be finite and >= 0");
-    if (n_rays <= 0 || n_rays > ((int64_t)1 << 30) || n_samples < 1 || n_samples > 4096) return fail(NRF_EINVAL, "nrf_info_terms_finish: bad sizes");
+    nrf::LossTerms lt{};
+    if (!loss_terms("nrf_info_terms_finish", loss, lt)) return NRF_EINVAL;
+    if (!sizes_ok("nrf_info_terms_finish", n_rays, n_samples)) return NRF_EINVAL;
     if (!ray_terms || !losses9 || (pt.n_patches > 0 && !patch_terms) || (it.ent_weight > 0.0f && !info_terms) || (it.kl_weight > 0.0f && !patch_kl))
         return fail(NRF_EINVAL, "null pointer");
-    nrf::LossTerms lt{};
-    lt.rgb_weight = loss->rgb_weight; lt.reg_weight = loss->reg_weight; lt.depth_weight = loss->depth_weight; lt.target_depth = loss->target_depth;
     const int r = nrf::launch_info_terms_finish(ray_terms, n_rays, n_samples, lt, rt, pt, it, patch_terms, info_terms, patch_kl, losses9,
                                                 (hipStream_t)stream);
     return r == NRF_OK ? NRF_OK : fail(r, "info terms finish launch failed");

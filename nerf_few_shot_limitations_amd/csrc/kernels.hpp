@@ -226,39 +226,39 @@ struct LossTerms {
     const float* noise;             // (R,S) standard normals, or NULL: in-kernel counter RNG
     uint64_t rng_seed;
 };
+// What every launch_composite_*loss_backward takes: the two heads (dense rows, or with slot (R,S) the compacted rows of the indexed
+// form, as d_rgb / d_sigma then are), the rays, the loss, the outputs and the flat gradient vector to clear
+struct LossLaunch {
+    const float* rgb; int rgb_stride; const float* sigma; int sigma_stride;
+    const float *z, *rays_d; int64_t n_rays; int S; int white_bkgd; const float* target;
+    LossTerms lt;
+    const int32_t* slot;            // or NULL
+    float* pred;                    // or NULL
+    float* d_rgb; int d_rgb_stride; float* d_sigma; int d_sigma_stride;
+    float* ray_terms;
+    float* zero_buf; int64_t zero_n;
+    hipStream_t s;
+};
 // ray_terms (3,R): squared rgb error | sum of w^2 | |depth - target_depth|
-int launch_composite_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
-                                   int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, float* pred, float* d_rgb,
-                                   int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n,
-                                   hipStream_t s, const int32_t* slot = nullptr);      // slot (R,S): the indexed form, rgb / sigma / d_* hold compacted rows
+int launch_composite_loss_backward(const LossLaunch& a);
 // The same launch with the two few-shot ray regularisers (ray_reg.hip; nerfhip.h: nrf_ray_reg, whose fields these are); ray_terms
 // (5,R): the three rows above | D_r | O_r.  launch_ray_terms_finish: losses6 from rows 3, 4 and the optimiser launch's four values.
 struct RayRegTerms { float dist_weight, dist_inv_span, occ_weight; int occ_samples; };
-int launch_composite_reg_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
-                                       int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, const RayRegTerms& rt,
-                                       const int32_t* slot, float* pred, float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride,
-                                       float* ray_terms, float* zero_buf, int64_t zero_n, hipStream_t s);
+int launch_composite_reg_loss_backward(const LossLaunch& a, const RayRegTerms& rt);
 int launch_ray_terms_finish(const float* ray_terms, int64_t n_rays, float dist_weight, float occ_weight, const float* losses4, float* losses6,
                             hipStream_t s);
 // The same launch with RegNeRF's depth-smoothness term on patches as well (patch_reg.hip; nerfhip.h: nrf_patch_reg, whose fields
 // these are): the last n_patches patch_size^2 rays are patch rays, target and target_depth hold the other rows.  patch_terms (N_p):
 // DS_p; patch_depth (N_p, P, P) or NULL.  launch_patch_terms_finish: losses7 from the five rows of ray_terms and patch_terms.
 struct PatchRegTerms { float depth_smooth_weight; int patch_size; int64_t n_patches; };
-int launch_composite_patch_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
-                                         int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, const RayRegTerms& rt,
-                                         const PatchRegTerms& pt, const int32_t* slot, float* pred, float* d_rgb, int d_rgb_stride, float* d_sigma,
-                                         int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n, float* patch_terms,
-                                         float* patch_depth, hipStream_t s);
+int launch_composite_patch_loss_backward(const LossLaunch& a, const RayRegTerms& rt, const PatchRegTerms& pt, float* patch_terms, float* patch_depth);
 int launch_patch_terms_finish(const float* ray_terms, int64_t n_rays, int S, const LossTerms& lt, const RayRegTerms& rt, const PatchRegTerms& pt,
                               const float* patch_terms, float* losses7, hipStream_t s);
 // The same launch with InfoNeRF's ray entropy and patch KL terms on top (info_reg.hip; nerfhip.h: nrf_info_reg, whose fields these
 // are).  info_terms (R): m_r H_r; patch_kl (N_p): K_p.  launch_info_terms_finish: losses9 from ray_terms, patch_terms and those two.
 struct InfoRegTerms { float ent_weight, ent_threshold, kl_weight; };
-int launch_composite_info_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
-                                        int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, const RayRegTerms& rt,
-                                        const PatchRegTerms& pt, const InfoRegTerms& it, const int32_t* slot, float* pred, float* d_rgb,
-                                        int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n,
-                                        float* patch_terms, float* patch_depth, float* info_terms, float* patch_kl, hipStream_t s);
+int launch_composite_info_loss_backward(const LossLaunch& a, const RayRegTerms& rt, const PatchRegTerms& pt, const InfoRegTerms& it,
+                                        float* patch_terms, float* patch_depth, float* info_terms, float* patch_kl);
 int launch_info_terms_finish(const float* ray_terms, int64_t n_rays, int S, const LossTerms& lt, const RayRegTerms& rt, const PatchRegTerms& pt,
                              const InfoRegTerms& it, const float* patch_terms, const float* info_terms, const float* patch_kl, float* losses9,
                              hipStream_t s);

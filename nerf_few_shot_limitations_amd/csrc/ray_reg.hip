@@ -13,23 +13,11 @@
 // are touched once per ray in vector registers (as indexed_loss_backward_kernel does), and with them the regularisers' five
 // values, the noise source and the two scales of the multi-term loss: the scalar file has no room for them next to the scans'
 // masks (without it: 12 - 15 spilled SGPRs).
-#include <algorithm>
-
-#include "kernels.hpp"
-#include "composite_core.hpp"
+#include "loss_walk.hpp"          // kBlock, grid_for, ray_reg_of
 
 namespace nrf {
 
 namespace {
-
-constexpr int kBlock = 256;
-
-inline unsigned grid_for(int64_t n, int block, int64_t cap) {
-    int64_t g = (n + block - 1) / block;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    return (unsigned)g;
-}
 
 // ray_loss (5,R): squared rgb error | sum of w^2 | |depth - target_depth| | D_r | O_r
 template <bool IDX>
@@ -101,31 +89,20 @@ __global__ void __launch_bounds__(1024) ray_terms_finish_kernel(const float* __r
 
 }  // namespace
 
-int launch_composite_reg_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
-                                       int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, const RayRegTerms& rt,
-                                       const int32_t* slot, float* pred, float* d_rgb, int d_rgb_stride, float* d_sigma, int d_sigma_stride,
-                                       float* ray_terms, float* zero_buf, int64_t zero_n, hipStream_t s) {
-    if (n_rays <= 0 || S < 1 || S > 64 * kMaxSegments) return NRF_EINVAL;
-    const LossExt ext = loss_ext_of(lt, n_rays, S);
-    RayReg reg{};
-    if (rt.dist_weight > 0.0f) {
-        reg.dist_scale = rt.dist_weight / (float)n_rays;
-        reg.kappa = rt.dist_inv_span;
-    }
-    if (rt.occ_weight > 0.0f) {
-        reg.occ_m = std::min(rt.occ_samples, S);
-        reg.occ_inv = 1.0f / (float)reg.occ_m;
-        reg.occ_scale = rt.occ_weight / ((float)n_rays * (float)reg.occ_m);
-    }
-    const int64_t work = std::max(n_rays * 64, (zero_n + 3) / 4);
+int launch_composite_reg_loss_backward(const LossLaunch& a, const RayRegTerms& rt) {
+    if (a.n_rays <= 0 || a.S < 1 || a.S > 64 * kMaxSegments) return NRF_EINVAL;
+    const LossExt ext = loss_ext_of(a.lt, a.n_rays, a.S);
+    const RayReg reg = ray_reg_of(rt, a.n_rays, a.S);
+    const int64_t work = std::max(a.n_rays * 64, (a.zero_n + 3) / 4);
     const dim3 grid(grid_for(work, kBlock, 16384)), block(kBlock);
-    if (slot)
-        hipLaunchKernelGGL(reg_loss_backward_kernel<true>, grid, block, 0, s, rgb, rgb_stride, sigma, sigma_stride, z, rays_d, n_rays, S, white_bkgd,
-                           target, lt.rgb_weight, pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, ext, reg, slot);
+    if (a.slot)
+        hipLaunchKernelGGL(reg_loss_backward_kernel<true>, grid, block, 0, a.s, a.rgb, a.rgb_stride, a.sigma, a.sigma_stride, a.z, a.rays_d, a.n_rays,
+                           a.S, a.white_bkgd, a.target, a.lt.rgb_weight, a.pred, a.d_rgb, a.d_rgb_stride, a.d_sigma, a.d_sigma_stride, a.ray_terms,
+                           a.zero_buf, a.zero_n, ext, reg, a.slot);
     else
-        hipLaunchKernelGGL(reg_loss_backward_kernel<false>, grid, block, 0, s, rgb, rgb_stride, sigma, sigma_stride, z, rays_d, n_rays, S, white_bkgd,
-                           target, lt.rgb_weight, pred, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, ray_terms, zero_buf, zero_n, ext, reg,
-                           (const int32_t*)nullptr);
+        hipLaunchKernelGGL(reg_loss_backward_kernel<false>, grid, block, 0, a.s, a.rgb, a.rgb_stride, a.sigma, a.sigma_stride, a.z, a.rays_d, a.n_rays,
+                           a.S, a.white_bkgd, a.target, a.lt.rgb_weight, a.pred, a.d_rgb, a.d_rgb_stride, a.d_sigma, a.d_sigma_stride, a.ray_terms,
+                           a.zero_buf, a.zero_n, ext, reg, (const int32_t*)nullptr);
     return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
 }
 

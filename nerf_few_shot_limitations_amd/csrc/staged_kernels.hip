@@ -1014,21 +1014,18 @@ int launch_composite_mse_backward(const float* rgb, int rgb_stride, const float*
     return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
 }
 
-int launch_composite_loss_backward(const float* rgb, int rgb_stride, const float* sigma, int sigma_stride, const float* z, const float* rays_d,
-                                   int64_t n_rays, int S, int white_bkgd, const float* target, const LossTerms& lt, float* pred, float* d_rgb,
-                                   int d_rgb_stride, float* d_sigma, int d_sigma_stride, float* ray_terms, float* zero_buf, int64_t zero_n,
-                                   hipStream_t s, const int32_t* slot) {
-    if (n_rays <= 0 || S > 64 * kMaxSegments) return NRF_EINVAL;
-    const LossExt ext = loss_ext_of(lt, n_rays, S);
-    const int64_t work = std::max(n_rays * 64, (zero_n + 3) / 4);
-    if (slot)
-        hipLaunchKernelGGL(indexed_loss_backward_kernel, dim3(grid_for(work, kBlock, 16384)), dim3(kBlock), 0, s, rgb, rgb_stride, sigma,
-                           sigma_stride, z, rays_d, n_rays, S, white_bkgd, target, lt.rgb_weight, pred, d_rgb, d_rgb_stride, d_sigma,
-                           d_sigma_stride, ray_terms, zero_buf, zero_n, ext, slot);
+int launch_composite_loss_backward(const LossLaunch& a) {
+    if (a.n_rays <= 0 || a.S > 64 * kMaxSegments) return NRF_EINVAL;
+    const LossExt ext = loss_ext_of(a.lt, a.n_rays, a.S);
+    const int64_t work = std::max(a.n_rays * 64, (a.zero_n + 3) / 4);
+    if (a.slot)
+        hipLaunchKernelGGL(indexed_loss_backward_kernel, dim3(grid_for(work, kBlock, 16384)), dim3(kBlock), 0, a.s, a.rgb, a.rgb_stride, a.sigma,
+                           a.sigma_stride, a.z, a.rays_d, a.n_rays, a.S, a.white_bkgd, a.target, a.lt.rgb_weight, a.pred, a.d_rgb, a.d_rgb_stride,
+                           a.d_sigma, a.d_sigma_stride, a.ray_terms, a.zero_buf, a.zero_n, ext, a.slot);
     else
-        hipLaunchKernelGGL(composite_loss_backward_kernel<true>, dim3(grid_for(work, kBlock, 16384)), dim3(kBlock), 0, s, rgb, rgb_stride, sigma,
-                           sigma_stride, z, rays_d, n_rays, S, white_bkgd, target, lt.rgb_weight, pred, d_rgb, d_rgb_stride, d_sigma,
-                           d_sigma_stride, ray_terms, zero_buf, zero_n, ext);
+        hipLaunchKernelGGL(composite_loss_backward_kernel<true>, dim3(grid_for(work, kBlock, 16384)), dim3(kBlock), 0, a.s, a.rgb, a.rgb_stride,
+                           a.sigma, a.sigma_stride, a.z, a.rays_d, a.n_rays, a.S, a.white_bkgd, a.target, a.lt.rgb_weight, a.pred, a.d_rgb,
+                           a.d_rgb_stride, a.d_sigma, a.d_sigma_stride, a.ray_terms, a.zero_buf, a.zero_n, ext);
     return hipGetLastError() == hipSuccess ? NRF_OK : NRF_EHIP;
 }
 
