@@ -922,6 +922,68 @@ def all_reduce_gradients(model, group=None, average=True):
 # ---------------------------------------------------------------------------------------------
 # one optimisation step without autograd in between
 # ---------------------------------------------------------------------------------------------
+_FOUR = ("total", "rgb", "depth", "reg")
+# The loss launch of a FusedStep by kind: (entry, entry behind the multi-term optimiser that completes the loss vector, names of
+# last_losses, rows of ray_loss).  mse and indexed may run in front of the plain optimiser, which leaves the first value alone.
+_LOSS_KINDS = {
+    "mse": ("nrf_composite_mse_backward", None, _FOUR, 3),
+    "multi": ("nrf_composite_loss_backward", None, _FOUR, 3),
+    "indexed": ("nrf_composite_loss_backward_indexed", None, _FOUR, 3),         # the step under a grid, plain or multi-term
+    "reg": ("nrf_composite_reg_loss_backward", "nrf_ray_terms_finish", _FOUR + ("dist", "occ"), 5),
+    "patch": ("nrf_composite_patch_loss_backward", "nrf_patch_terms_finish", _FOUR + ("dist", "occ", "smooth"), 5),
+    "info": ("nrf_composite_info_loss_backward", "nrf_info_terms_finish", _FOUR + ("dist", "occ", "smooth", "entropy", "kl"), 5),
+    "hier": ("nrf_composite_hier_loss_backward", None, ("total", "coarse", "fine"), 3),
+}
+
+
+class _LossPlan:
+    """One step's loss launch, decided once (FusedStep._loss_plan): the entry that runs, the structs and term buffers it is handed,
+    the launch behind the optimiser that completes the loss vector, and the names of that vector's values."""
+
+    def __init__(self, kind, multi):
+        self.kind, self.multi = kind, multi                 # multi: the clipped optimiser with the four loss values runs behind it
+        self.entry, self.finish_entry, names, _ = _LOSS_KINDS[kind]
+        self.names = names if multi or kind == "hier" else names[:1]
+        self.lo = self.reg = None           # nrf_loss_opts (every kind but mse), nrf_ray_reg (reg, patch, info)
+        self.tail = self.finish_tail = ()   # what the patch and information entries take behind the common arguments
+        self.keep = None                    # tensors whose pointers the launch reads: alive until it is enqueued
+        self.depth = False                  # target_depth was passed: the depth term is on
+        self.parts = None                   # hier: ((2,R) squared errors coarse | fine, R)
+
+    def launch(self, step, heads, d_heads, z, d, tgt, R, S, slot, st):
+        """The kind's entry on the step's buffers: the arguments all six share, written once, and the kind's own between and behind
+        them -- rgb_weight or the loss options, the ray regularisers, the slot map (None: dense), the patch and information tail."""
+        a = [*heads, L.ptr(z), L.ptr(d), R, S, step.white, L.ptr(tgt), step.rgb_weight if self.lo is None else C.byref(self.lo)]
+        if self.reg is not None:
+            a.append(C.byref(self.reg))
+        if self.kind not in ("mse", "multi"):               # dense or indexed
+            a.append(None if slot is None else slot.data_ptr())
+        L.check(getattr(L.lib(), self.entry)(*a, L.ptr(step.pred), *d_heads, L.ptr(step.ray_loss), L.ptr(step.grad), step.grad.numel(), st,
+                                             *self.tail))
+        self.keep = None
+
+    def finish(self, step, R, S, loss4, st):
+        """Behind the multi-term optimiser, which left loss4: one small launch more where the kind has terms of its own; returns the
+        step's loss vector, one value per name."""
+        if self.finish_entry is None:
+            return loss4
+        loss = torch.empty((len(self.names),), dtype=torch.float32, device=loss4.device)
+        if self.kind == "reg":              # the two new terms summed in a fixed order and appended to the four
+            a = (R, C.byref(self.reg), L.ptr(loss4))
+        else:                               # every value with the divisors of the batch layout (the optimiser's four divide by R);
+            a = (R, S, C.byref(self.lo), C.byref(self.reg), *self.finish_tail)      # loss_opts.target_depth: a flag here, not read
+        L.check(getattr(L.lib(), self.finish_entry)(L.ptr(step.ray_loss), *a, L.ptr(loss), st))
+        return loss
+
+    def losses(self, vec):
+        v = vec.reshape(-1)
+        if self.parts is None:
+            return dict(zip(self.names, v))
+        parts, R = self.parts
+        mse = parts.sum(dim=1) / (3.0 * R)                  # formed when asked for (torch reductions on the stream: no sync), from the step's buffer
+        return dict(zip(self.names, (v[0], mse[0], mse[1])))
+
+
 class FusedStep:
     """The body of the reference's inner loop -- render a batch of rays, `rgb_weight * mse(pred['rgb'], target)`
     (train.py:36-44,280-288; train_minimal.py:102-123), backward, Adam -- as a fixed sequence of libnerfhip calls on
@@ -1015,21 +1077,18 @@ class FusedStep:
             raise NotImplementedError("FusedStep: unknown network family")
         if min(float(rgb_weight), float(reg_weight), float(depth_weight), float(noise_std)) < 0.0:
             raise ValueError("FusedStep: loss weights and noise_std must be >= 0")
-        if not (float(dist_weight) >= 0.0 and float(occ_weight) >= 0.0 and math.isfinite(float(dist_weight)) and math.isfinite(float(occ_weight))):
-            raise ValueError("FusedStep: dist_weight and occ_weight must be finite and >= 0")
+        for names, values in (("dist_weight and occ_weight", (dist_weight, occ_weight)), ("depth_smooth_weight", (depth_smooth_weight,)),
+                              ("ent_weight", (ent_weight,)), ("ent_threshold", (ent_threshold,)), ("kl_weight", (kl_weight,))):
+            if not all(float(v) >= 0.0 and math.isfinite(float(v)) for v in values):
+                raise ValueError(f"FusedStep: {names} must be finite and >= 0")
         if int(occ_samples) < 0 or (float(occ_weight) > 0.0 and int(occ_samples) < 1):
             raise ValueError("FusedStep: occ_samples must be >= 1 with occ_weight > 0 (and never negative)")
         if dist_span is not None and not (math.isfinite(float(dist_span)) and float(dist_span) > 0.0):
             raise ValueError("FusedStep: dist_span must be finite and > 0 (None: far - near of the step)")
         if int(freq_reg_end) < 0:
             raise ValueError("FusedStep: freq_reg_end must be >= 0 (0: no frequency regularisation)")
-        if not (float(depth_smooth_weight) >= 0.0 and math.isfinite(float(depth_smooth_weight))):
-            raise ValueError("FusedStep: depth_smooth_weight must be finite and >= 0")
         if int(patch_size) != patch_size or not 2 <= int(patch_size) <= 16:
             raise ValueError("FusedStep: patch_size must be an integer in 2 ... 16")
-        for name, v in (("ent_weight", ent_weight), ("ent_threshold", ent_threshold), ("kl_weight", kl_weight)):
-            if not (float(v) >= 0.0 and math.isfinite(float(v))):
-                raise ValueError(f"FusedStep: {name} must be finite and >= 0")
         self.model = model
         self.freq_reg_end, self.freq_reg_dirs = int(freq_reg_end), bool(freq_reg_dirs)
         self.data_parallel = bool(data_parallel)
@@ -1040,22 +1099,40 @@ class FusedStep:
         self.dist_weight, self.occ_weight, self.occ_samples = float(dist_weight), float(occ_weight), int(occ_samples)
         self.dist_span = None if dist_span is None else float(dist_span)
         self.ray_reg = self.dist_weight > 0.0 or self.occ_weight > 0.0        # the step with the two few-shot terms
-        self._reg = None                    # nrf_ray_reg of the last regularised loss launch: _finish hands it to nrf_ray_terms_finish
         self.depth_smooth_weight, self.patch_size = float(depth_smooth_weight), int(patch_size)
         self.patch_reg = self.depth_smooth_weight > 0.0                       # the step with the patch-based depth-smoothness term
-        self._patch = self._patch_lo = None # nrf_patch_reg and nrf_loss_opts of the last patch loss launch, for nrf_patch_terms_finish
-        self._patch_terms = self._patch_depth = None
         self.ent_weight, self.ent_threshold, self.kl_weight = float(ent_weight), float(ent_threshold), float(kl_weight)
         self.info_reg = self.ent_weight > 0.0 or self.kl_weight > 0.0         # the step with InfoNeRF's ray entropy and / or patch KL term
-        self._info = None                   # nrf_info_reg of the last such loss launch, for nrf_info_terms_finish
-        self._info_terms = self._patch_kl = None
-        self.last_patch_depth = None        # (n_patches, P, P) view of a buffer of this object: the last patch step's rendered depths
+        self._reg_kind = "info" if self.info_reg else "patch" if self.patch_reg else "reg" if self.ray_reg else None
         self.seed = None if seed is None else int(seed)
         self.white = int(bool(white_bkgd))
-        self._loss_vec, self.last_grad_norm = None, None
-        self._hier_parts = None             # ((2,R) squared errors coarse | fine, R) of the last step when it was a hierarchical one
-        self._key = None
+        self._plan, self._loss_vec, self.last_grad_norm = None, None, None     # the last step's _LossPlan and what its optimiser launch left
         self.last_count = None              # M of the last step under an occupancy grid (step_rays / step_view with occupancy=)
+        self.last_patch_depth = None        # (n_patches, P, P) view of a buffer of this object: the last patch step's rendered depths
+        # The buffer sets, {name: (key, {buffer name: tensor})}; each is built when first needed and again when its key changes (_set):
+        #   plain  every step but the hierarchical one    ctx nbytes out4 d_out4 pred ray_loss grad
+        #   ray    step_rays / step_view, beside plain     last_z rays_d
+        #   grid   a step with occupancy=, beside ray      index slot pos count cws [dirs enc feats: the staged route's inputs]
+        #   patch, info   the term buffers of a step with the patch / information terms
+        #   hier   the hierarchical steps                  grad pred pred_coarse ray_loss last_z last_weights last_z_new + its own
+        # _PUBLIC names the buffers a caller reads: a step points them at the sets it ran on.  A hierarchical step drops plain and ray,
+        # so the plain step that follows it builds its own again; hier itself survives plain steps.
+        self._sets = {}
+        self.ctx = self.nbytes = self.out4 = self.d_out4 = self.pred = self.pred_coarse = self.ray_loss = self.grad = None
+        self.last_z = self.last_weights = self.last_z_new = None
+
+    _PUBLIC ={"plain": ("ctx", "nbytes", "out4", "d_out4", "pred", "ray_loss", "grad"), "ray": ("last_z",),
+               "hier": ("grad", "pred", "pred_coarse", "ray_loss", "last_z", "last_weights", "last_z_new")}
+
+    def _set(self, name, key, make):
+        """These tensors for this key: buffer set `name`, built by make() when its key changes; its public names pointed at it."""
+        s = self._sets.get(name)
+        if s is None or s[0] != key:
+            s = self._sets[name] = (key, make())
+        b = s[1]
+        for k in self._PUBLIC.get(name, ()):
+            setattr(self, k, b[k])
+        return b
 
     def _freq_reg(self):
         """The frequency mask of the step about to run, set on the model before anything of the step is packed."""
@@ -1075,33 +1152,21 @@ class FusedStep:
         (nerf_mlp.NeRFLoss's dict, unweighted components) of the multi-term one, and 'dist', 'occ' behind them of the step with the
         few-shot ray regularisers, and 'smooth' behind those of the step with the patch term, and 'entropy' and 'kl' behind that of
         the step with ent_weight or kl_weight > 0; None before the first step."""
-        v = self._loss_vec
-        if v is None:
-            return None
-        if self._hier_parts is not None:    # the hierarchical step: {'total', 'coarse', 'fine'}, the two unweighted mse terms
-            total = v if v.dim() == 0 else v[0]
-            parts, R = self._hier_parts
-            mse = parts.sum(dim=1) / (3.0 * R)              # formed when asked for (torch reductions on the stream: no sync), from the step's buffer
-            return {"total": total, "coarse": mse[0], "fine": mse[1]}
-        if v.dim() == 1 and v.numel() == 9:     # the step with the information terms: 'entropy' and 'kl' behind the seven
-            return {"total": v[0], "rgb": v[1], "depth": v[2], "reg": v[3], "dist": v[4], "occ": v[5], "smooth": v[6], "entropy": v[7], "kl": v[8]}
-        if v.dim() == 1 and v.numel() == 7:     # the step with the patch term: 'smooth' behind the six
-            return {"total": v[0], "rgb": v[1], "depth": v[2], "reg": v[3], "dist": v[4], "occ": v[5], "smooth": v[6]}
-        if v.dim() == 1 and v.numel() == 6:
-            return {"total": v[0], "rgb": v[1], "depth": v[2], "reg": v[3], "dist": v[4], "occ": v[5]}
-        return {"total": v} if v.dim() == 0 else {"total": v[0], "rgb": v[1], "depth": v[2], "reg": v[3]}
+        return None if self._plan is None else self._plan.losses(self._loss_vec)
 
     def _buffers(self, n, R, S, dev, h, mode):
+        """The plain step's buffers for n = R * S rows; returns their key, which the ray and the grid set share."""
         key = (n, R, S, str(dev), mode)
-        if self._key != key:
+
+        def make():
             f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-            self.ctx, self.nbytes = _context(h, mode, n, dev)
-            self.out4, self.d_out4 = f(n, 4), f(n, 4)                 # V1: [rgb, sigma] rows; V2: rgb | density packed in the same rows
-            self.pred = f(R, 3)
-            # row 0: squared rgb errors; rows 1, 2 (multi-term loss): sum of w^2, |depth error|; rows 3, 4 (ray regularisers): D_r, O_r
-            self.ray_loss = f(5 if self.ray_reg or self.patch_reg or self.info_reg else 3, R)
-            self.grad = torch.zeros(self.model.flat_params().flat.numel(), dtype=torch.float32, device=dev)
-            self._key = key
+            ctx, nbytes = _context(h, mode, n, dev)
+            # out4: V1: [rgb, sigma] rows; V2: rgb | density packed in the same rows
+            # ray_loss row 0: squared rgb errors; rows 1, 2 (multi-term loss): sum of w^2, |depth error|; rows 3, 4 (ray regularisers): D_r, O_r
+            return dict(ctx=ctx, nbytes=nbytes, out4=f(n, 4), d_out4=f(n, 4), pred=f(R, 3), ray_loss=f(_LOSS_KINDS[self._reg_kind or "mse"][3], R),
+                        grad=torch.zeros(self.model.flat_params().flat.numel(), dtype=torch.float32, device=dev))
+        self._set("plain", key, make)
+        return key
 
     def _check_outputs(self, n, d_dino_out, points_out=None):
         """The refusals of the per-sample outputs a step over n = R * S samples can be handed."""
@@ -1116,23 +1181,45 @@ class FusedStep:
                                        or points_out.numel() != n * 3):
             raise ValueError("points_out must be a contiguous float32 (R*S, 3) tensor on the GPU")
 
-    def _loss_setup(self, R, S, dev, target_depth, noise, always=False, n_sup=None):
-        """(multi, loss_opts, tensors its pointers need alive): multi = the step runs the general compositor/loss kernel and the
-        clipped optimiser; loss_opts is built only then (always=True: the step under a grid, whose one indexed kernel takes it
-        either way).  The noise seed of step t is seed + t: step_count is read before the step increments it."""
-        opt = self.opt
+    def _loss_plan(self, R, S, dev, target_depth, noise, slot=None, span=None, n_patches=0):
+        """The step's _LossPlan.  The multi-term step runs the general compositor/loss kernel and the clipped optimiser; its
+        nrf_loss_opts is also built for the step under a grid (slot), whose one indexed kernel takes it either way -- with every option
+        off its bits are the mse kernel's.  The noise seed of step t is seed + t: step_count is read before the step increments it.
+        span: the depth range the distortion term's midpoints are scaled by."""
+        opt, kind, f32 = self.opt, self._reg_kind, dict(dtype=torch.float32, device=dev)
         multi = (self.reg_weight > 0.0 or self.depth_weight > 0.0 or self.noise_std > 0.0 or opt.extended or target_depth is not None
-                 or noise is not None or self.ray_reg or self.patch_reg or self.info_reg)
-        if not (multi or always):
-            return False, None, None
-        td = None if target_depth is None else L.dev_f32(target_depth, dev).reshape(R if n_sup is None else n_sup)
-        nz = None if noise is None or self.noise_std == 0.0 else L.dev_f32(noise, dev).reshape(R, S)
-        seed = 0
-        if self.noise_std > 0.0 and nz is None:
-            if self.seed is None:
-                self.seed = L.fresh_seed()
-            seed = self.seed + opt.step_count
-        return multi, L.loss_opts(self.rgb_weight, self.reg_weight, self.depth_weight, L.ptr(td), self.noise_std, L.ptr(nz), seed), (td, nz)
+                 or noise is not None or kind is not None)
+        plan = _LossPlan(kind or ("indexed" if slot is not None else "multi" if multi else "mse"), multi)
+        if plan.kind != "mse":
+            td = None if target_depth is None else L.dev_f32(target_depth, dev).reshape(R - n_patches * self.patch_size ** 2)
+            nz = None if noise is None or self.noise_std == 0.0 else L.dev_f32(noise, dev).reshape(R, S)
+            seed = 0
+            if self.noise_std > 0.0 and nz is None:
+                if self.seed is None:
+                    self.seed = L.fresh_seed()
+                seed = self.seed + opt.step_count
+            plan.lo = L.loss_opts(self.rgb_weight, self.reg_weight, self.depth_weight, L.ptr(td), self.noise_std, L.ptr(nz), seed)
+            plan.keep, plan.depth = (td, nz), td is not None
+        if kind is not None:
+            span = self.dist_span if self.dist_span is not None else span
+            if self.dist_weight > 0.0 and not (span is not None and math.isfinite(span) and span > 0.0):
+                raise ValueError("dist_weight > 0 needs a depth range: pass dist_span= to FusedStep (__call__ has no near / far), "
+                                 "or step with far > near")
+            plan.reg = L.ray_reg(self.dist_weight, 1.0 / span if self.dist_weight > 0.0 else 0.0, self.occ_weight, self.occ_samples)
+        if kind in ("patch", "info"):       # the rays' depths (and distributions) meet in LDS between the entry's forward and its backward
+            P, n1 = self.patch_size, max(n_patches, 1)
+            if self.kl_weight > 0.0 and P * P * S > L.INFO_KL_MAX_LDS_FLOATS:
+                raise ValueError(f"kl_weight > 0 keeps a patch's distributions in LDS: patch_size^2 * n_samples = {P * P * S} exceeds "
+                                 f"{L.INFO_KL_MAX_LDS_FLOATS}")
+            t = self._set("patch", (n1, dev), lambda: dict(terms=torch.zeros((n1,), **f32), depth=torch.zeros((n1 * P * P,), **f32)))
+            self.last_patch_depth = t["depth"][: n_patches * P * P].view(n_patches, P, P)
+            plan.finish_tail = (C.byref(L.patch_reg(self.depth_smooth_weight, P, n_patches)), L.ptr(t["terms"]))
+            plan.tail = plan.finish_tail + (L.ptr(t["depth"]),)
+            if kind == "info":
+                t = self._set("info", (R, n1, dev), lambda: dict(terms=torch.zeros((R,), **f32), kl=torch.zeros((n1,), **f32)))
+                more = (C.byref(L.info_reg(self.ent_weight, self.ent_threshold, self.kl_weight)), L.ptr(t["terms"]), L.ptr(t["kl"]))
+                plan.tail, plan.finish_tail = plan.tail + more, plan.finish_tail + more
+        return plan
 
     def _patch_check(self, R, n_patches):
         """The refusals of n_patches on a batch of R rays; returns R_s, the number of supervised rays in front of the patch rays."""
@@ -1151,62 +1238,10 @@ class FusedStep:
     def _launch_loss(self, heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, slot=None, span=None, n_patches=0):
         """compositor -> d loss / d pred = 2 w (pred - target) / (3 R) -> compositor backward, and the flat gradient vector cleared:
         one launch (a ray's loss gradient needs only its own prediction); the rays' squared errors stay in ray_loss.  slot (the step
-        under a grid): the indexed kernel, for the plain and the multi-term loss alike.  With the few-shot ray regularisers on, the
-        one entry that carries them (dense or indexed); span: the depth range their midpoints are scaled by.  Returns `multi`."""
-        lib = L.lib()
-        self._hier_parts = None
-        multi, lo, keep = self._loss_setup(R, S, dev, target_depth, noise, always=slot is not None, n_sup=R - n_patches * self.patch_size ** 2)
-        if self.ray_reg or self.patch_reg or self.info_reg:
-            span = self.dist_span if self.dist_span is not None else span
-            if self.dist_weight > 0.0 and not (span is not None and math.isfinite(span) and span > 0.0):
-                raise ValueError("dist_weight > 0 needs a depth range: pass dist_span= to FusedStep (__call__ has no near / far), "
-                                 "or step with far > near")
-            self._reg = L.ray_reg(self.dist_weight, 1.0 / span if self.dist_weight > 0.0 else 0.0, self.occ_weight, self.occ_samples)
-        if self.patch_reg or self.info_reg:
-            # the one entry with the patch term (dense or indexed): the rays' depths meet in LDS between its forward and its backward
-            P = self.patch_size
-            if self.kl_weight > 0.0 and P * P * S > L.INFO_KL_MAX_LDS_FLOATS:
-                raise ValueError(f"kl_weight > 0 keeps a patch's distributions in LDS: patch_size^2 * n_samples = {P * P * S} exceeds "
-                                 f"{L.INFO_KL_MAX_LDS_FLOATS}")
-            if self._patch_terms is None or self._patch_terms.numel() != max(n_patches, 1) or self._patch_terms.device != dev:
-                self._patch_terms = torch.zeros((max(n_patches, 1),), dtype=torch.float32, device=dev)
-                self._patch_depth = torch.zeros((max(n_patches, 1) * P * P,), dtype=torch.float32, device=dev)
-            self.last_patch_depth = self._patch_depth[: n_patches * P * P].view(n_patches, P, P)
-            self._patch, self._patch_lo = L.patch_reg(self.depth_smooth_weight, P, n_patches), lo
-        if self.info_reg:
-            # the same entry with the ray entropy and the patch KL term: the same launch count, the patch's distributions meet in LDS
-            if self._info_terms is None or self._info_terms.numel() != R or self._info_terms.device != dev:
-                self._info_terms = torch.zeros((R,), dtype=torch.float32, device=dev)
-            if self._patch_kl is None or self._patch_kl.numel() != max(n_patches, 1) or self._patch_kl.device != dev:
-                self._patch_kl = torch.zeros((max(n_patches, 1),), dtype=torch.float32, device=dev)
-            self._info = L.info_reg(self.ent_weight, self.ent_threshold, self.kl_weight)
-            L.check(lib.nrf_composite_info_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), C.byref(self._reg),
-                                                         None if slot is None else slot.data_ptr(), L.ptr(self.pred), *d_heads,
-                                                         L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st, C.byref(self._patch),
-                                                         L.ptr(self._patch_terms), L.ptr(self._patch_depth), C.byref(self._info),
-                                                         L.ptr(self._info_terms), L.ptr(self._patch_kl)))
-        elif self.patch_reg:
-            L.check(lib.nrf_composite_patch_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), C.byref(self._reg),
-                                                          None if slot is None else slot.data_ptr(), L.ptr(self.pred), *d_heads,
-                                                          L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st, C.byref(self._patch),
-                                                          L.ptr(self._patch_terms), L.ptr(self._patch_depth)))
-        elif self.ray_reg:
-            L.check(lib.nrf_composite_reg_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), C.byref(self._reg),
-                                                        None if slot is None else slot.data_ptr(), L.ptr(self.pred), *d_heads,
-                                                        L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
-        elif slot is not None:
-            # the one indexed entry serves both steps: with every option off its bits are the mse kernel's
-            L.check(lib.nrf_composite_loss_backward_indexed(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo),
-                                                            slot.data_ptr(), L.ptr(self.pred), *d_heads, L.ptr(self.ray_loss),
-                                                            L.ptr(self.grad), self.grad.numel(), st))
-        elif multi:
-            L.check(lib.nrf_composite_loss_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), C.byref(lo), L.ptr(self.pred),
-                                                    *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
-        else:
-            L.check(lib.nrf_composite_mse_backward(*heads, L.ptr(z), L.ptr(d), R, S, self.white, L.ptr(tgt), self.rgb_weight, L.ptr(self.pred),
-                                                   *d_heads, L.ptr(self.ray_loss), L.ptr(self.grad), self.grad.numel(), st))
-        del keep                            # (td, nz: alive until the launch that reads them is enqueued)
-        return multi
+        under a grid): the indexed kernel, or the regularised entry run indexed.  Returns the step's _LossPlan."""
+        plan = self._loss_plan(R, S, dev, target_depth, noise, slot, span, n_patches)
+        plan.launch(self, heads, d_heads, z, d, tgt, R, S, slot, st)
+        return plan
 
     def _network_backward(self, h, mode, rows, out, d_out, ctx, st, d_dino_out=None, nbytes=None):
         """dZ chain + weight gradients over the first `rows` rows, added into the flat gradient vector [-> dL/d dino].  nbytes: of a
@@ -1221,47 +1256,33 @@ class FusedStep:
             if d_dino_out is not None:
                 _dino_grad(self.model, mode, rows, self.ctx, self.nbytes, d_dino_out.device, out=d_dino_out)
 
-    def _finish(self, multi, R, S, dev, target_depth, st, loss_weight=None):
-        """[all-reduce ->] the optimiser's launch with the loss as its side job, the bookkeeping, and the parameters marked newer than
-        the packed streams (call with the device current).  Returns the step's total loss (a device scalar).  loss_weight: the factor
-        on sum(ray_loss[0]) / (3 R) when it is not rgb_weight (the hierarchical step's ray_loss carries its two weights already)."""
-        opt, lib = self.opt, L.lib()
+    def _finish(self, plan, R, S, dev, st, loss_weight=None):
+        """[all-reduce ->] the optimiser's launch with the loss as its side job [-> the plan's launch behind it], the bookkeeping, and
+        the parameters marked newer than the packed streams (call with the device current).  Returns the step's total loss (a device
+        scalar).  loss_weight: the factor on sum(ray_loss[0]) / (3 R) when it is not rgb_weight (the hierarchical step's ray_loss
+        carries its two weights already)."""
+        opt = self.opt
         loss_weight = self.rgb_weight if loss_weight is None else loss_weight
         if self.data_parallel:
             _all_reduce_mean(self.grad, self.group)
         fp, flat = opt._buffers()
         opt.step_count += 1
-        if multi:
+        if plan.multi:
             # [norm partials ->] clipped Adam / AdamW, and as a side job of its launch the loss terms summed in a fixed order
             loss = torch.empty((4,), dtype=torch.float32, device=dev)
-            opt._update(flat, self.grad, self.ray_loss, R, S, (loss_weight, self.depth_weight if target_depth is not None else 0.0,
-                                                               self.reg_weight), loss)
-            if self.info_reg:
-                # one small launch more, in the patch step's place: all nine values with the divisors of the batch layout
-                loss = torch.empty((9,), dtype=torch.float32, device=dev)
-                L.check(lib.nrf_info_terms_finish(L.ptr(self.ray_loss), R, S, C.byref(self._patch_lo), C.byref(self._reg), C.byref(self._patch),
-                                                  L.ptr(self._patch_terms), C.byref(self._info), L.ptr(self._info_terms), L.ptr(self._patch_kl),
-                                                  L.ptr(loss), st))
-            elif self.patch_reg:
-                # one small launch more: all seven values with the divisors of the batch layout (the optimiser's four divide by R)
-                loss = torch.empty((7,), dtype=torch.float32, device=dev)
-                L.check(lib.nrf_patch_terms_finish(L.ptr(self.ray_loss), R, S, C.byref(self._patch_lo), C.byref(self._reg), C.byref(self._patch),
-                                                   L.ptr(self._patch_terms), L.ptr(loss), st))      # (loss_opts.target_depth: a flag here, not read)
-            elif self.ray_reg:
-                # one small launch more: the two new terms summed in a fixed order and appended to the four
-                loss4, loss = loss, torch.empty((6,), dtype=torch.float32, device=dev)
-                L.check(lib.nrf_ray_terms_finish(L.ptr(self.ray_loss), R, C.byref(self._reg), L.ptr(loss4), L.ptr(loss), st))
-            self._loss_vec, self.last_grad_norm = loss, opt.last_grad_norm
-            loss = loss[0]
+            opt._update(flat, self.grad, self.ray_loss, R, S, (loss_weight, self.depth_weight if plan.depth else 0.0, self.reg_weight), loss)
+            loss = plan.finish(self, R, S, loss, st)
+            self.last_grad_norm, total = opt.last_grad_norm, loss[0]
         else:
             # Adam, and as a side job of its launch the loss value: rgb_weight * sum(ray_loss) / (3 R) in a fixed order
-            loss = torch.empty((), dtype=torch.float32, device=dev)
-            L.check(lib.nrf_adam_step_loss(L.ptr(flat), L.ptr(self.grad), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq), flat.numel(), opt.lr,
-                                           opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, opt.step_count, L.ptr(self.ray_loss), R,
-                                           loss_weight, L.ptr(loss), st))
-            self._loss_vec, self.last_grad_norm = loss, None
+            loss = total = torch.empty((), dtype=torch.float32, device=dev)
+            L.check(L.lib().nrf_adam_step_loss(L.ptr(flat), L.ptr(self.grad), L.ptr(opt.exp_avg), L.ptr(opt.exp_avg_sq), flat.numel(), opt.lr,
+                                               opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, opt.step_count, L.ptr(self.ray_loss), R,
+                                               loss_weight, L.ptr(loss), st))
+            self.last_grad_norm = None
+        self._plan, self._loss_vec = plan, loss
         self.model._gen += 1
-        return loss
+        return total
 
     @torch.no_grad()
     def __call__(self, points, z_vals, rays_d, target, dirs=None, dino=None, target_depth=None, noise=None, d_dino_out=None, n_patches=0):
@@ -1301,11 +1322,57 @@ class FusedStep:
                 dirs_d = L.dev_f32(dirs, dev).reshape(n, 3)
                 dino_d = L.dev_f32(dino, dev).reshape(n, m.dino_dim) if m.net == L.NRF_NET_V3 else None
                 L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(pts), L.ptr(dirs_d), L.ptr(dino_d), n, L.ptr(out[0]), L.ptr(out[1]), ctx, self.nbytes, st))
-            multi = self._launch_loss(heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, n_patches=n_patches)
+            plan = self._launch_loss(heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, n_patches=n_patches)
             self._network_backward(h, mode, n, out, d_out, ctx, st, d_dino_out)
-            return self._finish(multi, R, S, dev, target_depth, st)
+            return self._finish(plan, R, S, dev, st)
 
     # ---- the same step from rays: sampling, encoding and the feature fetch happen inside the saving forward ----------------
+    @staticmethod
+    def _rays_source(rays_o, rays_d, target):
+        """Rays given by origin and direction, as the ray steps take them: (R, device, make_rays(z, d_out, p_out) -> nrf_train_rays, the
+        (R,3) directions the compositor reads, target)."""
+        o = L.dev_f32(rays_o).reshape(-1, 3)
+        d = L.dev_f32(rays_d, o.device).reshape(-1, 3)
+        if d.shape != o.shape:
+            raise ValueError("rays_o and rays_d must both be (R,3)")
+        return o.shape[0], o.device, lambda z, d_out, p_out=None: L.train_rays(rays_o=L.ptr(o), rays_d=L.ptr(d), z_vals=z, points_out=p_out), d, target
+
+    @staticmethod
+    def _view_source(image, pose, H, W, focal, pixels, target):
+        """Pixels of a pinhole view, in the same form; the directions are None: the kernel writes them (d_out) for the compositor."""
+        if not (isinstance(pixels, torch.Tensor) and pixels.is_cuda and pixels.dtype == torch.int64 and pixels.dim() == 1):
+            raise ValueError("pixels must be a 1-d int64 tensor of ray ids on the GPU")
+        pix = pixels.contiguous()
+        H, W = int(H), int(W)
+        if target is None:
+            img = L.dev_f32(image, pix.device)
+            if img.numel() != H * W * 3:
+                raise ValueError("image must be (H,W,3) (or pass target=)")
+            target = img.reshape(-1, 3)[pix]
+        from .ray_sampler import _c2w12
+        c2w = pose if isinstance(pose, C.Array) else _c2w12(pose)
+        return (pix.shape[0], pix.device,
+                lambda z, d_out, p_out=None: L.train_rays(pixels=pix.data_ptr(), H=H, W=W, focal=focal, c2w=c2w, z_vals=z, rays_d_out=d_out, points_out=p_out),
+                None, target)
+
+    def _prologue(self, R, S, dev, target, t_rand, dino, z_in=None, d_dino_out=None, points_out=None, n_patches=0):
+        """What every ray step does before its buffers: the refusals of the batch, target, jitter and depths on the device, the DINO
+        struct (V3), the frequency mask and the packed handle.  Returns (tgt, t_rand, z_in, nrf_dino, its tensors, handle, mode)."""
+        if R < 1:
+            raise ValueError("a step needs at least one ray")
+        self._check_outputs(R * S, d_dino_out, points_out)
+        tgt = L.dev_f32(target, dev).reshape(self._patch_check(R, n_patches), 3)
+        tr = L.dev_f32(t_rand, dev).reshape(R, S) if t_rand is not None else None
+        zin = L.dev_f32(z_in, dev).reshape(R, S) if z_in is not None else None
+        dn = keep = None
+        if self.model.net == L.NRF_NET_V3:
+            if dino is None:
+                raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
+            from .renderer import make_dino
+            dn, keep = make_dino(**dino) if isinstance(dino, dict) else dino
+        self._freq_reg()
+        return (tgt, tr, zin, dn, keep) + _train_handle(self.model, dev)
+
     @torch.no_grad()
     def step_rays(self, rays_o, rays_d, target, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False, z_in=None,
                   dino=None, target_depth=None, noise=None, d_dino_out=None, points_out=None, occupancy=None, grid_inputs="staged", n_patches=0):
@@ -1340,13 +1407,8 @@ class FusedStep:
 
         n_patches: as in __call__ -- the last n_patches * patch_size^2 rays are patch rays (ray_sampler.patch_rays writes them), target
         (R_s,3) and target_depth (R_s) belong to the rays in front of them; with or without occupancy=, on both grid_inputs routes."""
-        o = L.dev_f32(rays_o).reshape(-1, 3)
-        d = L.dev_f32(rays_d, o.device).reshape(-1, 3)
-        if d.shape != o.shape:
-            raise ValueError("rays_o and rays_d must both be (R,3)")
-        return self._ray_step(o.shape[0], o.device, lambda z, d_out, p_out: L.train_rays(rays_o=L.ptr(o), rays_d=L.ptr(d), z_vals=z, points_out=p_out), d,
-                              target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise, d_dino_out, points_out,
-                              occupancy, grid_inputs, n_patches)
+        return self._ray_step(*self._rays_source(rays_o, rays_d, target), near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino,
+                              target_depth, noise, d_dino_out, points_out, occupancy, grid_inputs, n_patches)
 
     @torch.no_grad()
     def step_view(self, image, pose, H, W, focal, pixels, near, far, n_samples, perturb=True, t_rand=None, seed=None, lindisp=False,
@@ -1361,22 +1423,8 @@ class FusedStep:
         view has one pose, and the patches come from poses of their own (step_rays)."""
         if self.patch_reg or self.kl_weight > 0.0:
             raise ValueError("step_view takes one pose per call: a FusedStep with depth_smooth_weight or kl_weight > 0 steps through step_rays or __call__")
-        if not (isinstance(pixels, torch.Tensor) and pixels.is_cuda and pixels.dtype == torch.int64 and pixels.dim() == 1):
-            raise ValueError("pixels must be a 1-d int64 tensor of ray ids on the GPU")
-        pix = pixels.contiguous()
-        H, W = int(H), int(W)
-        if target is None:
-            img = L.dev_f32(image, pix.device)
-            if img.numel() != H * W * 3:
-                raise ValueError("image must be (H,W,3) (or pass target=)")
-            target = img.reshape(-1, 3)[pix]
-        from .ray_sampler import _c2w12
-        c2w = pose if isinstance(pose, C.Array) else _c2w12(pose)
-        return self._ray_step(pix.shape[0], pix.device,
-                              lambda z, d_out, p_out: L.train_rays(pixels=pix.data_ptr(), H=H, W=W, focal=focal, c2w=c2w, z_vals=z, rays_d_out=d_out,
-                                                                   points_out=p_out),
-                              None, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise, d_dino_out, points_out,
-                              occupancy, grid_inputs)
+        return self._ray_step(*self._view_source(image, pose, H, W, focal, pixels, target), near, far, n_samples, perturb, t_rand, seed, lindisp,
+                              z_in, dino, target_depth, noise, d_dino_out, points_out, occupancy, grid_inputs)
 
     # ---- the hierarchical step: a coarse and a fine image of one network, every sample evaluated once --------------------------
     def _hier_check(self, n_samples, n_importance, coarse_weight, occupancy=None, d_dino_out=None, points_out=None):
@@ -1435,12 +1483,7 @@ class FusedStep:
         the plain step.  Refused with ValueError: a step object with reg_weight, depth_weight or noise_std > 0, occupancy=,
         d_dino_out=, points_out=, n_importance < 1, n_samples + n_importance > 4096, coarse_weight < 0."""
         chk = self._hier_check(n_samples, n_importance, coarse_weight, occupancy, d_dino_out, points_out)
-        o = L.dev_f32(rays_o).reshape(-1, 3)
-        d = L.dev_f32(rays_d, o.device).reshape(-1, 3)
-        if d.shape != o.shape:
-            raise ValueError("rays_o and rays_d must both be (R,3)")
-        return self._hier_step(o.shape[0], o.device, lambda z, d_out: L.train_rays(rays_o=L.ptr(o), rays_d=L.ptr(d), z_vals=z), d, target, near, far,
-                               chk, perturb, t_rand, seed, lindisp, u, dino)
+        return self._hier_step(*self._rays_source(rays_o, rays_d, target), near, far, chk, perturb, t_rand, seed, lindisp, u, dino)
 
     @torch.no_grad()
     def step_view_hierarchical(self, image, pose, H, W, focal, pixels, near, far, n_samples, n_importance, perturb=True, t_rand=None,
@@ -1450,29 +1493,13 @@ class FusedStep:
         ray ids, the target `target` (R,3) or image.reshape(-1,3)[pixels]; jitter and uniforms are keyed by the position in `pixels`,
         so the step equals step_rays_hierarchical on the gathered rays to the bit."""
         chk = self._hier_check(n_samples, n_importance, coarse_weight, occupancy, d_dino_out, points_out)
-        if not (isinstance(pixels, torch.Tensor) and pixels.is_cuda and pixels.dtype == torch.int64 and pixels.dim() == 1):
-            raise ValueError("pixels must be a 1-d int64 tensor of ray ids on the GPU")
-        pix = pixels.contiguous()
-        H, W = int(H), int(W)
-        if target is None:
-            img = L.dev_f32(image, pix.device)
-            if img.numel() != H * W * 3:
-                raise ValueError("image must be (H,W,3) (or pass target=)")
-            target = img.reshape(-1, 3)[pix]
-        from .ray_sampler import _c2w12
-        c2w = pose if isinstance(pose, C.Array) else _c2w12(pose)
-        return self._hier_step(pix.shape[0], pix.device,
-                               lambda z, d_out: L.train_rays(pixels=pix.data_ptr(), H=H, W=W, focal=focal, c2w=c2w, z_vals=z, rays_d_out=d_out),
-                               None, target, near, far, chk, perturb, t_rand, seed, lindisp, u, dino)
+        return self._hier_step(*self._view_source(image, pose, H, W, focal, pixels, target), near, far, chk, perturb, t_rand, seed, lindisp, u, dino)
 
     def _hier_buffers(self, R, S, Ni, dev, h, mode):
-        """The hierarchical step's buffers, kept apart from the plain step's (a FusedStep may take both kinds of step); the ones a
-        caller or _finish reads by name -- grad, pred, ray_loss, last_z -- are pointed at them for the step."""
-        key = (R, S, Ni, str(dev), mode)
-        b = getattr(self, "_hb", None)
-        if b is None or b["key"] != key:
+        """The hierarchical step's buffers, kept apart from the plain step's (a FusedStep may take both kinds of step)."""
+        def make():
             f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-            b = {"key": key}
+            b = {}
             b["ctx_c"], b["nbytes_c"] = _context(h, mode, R * S, dev)
             b["ctx_n"], b["nbytes_n"] = _context(h, mode, R * Ni, dev)
             for k, rows in (("c", R * S), ("n", R * Ni)):
@@ -1480,33 +1507,21 @@ class FusedStep:
             b["pred"], b["pred_coarse"], b["rays_d"] = f(R, 3), f(R, 3), f(R, 3)
             b["ray_loss"] = torch.zeros((3, R), dtype=torch.float32, device=dev)     # row 0: w_c se_c + w_f se_f; rows 1, 2 stay 0 (the clipped optimiser's side job reads three rows)
             b["parts"] = f(2, R)
-            b["z"], b["w"], b["z_new"], b["z_new_out"] = f(R, S), f(R, S), f(R, Ni), f(R, Ni)
+            b["last_z"], b["last_weights"], b["last_z_new"], b["z_new_out"] = f(R, S), f(R, S), f(R, Ni), f(R, Ni)
             b["ws"] = torch.empty((max(int(L.lib().nrf_hier_train_workspace_bytes(R, S, Ni)), 16) // 4,), dtype=torch.float32, device=dev)
             b["grad"] = torch.zeros(self.model.flat_params().flat.numel(), dtype=torch.float32, device=dev)
-            self._hb = b
-        self.grad, self.pred, self.pred_coarse, self.ray_loss = b["grad"], b["pred"], b["pred_coarse"], b["ray_loss"]
-        self.last_z, self.last_weights, self.last_z_new = b["z"], b["w"], b["z_new"]
-        self._key = self._ray_key = None    # the plain step's buffers are no longer the ones these names point at: it takes its own again
-        return b
+            return b
+        self._sets.pop("plain", None)       # grad, pred, ray_loss and last_z leave the plain step's buffers: it takes its own again
+        self._sets.pop("ray", None)
+        return self._set("hier", (R, S, Ni, str(dev), mode), make)
 
     def _hier_step(self, R, dev, make_rays, d, target, near, far, chk, perturb, t_rand, seed, lindisp, u, dino):
         """The launch sequence of step_rays_hierarchical; d is the caller's (R,3) directions or None (pixel mode)."""
-        from .renderer import _opts, make_dino
+        from .renderer import _opts
         S, Ni, w_coarse, w_fine = chk
-        m = self.model
-        v1, v3 = m.net == L.NRF_NET_V1, m.net == L.NRF_NET_V3
-        if R < 1:
-            raise ValueError("a step needs at least one ray")
-        tgt = L.dev_f32(target, dev).reshape(R, 3)
-        tr = L.dev_f32(t_rand, dev).reshape(R, S) if t_rand is not None else None
-        dn = keep = None
-        if v3:
-            if dino is None:
-                raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
-            dn, keep = make_dino(**dino) if isinstance(dino, dict) else dino
-        lib = L.lib()
-        self._freq_reg()
-        h, mode = _train_handle(m, dev)
+        m, lib = self.model, L.lib()
+        v1 = m.net == L.NRF_NET_V1
+        tgt, tr, _, dn, keep, h, mode = self._prologue(R, S, dev, target, t_rand, dino)
         with torch.cuda.device(dev):
             if u is None:
                 uu, stride = (torch.rand((R, Ni), dtype=torch.float32, device=dev), Ni) if perturb else (L.u_row(Ni, dev), 0)
@@ -1519,7 +1534,7 @@ class FusedStep:
                 else:
                     raise ValueError("u must be (R, n_importance) or one shared row (n_importance)")
             b = self._hier_buffers(R, S, Ni, dev, h, mode)
-            z, w, z_new = b["z"], b["w"], b["z_new"]
+            z, w, z_new = b["last_z"], b["last_weights"], b["last_z_new"]
             if d is None:
                 d = b["rays_d"]
             st = L.stream_ptr()
@@ -1546,18 +1561,18 @@ class FusedStep:
                             d_rgb_coarse=d_heads_c[0], d_sigma_coarse=_addr(d_heads_c[2]), d_rgb_new=d_heads_n[0], d_sigma_new=_addr(d_heads_n[2]),
                             pred_coarse=L.ptr(self.pred_coarse), pred_fine=L.ptr(self.pred), ray_loss=L.ptr(self.ray_loss), ray_parts=L.ptr(b["parts"]),
                             zero_buf=L.ptr(self.grad), zero_n=self.grad.numel(), workspace=b["ws"].data_ptr(), workspace_bytes=b["ws"].numel() * 4)
-            L.check(lib.nrf_composite_hier_loss_backward(C.byref(a), R, S, Ni, st))
+            plan = _LossPlan("hier", self.opt.extended)
+            plan.parts = (b["parts"], R)
+            L.check(getattr(lib, plan.entry)(C.byref(a), R, S, Ni, st))
             self._network_backward(h, mode, R * S, out_c, d_out_c, ctx_c, st, nbytes=b["nbytes_c"])
             self._network_backward(h, mode, R * Ni, out_n, d_out_n, ctx_n, st, nbytes=b["nbytes_n"])
-            loss = self._finish(self.opt.extended, R, S + Ni, dev, None, st, loss_weight=1.0)
-            self._hier_parts = (b["parts"], R)
-            return loss
+            return self._finish(plan, R, S + Ni, dev, st, loss_weight=1.0)
 
     def _ray_step(self, R, dev, make_rays, d, target, near, far, n_samples, perturb, t_rand, seed, lindisp, z_in, dino, target_depth, noise,
                   d_dino_out, points_out, occupancy=None, grid_inputs="staged", n_patches=0):
         """__call__'s sequence with nrf_mlp_forward_train_rays in front -- or, under an occupancy grid, _grid_forward; d is the
         caller's (R,3) directions or None (pixel mode: the kernel writes them for the compositor)."""
-        from .renderer import _opts, make_dino
+        from .renderer import _opts
         if grid_inputs not in ("staged", "rays"):
             raise ValueError('grid_inputs must be "staged" or "rays"')
         if occupancy is None and grid_inputs != "staged":
@@ -1569,53 +1584,38 @@ class FusedStep:
                 raise ValueError("occupancy is not combined with d_dino_out / points_out: the step under a grid hands out no per-sample gradients")
             if not isinstance(occupancy, OccupancyGrid):
                 raise TypeError("occupancy must be an occupancy.OccupancyGrid")
-        m = self.model
-        S = int(n_samples)
+        m, lib = self.model, L.lib()
+        S, n_patches = int(n_samples), int(n_patches)
         n = R * S
-        v1, v3 = m.net == L.NRF_NET_V1, m.net == L.NRF_NET_V3
-        if R < 1:
-            raise ValueError("a step needs at least one ray")
-        self._check_outputs(n, d_dino_out, points_out)
-        n_patches = int(n_patches)
-        tgt = L.dev_f32(target, dev).reshape(self._patch_check(R, n_patches), 3)
-        tr = L.dev_f32(t_rand, dev).reshape(R, S) if t_rand is not None else None
-        zin = L.dev_f32(z_in, dev).reshape(R, S) if z_in is not None else None
-        dn = keep = None
-        if v3:
-            if dino is None:
-                raise ValueError("a use_dino model needs dino=dict(features=, pose=, focal=, H=, W=)")
-            dn, keep = make_dino(**dino) if isinstance(dino, dict) else dino
-        lib = L.lib()
-        self._freq_reg()
-        h, mode = _train_handle(m, dev)
+        v1 = m.net == L.NRF_NET_V1
+        tgt, tr, zin, dn, keep, h, mode = self._prologue(R, S, dev, target, t_rand, dino, z_in, d_dino_out, points_out, n_patches)
         with torch.cuda.device(dev):
-            self._buffers(n, R, S, dev, h, mode)
-            if getattr(self, "_ray_key", None) != self._key:
-                self.last_z = torch.empty((R, S), dtype=torch.float32, device=dev)
-                self._rays_d = torch.empty((R, 3), dtype=torch.float32, device=dev)
-                self._ray_key = self._key
+            key = self._buffers(n, R, S, dev, h, mode)
+            rb = self._set("ray", key, lambda: dict(last_z=torch.empty((R, S), dtype=torch.float32, device=dev),
+                                                    rays_d=torch.empty((R, 3), dtype=torch.float32, device=dev)))
             z = self.last_z
             opts = _opts(near, far, S, perturb, tr, seed, lindisp, 0.0, self.white, L.TRAIN_MODE[m.mma_mode], dn, dev, zin)
-            rays = make_rays(L.ptr(z), L.ptr(self._rays_d), L.ptr(points_out))
+            rays = make_rays(L.ptr(z), L.ptr(rb["rays_d"]), L.ptr(points_out))
             if d is None:
-                d = self._rays_d
+                d = rb["rays_d"]
             st = L.stream_ptr()
             ctx = C.c_void_p(self.ctx.data_ptr())
             *out, heads = _heads(self.out4, n, v1)
             *d_out, d_heads = _heads(self.d_out4, n, v1)
             if occupancy is not None:
-                rows, slot = self._grid_forward(rays, R, S, dev, opts, occupancy, dn, h, mode, out, ctx, st, by_rays, points_out), self._slot
+                rows, slot = self._grid_forward(key, rays, R, S, dev, opts, occupancy, dn, h, mode, out, ctx, st, by_rays, points_out)
             else:
                 L.check(lib.nrf_mlp_forward_train_rays(h, C.byref(rays), R, C.byref(opts), L.ptr(out[0]), L.ptr(out[1]), ctx, self.nbytes, st))
                 rows, slot = n, None
             del keep
-            multi = self._launch_loss(heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, slot, span=float(far) - float(near), n_patches=n_patches)
+            plan = self._launch_loss(heads, d_heads, z, d, tgt, R, S, dev, target_depth, noise, st, slot, span=float(far) - float(near), n_patches=n_patches)
             if occupancy is None or rows:
                 self._network_backward(h, mode, rows, out, d_out, ctx, st, d_dino_out)
-            return self._finish(multi, R, S, dev, target_depth, st)
+            return self._finish(plan, R, S, dev, st)
 
-    def _grid_forward(self, rays, R, S, dev, opts, occupancy, dn, h, mode, out, ctx, st, by_rays=False, points_out=None):
-        """The saving forward of the step under an occupancy grid (nerfhip.h: nrf_occupancy_compact_rays); returns M.  The step:
+    def _grid_forward(self, key, rays, R, S, dev, opts, occupancy, dn, h, mode, out, ctx, st, by_rays=False, points_out=None):
+        """The saving forward of the step under an occupancy grid (nerfhip.h: nrf_occupancy_compact_rays); returns (M, the slot map of
+        the indexed loss launch).  key: of the plain step's buffers, which the grid's share.  The step:
 
             compact -> read M back -> [V1: encode | V3: project + fetch] of the M points -> saving forward on M rows
             -> indexed compositor, loss and backward (clears the gradient vector) -> dZ chain + weight gradients on M rows
@@ -1633,36 +1633,33 @@ class FusedStep:
         an all-ones grid every bit of the step is the plain ray step's, for all three families."""
         m, lib, n = self.model, L.lib(), R * S
         v1, v3 = m.net == L.NRF_NET_V1, m.net == L.NRF_NET_V3
-        if getattr(self, "_grid_key", None) != self._key:
-            self._index = torch.empty((n,), dtype=torch.int32, device=dev)
-            self._slot = torch.empty((n,), dtype=torch.int32, device=dev)
-            self._pos = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            self._dirs = self._enc = self._feats = None
-            self._count = torch.zeros((1,), dtype=torch.int64, device=dev)
-            self._cws = torch.empty((int(lib.nrf_occupancy_compact_workspace_bytes(R)),), dtype=torch.uint8, device=dev)
-            self._grid_key = self._key
-        if not by_rays and self._dirs is None and self._enc is None:      # the staged route's per-sample inputs, on its first step
-            self._dirs = None if v1 else torch.empty((n, 3), dtype=torch.float32, device=dev)
-            self._enc = torch.empty((n, 3 * (2 * m.pos_freq + 1)), dtype=torch.float32, device=dev) if v1 else None
-            self._feats = torch.empty((n, m.dino_dim), dtype=torch.float32, device=dev) if v3 else None
+        g = self._set("grid", key, lambda: dict(
+            index=torch.empty((n,), dtype=torch.int32, device=dev), slot=torch.empty((n,), dtype=torch.int32, device=dev),
+            pos=torch.empty((n, 3), dtype=torch.float32, device=dev), dirs=None, enc=None, feats=None,
+            count=torch.zeros((1,), dtype=torch.int64, device=dev),
+            cws=torch.empty((int(lib.nrf_occupancy_compact_workspace_bytes(R)),), dtype=torch.uint8, device=dev)))
+        if not by_rays and g["dirs"] is None and g["enc"] is None:      # the staged route's per-sample inputs, on its first step
+            g["dirs"] = None if v1 else torch.empty((n, 3), dtype=torch.float32, device=dev)
+            g["enc"] = torch.empty((n, 3 * (2 * m.pos_freq + 1)), dtype=torch.float32, device=dev) if v1 else None
+            g["feats"] = torch.empty((n, m.dino_dim), dtype=torch.float32, device=dev) if v3 else None
         occ, occ_keep = occupancy.struct(dev)
-        pos = points_out if by_rays and points_out is not None else self._pos
-        cp = L.compact(n, self._index.data_ptr(), self._slot.data_ptr(), L.ptr(pos), None if by_rays else L.ptr(self._dirs), self._count.data_ptr(),
-                       self._cws.data_ptr(), self._cws.numel())
+        pos = points_out if by_rays and points_out is not None else g["pos"]
+        cp = L.compact(n, g["index"].data_ptr(), g["slot"].data_ptr(), L.ptr(pos), None if by_rays else L.ptr(g["dirs"]), g["count"].data_ptr(),
+                       g["cws"].data_ptr(), g["cws"].numel())
         L.check(lib.nrf_occupancy_compact_rays(C.byref(rays), R, C.byref(opts), C.byref(occ), C.byref(cp), st))
-        M = int(self._count.item())         # the step's only synchronisation: 8 bytes
+        M = int(g["count"].item())         # the step's only synchronisation: 8 bytes
         self.last_count = M
         if M and by_rays:
-            L.check(lib.nrf_mlp_forward_train_rays_indexed(h, C.byref(rays), R, C.byref(opts), self._index.data_ptr(), M, L.ptr(out[0]), L.ptr(out[1]),
+            L.check(lib.nrf_mlp_forward_train_rays_indexed(h, C.byref(rays), R, C.byref(opts), g["index"].data_ptr(), M, L.ptr(out[0]), L.ptr(out[1]),
                                                            ctx, self.nbytes, st))
         elif M:
             if v1:
-                L.check(lib.nrf_encode(L.ptr(self._pos), M, 3, m.pos_freq, 1, None, L.ptr(self._enc), st))
-                L.check(lib.nrf_mlp_forward_train_v1(h, mode, L.ptr(self._enc), M, L.ptr(out[0]), ctx, self.nbytes, st))
+                L.check(lib.nrf_encode(L.ptr(g["pos"]), M, 3, m.pos_freq, 1, None, L.ptr(g["enc"]), st))
+                L.check(lib.nrf_mlp_forward_train_v1(h, mode, L.ptr(g["enc"]), M, L.ptr(out[0]), ctx, self.nbytes, st))
             else:
                 if v3:
-                    L.check(lib.nrf_project_fetch(C.byref(dn), L.ptr(self._pos), M, L.ptr(self._feats), None, st))
-                L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(self._pos), L.ptr(self._dirs), L.ptr(self._feats), M, L.ptr(out[0]), L.ptr(out[1]),
+                    L.check(lib.nrf_project_fetch(C.byref(dn), L.ptr(g["pos"]), M, L.ptr(g["feats"]), None, st))
+                L.check(lib.nrf_mlp_forward_train(h, mode, L.ptr(g["pos"]), L.ptr(g["dirs"]), L.ptr(g["feats"]), M, L.ptr(out[0]), L.ptr(out[1]),
                                                   ctx, self.nbytes, st))
         del occ_keep
-        return M
+        return M, g["slot"]
