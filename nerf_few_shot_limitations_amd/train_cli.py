@@ -128,11 +128,13 @@ this command.
 from __future__ import annotations
 
 import argparse
+import contextlib
 import ctypes as C
 import json
 import math
 import os
 import time
+from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as F
@@ -140,7 +142,7 @@ import torch.nn.functional as F
 from . import _lib as L
 from . import (dino_model_from_config, evaluate_views, get_rays, load_blender_data, load_checkpoint_into, load_config, model_from_config,
                precompute_dino_features, render_settings, sample_points_along_rays)
-from .ray_sampler import _c2w12
+from .ray_sampler import _c2w12, patch_rays, sample_patch_poses
 from .renderer import make_dino
 from .training import FusedStep, project_fetch_backward
 
@@ -189,215 +191,230 @@ def fetch_features(dino_struct, pts):
     return feats
 
 
+# ---- the flags, read once -------------------------------------------------------------------------------------------------------
+OCCUPANCY_FLAGS = ("occupancy_box", "occupancy_threshold", "occupancy_decay", "occupancy_refresh_every", "occupancy_cells_per_refresh",
+                   "occupancy_warmup")
+# the flags the checks and the option readers look at, with what an absent (or None) one counts as (the type is the default's), and
+# those that stay None unless given, with their type
+_DEFAULTS = dict(n_importance=0, recipe="train", dist_weight=0.0, occ_weight=0.0, depth_smooth_weight=0.0, patch_size=8, patches_per_step=16,
+                 patch_stride=1, entropy_weight=0.0, entropy_unseen=False, kl_weight=0.0, freq_reg_end=0, no_freq_reg_dirs=False,
+                 occupancy_res=0, occupancy_per_view=False, train_extractor=False, fused_inputs=False)
+_OPTIONAL = dict(coarse_weight=float, occ_samples=int, entropy_threshold=float)
+
+
+class Flags(SimpleNamespace):
+    """What flags_of returns."""
+
+
+def flags_of(args):
+    """The one reading of an argparse namespace, partial or complete (a Flags passes through): every flag of _DEFAULTS and _OPTIONAL
+    with its default applied and its type fixed; every other attribute as it is -- one the namespace lacks is missing here too, so the
+    checks that read such fields read them one at a time, in the order they always did, and raise where they did; and the facts several checks ask for -- grid_flags (the OCCUPANCY_FLAGS that were given), grid_given (any --occupancy-*
+    flag was), draws_patches (every batch gets patches of unseen poses behind its supervised rays: --depth-smooth-weight, --kl-weight,
+    or --entropy-weight with --entropy-unseen) and hierarchical (--n-importance > 0)."""
+    if isinstance(args, Flags):
+        return args
+    f = Flags(**vars(args))
+    for name, default in {**_DEFAULTS, **dict.fromkeys(_OPTIONAL)}.items():
+        v = getattr(args, name, None)
+        setattr(f, name, default if v is None else _OPTIONAL.get(name, type(default))(v))
+    f.grid_flags = [name for name in OCCUPANCY_FLAGS if vars(f).get(name) is not None]
+    f.grid_given = bool(f.occupancy_res or f.occupancy_per_view or f.grid_flags)
+    f.draws_patches = f.depth_smooth_weight > 0.0 or f.kl_weight > 0.0 or (f.entropy_weight > 0.0 and f.entropy_unseen)
+    f.hierarchical = f.n_importance > 0
+    return f
+
+
+def _refusal(*checks):
+    """The message of the first (fault, message) whose fault is there; None when none is.  Every fault is evaluated before the first is
+    picked, so a fault here reads only fields that flags_of always sets: one that can raise is an `if` of its own, in its place."""
+    return next((message for fault, message in checks if fault), None)
+
+
+def _finite(*weights):
+    return all(w >= 0.0 and math.isfinite(w) for w in weights)
+
+
 def extractor_args_error(args, cfg):
     """Why --train-extractor cannot run with these arguments / this config (None: it can).  Decided before any GPU work."""
-    if not getattr(args, "train_extractor", False):
+    f = flags_of(args)
+    if not f.train_extractor:
         return None
     model_cfg = cfg.get("model", {}) or {}
     if not bool(model_cfg.get("use_dino", True)):
         return "--train-extractor: this config has use_dino: false, there is no extractor"
-    if args.dino_maps:
+    if f.dino_maps:                                       # (fields without a default, read one at a time: not for _refusal)
         return "--train-extractor needs the extractor itself (--dino-weights or --dino-random-init): --dino-maps are constants"
-    if not (args.dino_weights or args.dino_random_init):
+    if not (f.dino_weights or f.dino_random_init):
         return "--train-extractor needs --dino-weights <local Dinov2Model checkpoint> or --dino-random-init"
-    if args.data_parallel:
+    if f.data_parallel:
         return "--train-extractor with --data-parallel is not built (the per-view map gradient would need its own all-reduce)"
-    if model_cfg.get("dino_model_type", "single_scale") == "multi_scale":
-        return ("--train-extractor: MultiScaleDINOFeatures runs its backbone under no_grad (multi_scale_dino.py:87), its LoRA matrices "
-                "would receive no gradient")
-    if not bool((cfg.get("dino_model", {}) or {}).get("use_lora", True)):
-        return "--train-extractor: dino_model.use_lora is false, the trainable set of train.py:105-110 is empty"
-    return None
+    return _refusal(
+        (model_cfg.get("dino_model_type", "single_scale") == "multi_scale",
+         "--train-extractor: MultiScaleDINOFeatures runs its backbone under no_grad (multi_scale_dino.py:87), its LoRA matrices would receive no gradient"),
+        (not bool((cfg.get("dino_model", {}) or {}).get("use_lora", True)),
+         "--train-extractor: dino_model.use_lora is false, the trainable set of train.py:105-110 is empty"))
 
 
 def hierarchical_args_error(args, cfg=None):
     """Why --n-importance / --coarse-weight cannot run with these arguments (None: they can, or neither was given).  Decided before
     any GPU work, in the style of occupancy_args_error."""
-    n = int(getattr(args, "n_importance", 0) or 0)
-    w = getattr(args, "coarse_weight", None)
-    if n < 0:
-        return "--n-importance must be >= 0 (0: off)"
-    if w is not None and not w >= 0.0:
-        return "--coarse-weight must be >= 0"
-    if n == 0:
-        if w is not None:
-            return "--coarse-weight needs --n-importance N (N > 0): without the hierarchical step the flag would be ignored"
-        return None
-    if getattr(args, "recipe", "train") == "multiscale":
-        return ("--n-importance with --recipe multiscale is refused: the regulariser, the depth term and the density noise are not part of "
-                "the hierarchical step")
-    if int(getattr(args, "occupancy_res", 0) or 0) or getattr(args, "occupancy_per_view", False) or any(
-            getattr(args, f, None) is not None for f in OCCUPANCY_FLAGS):
-        return "--n-importance is not combined with --occupancy-*: the hierarchical step runs under no grid"
-    if getattr(args, "train_extractor", False):
-        return "--n-importance with --train-extractor is refused: the hierarchical step hands out no per-sample gradients"
-    return None
+    f = flags_of(args)
+    n, w = f.n_importance, f.coarse_weight
+    return _refusal(
+        (n < 0, "--n-importance must be >= 0 (0: off)"),
+        (w is not None and not w >= 0.0, "--coarse-weight must be >= 0"),
+        (n == 0 and w is not None, "--coarse-weight needs --n-importance N (N > 0): without the hierarchical step the flag would be ignored"),
+        (n > 0 and f.recipe == "multiscale", "--n-importance with --recipe multiscale is refused: the regulariser, the depth term and the density "
+                                             "noise are not part of the hierarchical step"),
+        (n > 0 and f.grid_given, "--n-importance is not combined with --occupancy-*: the hierarchical step runs under no grid"),
+        (n > 0 and f.train_extractor, "--n-importance with --train-extractor is refused: the hierarchical step hands out no per-sample gradients"))
 
 
 def ray_reg_args_error(args):
     """Why --dist-weight / --occ-weight / --occ-samples cannot run with these arguments (None: they can, or none was given).  Decided
     before any GPU work, like hierarchical_args_error."""
-    dw, ow = float(getattr(args, "dist_weight", 0.0) or 0.0), float(getattr(args, "occ_weight", 0.0) or 0.0)
-    k = getattr(args, "occ_samples", None)
-    if not (dw >= 0.0 and ow >= 0.0 and math.isfinite(dw) and math.isfinite(ow)):
-        return "--dist-weight and --occ-weight must be finite and >= 0 (0: off)"
-    if ow > 0.0 and (k is None or int(k) < 1):
-        return "--occ-weight needs --occ-samples K (K >= 1): the number of samples at the front of every ray the penalty covers"
-    if ow == 0.0 and k is not None:
-        return "--occ-samples needs --occ-weight W (W > 0): without the occlusion term the flag would be ignored"
-    if (dw > 0.0 or ow > 0.0) and int(getattr(args, "n_importance", 0) or 0) > 0:
-        return "--dist-weight / --occ-weight with --n-importance is refused: the hierarchical step takes the plain rgb loss"
-    return None
+    f = flags_of(args)
+    dw, ow, k = f.dist_weight, f.occ_weight, f.occ_samples
+    return _refusal(
+        (not _finite(dw, ow), "--dist-weight and --occ-weight must be finite and >= 0 (0: off)"),
+        (ow > 0.0 and (k is None or k < 1),
+         "--occ-weight needs --occ-samples K (K >= 1): the number of samples at the front of every ray the penalty covers"),
+        (ow == 0.0 and k is not None, "--occ-samples needs --occ-weight W (W > 0): without the occlusion term the flag would be ignored"),
+        ((dw > 0.0 or ow > 0.0) and f.hierarchical,
+         "--dist-weight / --occ-weight with --n-importance is refused: the hierarchical step takes the plain rgb loss"))
 
 
 def ray_reg_options(args, near, far):
     """FusedStep's keywords of --dist-weight / --occ-weight / --occ-samples ({} when both are off); dist_span = far - near, so that the
     per-sample route (`step(points, z_vals, ...)`, which has no near / far) scales the midpoints as the ray routes do."""
-    dw, ow = float(getattr(args, "dist_weight", 0.0) or 0.0), float(getattr(args, "occ_weight", 0.0) or 0.0)
-    if dw == 0.0 and ow == 0.0:
+    f = flags_of(args)
+    if f.dist_weight == 0.0 and f.occ_weight == 0.0:
         return {}
-    return dict(dist_weight=dw, occ_weight=ow, occ_samples=int(getattr(args, "occ_samples", None) or 0), dist_span=float(far) - float(near))
+    return dict(dist_weight=f.dist_weight, occ_weight=f.occ_weight, occ_samples=f.occ_samples or 0, dist_span=float(far) - float(near))
 
 
 def patch_reg_args_error(args):
     """Why --depth-smooth-weight and its companions cannot run with these arguments (None: they can, or the weight is 0).  Decided
     before a config or a data set is read, like ray_reg_args_error."""
-    w = float(getattr(args, "depth_smooth_weight", 0.0) or 0.0)
-    if not (w >= 0.0 and math.isfinite(w)):
+    f = flags_of(args)
+    if not _finite(f.depth_smooth_weight):
         return "--depth-smooth-weight must be finite and >= 0 (0: off)"
-    if w == 0.0:
-        return None
-    return patch_draw_error(args, "--depth-smooth-weight")
+    return patch_draw_error(f, "--depth-smooth-weight") if f.depth_smooth_weight > 0.0 else None
 
 
 def patch_draw_error(args, flag):
     """Why the trainer cannot draw patches for `flag` (--depth-smooth-weight, --kl-weight, --entropy-unseen) with these arguments."""
-    P, n, k = (getattr(args, a, d) for a, d in (("patch_size", 8), ("patches_per_step", 16), ("patch_stride", 1)))
-    if not 2 <= int(P) <= 16:
-        return "--patch-size must be in 2 ... 16"
-    if int(n) < 1:
-        return "--patches-per-step must be >= 1"
-    if int(k) < 1:
-        return "--patch-stride must be >= 1"
-    if int(getattr(args, "n_importance", 0) or 0) > 0:
-        return f"{flag} with --n-importance is refused: the hierarchical step takes the plain rgb loss"
-    if getattr(args, "fused_inputs", False):
-        return f"{flag} with --fused-inputs is refused: a view step has one pose, the patches come from poses of their own"
-    if int(getattr(args, "occupancy_res", 0) or 0) or getattr(args, "occupancy_per_view", False) or any(
-            getattr(args, f, None) is not None for f in OCCUPANCY_FLAGS):
-        return f"{flag} is not combined with --occupancy-*: the trainer's grid route steps view by view"
-    if getattr(args, "train_extractor", False):
-        return f"{flag} with --train-extractor is refused: the patch rays belong to no view whose map could take their gradient"
-    return None
+    f = flags_of(args)
+    return _refusal(
+        (not 2 <= f.patch_size <= 16, "--patch-size must be in 2 ... 16"),
+        (f.patches_per_step < 1, "--patches-per-step must be >= 1"),
+        (f.patch_stride < 1, "--patch-stride must be >= 1"),
+        (f.hierarchical, f"{flag} with --n-importance is refused: the hierarchical step takes the plain rgb loss"),
+        (f.fused_inputs, f"{flag} with --fused-inputs is refused: a view step has one pose, the patches come from poses of their own"),
+        (f.grid_given, f"{flag} is not combined with --occupancy-*: the trainer's grid route steps view by view"),
+        (f.train_extractor, f"{flag} with --train-extractor is refused: the patch rays belong to no view whose map could take their gradient"))
 
 
 def info_reg_args_error(args):
     """Why --entropy-weight / --entropy-threshold / --entropy-unseen / --kl-weight cannot run with these arguments (None: they can, or
     none was given).  Decided before a config or a data set is read: the entropy flag has --dist-weight's refusals, the KL flag and
     --entropy-unseen, which draw patches, --depth-smooth-weight's."""
-    ew, kw = float(getattr(args, "entropy_weight", 0.0) or 0.0), float(getattr(args, "kl_weight", 0.0) or 0.0)
-    th = getattr(args, "entropy_threshold", None)
-    unseen = bool(getattr(args, "entropy_unseen", False))
-    if not (ew >= 0.0 and kw >= 0.0 and math.isfinite(ew) and math.isfinite(kw)):
-        return "--entropy-weight and --kl-weight must be finite and >= 0 (0: off)"
-    if th is not None and not (float(th) >= 0.0 and math.isfinite(float(th))):
-        return "--entropy-threshold must be finite and >= 0"
-    if th is not None and ew == 0.0 and kw == 0.0:
-        return "--entropy-threshold needs --entropy-weight or --kl-weight: without either term the flag would be ignored"
-    if unseen and ew == 0.0:
-        return "--entropy-unseen needs --entropy-weight W (W > 0): it draws patches of unseen poses for the entropy term"
-    if ew > 0.0 and int(getattr(args, "n_importance", 0) or 0) > 0:
-        return "--entropy-weight with --n-importance is refused: the hierarchical step takes the plain rgb loss"
-    if kw > 0.0:
-        return patch_draw_error(args, "--kl-weight")
-    if unseen:
-        return patch_draw_error(args, "--entropy-unseen")
-    return None
+    f = flags_of(args)
+    ew, kw, th, unseen = f.entropy_weight, f.kl_weight, f.entropy_threshold, f.entropy_unseen
+    problem = _refusal(
+        (not _finite(ew, kw), "--entropy-weight and --kl-weight must be finite and >= 0 (0: off)"),
+        (th is not None and not _finite(th), "--entropy-threshold must be finite and >= 0"),
+        (th is not None and ew == 0.0 and kw == 0.0,
+         "--entropy-threshold needs --entropy-weight or --kl-weight: without either term the flag would be ignored"),
+        (unseen and ew == 0.0, "--entropy-unseen needs --entropy-weight W (W > 0): it draws patches of unseen poses for the entropy term"),
+        (ew > 0.0 and f.hierarchical, "--entropy-weight with --n-importance is refused: the hierarchical step takes the plain rgb loss"))
+    if problem or not (kw > 0.0 or unseen):
+        return problem
+    return patch_draw_error(f, "--kl-weight" if kw > 0.0 else "--entropy-unseen")
 
 
 def info_reg_options(args):
     """FusedStep's keywords of --entropy-weight / --entropy-threshold / --kl-weight ({} when both weights are 0); patch_size with them
     when the step draws patches for these terms alone (--depth-smooth-weight hands it over itself)."""
-    ew, kw = float(getattr(args, "entropy_weight", 0.0) or 0.0), float(getattr(args, "kl_weight", 0.0) or 0.0)
-    if ew == 0.0 and kw == 0.0:
+    f = flags_of(args)
+    if f.entropy_weight == 0.0 and f.kl_weight == 0.0:
         return {}
-    th = getattr(args, "entropy_threshold", None)
-    out = dict(ent_weight=ew, ent_threshold=0.01 if th is None else float(th), kl_weight=kw)
-    if draws_patches(args) and not float(getattr(args, "depth_smooth_weight", 0.0) or 0.0) > 0.0:
-        out["patch_size"] = int(getattr(args, "patch_size", 8))
+    out = dict(ent_weight=f.entropy_weight, ent_threshold=0.01 if f.entropy_threshold is None else f.entropy_threshold, kl_weight=f.kl_weight)
+    if f.draws_patches and not f.depth_smooth_weight > 0.0:
+        out["patch_size"] = f.patch_size
     return out
 
 
 def draws_patches(args):
     """Whether every batch gets patches of unseen poses behind its supervised rays: --depth-smooth-weight, --kl-weight, or
     --entropy-weight with --entropy-unseen."""
-    return (float(getattr(args, "depth_smooth_weight", 0.0) or 0.0) > 0.0 or float(getattr(args, "kl_weight", 0.0) or 0.0) > 0.0
-            or (float(getattr(args, "entropy_weight", 0.0) or 0.0) > 0.0 and bool(getattr(args, "entropy_unseen", False))))
+    return flags_of(args).draws_patches
 
 
 def patch_reg_options(args):
     """FusedStep's keywords of --depth-smooth-weight / --patch-size ({} when off)."""
-    w = float(getattr(args, "depth_smooth_weight", 0.0) or 0.0)
-    return dict(depth_smooth_weight=w, patch_size=int(getattr(args, "patch_size", 8))) if w > 0.0 else {}
+    f = flags_of(args)
+    return dict(depth_smooth_weight=f.depth_smooth_weight, patch_size=f.patch_size) if f.depth_smooth_weight > 0.0 else {}
 
 
 def freq_reg_args_error(args):
     """Why --freq-reg-end / --no-freq-reg-dirs cannot run with these arguments (None: they can, or neither was given).  The mask
     goes with every recipe and route: it lives in the re-pack and the weight gradients, which all of them share."""
-    n = getattr(args, "freq_reg_end", 0) or 0
-    if int(n) < 0:
-        return "--freq-reg-end must be >= 0 (0: off)"
-    if int(n) == 0 and getattr(args, "no_freq_reg_dirs", False):
-        return "--no-freq-reg-dirs needs --freq-reg-end N (N > 0): without the frequency mask the flag would be ignored"
-    return None
+    f = flags_of(args)
+    return _refusal(
+        (f.freq_reg_end < 0, "--freq-reg-end must be >= 0 (0: off)"),
+        (f.freq_reg_end == 0 and f.no_freq_reg_dirs,
+         "--no-freq-reg-dirs needs --freq-reg-end N (N > 0): without the frequency mask the flag would be ignored"))
 
 
 def freq_reg_options(args):
     """FusedStep's keywords of --freq-reg-end / --no-freq-reg-dirs ({} when off)."""
-    n = int(getattr(args, "freq_reg_end", 0) or 0)
-    return dict(freq_reg_end=n, freq_reg_dirs=not getattr(args, "no_freq_reg_dirs", False)) if n > 0 else {}
-
-
-OCCUPANCY_FLAGS = ("occupancy_box", "occupancy_threshold", "occupancy_decay", "occupancy_refresh_every", "occupancy_cells_per_refresh",
-                   "occupancy_warmup")
+    f = flags_of(args)
+    return dict(freq_reg_end=f.freq_reg_end, freq_reg_dirs=not f.no_freq_reg_dirs) if f.freq_reg_end > 0 else {}
 
 
 def occupancy_args_error(args, cfg):
     """Why the --occupancy-* arguments cannot run with these arguments / this config (None: they can, or none was given).
-    Decided before any GPU work."""
-    res = int(getattr(args, "occupancy_res", 0) or 0)
-    given = [f for f in OCCUPANCY_FLAGS if getattr(args, f, None) is not None]
-    per_view = bool(getattr(args, "occupancy_per_view", False))
+    Decided before any GPU work.  The values of the OCCUPANCY_FLAGS are read last, once a grid is known to be asked for and allowed."""
+    f = flags_of(args)
+    res, per_view = f.occupancy_res, f.occupancy_per_view
     use_dino = bool((cfg.get("model", {}) or {}).get("use_dino", True))
-    if per_view and res == 0:
-        return "--occupancy-per-view needs --occupancy-res N (N > 0): without a grid the flag would be ignored"
-    if per_view and not use_dino:
-        return ("--occupancy-per-view: this config has use_dino: false -- such a field does not depend on the view, the single grid of "
-                "--occupancy-res serves every batch")
-    if res == 0:
-        if given:
-            return "--" + given[0].replace("_", "-") + " needs --occupancy-res N (N > 0): without a grid the flag would be ignored"
-        return None
-    if res < 32 or res > 512 or res % 32:
-        return "--occupancy-res must be a multiple of 32 in 32..512 (0: off)"
-    if use_dino and not per_view:
-        return ("--occupancy-res: this config has use_dino: true -- a grid of such a field belongs to ONE source view, the batches of a run "
-                "condition on the view they came from")
-    if getattr(args, "train_extractor", False) and not per_view:
-        return "--occupancy-res with --train-extractor is refused: a step under a grid hands out no per-sample gradients"
-    box = args.occupancy_box
-    if box is not None and not (box[0] < box[1]):
+    problem = _refusal(
+        (per_view and res == 0, "--occupancy-per-view needs --occupancy-res N (N > 0): without a grid the flag would be ignored"),
+        (per_view and not use_dino, "--occupancy-per-view: this config has use_dino: false -- such a field does not depend on the view, the "
+                                    "single grid of --occupancy-res serves every batch"),
+        (res == 0 and f.grid_flags, "--" + "".join(f.grid_flags[:1]).replace("_", "-") + " needs --occupancy-res N (N > 0): without a grid "
+                                    "the flag would be ignored"),
+        (res != 0 and (res < 32 or res > 512 or res % 32), "--occupancy-res must be a multiple of 32 in 32..512 (0: off)"),
+        (res != 0 and use_dino and not per_view, "--occupancy-res: this config has use_dino: true -- a grid of such a field belongs to ONE source "
+                                                 "view, the batches of a run condition on the view they came from"),
+        (res != 0 and f.train_extractor and not per_view,
+         "--occupancy-res with --train-extractor is refused: a step under a grid hands out no per-sample gradients"))
+    if problem or res == 0:
+        return problem
+    if f.occupancy_box is not None and not (f.occupancy_box[0] < f.occupancy_box[1]):      # (fields without a default, read one at a time: not for _refusal)
         return "--occupancy-box LO HI needs LO < HI"
-    if args.occupancy_decay is not None and not (0.0 <= args.occupancy_decay <= 1.0):
+    if f.occupancy_decay is not None and not (0.0 <= f.occupancy_decay <= 1.0):
         return "--occupancy-decay must be in [0, 1]"
-    if args.occupancy_refresh_every is not None and args.occupancy_refresh_every < 1:
+    if f.occupancy_refresh_every is not None and f.occupancy_refresh_every < 1:
         return "--occupancy-refresh-every must be >= 1"
-    c = args.occupancy_cells_per_refresh
+    c = f.occupancy_cells_per_refresh
     if c is not None and (c < 32 or c % 32):
         return "--occupancy-cells-per-refresh must be a positive multiple of 32"
-    if args.occupancy_warmup is not None and args.occupancy_warmup < 0:
-        return "--occupancy-warmup must be >= 0"
-    return None
+    return "--occupancy-warmup must be >= 0" if f.occupancy_warmup is not None and f.occupancy_warmup < 0 else None
+
+
+# main's refusals, in the order they are reported: those of the flags alone, decided before the config is read, then those that read it
+FLAG_CHECKS = (hierarchical_args_error, ray_reg_args_error, patch_reg_args_error, info_reg_args_error, freq_reg_args_error)
+CONFIG_CHECKS = (extractor_args_error, occupancy_args_error)
+
+
+def _grid_keywords(f):
+    """OccupancySchedule's keywords of the --occupancy-* flags that were given (the others keep its defaults)."""
+    kw = dict(box=f.occupancy_box, threshold=f.occupancy_threshold, decay=f.occupancy_decay, refresh_every=f.occupancy_refresh_every,
+              cells_per_refresh=f.occupancy_cells_per_refresh, warmup=f.occupancy_warmup)
+    return {k: v for k, v in kw.items() if v is not None}
 
 
 class OccupancySchedule:
@@ -415,10 +432,8 @@ class OccupancySchedule:
 
     @classmethod
     def from_args(cls, args, device):
-        kw = {k: v for k, v in dict(box=args.occupancy_box, threshold=args.occupancy_threshold, decay=args.occupancy_decay,
-                                    refresh_every=args.occupancy_refresh_every, cells_per_refresh=args.occupancy_cells_per_refresh,
-                                    warmup=args.occupancy_warmup).items() if v is not None}
-        return cls(args.occupancy_res, device=device, **kw)
+        f = flags_of(args)
+        return cls(f.occupancy_res, device=device, **_grid_keywords(f))
 
     def current(self):
         """The grid of the next step: all ones until the warm-up is over."""
@@ -462,10 +477,8 @@ class PerViewOccupancy:
 
     @classmethod
     def from_args(cls, args, n_views, device):
-        kw = {k: v for k, v in dict(box=args.occupancy_box, threshold=args.occupancy_threshold, decay=args.occupancy_decay,
-                                    refresh_every=args.occupancy_refresh_every, cells_per_refresh=args.occupancy_cells_per_refresh,
-                                    warmup=args.occupancy_warmup).items() if v is not None}
-        return cls(n_views, args.occupancy_res, device=device, **kw)
+        f = flags_of(args)
+        return cls(n_views, f.occupancy_res, device=device, **_grid_keywords(f))
 
     def view(self, v):
         return self.views[v]
@@ -530,6 +543,78 @@ class ExtractorTrainer:
         self.map = self.d_map = None
 
 
+# ---- one epoch ------------------------------------------------------------------------------------------------------------------
+def _epoch_route(model, occupancy, extractor, fused_inputs, n_importance, patches, draws):
+    """train_epoch's combination checks; returns (whether the batches run on the fused-input route, whether `occupancy` holds one
+    grid per view)."""
+    use_dino, per_view = model.net == L.NRF_NET_V3, isinstance(occupancy, PerViewOccupancy)
+    grid, fused = occupancy is not None, fused_inputs or occupancy is not None or n_importance > 0
+    problem = _refusal(
+        (per_view and not use_dino, "per-view occupancy grids belong to use_dino models: the other fields do not depend on the view"),
+        (grid and not per_view and (use_dino or extractor is not None),
+         "training under an occupancy grid is not combined with use_dino models or a trained extractor"),
+        (n_importance > 0 and (grid or extractor is not None), "the hierarchical step is not combined with an occupancy grid or a trained extractor"),
+        (patches is not None and (fused or extractor is not None),
+         "patches go with the staged route alone: not with fused_inputs, an occupancy grid, the hierarchical step or a trained extractor"),
+        (patches is not None and draws is not None, "patches are not combined with draws: a recorded run holds no jitter for the patch rays"))
+    if problem:
+        raise ValueError(problem)
+    return fused, per_view
+
+
+def _view_batch(ep, vw, idx, t_rand, seed):
+    """One batch of the fused-input route: one `step.step_view` (or `step_view_hierarchical`) on the pixel ids `idx` of the view `vw`,
+    under the view's grid when there is one, then the grid's and the extractor's share.  Returns (loss, ray-samples)."""
+    step, extractor, S = ep.step, ep.extractor, ep.S
+    n = idx.shape[0]
+    kw = dict(dino=vw.dino, seed=seed, target=vw.tgt[idx])
+    if extractor is not None:
+        d_feats = extractor.feats_grad_buffer(n * S, int(vw.view_map.shape[-1]))
+        if ep.pts_buf is None or ep.pts_buf.shape[0] < n * S:
+            ep.pts_buf = torch.empty((n * S, 3), dtype=torch.float32, device=vw.tgt.device)
+        kw.update(d_dino_out=d_feats, points_out=ep.pts_buf[:n * S])
+    if vw.sched is not None:
+        kw["occupancy"] = vw.sched.current()
+    if ep.per_view:
+        kw["grid_inputs"] = "rays"
+    if ep.Ni > 0:
+        loss = step.step_view_hierarchical(None, vw.c2w, ep.Ht, ep.Wt, vw.f_t, idx, ep.near, ep.far, S, ep.Ni, perturb=True, t_rand=t_rand,
+                                           coarse_weight=ep.coarse_weight, **kw)
+    else:
+        loss = step.step_view(None, vw.c2w, ep.Ht, ep.Wt, vw.f_t, idx, ep.near, ep.far, S, perturb=True, t_rand=t_rand, **kw)
+    if vw.sched is not None:
+        vw.sched.after_step(step.model, dino=vw.cam if ep.per_view else None)
+    if extractor is not None:
+        rows = step.last_count if ep.per_view else n * S          # under a grid: the kept samples, as dense rows
+        if rows:
+            extractor.add_batch(vw.cam, ep.pts_buf[:rows], d_feats[:rows])
+    return loss, n * (S + ep.Ni)
+
+
+def _staged_batch(ep, vw, idx, t_rand, seed):
+    """One batch of the staged route: torch gathers, sample_points_along_rays, the expanded directions and fetch_features in front of
+    one `step(...)`, the patches of unseen poses behind the supervised rays when the epoch draws them.  Returns (loss, ray-samples)."""
+    step, extractor, S = ep.step, ep.extractor, ep.S
+    o, d, t = vw.ro[idx], vw.rd[idx], vw.tgt[idx]
+    n_p = 0
+    if ep.patches is not None:
+        n_p = int(ep.patches["n"])
+        pp = sample_patch_poses(ep.train_poses, n_p, ep.patches["generator"]).to(o.device)
+        o_p, d_p = patch_rays(ep.Ht, ep.Wt, ep.f_s, pp, step.patch_size, ep.patches["generator"], ep.patches["stride"])
+        o, d = torch.cat([o, o_p]), torch.cat([d, d_p])
+    pts, z = sample_points_along_rays(o, d, ep.near, ep.far, S, perturb=True, t_rand=t_rand, seed=seed)
+    n = o.shape[0]
+    dirs = d[:, None, :].expand(n, S, 3).reshape(-1, 3)                         # train.py:225: raw ray directions per sample
+    feats = fetch_features(vw.dino, pts.reshape(-1, 3)) if ep.use_dino else None
+    if extractor is not None:
+        d_feats = extractor.feats_grad_buffer(n * S, feats.shape[1])
+        loss = step(pts.reshape(-1, 3), z, d, t, dirs=dirs, dino=feats, d_dino_out=d_feats)
+        extractor.add_batch(vw.cam, pts.reshape(-1, 3), d_feats)
+    else:
+        loss = step(pts.reshape(-1, 3), z, d, t, dirs=dirs, dino=feats, **({"n_patches": n_p} if n_p else {}))
+    return loss, n * S
+
+
 def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, dino_maps=None, max_batches=None, rank=0, world=1,
                 extractor=None, fused_inputs=False, occupancy=None, draws=None, n_importance=0, coarse_weight=1.0, patches=None):
     """One pass of train.py:261-290 over the training views; returns (mean loss, ray-samples processed).
@@ -553,39 +638,27 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
     takes rays rank, rank+world, ... of each batch -- the batches are those of one process (the stratified jitter of a ray is
     keyed by its position inside the call, so the sample depths differ from a single-process run's)."""
     Ht, Wt, S, batch = schedule_for(cfg, epoch)
-    model = step.model
-    use_dino = model.net == L.NRF_NET_V3
-    per_view = isinstance(occupancy, PerViewOccupancy)
-    if occupancy is not None:
-        if per_view and not use_dino:
-            raise ValueError("per-view occupancy grids belong to use_dino models: the other fields do not depend on the view")
-        if not per_view and (use_dino or extractor is not None):
-            raise ValueError("training under an occupancy grid is not combined with use_dino models or a trained extractor")
-        fused_inputs = True
-    Ni = int(n_importance)
-    if Ni > 0:
-        if occupancy is not None or extractor is not None:
-            raise ValueError("the hierarchical step is not combined with an occupancy grid or a trained extractor")
-        fused_inputs = True
-    if patches is not None and (fused_inputs or occupancy is not None or Ni > 0 or extractor is not None):
-        raise ValueError("patches go with the staged route alone: not with fused_inputs, an occupancy grid, the hierarchical step or a trained extractor")
-    if patches is not None and draws is not None:
-        raise ValueError("patches are not combined with draws: a recorded run holds no jitter for the patch rays")
-    train_poses = torch.stack([p.detach().cpu() for p in poses]) if patches is not None else None      # what the unseen poses are drawn around
+    use_dino = step.model.net == L.NRF_NET_V3
+    fused_inputs, per_view = _epoch_route(step.model, occupancy, extractor, fused_inputs, int(n_importance), patches, draws)
+    run_batch = _view_batch if fused_inputs else _staged_batch
+    # what every batch of the epoch reads; pts_buf: the fused route's sample positions for the extractor, grown when a batch needs more
+    ep = SimpleNamespace(step=step, extractor=extractor, per_view=per_view, use_dino=use_dino, patches=patches, Ht=Ht, Wt=Wt, S=S,
+                         Ni=int(n_importance), near=near, far=far, coarse_weight=coarse_weight, pts_buf=None,
+                         train_poses=torch.stack([p.detach().cpu() for p in poses]) if patches is not None else None,      # what the unseen poses are drawn around
+                         f_s=focal if (Ht, Wt) == (H, W) else focal * (Ht / H))      # the focal length of the schedule's rays (view_target)
     total, n_batches, samples = None, 0, 0
-    pts_buf = None
-    f_s = focal if (Ht, Wt) == (H, W) else focal * (Ht / H)                    # the focal length of the schedule's rays (view_target)
     for v in range(len(images)):
+        vw = SimpleNamespace()                            # what the view's batches read
         if fused_inputs:
-            tgt, f_t = view_target(images[v], H, W, focal, Ht, Wt)
-            n_view, dev_v, c2w = Ht * Wt, tgt.device, _c2w12(poses[v])              # the camera of the view's batches, converted once
+            vw.tgt, vw.f_t = view_target(images[v], H, W, focal, Ht, Wt)
+            n_view, dev_v, vw.c2w = Ht * Wt, vw.tgt.device, _c2w12(poses[v])        # the camera of the view's batches, converted once
         else:
-            ro, rd, tgt = view_rays(images[v], poses[v], H, W, focal, Ht, Wt)
-            n_view, dev_v = ro.shape[0], ro.device
-        view_map = extractor.begin_view(v) if extractor is not None else (dino_maps[v:v + 1] if use_dino else None)
-        dino = make_dino(view_map, poses[v], focal, H, W) if use_dino else None                 # train.py:204-206: full-resolution intrinsics
-        cam = dict(features=view_map, pose=poses[v], focal=focal, H=H, W=W)
-        sched = occupancy.view(v) if per_view else occupancy
+            vw.ro, vw.rd, vw.tgt = view_rays(images[v], poses[v], H, W, focal, Ht, Wt)
+            n_view, dev_v = vw.ro.shape[0], vw.ro.device
+        vw.view_map = extractor.begin_view(v) if extractor is not None else (dino_maps[v:v + 1] if use_dino else None)
+        vw.dino = make_dino(vw.view_map, poses[v], focal, H, W) if use_dino else None           # train.py:204-206: full-resolution intrinsics
+        vw.cam = dict(features=vw.view_map, pose=poses[v], focal=focal, H=H, W=W)
+        vw.sched = occupancy.view(v) if per_view else occupancy
         if draws is None:
             order = torch.randperm(n_view, device=dev_v, generator=gen)
         else:
@@ -597,58 +670,10 @@ def train_epoch(step, cfg, epoch, images, poses, H, W, focal, near, far, gen, di
                 if idx.shape[0] == 0:
                     continue
             t_rand = None if draws is None else draws.jitter(v, i, idx.shape[0], S)
-            if fused_inputs:
-                n = idx.shape[0]
-                kw = dict(dino=dino, seed=epoch * 1_000_003 + v * 10_007 + i, target=tgt[idx])
-                if extractor is not None:
-                    d_feats = extractor.feats_grad_buffer(n * S, int(view_map.shape[-1]))
-                    if pts_buf is None or pts_buf.shape[0] < n * S:
-                        pts_buf = torch.empty((n * S, 3), dtype=torch.float32, device=tgt.device)
-                    kw.update(d_dino_out=d_feats, points_out=pts_buf[:n * S])
-                if occupancy is not None:
-                    kw["occupancy"] = sched.current()
-                if per_view:
-                    kw["grid_inputs"] = "rays"
-                if Ni > 0:
-                    loss = step.step_view_hierarchical(None, c2w, Ht, Wt, f_t, idx, near, far, S, Ni, perturb=True, t_rand=t_rand,
-                                                       coarse_weight=coarse_weight, **kw)
-                else:
-                    loss = step.step_view(None, c2w, Ht, Wt, f_t, idx, near, far, S, perturb=True, t_rand=t_rand, **kw)
-                if occupancy is not None:
-                    sched.after_step(model, dino=cam if per_view else None)
-                if extractor is not None:
-                    rows = step.last_count if per_view else n * S          # under a grid: the kept samples, as dense rows
-                    if rows:
-                        extractor.add_batch(cam, pts_buf[:rows], d_feats[:rows])
-                total = loss if total is None else total + loss
-                n_batches += 1
-                samples += n * (S + Ni)
-                if max_batches is not None and n_batches >= max_batches:
-                    if extractor is not None:
-                        extractor.end_view()
-                    return float(total) / n_batches, samples
-                continue
-            o, d, t = ro[idx], rd[idx], tgt[idx]
-            n_p = 0
-            if patches is not None:
-                from .ray_sampler import patch_rays, sample_patch_poses
-                n_p = int(patches["n"])
-                pp = sample_patch_poses(train_poses, n_p, patches["generator"]).to(o.device)
-                o_p, d_p = patch_rays(Ht, Wt, f_s, pp, step.patch_size, patches["generator"], patches["stride"])
-                o, d = torch.cat([o, o_p]), torch.cat([d, d_p])
-            pts, z = sample_points_along_rays(o, d, near, far, S, perturb=True, t_rand=t_rand, seed=epoch * 1_000_003 + v * 10_007 + i)
-            n = o.shape[0]
-            dirs = d[:, None, :].expand(n, S, 3).reshape(-1, 3)                         # train.py:225: raw ray directions per sample
-            feats = fetch_features(dino, pts.reshape(-1, 3)) if use_dino else None
-            if extractor is not None:
-                d_feats = extractor.feats_grad_buffer(n * S, feats.shape[1])
-                loss = step(pts.reshape(-1, 3), z, d, t, dirs=dirs, dino=feats, d_dino_out=d_feats)
-                extractor.add_batch(cam, pts.reshape(-1, 3), d_feats)
-            else:
-                loss = step(pts.reshape(-1, 3), z, d, t, dirs=dirs, dino=feats, **({"n_patches": n_p} if n_p else {}))
+            loss, done = run_batch(ep, vw, idx, t_rand, epoch * 1_000_003 + v * 10_007 + i)
             total = loss if total is None else total + loss
             n_batches += 1
-            samples += n * S
+            samples += done
             if max_batches is not None and n_batches >= max_batches:
                 if extractor is not None:
                     extractor.end_view()                                                # step with what has been accumulated
@@ -712,7 +737,8 @@ def resume_from(ckpt, model, step):
     return start, best
 
 
-def main(argv=None):
+# ---- the command, phase by phase ------------------------------------------------------------------------------------------------
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", required=True)
     ap.add_argument("--data", required=True, help="dataset directory holding transforms_train.json / transforms_test.json")
@@ -788,128 +814,167 @@ def main(argv=None):
     ap.add_argument("--rehearse", action="store_true",
                     help="--data-parallel on a box with ONE GPU: every rank on cuda:0, the gradient all-reduce over gloo through host memory "
                          "(RCCL refuses two ranks on one card); exercises the sharding and the collective, not multi-GPU speed")
-    args = ap.parse_args(argv)
-    problem = (hierarchical_args_error(args) or ray_reg_args_error(args) or patch_reg_args_error(args) or info_reg_args_error(args) or freq_reg_args_error(args) or extractor_args_error(args, load_config(args.config))
-               or occupancy_args_error(args, load_config(args.config)))
+    return ap
+
+
+def refuse(f):
+    """SystemExit with the first refusal of FLAG_CHECKS, then of CONFIG_CHECKS; returns the config, which is read here, once."""
+    problem = next(filter(None, (check(f) for check in FLAG_CHECKS)), None)
+    cfg = None if problem else load_config(f.config)
+    problem = problem or next(filter(None, (check(f, cfg) for check in CONFIG_CHECKS)), None)
     if problem:
         raise SystemExit(problem)
-    rank, world = 0, 1
-    if args.data_parallel:
-        import torch.distributed as dist
-        local = 0 if args.rehearse else int(os.environ.get("LOCAL_RANK", "0"))
-        torch.cuda.set_device(local)
-        if not dist.is_initialized():
-            if args.rehearse:
-                dist.init_process_group(backend="gloo")
-            else:
-                dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local))
-        rank, world = dist.get_rank(), dist.get_world_size()
+    return cfg
 
-    torch.manual_seed(args.seed)                          # parameter init (when no checkpoint is given) and the ray shuffles
-    cfg = load_config(args.config)
-    rs = render_settings(cfg)
-    out_dir = args.out or cfg["output"]["save_dir"]
-    epochs = args.epochs if args.epochs is not None else int(cfg["training"]["epochs"])
-    name = cfg.get("experiment", {}).get("name", "run")
+
+@contextlib.contextmanager
+def distributed(f):
+    """(rank, world) of this process: (0, 1), or under --data-parallel those of the process group, open for the length of the block."""
+    if not f.data_parallel:
+        yield 0, 1
+        return
+    import torch.distributed as dist
+    local = 0 if f.rehearse else int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local)
+    if not dist.is_initialized():
+        dist.init_process_group(**(dict(backend="gloo") if f.rehearse else dict(backend="nccl", device_id=torch.device("cuda", local))))
+    yield dist.get_rank(), dist.get_world_size()
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def load_scene(f, cfg):
+    """The run record, with what --data holds: dev, the training views on it (images, poses, H, W, focal) and the test views (test_images,
+    test_poses).  `main` adds the rest, each field where the phase that makes it returns: rank, world, out_dir, name; dino_maps, ext;
+    model, step; gen, patches, occ, first_epoch, best; targets, eval_dino."""
     res = cfg["data"].get("resolution")
-    images, poses, (H, W, focal) = load_blender_data(args.data, "train", img_size=res)
+    images, poses, (H, W, focal) = load_blender_data(f.data, "train", img_size=res)
     nv = cfg["data"].get("num_views")
     if nv:
         images, poses = images[:nv], poses[:nv]                                          # train.py:141-143
     dev = torch.device("cuda", torch.cuda.current_device())
     images = [im.permute(1, 2, 0).float().to(dev) for im in images]
     poses = [p.float() for p in poses]
-    test_images, test_poses, _ = load_blender_data(args.data, "test", img_size=res)
-    if args.max_test_views:
-        test_images, test_poses = test_images[: args.max_test_views], test_poses[: args.max_test_views]
+    test_images, test_poses, _ = load_blender_data(f.data, "test", img_size=res)
+    if f.max_test_views:
+        test_images, test_poses = test_images[: f.max_test_views], test_poses[: f.max_test_views]
+    return SimpleNamespace(dev=dev, images=images, poses=poses, H=H, W=W, focal=focal, test_images=test_images, test_poses=test_poses)
 
-    use_dino = bool(cfg.get("model", {}).get("use_dino", True))
-    dino_maps, dino_dim, ext = None, 64, None
-    if use_dino:
-        if args.dino_maps:
-            dino_maps = torch.load(args.dino_maps, map_location="cpu", weights_only=True).float().to(dev)
-        elif args.dino_weights or args.dino_random_init:
-            extractor = dino_model_from_config(cfg, weights=args.dino_weights).to(dev)           # train.py:57-75
-            dino_maps = precompute_dino_features(extractor, torch.stack(images)[..., :3]).float()   # train.py:158-169: once, under no_grad
-            if args.train_extractor:
-                o = cfg["optimizer"]
-                ext = ExtractorTrainer(extractor, torch.stack(images)[..., :3], float(o["lr"]), float(o["weight_decay"]))
-            del extractor
-        else:
-            raise SystemExit("this config conditions on DINO features: pass --dino-weights <local Dinov2Model checkpoint> (or --dino-random-init), "
-                             "or --dino-maps <tensor (V,Hp,Wp,C) saved with torch.save>, one map per training view")
-        if dino_maps.dim() != 4 or dino_maps.shape[0] < len(images):
-            raise SystemExit("--dino-maps must hold one (Hp,Wp,C) map per training view")
-        dino_dim = int(dino_maps.shape[-1])
-    model = model_from_config(cfg, dino_dim=dino_dim, mma_mode=args.mode)
-    ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=True) if args.checkpoint else None
+
+def dino_source(f, cfg, run):
+    """(maps (V,Hp,Wp,C), their channel count, ExtractorTrainer or None) of a use_dino config -- --dino-maps, or the config's extractor
+    run once over the training views (and kept, under --train-extractor); (None, 64, None) otherwise."""
+    if not bool(cfg.get("model", {}).get("use_dino", True)):
+        return None, 64, None
+    ext = None
+    if f.dino_maps:
+        dino_maps = torch.load(f.dino_maps, map_location="cpu", weights_only=True).float().to(run.dev)
+    elif f.dino_weights or f.dino_random_init:
+        extractor = dino_model_from_config(cfg, weights=f.dino_weights).to(run.dev)           # train.py:57-75
+        dino_maps = precompute_dino_features(extractor, torch.stack(run.images)[..., :3]).float()   # train.py:158-169: once, under no_grad
+        if f.train_extractor:
+            ext = ExtractorTrainer(extractor, torch.stack(run.images)[..., :3], float(cfg["optimizer"]["lr"]), float(cfg["optimizer"]["weight_decay"]))
+    else:
+        raise SystemExit("this config conditions on DINO features: pass --dino-weights <local Dinov2Model checkpoint> (or --dino-random-init), "
+                         "or --dino-maps <tensor (V,Hp,Wp,C) saved with torch.save>, one map per training view")
+    if dino_maps.dim() != 4 or dino_maps.shape[0] < len(run.images):
+        raise SystemExit("--dino-maps must hold one (Hp,Wp,C) map per training view")
+    return dino_maps, int(dino_maps.shape[-1]), ext
+
+
+def build_step(f, cfg, rs, run, dino_dim):
+    """(model, FusedStep, the --checkpoint's dictionary or None): the model of the config with the checkpoint's weights (and the
+    extractor's) loaded, on the device, and the step the flags ask for."""
+    model = model_from_config(cfg, dino_dim=dino_dim, mma_mode=f.mode)
+    ckpt = torch.load(f.checkpoint, map_location="cpu", weights_only=True) if f.checkpoint else None
     if ckpt is not None:
         load_checkpoint_into(model, ckpt)
-        if ext is not None and "dino_model_state_dict" in ckpt:
-            ext.extractor.load_state_dict(ckpt["dino_model_state_dict"])
+        if run.ext is not None and "dino_model_state_dict" in ckpt:
+            run.ext.extractor.load_state_dict(ckpt["dino_model_state_dict"])
             if "dino_optimizer_state_dict" in ckpt:
-                ext.opt.load_state_dict(ckpt["dino_optimizer_state_dict"])
-    model.dino_grad = ext is not None
-    model = model.to(dev).train()
-    step = FusedStep(model, white_bkgd=rs["white_bkgd"], data_parallel=world > 1, **step_options(cfg, args.recipe),
-                     **({"seed": args.seed} if args.recipe == "multiscale" else {}), **ray_reg_options(args, rs["near"], rs["far"]),
-                     **freq_reg_options(args), **patch_reg_options(args), **info_reg_options(args))
-    gen = torch.Generator(device=dev)
-    gen.manual_seed(args.seed)
+                run.ext.opt.load_state_dict(ckpt["dino_optimizer_state_dict"])
+    model.dino_grad = run.ext is not None
+    model = model.to(run.dev).train()
+    step = FusedStep(model, white_bkgd=rs["white_bkgd"], data_parallel=run.world > 1, **step_options(cfg, f.recipe),
+                     **({"seed": f.seed} if f.recipe == "multiscale" else {}), **ray_reg_options(f, rs["near"], rs["far"]),
+                     **freq_reg_options(f), **patch_reg_options(f), **info_reg_options(f))
+    return model, step, ckpt
+
+
+def training_state(f, run, ckpt):
+    """What the epochs carry besides the weights: (the shuffle generator, the patch draws or None, the occupancy grids or None -- the
+    single grid is not part of a checkpoint: a resumed run starts again from the all-ones grid and its warm-up; the per-view grids
+    are -- and from the checkpoint the first epoch to run and the best PSNR)."""
+    gen = torch.Generator(device=run.dev)
+    gen.manual_seed(f.seed)
     patches = None
-    if draws_patches(args):                               # the patch draws: a CPU generator of their own, another stream on every rank
-        patches = dict(n=args.patches_per_step, stride=args.patch_stride, generator=torch.Generator().manual_seed(args.seed * 1_000_003 + 7919 * (rank + 1)))
-    # (the single grid is not part of a checkpoint: a resumed run starts again from the all-ones grid and its warm-up; the per-view
-    # grids are)
+    if f.draws_patches:                                   # the patch draws: a CPU generator of their own, another stream on every rank
+        patches = dict(n=f.patches_per_step, stride=f.patch_stride,
+                       generator=torch.Generator().manual_seed(f.seed * 1_000_003 + 7919 * (run.rank + 1)))
     occ = None
-    if args.occupancy_res:
-        occ = PerViewOccupancy.from_args(args, len(images), dev) if args.occupancy_per_view else OccupancySchedule.from_args(args, dev)
+    if f.occupancy_res:
+        occ = PerViewOccupancy.from_args(f, len(run.images), run.dev) if f.occupancy_per_view else OccupancySchedule.from_args(f, run.dev)
     if ckpt is not None and isinstance(occ, PerViewOccupancy) and "occupancy_per_view_state" in ckpt:
         occ.load_state_dict(ckpt["occupancy_per_view_state"])
-    best, log, first_epoch = 0.0, [], 0
-    if ckpt is not None:
-        first_epoch, best = resume_from(ckpt, model, step)
-    targets = test_images.permute(0, 2, 3, 1).contiguous()
-    eval_dino = dict(features=dino_maps[0:1], pose=poses[0], focal=focal, H=H, W=W) if use_dino else None      # train.py:203-208
-    for epoch in range(first_epoch, epochs):
-        step.opt.lr = lr_at(cfg, epoch)
-        if ext is not None:
-            ext.set_lr(lr_at(cfg, epoch))
-        t0 = time.perf_counter()
-        loss, samples = train_epoch(step, cfg, epoch, images, poses, H, W, focal, rs["near"], rs["far"], gen, dino_maps, args.max_batches, rank, world,
-                                    extractor=ext, fused_inputs=args.fused_inputs, occupancy=occ, n_importance=args.n_importance,
-                                    coarse_weight=1.0 if args.coarse_weight is None else args.coarse_weight, patches=patches)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        rec = {"epoch": epoch + 1, "loss": loss, "lr": step.opt.lr, "seconds": round(dt, 3), "Msamples_per_s": round(world * samples / dt / 1e6, 2)}
-        if occ is not None:
-            rec["occupied_fraction"] = round(occ.occupied_fraction if args.occupancy_per_view else occ.current().occupied_fraction, 4)
-        if rank != 0:                                                         # every rank holds the same parameters: rank 0 validates and writes
-            log.append(rec)
-            continue
-        if (epoch + 1) % int(cfg["output"]["val_freq"]) == 0 or epoch + 1 == epochs:
-            if ext is not None:                                               # the extractor moved: view 0's map as it is now, under no_grad
-                eval_dino["features"] = precompute_dino_features(ext.extractor, ext.images[0:1]).float()
-            m = evaluate_views(model, test_poses, H, W, focal, rs["near"], rs["far"], rs["n_samples"], targets=targets, white_bkgd=rs["white_bkgd"],
-                               mma_mode=args.eval_mode, dino=eval_dino, out_dir=os.path.join(out_dir, f"val_{epoch + 1}"),
-                               N_importance=args.n_importance)
-            model.train()
-            rec.update(psnr=m["psnr"], ssim=m["ssim"])
-            if m["psnr"] > best:
-                best = m["psnr"]
-                save_checkpoint(os.path.join(out_dir, f"best_{name}.pth"), model, step, epoch, best, cfg, args.recipe, ext, occ)
-        if (epoch + 1) % int(cfg["output"]["save_freq"]) == 0:
-            save_checkpoint(os.path.join(out_dir, f"epoch_{epoch + 1}.pth"), model, step, epoch, best, cfg, args.recipe, ext, occ)
-        log.append(rec)
-        print(json.dumps(rec), flush=True)
-    if rank == 0:
-        os.makedirs(out_dir, exist_ok=True)
-        with open(os.path.join(out_dir, "train_log.json"), "w") as f:
-            json.dump(log, f, indent=1)
-    if args.data_parallel:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
+    return (gen, patches, occ, *(resume_from(ckpt, run.model, run.step) if ckpt is not None else (0, 0.0)))
+
+
+def run_epoch(f, cfg, rs, run, epoch, epochs):
+    """One epoch's record: the epoch trained at its learning rate and, on rank 0 (every rank holds the same parameters), the
+    validation and the checkpoints that are due behind it."""
+    step, ext, occ, model = run.step, run.ext, run.occ, run.model
+    step.opt.lr = lr_at(cfg, epoch)
+    if ext is not None:
+        ext.set_lr(lr_at(cfg, epoch))
+    t0 = time.perf_counter()
+    loss, samples = train_epoch(step, cfg, epoch, run.images, run.poses, run.H, run.W, run.focal, rs["near"], rs["far"], run.gen, run.dino_maps,
+                                f.max_batches, run.rank, run.world, extractor=ext, fused_inputs=f.fused_inputs, occupancy=occ,
+                                n_importance=f.n_importance, coarse_weight=1.0 if f.coarse_weight is None else f.coarse_weight, patches=run.patches)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    rec = {"epoch": epoch + 1, "loss": loss, "lr": step.opt.lr, "seconds": round(dt, 3), "Msamples_per_s": round(run.world * samples / dt / 1e6, 2)}
+    if occ is not None:
+        rec["occupied_fraction"] = round(occ.occupied_fraction if f.occupancy_per_view else occ.current().occupied_fraction, 4)
+    if run.rank != 0:
+        return rec
+    if (epoch + 1) % int(cfg["output"]["val_freq"]) == 0 or epoch + 1 == epochs:
+        if ext is not None:                                               # the extractor moved: view 0's map as it is now, under no_grad
+            run.eval_dino["features"] = precompute_dino_features(ext.extractor, ext.images[0:1]).float()
+        m = evaluate_views(model, run.test_poses, run.H, run.W, run.focal, rs["near"], rs["far"], rs["n_samples"], targets=run.targets,
+                           white_bkgd=rs["white_bkgd"], mma_mode=f.eval_mode, dino=run.eval_dino, out_dir=os.path.join(run.out_dir, f"val_{epoch + 1}"),
+                           N_importance=f.n_importance)
+        model.train()
+        rec.update(psnr=m["psnr"], ssim=m["ssim"])
+        if m["psnr"] > run.best:
+            run.best = m["psnr"]
+            save_checkpoint(os.path.join(run.out_dir, f"best_{run.name}.pth"), model, step, epoch, run.best, cfg, f.recipe, ext, occ)
+    if (epoch + 1) % int(cfg["output"]["save_freq"]) == 0:
+        save_checkpoint(os.path.join(run.out_dir, f"epoch_{epoch + 1}.pth"), model, step, epoch, run.best, cfg, f.recipe, ext, occ)
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
+def main(argv=None):
+    f = flags_of(build_parser().parse_args(argv))
+    cfg = refuse(f)
+    with distributed(f) as (rank, world):
+        torch.manual_seed(f.seed)                         # parameter init (when no checkpoint is given) and the ray shuffles
+        rs = render_settings(cfg)
+        out_dir = f.out or cfg["output"]["save_dir"]
+        epochs = f.epochs if f.epochs is not None else int(cfg["training"]["epochs"])
+        run = load_scene(f, cfg)
+        run.rank, run.world, run.out_dir, run.name = rank, world, out_dir, cfg.get("experiment", {}).get("name", "run")
+        run.dino_maps, dino_dim, run.ext = dino_source(f, cfg, run)
+        run.model, run.step, ckpt = build_step(f, cfg, rs, run, dino_dim)
+        run.gen, run.patches, run.occ, run.first_epoch, run.best = training_state(f, run, ckpt)
+        run.targets = run.test_images.permute(0, 2, 3, 1).contiguous()
+        use_dino = run.dino_maps is not None              # train.py:203-208: validation conditions on training view 0
+        run.eval_dino = dict(features=run.dino_maps[0:1], pose=run.poses[0], focal=run.focal, H=run.H, W=run.W) if use_dino else None
+        log = [run_epoch(f, cfg, rs, run, epoch, epochs) for epoch in range(run.first_epoch, epochs)]
+        if rank == 0:
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, "train_log.json"), "w") as fh:
+                json.dump(log, fh, indent=1)
     return log
 
 
