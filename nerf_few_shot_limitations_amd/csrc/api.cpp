@@ -37,9 +37,8 @@ struct nrf_model {
     bool lin_stale = false;                 // parameters were last set from a device vector: the host copy `lin` is old
     bool bfresh[3] = {false, false, false}; // backward stream of the mode matches the current parameters
     nrf::ParamLayout layout;
-    nrf::NetPlan bplan;                     // the dZ chain's layers, and behind them (V3) the feature-gradient kernel's W0d^T layer:
-    int g_frags16 = 0;                      // one device stream, one gather table, one re-pack, one freshness flag; 16-bit fragments of that layer
-    int i_frags16[2] = {0, 0};              // the same for input_grad_kernel's W0^T and (V2) color_layers.0^T layers; V3: input_grad_v3_kernel's, behind W0d^T
+    nrf::NetPlan bplan;                     // the dZ chain's layers, and behind them the post-chain gradient kernels' (ensure_train: the riders):
+                                            // one device stream, one gather table, one re-pack, one freshness flag
     nrf::TrainPlan tplan;
     nrf::TrainDev train{};
     void* d_bstream[3] = {nullptr, nullptr, nullptr};
@@ -233,32 +232,30 @@ int ensure_train(nrf_model* m) {
         return fail(NRF_EUNSUPPORTED, err);
     if ((int)m->tplan.slot_tiles.size() > nrf::kMaxSlots || (int)m->tplan.jobs.size() > nrf::kMaxJobs || m->tplan.n_mask_slots > nrf::kMaxMaskSlots)
         return fail(NRF_EUNSUPPORTED, "network too deep for the training path");
+    // The riders: layers of the post-chain gradient kernels (train_post_grad_core.hpp) behind the chain's layers in the same
+    // stream -- the chain kernels wrap at n_bchunks and never see them.  First (V3) W0d^T of dino_grad_kernel, then the input
+    // gradient's: W0^T and (V2) color_layers.0^T restricted to the encodings (train_input_grad_impl.hpp), on V3 W0p^T and
+    // color_layers.0^T's direction tile (train_input_grad_v3_impl.hpp).
     const bool v3 = m->arch.net == NRF_NET_V3;
-    if (v3) {
-        // W0d^T (train_dino_grad_impl.hpp) rides behind the chain's layers: the chain kernels wrap at n_bchunks and never see it
-        nrf::NetPlan gplan;
-        if (!nrf::make_dino_grad_plan(m->arch, m->lin, gplan, err)) return fail(NRF_EUNSUPPORTED, err);
-        m->g_frags16 = gplan.layers[0].MT * gplan.layers[0].KT * 2;
-        m->bplan.layers.push_back(gplan.layers[0]);
-    }
-    // behind it the input gradient's layers ride in the same way: W0^T and color_layers.0^T restricted to the encodings
-    // (train_input_grad_impl.hpp), on V3 W0p^T and color_layers.0^T's direction tile (train_input_grad_v3_impl.hpp)
-    nrf::NetPlan iplan;
+    nrf::NetPlan gplan, iplan;
+    if (v3 && !nrf::make_dino_grad_plan(m->arch, m->lin, gplan, err)) return fail(NRF_EUNSUPPORTED, err);
     if (!(v3 ? nrf::make_input_grad_v3_plan : nrf::make_input_grad_plan)(m->arch, m->lin, iplan, err)) return fail(NRF_EUNSUPPORTED, err);
-    for (size_t i = 0; i < iplan.layers.size() && i < 2; ++i) {
-        m->i_frags16[i] = iplan.layers[i].MT * iplan.layers[i].KT * 2;
-        m->bplan.layers.push_back(iplan.layers[i]);
-    }
+    std::vector<int> rider_frags16;              // 16-bit fragments of each rider; the first gplan.layers.size() are gstream's
+    for (const nrf::NetPlan* p : {&gplan, &iplan})
+        for (const nrf::LayerPlan& L : p->layers) {
+            rider_frags16.push_back(L.MT * L.KT * 2);
+            m->bplan.layers.push_back(L);
+        }
     for (int mode = 0; mode < 3; ++mode) {
         // under the mask the mode's forward stream holds; current only if that is also the recorded one
         std::vector<nrf::HostLinear> scaled;
         const nrf::PackedStream ps = nrf::pack_stream(m->bplan, pack_source(m, m->freq_packed_active[mode], m->freq_packed[mode], scaled), mode);
         NRF_HIP(hipMalloc(&m->d_bstream[mode], ps.bytes.size()));
         NRF_HIP(hipMemcpy(m->d_bstream[mode], ps.bytes.data(), ps.bytes.size(), hipMemcpyHostToDevice));
-        // the layer is whole chunks: 16 fragments per chunk, DT * 16 (16-bit) or DT * 32 (fp32) fragments
-        const uint32_t g_chunks = (uint32_t)(m->g_frags16 * (mode == NRF_MMA_F32 ? 2 : 1) / 16);
-        uint32_t i_chunks = 0;                  // every layer starts on a chunk boundary (packing.cpp:stream_sources)
-        for (int i = 0; i < 2; ++i) i_chunks += (uint32_t)((m->i_frags16[i] * (mode == NRF_MMA_F32 ? 2 : 1) + 15) / 16);
+        // 16 fragments per chunk, twice the fragments in fp32; every layer starts on a chunk boundary (packing.cpp:stream_sources)
+        uint32_t g_chunks = 0, i_chunks = 0;
+        for (size_t r = 0; r < rider_frags16.size(); ++r)
+            (r < gplan.layers.size() ? g_chunks : i_chunks) += (uint32_t)((rider_frags16[r] * (mode == NRF_MMA_F32 ? 2 : 1) + 15) / 16);
         m->train.bstream[mode] = m->d_bstream[mode];
         m->train.n_bchunks[mode] = ps.n_chunks - g_chunks - i_chunks;
         m->train.gstream[mode] = g_chunks ? static_cast<const char*>(m->d_bstream[mode]) + (size_t)m->train.n_bchunks[mode] * 16 * 1024 : nullptr;

@@ -392,78 +392,72 @@ bool make_backward_plan(const nrf_arch& a, const std::vector<HostLinear>& lin, N
     return true;
 }
 
-// The A operand of dino_grad_kernel (train_dino_grad_impl.hpp): W0d^T, the F0T layer above restricted to the DT DINO tiles
-// of fusion.0's input -- K = fusion.0's 256 rows, output row r = channel r of the fetched feature.
+// The two recipes of the post-chain gradient kernels' A operands (train_post_grad_core.hpp), layers that ride behind the chain's
+// in the backward stream.  Both are lin[li]^T restricted to a window of its input tiles: K = its `rows` rows, output row r =
+// input column col[32 * first + r] of the forward plan's layer, so accumulator register r of lane half h in output tile m is the
+// derivative of feature (slot 16m + r, half h) of feature_map.hpp.
+namespace {
+
+LayerPlan transposed_window(int li, int rows, const std::vector<int>& col, int first, int MT, int bias_off) {
+    LayerPlan L; L.transposed = true; L.KT = rows / 32; L.MT = MT; L.krow.assign(rows, {-1, 0});
+    for (int k = 0; k < rows; ++k) L.krow[k] = {li, k};
+    L.rcol.assign(col.begin() + 32 * first, col.begin() + 32 * (first + MT));
+    L.bias_off = bias_off;
+    return L;
+}
+
+// the first Linear (W0 of V1 / V2, fusion.0 of V3), transposed, restricted to MT of its input tiles from `first` on
+LayerPlan first_linear_T(const nrf_arch& a, const NetPlan& fwd, int first, int MT) {
+    return transposed_window(0, a.hidden, fwd.layers[0].col, first, MT, 0);
+}
+
+// color_layers.0 ([feature_vec | PE(dir)] -> 128: layer `fwd_i` of the forward plan, Linear `li`), transposed, restricted to its
+// direction tile
+LayerPlan colour0_direction_T(const nrf_arch& a, const NetPlan& fwd, int fwd_i, int li, int bias_off) {
+    return transposed_window(li, a.hidden / 2, fwd.layers[fwd_i].col, a.hidden / 32, 1, bias_off);
+}
+
+// a plan of one or two such layers
+void ride(NetPlan& plan, LayerPlan L) {
+    plan.n_bias = L.bias_off + 32 * L.MT;
+    plan.layers.push_back(std::move(L));
+}
+
+}  // namespace
+
+// dino_grad_kernel (train_dino_grad_impl.hpp): W0d^T, the DT DINO tiles of fusion.0's input.
 bool make_dino_grad_plan(const nrf_arch& a, const std::vector<HostLinear>& lin, NetPlan& plan, std::string& err) {
     plan = NetPlan();
     if (a.net != NRF_NET_V3) { err = "the DINO feature gradient belongs to the V3 network"; return false; }
     NetPlan fwd;
     if (!make_plan(a, lin, fwd, err)) return false;
-    const LayerPlan& F0 = fwd.layers[0];
-    const int H = a.hidden, HT = H / 32, DT = a.dino_dim / 32, PT = F0.KT - DT;
-    LayerPlan L; L.transposed = true; L.KT = HT; L.MT = DT; L.krow.assign(32 * HT, {-1, 0});
-    for (int k = 0; k < H; ++k) L.krow[k] = {0, k};
-    L.rcol.assign(F0.col.begin() + 32 * PT, F0.col.begin() + 32 * F0.KT);
-    L.bias_off = 0;
-    plan.layers.push_back(std::move(L));
-    plan.n_bias = 32 * DT;
+    const int DT = a.dino_dim / 32;
+    ride(plan, first_linear_T(a, fwd, fwd.layers[0].KT - DT, DT));
     return true;
 }
 
-// The A operands of input_grad_kernel (train_input_grad_impl.hpp), both in the manner of make_dino_grad_plan.  Layer 0: W0^T of
-// the first Linear restricted to its positional-encoding tiles -- K = its 256 rows, rcol = the forward plan's col, so accumulator
-// register r of lane half h in output tile m is the derivative of feature (slot 16m + r, half h) of feature_map.hpp.  Layer 1
-// (V2): color_layers.0^T restricted to its direction-encoding tile -- K = its 128 rows.
+// input_grad_kernel (train_input_grad_impl.hpp): W0^T over all of its positional-encoding tiles, and (V2) color_layers.0^T.
 bool make_input_grad_plan(const nrf_arch& a, const std::vector<HostLinear>& lin, NetPlan& plan, std::string& err) {
     plan = NetPlan();
     if (a.net != NRF_NET_V1 && a.net != NRF_NET_V2) { err = "the input gradient is built for the V1 and V2 networks"; return false; }
     NetPlan fwd;
     if (!make_plan(a, lin, fwd, err)) return false;
-    const int H = a.hidden, HT = H / 32, n = a.n_layers;
-    const LayerPlan& F0 = fwd.layers[0];
-    LayerPlan L; L.transposed = true; L.KT = HT; L.MT = F0.KT; L.krow.assign(32 * HT, {-1, 0});
-    for (int k = 0; k < H; ++k) L.krow[k] = {0, k};
-    L.rcol = F0.col;
-    L.bias_off = 0;
-    int off = 32 * L.MT;
-    plan.layers.push_back(std::move(L));
-    if (a.net == NRF_NET_V2) {
-        const LayerPlan& C0 = fwd.layers[n + 2];                                   // [feature_vec | PE(dir)] -> 128
-        LayerPlan D; D.transposed = true; D.KT = H / 64; D.MT = 1; D.krow.assign(32 * D.KT, {-1, 0});
-        for (int k = 0; k < H / 2; ++k) D.krow[k] = {n + 2, k};
-        D.rcol.assign(C0.col.begin() + H, C0.col.begin() + H + 32);
-        D.bias_off = off;
-        off += 32;
-        plan.layers.push_back(std::move(D));
-    }
-    plan.n_bias = off;
+    const int PT = fwd.layers[0].KT, n = a.n_layers;
+    ride(plan, first_linear_T(a, fwd, 0, PT));
+    if (a.net == NRF_NET_V2) ride(plan, colour0_direction_T(a, fwd, n + 2, n + 2, 32 * PT));
     return true;
 }
 
-// The A operands of input_grad_v3_kernel (train_input_grad_v3_impl.hpp), the V3 sibling of the plan above.  Layer 0: W0p^T, the
-// F0T layer of make_backward_plan restricted to the PT positional tiles of fusion.0's input (make_dino_grad_plan takes the DT
-// tiles behind them) -- K = fusion.0's 256 rows, rcol = the forward plan's col of those tiles.  Layer 1: color_layers.0^T
-// restricted to its direction-encoding tile, as for V2.
+// input_grad_v3_kernel (train_input_grad_v3_impl.hpp): W0p^T, the PT positional tiles of fusion.0's input in front of the DINO
+// tiles, and color_layers.0^T (make_train_plan: the colour branch at forward layer 7 + n, Linear 5 + n).
 bool make_input_grad_v3_plan(const nrf_arch& a, const std::vector<HostLinear>& lin, NetPlan& plan, std::string& err) {
     plan = NetPlan();
     if (a.net != NRF_NET_V3) { err = "this input-gradient plan belongs to the V3 network"; return false; }
     NetPlan fwd;
     if (!make_plan(a, lin, fwd, err)) return false;
-    const int H = a.hidden, HT = H / 32, n = a.n_layers, DT = a.dino_dim / 32;
-    const LayerPlan& F0 = fwd.layers[0];
-    const int PT = F0.KT - DT;
-    LayerPlan L; L.transposed = true; L.KT = HT; L.MT = PT; L.krow.assign(32 * HT, {-1, 0});
-    for (int k = 0; k < H; ++k) L.krow[k] = {0, k};
-    L.rcol.assign(F0.col.begin(), F0.col.begin() + 32 * PT);
-    L.bias_off = 0;
-    plan.layers.push_back(std::move(L));
-    const LayerPlan& C0 = fwd.layers[7 + n + 2];                                   // [feature_vec | PE(dir)] -> 128 (make_train_plan: colour branch at 7 + n)
-    LayerPlan D; D.transposed = true; D.KT = H / 64; D.MT = 1; D.krow.assign(32 * D.KT, {-1, 0});
-    for (int k = 0; k < H / 2; ++k) D.krow[k] = {5 + n + 2, k};
-    D.rcol.assign(C0.col.begin() + H, C0.col.begin() + H + 32);
-    D.bias_off = 32 * PT;
-    plan.layers.push_back(std::move(D));
-    plan.n_bias = 32 * PT + 32;
+    const int PT = fwd.layers[0].KT - a.dino_dim / 32, n = a.n_layers;
+    ride(plan, first_linear_T(a, fwd, 0, PT));
+    ride(plan, colour0_direction_T(a, fwd, 7 + n + 2, 5 + n + 2, 32 * PT));
     return true;
 }
 
